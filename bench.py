@@ -9,18 +9,28 @@ Lambert shading and the mirror-bounce loop, written to a framebuffer resident in
 Metric (BASELINE.json): Mrays/s on scenes/20spheres.yml; a ray = one primary, shadow or reflection ray
 (SURVEY.md 8(d)); rays per frame are counted by the kernel itself (RT_FLAG_COUNT pass before timing).
 
-N = 1: BASELINE config 2, 20spheres @ 1920x1080, camera = identity (the reference host's start-up pose), RGBA32F; the line
-also carries a `configs` array with all five BASELINE configs on this GPU (short regions) and `single_frame_ms`, what update()
-returns for one synchronised frame (src/update-cuda.cu:178-189).
+N = 1: BASELINE config 2, 20spheres @ 1920x1080, camera = identity (the reference host's start-up pose), RGBA32F.
 N > 1: BASELINE config 5, 20spheres @ 7680x4320 -- the configuration BASELINE.json names for several GPUs -- rows band-cyclic
 over the N ranks (no data-path communication while rendering), one RCCL gather to rank 0 per frame + a device reassembly
-kernel on rank 0, as BASELINE.json's north_star prescribes: total work is fixed ("scaling": "strong").  Rank 0 first renders
-the whole 8K frame alone, so that the line carries its own denominator (`speedup_vs_1gpu_config5`), and the ranks measure the
-link bandwidth into rank 0 (`gather_bound_ms`).  The headline `value` is measured on the SAME output as N = 1 (RGBA32F, dense
-rows); the RGBA8 / sparse-tile transport is timed in a second region and reported as `config.alt`.  (--workload config2w keeps
-the weak-scaled 1080p workload of rounds 1-2.)
+kernel on rank 0, as BASELINE.json's north_star prescribes: total work is fixed ("scaling": "strong").  The headline `value`
+is measured on the SAME output as N = 1 (RGBA32F, dense rows).  (--workload config2w keeps the weak-scaled 1080p workload of
+rounds 1-2.)
 
-Prints ONE JSON line (rank 0).  The oracle (oracle/) is used ONLY for the `cpu_baseline` legs.
+A plain run does what the headline needs and nothing else: set-up (one counting frame per camera pose, for the rays), W warm-up
+steps, the K timed steps, the outputs (--dump-outputs DIR), the result line.  --full adds everything else, each leg still
+switched off by its --no-* option:
+  N = 1: a `configs` array with all five BASELINE configs on this GPU (short regions, each with an oracle row sample) and
+  `single_frame_ms`, what update() returns for one synchronised frame (src/update-cuda.cu:178-189); the orbit statistics; the
+  1-thread and all-cores CPU baselines; the last timed frame checked against a plain launch of the same frame.
+  N > 1: rank 0 first renders the whole frame alone, so that the line carries its own denominator (`speedup_vs_1gpu_config5`);
+  the ranks measure the link bandwidth into rank 0 (`gather_bound_ms`); the RGBA8 / sparse-tile transport is timed in a second
+  region and reported as `config.alt`; the gathered frames are checked against a single-context render.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the frame of the last timed step, the (H, W, 4) framebuffer a caller of
+the timed path receives, as DIR/frame.npy in float32 (RGBA8 as 0..255); a frame over 64 MB is cut to a fixed, seeded sample of
+its rows.  The inputs (scene file, camera poses) depend on the arguments alone, so two builds can be compared output for output.
+
+Prints ONE JSON line (rank 0).  The oracle (oracle/) is used ONLY for the `cpu_baseline` legs and the row samples of --full.
 """
 import argparse
 import hashlib
@@ -45,6 +55,8 @@ CONFIGS = {"config1": ("quadratic", 640, 480, None), "config2": ("20spheres", 19
            "config4": ("clebsch", 3840, 2160, None), "config5": ("20spheres", 7680, 4320, None)}
 KERNEL_SOURCES = ["cuda-ray-tracer_amd/csrc/rt_wavefront.hip", "cuda-ray-tracer_amd/csrc/rt_math.hpp",
                   "cuda-ray-tracer_amd/csrc/rt_scene_dev.h", "cuda-ray-tracer_amd/csrc/rt_wavefront_math.hpp"]
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_SEED = 20260101        # --dump-outputs: the row sample of a frame over DUMP_MAX_BYTES
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -657,6 +669,20 @@ def link_bandwidth(dist, torch, rank, world, dev, cdev, nccl, mbytes=64):
             "what": "per_peer: dist.send / recv of one message, one peer at a time; gather_ingest: dist.gather of one message per rank, bytes from the other ranks "
                     "arriving at rank 0 / wall time (world 1: the self copy)"}
 
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: `frame` is the (H, W, 4) device framebuffer of the last timed step.  Written as DIR/frame.npy in float32;
+    over DUMP_MAX_BYTES, only a fixed seeded sample of its rows (the same rows for the same frame size)."""
+    import numpy as np
+    import torch
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    row_bytes = W * 4 * 4
+    if H * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(H, DUMP_MAX_BYTES // row_bytes, replace=False))
+        frame = frame[torch.from_numpy(rows).to(frame.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), frame.to(torch.float32).cpu().numpy())
+
 # ----------------------------------------------------------------------------------------------------------------
 def run_rank(args, world):
     import numpy as np
@@ -705,7 +731,7 @@ def run_rank(args, world):
 
     # ---- N > 1: rank 0 renders the whole frame alone (the denominator of the speed-up), then the links into rank 0 are measured ----
     one_gpu = links = None
-    if dist_on and not args.no_one_gpu:
+    if dist_on and args.full and not args.no_one_gpu:
         if rank == 0:
             one_gpu = {"rgba32f_ms": one_gpu_frame_ms(pkg, scene, local_rank, flags, cams[0], pkg.RT_FMT_RGBA32F),
                        "rgba8_ms": one_gpu_frame_ms(pkg, scene, local_rank, flags, cams[0], pkg.RT_FMT_RGBA8),
@@ -740,10 +766,12 @@ def run_rank(args, world):
     main = FramePath(env, args.format, "dense" if args.format == "rgba32f" else args.gather, cams)
     dt, kernel_ms = main.run_timed(args.steps, args.warmup)
     rays_timed = rays_in(args.steps, args.warmup)
-    check_main = main.frame_check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, main.full[(main.k - 1) & 1] if dist_on else main.local[0][:main.ren.local_rows])
+    check_main = main.frame_check() if args.full else None
     gather_main = main.gather_report() if dist_on else None
     timed_frame_ok = None
-    if not dist_on and len(cams) == 1:   # the last frame of the timed region (graph or not) against one more plain launch of the same frame
+    if args.full and not dist_on and len(cams) == 1:   # the last frame of the timed region (graph or not) against one more plain launch of the same frame
         last = main.local[0].clone()
         main.ren.update(cams[0], dev_fb=main.local[0].data_ptr(), stream=main.stream.cuda_stream, timed=False)
         main.stream.synchronize()
@@ -753,7 +781,7 @@ def run_rank(args, world):
 
     # ---- N > 1: the display wire format (RGBA8, sparse tiles) timed the same way, reported next to the headline ----
     alt = None
-    if dist_on and args.format == "rgba32f" and not args.no_alt:
+    if dist_on and args.full and args.format == "rgba32f" and not args.no_alt:
         ap = FramePath(env, "rgba8", args.gather, cams)
         adt, akms = ap.run_timed(args.steps, args.warmup)
         acheck = ap.frame_check()
@@ -766,7 +794,7 @@ def run_rank(args, world):
 
     # ---- N = 1, static camera: the same kernel over an orbit of 24 poses (frame time depends on the view) ----
     orbit = None
-    if not dist_on and args.camera == "static" and args.workload_name == "config2" and not args.no_orbit:
+    if args.full and not dist_on and args.camera == "static" and args.workload_name == "config2" and not args.no_orbit:
         ts = []
         for i in range(n_orbit):
             cam = orbit_pose(pkg, i, n_orbit)
@@ -892,7 +920,7 @@ def run_rank(args, world):
                                                       "speedup": one_gpu["rgba32f_ms"] / max(one_gpu["rgba32f_ms"] / n, g_ms)}
             result["predicted_rgba32f_dense"] = {"table": pred, "what": "step = max(render / N, one rank's rows over one xGMI link at 50 / 75 GB/s), pipelined over two buffer sets (DESIGN.md section 7): "
                                                  "the RGBA32F frame is bound by the gather as soon as N > 1; only the RGBA8 sparse transport (config.alt) can follow the kernel"}
-        if not dist_on and args.workload_name == "config2" and args.kernel == "wavefront" and args.camera == "static" and not args.no_configs:
+        if args.full and not dist_on and args.workload_name == "config2" and args.kernel == "wavefront" and args.camera == "static" and not args.no_configs:
             # ---- all five BASELINE configs on this GPU + what update() returns for one frame ----
             result["configs"] = []
             for name in ("config1", "config2", "config3", "config4", "config5"):
@@ -900,7 +928,7 @@ def run_rank(args, world):
             result["single_frame_ms"] = result["configs"][1]["single_frame_ms"]
             result["single_frame_ms_what"] = ("median of 20 synchronised single frames of the headline workload, one HIP event pair around each launch: what update() returns "
                                               "(src/update-cuda.cu:178-189); the headline's ms_per_step is per frame of frames issued back to back")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             O = graft.load_oracle()
             osc = O.load_scene(os.path.join(ROOT, "scenes", scene_name + ".yml")).with_size(W, H, max_refl)
             cam0 = cams[0]
@@ -956,17 +984,24 @@ def main():
                     help="nccl = RCCL (the product path). gloo stages the gather through host memory and lets several ranks share "
                          "one GPU: only for rehearsing the N>1 code path on a 1-GPU box")
     ap.add_argument("--force-dist", action="store_true", help="N = 1: run the N > 1 code path (process group, gather, reassembly) with one rank")
-    ap.add_argument("--no-alt", action="store_true")
-    ap.add_argument("--no-orbit", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="N = 1: skip the `configs` array (all five BASELINE configs, short regions)")
-    ap.add_argument("--no-one-gpu", action="store_true", help="N > 1: skip rank 0's single-GPU render of the whole frame and the link measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other leg (see the module docstring): BASELINE configs, orbit, CPU baselines, checks; N > 1: "
+                         "1-GPU denominator, links, RGBA8 transport.  Off by default: a plain run measures only the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last timed step as DIR/frame.npy (float32; a seeded row sample over 64 MB)")
+    ap.add_argument("--no-alt", action="store_true", help="--full, N > 1: skip the RGBA8 transport (config.alt)")
+    ap.add_argument("--no-orbit", action="store_true", help="--full, N = 1: skip the orbit statistics")
+    ap.add_argument("--no-configs", action="store_true", help="--full, N = 1: skip the `configs` array (all five BASELINE configs, short regions)")
+    ap.add_argument("--no-one-gpu", action="store_true", help="--full, N > 1: skip rank 0's single-GPU render of the whole frame and the link measurement")
     ap.add_argument("--no-graph", action="store_true", help="N = 1: time K plain launches instead of one hipGraph of them")
     ap.add_argument("--settle", type=int, default=0, help="N = 1: untimed frames in front of the --warmup steps (experiments)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the oracle row samples of `configs`")
     ap.add_argument("--cpu-frames", type=int, default=2)
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
             sys.exit(spawn_ranks(args.gpus))

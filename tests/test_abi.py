@@ -22,7 +22,7 @@ def test_header_and_binding_agree(pkg):
 
 def test_library_exports_every_declared_symbol(pkg):
     """libmi355rt.so exports the single-GPU ABI, libmi355rt_multi.so (the only one that links RCCL) the rt_*_multi entry points."""
-    lib = ctypes.CDLL(pkg.LIB_PATH)
+    lib = pkg.lib()   # (not a bare CDLL: pkg.lib() loads torch's HIP runtime first; a test process that loaded ours first has no device later)
     multi = ctypes.CDLL(pkg.MULTI_LIB_PATH)
     for name in declared_functions():
         assert hasattr(multi if name in pkg.MULTI_ABI_SYMBOLS else lib, name), name

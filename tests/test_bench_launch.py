@@ -54,7 +54,7 @@ def test_more_ranks_than_gpus_fails_loudly():
 @pytest.mark.parametrize("gather", ["dense", "sparse"])
 def test_rccl_path_with_one_rank(gather):
     """backend nccl (= RCCL) at world size 1: the very step() / assemble() / flush() code of the N > 1 bench, one rank."""
-    p = _run(["--gpus", "1", "--force-dist", "--steps", "6", "--warmup", "3", "--gather", gather, "--no-cpu-baseline"])
+    p = _run(["--gpus", "1", "--force-dist", "--full", "--steps", "6", "--warmup", "3", "--gather", gather, "--no-cpu-baseline"])
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
     assert r["n_gpus"] == 1 and r["rccl_ranks"] == 1
@@ -78,7 +78,7 @@ def test_rccl_path_with_one_rank(gather):
 def test_sparse_overflow_is_resent_densely():
     """A message capacity that is too small: the overflowed frames are sent again as dense rows and counted, and the frame
     rank 0 ends up with is still the single-context frame."""
-    p = _run(["--gpus", "1", "--force-dist", "--steps", "4", "--warmup", "2", "--sparse-capacity", "100", "--no-cpu-baseline"])
+    p = _run(["--gpus", "1", "--force-dist", "--full", "--steps", "4", "--warmup", "2", "--sparse-capacity", "100", "--no-cpu-baseline"])
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
     alt = r["config"]["alt"]
@@ -91,7 +91,7 @@ def test_sparse_overflow_is_resent_densely():
 def test_timed_region_as_one_graph_or_as_plain_launches(graph):
     """N = 1: the K timed frames are launched as one captured hipGraph (default) or one by one (--no-graph); either way the JSON
     line says which, and the last frame of the timed region equals a plain launch of the same frame."""
-    p = _run(["--steps", "7", "--warmup", "3", "--no-orbit", "--no-cpu-baseline"] + ([] if graph else ["--no-graph"]))
+    p = _run(["--full", "--steps", "7", "--warmup", "3", "--no-orbit", "--no-cpu-baseline"] + ([] if graph else ["--no-graph"]))
     assert p.returncode == 0, p.stderr[-3000:]
     r = json.loads(p.stdout.strip().splitlines()[-1])
     roof = r["roofline"]
@@ -104,3 +104,24 @@ def test_timed_region_as_one_graph_or_as_plain_launches(graph):
         assert c["ms_per_step"] > 0 and c["single_frame_ms"] > 0 and c["value"] > 0 and 0 < c["roofline"]["frac"] < 1
     assert r["single_frame_ms"] == r["configs"][1]["single_frame_ms"]
     assert "config2" in r["config"]["workload"] and "1920x1080" in r["config"]["workload"]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_frame(tmp_path, oracle):
+    """Without --full the line carries the headline only (no configs, orbit, CPU baselines), and --dump-outputs writes the frame
+    of the last timed step: the 1080p RGBA32F framebuffer, equal to the oracle's frame on a sample of rows."""
+    import numpy as np
+    from conftest import compare, scene_path
+    out = tmp_path / "outputs"
+    p = _run(["--steps", "5", "--warmup", "2", "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    r = json.loads(p.stdout.strip().splitlines()[-1])
+    assert r["steps"] == 5 and r["ms_per_step"] > 0 and r["value"] > 0 and r["unit"] == "Mrays/s" and r["higher_is_better"] is True
+    assert not {"configs", "camera_orbit", "cpu_baseline", "cpu_baseline_all_cores", "single_frame_ms"} & set(r)
+    assert [f.name for f in out.iterdir()] == ["frame.npy"]
+    img = np.load(out / "frame.npy")
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 4)
+    rows = np.arange(0, 1080, 45, dtype=np.uint32)
+    want = oracle.load_scene(scene_path("20spheres")).with_size(1920, 1080, None).render(rows=rows, nthreads=min(16, os.cpu_count() or 1))
+    c = compare(img[rows][..., :3], want)
+    assert c["n_bad"] == 0, c

@@ -12,8 +12,8 @@ mkdir -p $O
 step() { t=$1; out=$2; shift 2; echo "== [$t s] $*"; timeout -k 10 $t bash -c "$*" > $out 2>&1; rc=$?; echo "rc=$rc"; tail -n 2 $out | cut -c1-300; if [ $rc -ge 124 ]; then echo "step killed: stopping"; exit $rc; fi; }
 if [ "${PART:-1}" = 1 ]; then
 step 900 $O/pytest_gpu.txt "python -m pytest tests -q -m gpu"
-step 300 $O/bench.json "python bench.py 2> $O/bench.err"
-step 300 $O/bench_force_dist.json "python bench.py --force-dist --steps 50 --warmup 10 --no-cpu-baseline 2> $O/bench_force_dist.err"
+step 300 $O/bench.json "python bench.py --full 2> $O/bench.err"
+step 300 $O/bench_force_dist.json "python bench.py --full --force-dist --steps 50 --warmup 10 --no-cpu-baseline 2> $O/bench_force_dist.err"
 step 300 $O/all_configs.txt "python tests/tools/config_bench.py"
 step 300 $O/flythrough.txt "python tools/flythrough_bench.py"
 step 400 $O/ab_lean_general.txt "MI355RT_LEAN=always python tools/ab_flags.py lean=0 general=256"
