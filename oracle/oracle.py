@@ -84,6 +84,11 @@ def lib():
         L.orc_checksum.restype = C.c_double
         L.orc_checksum.argtypes = [fp, C.c_uint64]
         L.orc_camera_matrix.argtypes = [dp, C.c_double, C.c_double, dp]
+        u64p = C.POINTER(C.c_uint64)
+        L.orc_libm_mode.argtypes = [C.c_int]
+        L.orc_libm_table.argtypes = [C.c_int, u64p, dp, C.c_uint64]
+        L.orc_libm_recorded.restype = C.c_uint64
+        L.orc_libm_recorded.argtypes = [C.c_int, u64p, C.c_uint64]
         _LIB = L
     return _LIB
 
@@ -190,6 +195,91 @@ class Scene:
                               out.ctypes.data_as(C.POINTER(C.c_float)),
                               C.byref(cnt) if counters else None, int(nthreads))
         return (out, cnt.as_dict()) if counters else out
+
+
+# --------------------------------------------------------------------------------------------------
+# The cubic solver's cbrt / acos / cos from elsewhere (orc_libm_*, rt_oracle.h)
+# --------------------------------------------------------------------------------------------------
+LIBM_FUNCS = ("cbrt", "acos", "cos")
+_LIBM_MODES = {"off": 0, "record": 1, "replace": 2, "explore": 3}
+
+
+def _bits(x):
+    return np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+
+
+class Libm:
+    """Tables of cbrt / acos / cos values keyed by the argument's bits: {name: (sorted uint64 keys, float64 values)}."""
+
+    def __init__(self):
+        self.tables = {f: (np.empty(0, np.uint64), np.empty(0, np.float64)) for f in LIBM_FUNCS}
+
+    def add(self, name, args, values):
+        keys, vals = self.tables[name]
+        keys = np.concatenate([keys, _bits(args)])
+        vals = np.concatenate([vals, np.asarray(values, dtype=np.float64)])
+        keys, first = np.unique(keys, return_index=True)
+        self.tables[name] = (keys, vals[first])
+
+    def args(self, name):
+        return self.tables[name][0].view(np.float64)
+
+    def __len__(self):
+        return sum(len(k) for k, _ in self.tables.values())
+
+
+class libm_hook:
+    """Context manager around any oracle call (render, orc_intersect_ray_ex, ...): mode "record" keeps every distinct argument
+    the solver passes to cbrt / acos / cos (and still uses glibc); mode "replace" takes the values from `libm` (a Libm) and keeps
+    the arguments it lacks as misses (answered with NaN, never with glibc); mode "explore" is "replace" with misses answered by
+    glibc, so that what follows from them is seen in the same run.  On exit `.seen[name]` holds the kept arguments (float64) and
+    the oracle is back to glibc."""
+
+    def __init__(self, mode, libm=None):
+        self.mode, self.libm, self.seen = mode, libm, {}
+
+    def __enter__(self):
+        L = lib()
+        L.orc_libm_mode(_LIBM_MODES[self.mode])
+        if self.mode in ("replace", "explore"):
+            for i, f in enumerate(LIBM_FUNCS):
+                keys, vals = self.libm.tables[f]
+                L.orc_libm_table(i, keys.ctypes.data_as(C.POINTER(C.c_uint64)), vals.ctypes.data_as(C.POINTER(C.c_double)), len(keys))
+        return self
+
+    def __exit__(self, *exc):
+        L = lib()
+        for i, f in enumerate(LIBM_FUNCS):
+            n = int(L.orc_libm_recorded(i, None, 0))
+            out = np.empty(n, dtype=np.uint64)
+            L.orc_libm_recorded(i, out.ctypes.data_as(C.POINTER(C.c_uint64)), n)
+            self.seen[f] = np.sort(out).view(np.float64)
+        L.orc_libm_mode(0)
+        for i in range(len(LIBM_FUNCS)):
+            L.orc_libm_table(i, None, None, 0)
+        return False
+
+
+def under_libm(run, evaluate, libm=None, max_rounds=10):
+    """`run()` (any oracle computation) with the solver's cbrt / acos / cos taken from `evaluate(name, float64 args) -> values`
+    (another implementation: the device's).  Run with the table so far, glibc standing in for what it lacks (mode "explore"),
+    evaluate the arguments it lacked, and repeat until a run lacks none: that run used the table's values only.  Values of the
+    other library move later arguments (cos(theta + 2 pi / 3) follows from acos; shadow and bounce rays follow from roots), hence
+    the repetition: a ray's solve can take two rounds (acos, then cos), so a frame with R reflections needs at most 2 (R + 2) when
+    every value differs -- three to six in practice with mirrors.  Returns (that run's result, the Libm, rounds of evaluation); fails
+    when `max_rounds` rounds leave misses."""
+    libm = Libm() if libm is None else libm
+    for rounds in range(max_rounds + 1):
+        with libm_hook("explore", libm) as h:
+            out = run()
+        if not any(len(v) for v in h.seen.values()):
+            return out, libm, rounds
+        if rounds == max_rounds:
+            break
+        for f in LIBM_FUNCS:
+            if len(h.seen[f]):
+                libm.add(f, h.seen[f], evaluate(f, h.seen[f]))
+    raise AssertionError(f"the oracle under another libm still misses {sum(len(v) for v in h.seen.values())} arguments after {max_rounds} rounds")
 
 
 def checksum(img):

@@ -269,6 +269,113 @@ static void ray_poly(const double k[ORC_NCOEF], const double o[3], const double 
 #undef Y
 #undef Z
 
+/* ------------------------------------------------------------------------------------------------
+ * Special functions of the cubic solver behind a hook (orc_libm_*, rt_oracle.h).  Off: glibc, as
+ * the reference.  Record: glibc, and every distinct argument is kept, per function, by its bits.
+ * Replace: the value comes from a caller's table sorted by argument bits; an argument the table lacks
+ * is kept as a miss and answered with NaN -- never with glibc's value.  Explore: as replace, but a miss
+ * is answered with glibc's value, so that what follows from it is seen too (a run without misses is a
+ * replace run).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t *keys;
+    unsigned char *used;
+    size_t n, cap; /* cap: a power of two */
+} bitset;
+
+static int g_libm_mode = ORC_LIBM_OFF;
+static pthread_mutex_t g_libm_lock = PTHREAD_MUTEX_INITIALIZER;
+static struct {
+    const uint64_t *keys;
+    const double *vals;
+    uint64_t n;
+} g_libm_tab[ORC_LIBM_NFN];
+static bitset g_libm_seen[ORC_LIBM_NFN];
+
+static inline uint64_t mix64(uint64_t k)
+{
+    k ^= k >> 33;
+    k *= 0xff51afd7ed558ccdULL;
+    k ^= k >> 33;
+    return k;
+}
+
+static void bitset_clear(bitset *s)
+{
+    free(s->keys);
+    free(s->used);
+    memset(s, 0, sizeof(*s));
+}
+
+static int bitset_add(bitset *s, uint64_t k)
+{
+    if (2 * (s->n + 1) > s->cap) {
+        bitset old = *s;
+        s->cap = old.cap ? 2 * old.cap : 1024;
+        s->keys = (uint64_t *) calloc(s->cap, sizeof(uint64_t));
+        s->used = (unsigned char *) calloc(s->cap, 1);
+        if (!s->keys || !s->used) abort();
+        s->n = 0;
+        for (size_t i = 0; i < old.cap; i++)
+            if (old.used[i]) bitset_add(s, old.keys[i]);
+        free(old.keys);
+        free(old.used);
+    }
+    size_t i = (size_t) mix64(k) & (s->cap - 1);
+    while (s->used[i]) {
+        if (s->keys[i] == k) return 0;
+        i = (i + 1) & (s->cap - 1);
+    }
+    s->used[i] = 1;
+    s->keys[i] = k;
+    s->n++;
+    return 1;
+}
+
+static double libm(int fn, double x)
+{
+    if (g_libm_mode == ORC_LIBM_OFF) return fn == ORC_LIBM_CBRT ? cbrt(x) : fn == ORC_LIBM_ACOS ? acos(x) : cos(x);
+    uint64_t k;
+    memcpy(&k, &x, sizeof(k));
+    if (g_libm_mode == ORC_LIBM_REPLACE || g_libm_mode == ORC_LIBM_EXPLORE) {
+        const uint64_t *keys = g_libm_tab[fn].keys;
+        uint64_t lo = 0, hi = g_libm_tab[fn].n;
+        while (lo < hi) {
+            uint64_t mid = lo + (hi - lo) / 2;
+            if (keys[mid] < k) lo = mid + 1;
+            else hi = mid;
+        }
+        if (lo < g_libm_tab[fn].n && keys[lo] == k) return g_libm_tab[fn].vals[lo];
+    }
+    pthread_mutex_lock(&g_libm_lock);
+    bitset_add(&g_libm_seen[fn], k);
+    pthread_mutex_unlock(&g_libm_lock);
+    if (g_libm_mode == ORC_LIBM_REPLACE) return NAN;
+    return fn == ORC_LIBM_CBRT ? cbrt(x) : fn == ORC_LIBM_ACOS ? acos(x) : cos(x);
+}
+
+void orc_libm_mode(int mode)
+{
+    g_libm_mode = mode;
+    for (int f = 0; f < ORC_LIBM_NFN; f++) bitset_clear(&g_libm_seen[f]);
+}
+
+void orc_libm_table(int fn, const uint64_t *keys, const double *vals, uint64_t n)
+{
+    g_libm_tab[fn].keys = keys;
+    g_libm_tab[fn].vals = vals;
+    g_libm_tab[fn].n = n;
+}
+
+uint64_t orc_libm_recorded(int fn, uint64_t *out, uint64_t cap)
+{
+    const bitset *s = &g_libm_seen[fn];
+    uint64_t m = 0;
+    for (size_t i = 0; i < s->cap && m < cap; i++)
+        if (s->used[i]) out[m++] = s->keys[i];
+    return s->n;
+}
+
 /* root selection, surface_impl.h:105-155 */
 static double solve_poly(double t3, double t2, double t1, double t0, int *branch)
 {
@@ -284,18 +391,18 @@ static double solve_poly(double t3, double t2, double t1, double t0, int *branch
             /* one real root: Cardano, :113-118 -- not filtered, may be negative */
             *branch = 4;
             delta = sqrt(delta);
-            q = cbrt(r + delta);
-            r = cbrt(r - delta);
+            q = libm(ORC_LIBM_CBRT, r + delta);
+            r = libm(ORC_LIBM_CBRT, r - delta);
             return q + r - t2 / 3.0;
         }
         /* three real roots: trigonometric form, :120-133 */
         *branch = 5;
-        double theta = acos(r / sqrt(-q * q * q)) / 3.0;
+        double theta = libm(ORC_LIBM_ACOS, r / sqrt(-q * q * q)) / 3.0;
         double c = 2.0 * sqrt(-q);
-        double x = c * cos(theta) - t2 / 3.0;
-        double x1 = c * cos(theta + K_TWO_THIRD_PI) - t2 / 3.0;
+        double x = c * libm(ORC_LIBM_COS, theta) - t2 / 3.0;
+        double x1 = c * libm(ORC_LIBM_COS, theta + K_TWO_THIRD_PI) - t2 / 3.0;
         if (x1 >= K_EPS && x1 < x) x = x1;
-        x1 = c * cos(theta + 2.0 * K_TWO_THIRD_PI) - t2 / 3.0;
+        x1 = c * libm(ORC_LIBM_COS, theta + 2.0 * K_TWO_THIRD_PI) - t2 / 3.0;
         if (x1 >= K_EPS && x1 < x) x = x1;
         return x;
     }

@@ -111,6 +111,21 @@ void orc_render_rows(const orc_scene *scene, const double cam[16], const uint32_
 /* Sum of all channels accumulated in double (SURVEY.md section 8 "checksum"). */
 double orc_checksum(const float *rgb, uint64_t n_floats);
 
+/* ---- the cubic solver's special functions (test infrastructure: a frame under another libm) ----
+ * solve_poly (surface_impl.h:106-136) takes cbrt, acos and cos through a hook.  ORC_LIBM_OFF (the default): glibc.
+ * ORC_LIBM_RECORD: glibc, and every distinct argument is kept per function, keyed by its bit pattern.
+ * ORC_LIBM_REPLACE: the value is looked up in the table of orc_libm_table (keys = argument bits, ascending; the
+ * caller keeps both arrays alive); an argument it lacks is kept as a miss and answered with NaN, never with glibc's.
+ * ORC_LIBM_EXPLORE: as replace, but a miss is answered with glibc's value (and kept), so that the arguments which follow
+ * from it are seen in the same run; a run that kept no miss used the table's values only.
+ * orc_libm_mode also forgets what was kept.  Thread-safe for orc_render_rows; set the mode between calls only. */
+enum { ORC_LIBM_OFF = 0, ORC_LIBM_RECORD = 1, ORC_LIBM_REPLACE = 2, ORC_LIBM_EXPLORE = 3 };
+enum { ORC_LIBM_CBRT = 0, ORC_LIBM_ACOS = 1, ORC_LIBM_COS = 2, ORC_LIBM_NFN = 3 };
+void orc_libm_mode(int mode);
+void orc_libm_table(int fn, const uint64_t *keys, const double *vals, uint64_t n);
+/* the arguments kept (recorded or missed) for fn: returns their number, copies up to cap of them (in no order) */
+uint64_t orc_libm_recorded(int fn, uint64_t *out, uint64_t cap);
+
 /* ---- host camera (src/ray-tracer.cpp:44-58): inverse(lookAt(pos, pos - dir, up)) ---- */
 void orc_camera_matrix(const double pos[3], double yaw_deg, double pitch_deg, double out_cam[16]);
 

@@ -7,11 +7,15 @@ a world = 8, band = 16 render on one GPU whose reassembly equals the single-cont
 """
 import json
 import os
+import sys
 
 import numpy as np
 import pytest
 
-from conftest import compare, scene_path
+from conftest import ROOT, compare, scene_path
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import cubic_device_lab as D  # noqa: E402  (the oracle under the device's cbrt / acos / cos)
 
 pytestmark = pytest.mark.gpu
 
@@ -70,6 +74,10 @@ def test_config4_clebsch_full_size(pkg, oracle):
     assert len(rows) == 6
     c = compare(a[rows][..., :3], _oracle_rows(oracle, cfg, rows))
     assert c["n_bad_pixels"] <= max(2, int(0.0004 * len(rows) * cfg["w"])), c
+    # ... and against the oracle under the device's cbrt / acos / cos (tests/tools/cubic_device_lab.py): none beyond 1e-5
+    s = oracle.load_scene(scene_path(cfg["scene"])).with_size(cfg["w"], cfg["h"], cfg["max_reflections"])
+    c = D.compare_device_libm(pkg, a[rows][..., :3], s, rows=np.asarray(rows, dtype=np.uint32), nthreads=16)
+    assert c["n_bad_pixels"] == 0, c
     # the checksum of SURVEY's table: last-ulp differences of the special functions move a channel by ~1e-7 relative (random
     # sign over 25 M channels) and a pixel that flips at a solver discontinuity by < 1; 5.0 of 5.0e6 allows a handful
     d = abs(_checksum(a) - cfg["checksum"])

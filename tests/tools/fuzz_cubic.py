@@ -2,8 +2,9 @@
 """Fuzz the degree-3 path: N random scenes with one or two random cubic surfaces (dense or sparse coefficients) next
 to spheres / a plane, random lights and cameras.  Device cbrt / acos / cos differ from glibc's in the last ulp, so the
 bar is the north star's 1e-5 relative per channel; pixels beyond it are solver flips at root discontinuities
-(tangent rays, triple roots) and are counted.  The wavefront and the simple kernel share the device functions and must
-agree bit for bit.  usage: python tests/tools/fuzz_cubic.py [n_scenes] [first_seed]"""
+(tangent rays, triple roots) and are counted -- against the oracle as it is (glibc) and against the oracle under the device's
+cbrt / acos / cos (tests/tools/cubic_device_lab.py), where none is expected.  The wavefront and the simple kernel share the device
+functions and must agree bit for bit.  usage: python tests/tools/fuzz_cubic.py [n_scenes] [first_seed]"""
 import os
 import sys
 
@@ -18,6 +19,8 @@ pkg = graft.load_package()
 O = graft.load_oracle()
 from conftest import compare  # noqa: E402
 from test_gpu_parity import oracle_from, render_desc  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import cubic_device_lab as D  # noqa: E402
 
 
 def scene(seed):
@@ -50,14 +53,22 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     kernels_differ, over, worst, px_total, px_bad, px_diff, exact = 0, 0, 0.0, 0, 0, 0, 0
+    dl_bad, dl_diff, dl_exact = 0, 0, 0
     for seed in range(first, first + n):
         s, cam, npx = scene(seed)
         a = render_desc(pkg, s, cam)
         if not np.array_equal(a, render_desc(pkg, s, cam, flags=pkg.RT_FLAG_SIMPLE)):
             kernels_differ += 1
             print(f"seed {seed}: wavefront and simple kernels differ")
-        want = oracle_from(pkg, O, s).render(cam=cam, nthreads=4)
+        osc = oracle_from(pkg, O, s)
+        want = osc.render(cam=cam, nthreads=4)
         c = compare(a[..., :3], want)
+        cd = D.compare_device_libm(pkg, a[..., :3], osc, cam=cam, nthreads=4)
+        dl_bad += cd["n_bad_pixels"]
+        dl_diff += cd["not_identical_pixels"]
+        dl_exact += cd["not_identical_pixels"] == 0
+        if cd["n_bad_pixels"]:
+            print(f"seed {seed}: {cd['n_bad_pixels']} pixels beyond 1e-5 of the device-libm oracle at (row, column) {cd['bad'][:8]}")
         nd = int(np.any(a[..., :3] != want, axis=-1).sum())
         px_diff += nd
         exact += nd == 0
@@ -73,7 +84,8 @@ def main():
     print(f"cubic fuzz: {n} scenes, {px_bad} of {px_total} pixels beyond 1e-5 relative ({100.0 * px_bad / max(px_total, 1):.4f} %), worst scene {100 * worst:.2f} %, "
           f"{over} scenes over the 0.2 % test bound, {kernels_differ} with kernels disagreeing; {exact} scenes bit-identical to the oracle, "
           f"{px_diff} pixels differ in some bit")
-    return 1 if kernels_differ else 0
+    print(f"against the oracle under the device's cbrt / acos / cos: {dl_bad} pixels beyond 1e-5, {dl_exact} scenes bit-identical, {dl_diff} pixels differ in some bit")
+    return 1 if kernels_differ or dl_bad else 0
 
 
 if __name__ == "__main__":
