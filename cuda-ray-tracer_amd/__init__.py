@@ -31,15 +31,16 @@ ABI_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_set_last_error", "rt_scene_load_file", "rt_scene_new", "rt_scene_add_object",
     "rt_scene_add_light", "rt_surface_make", "rt_scene_set_size", "rt_scene_set_max_reflections",
     "rt_scene_get_desc", "rt_scene_free", "rt_camera_matrix", "rt_create", "rt_render", "rt_local_rows", "rt_max_local_rows",
-    "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_sparse_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
+    "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
 MULTI_ABI_SYMBOLS = ["rt_create_multi", "rt_render_multi", "rt_multi_wait", "rt_multi_fb", "rt_multi_stream", "rt_multi_download", "rt_multi_info",
-                     "rt_multi_destroy"]
+                     "rt_multi_last_transfer", "rt_multi_destroy"]
 RT_MULTI_SELF_EXCHANGE = 0x10000
 RT_MULTI_BANDWISE = 0x20000
+RT_MULTI_SPARSE = 0x40000
 
 
 class RtError(RuntimeError):
@@ -139,6 +140,8 @@ def lib():
         L.rt_assemble.argtypes = [vp, vp, vp, vp]
         L.rt_sparse_bytes.argtypes = [C.c_uint32]
         L.rt_sparse_bytes.restype = C.c_size_t
+        L.rt_sparse_msg_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        L.rt_sparse_msg_bytes.restype = C.c_size_t
         L.rt_pack_sparse.argtypes = [vp, vp, vp, C.c_uint32, vp]
         L.rt_render_sparse.argtypes = [vp, dp, vp, C.c_uint32, vp, fp]
         L.rt_assemble_sparse.argtypes = [vp, vp, C.c_uint32, vp, vp]
@@ -191,6 +194,7 @@ def multi_lib():
         M.rt_multi_stream.restype = vp
         M.rt_multi_download.argtypes = [vp, vp, C.c_size_t]
         M.rt_multi_info.argtypes = [vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        M.rt_multi_last_transfer.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         M.rt_multi_destroy.argtypes = [vp]
         _mlib = M
     return _mlib
@@ -302,7 +306,7 @@ def desc_from_arrays(width, height, vertical_fov, bg_color, max_reflections, coe
 
 
 from .sharding import (band_rows_of_rank, max_local_rows, assemble_index, gather_to_root, assemble_torch, sparse_words, bg_rgba8,  # noqa: E402,F401
-                       pack_sparse_numpy, assemble_sparse_numpy)
+                       bg_rgba32f, pack_sparse_numpy, assemble_sparse_numpy)
 
 
 class Renderer:
@@ -367,10 +371,15 @@ class Renderer:
     def assemble(self, gathered_ptr, full_ptr, stream=None):
         _check(lib().rt_assemble(self._h, C.c_void_p(gathered_ptr), C.c_void_p(full_ptr), C.c_void_p(stream) if stream else None))
 
-    # sparse transport of an RGBA8 frame (tiles with content only): see include/mi355rt.h
+    # sparse transport of a frame (tiles with content only): see include/mi355rt.h
     @staticmethod
     def sparse_bytes(capacity_tiles):
+        """Size of an RGBA8 message (rt_sparse_bytes)."""
         return int(lib().rt_sparse_bytes(int(capacity_tiles)))
+
+    def sparse_msg_bytes(self, capacity_tiles):
+        """Size of a message in this renderer's own format (rt_sparse_msg_bytes)."""
+        return int(lib().rt_sparse_msg_bytes(int(self.fmt), int(capacity_tiles)))
 
     def update_sparse(self, msg_ptr, capacity_tiles, cam=None, stream=None, timed=True):
         """update() whose output is a sparse message (tiles with hits only) instead of a framebuffer."""
@@ -444,6 +453,12 @@ class MultiRenderer:
         n, t = C.c_uint32(), C.c_uint32()
         _check(multi_lib().rt_multi_info(self._h, C.byref(n), C.byref(t)))
         self.n_contexts, self.transport = n.value, {0: "in place", 1: "device copies", 2: "rccl"}[t.value]
+
+    def last_transfer(self):
+        """(bytes_sent, bytes_dense) of the last frame: what travelled to the root, and what the dense transport moves."""
+        sent, dense = C.c_uint64(), C.c_uint64()
+        _check(multi_lib().rt_multi_last_transfer(self._h, C.byref(sent), C.byref(dense)))
+        return int(sent.value), int(dense.value)
 
     def update(self, cam=None, full_ptr=None, timed=True):
         cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)

@@ -29,8 +29,9 @@ extern "C" hipError_t rt_launch_wavefront_fast(const FrameArgs *, const DevObjec
 extern "C" size_t rt_wavefront_lds_bytes_strict(uint32_t, uint32_t, int, uint32_t, int, uint32_t);
 
 extern "C" hipError_t rt_launch_assemble_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, hipStream_t);
-extern "C" hipError_t rt_launch_pack_sparse_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t rt_launch_assemble_sparse_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, void *, uint32_t, uint32_t, hipStream_t);
+extern "C" hipError_t rt_launch_pack_sparse_strict(const void *, void *, uint32_t, uint32_t, const uint32_t *, uint32_t, int, hipStream_t);
+extern "C" hipError_t rt_launch_assemble_sparse_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, uint32_t, void *, uint32_t,
+                                                       uint32_t, int, hipStream_t);
 
 namespace {
 
@@ -789,7 +790,6 @@ extern "C" int rt_render(rt_ctx *ctx, const double cam[16], void *dev_fb, void *
 extern "C" int rt_render_sparse(rt_ctx *ctx, const double cam[16], void *dev_msg, uint32_t capacity_tiles, void *stream, float *ms)
 {
     if (!ctx || !cam || !dev_msg) return fail(RT_ERR_INVALID, "rt_render_sparse: null argument");
-    if (ctx->cfg.format != RT_FMT_RGBA8) return fail(RT_ERR_INVALID, "rt_render_sparse: the context does not render RGBA8");
     if (ctx->cfg.flags & RT_FLAG_SIMPLE) return fail(RT_ERR_INVALID, "rt_render_sparse: not available with RT_FLAG_SIMPLE");
     return render_impl(ctx, cam, dev_msg, stream, ms, true, capacity_tiles);
 }
@@ -851,17 +851,41 @@ static uint32_t bg_rgba8(const FrameArgs &fa)
     return r | (g << 8) | (b << 16) | (255u << 24);
 }
 
+// the background pixel of the context's format as four words (what the sparse kernels compare with and paint): RGBA8 in word 0,
+// RGBA32F the bits of (bg_color, 1.0f) -- what the render kernels store for a pixel without hits
+struct BgPixel {
+    uint32_t w[4];
+};
+static BgPixel bg_pixel(const rt_ctx *ctx)
+{
+    BgPixel p{};
+    if (ctx->cfg.format == RT_FMT_RGBA8) {
+        p.w[0] = bg_rgba8(ctx->fa);
+    } else {
+        const float f[4] = {ctx->fa.bg[0], ctx->fa.bg[1], ctx->fa.bg[2], 1.0f};
+        std::memcpy(p.w, f, sizeof(f));
+    }
+    return p;
+}
+
 extern "C" size_t rt_sparse_bytes(uint32_t capacity_tiles)
 {
     return ((size_t) ((4u + capacity_tiles + 3u) & ~3u) + (size_t) capacity_tiles * 256u) * sizeof(uint32_t);
 }
 
+extern "C" size_t rt_sparse_msg_bytes(uint32_t format, uint32_t capacity_tiles)
+{
+    if (format == RT_FMT_RGBA8) return rt_sparse_bytes(capacity_tiles);
+    if (format == RT_FMT_RGBA32F) return ((size_t) ((4u + capacity_tiles + 3u) & ~3u) + (size_t) capacity_tiles * 1024u) * sizeof(uint32_t);
+    return 0;
+}
+
 extern "C" int rt_pack_sparse(rt_ctx *ctx, const void *dev_fb, void *dev_msg, uint32_t capacity_tiles, void *stream)
 {
     if (!ctx || !dev_msg) return fail(RT_ERR_INVALID, "rt_pack_sparse: null argument");
-    if (ctx->cfg.format != RT_FMT_RGBA8) return fail(RT_ERR_INVALID, "rt_pack_sparse: the context does not render RGBA8");
-    hipError_t e = rt_launch_pack_sparse_strict(dev_fb ? dev_fb : ctx->d_fb, dev_msg, ctx->fa.width, ctx->local_rows, bg_rgba8(ctx->fa), capacity_tiles,
-                                                (hipStream_t) stream);
+    const BgPixel bg = bg_pixel(ctx);
+    hipError_t e = rt_launch_pack_sparse_strict(dev_fb ? dev_fb : ctx->d_fb, dev_msg, ctx->fa.width, ctx->local_rows, bg.w, capacity_tiles,
+                                                ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pack launch failed: %s", hipGetErrorString(e));
     return RT_OK;
 }
@@ -869,9 +893,9 @@ extern "C" int rt_pack_sparse(rt_ctx *ctx, const void *dev_fb, void *dev_msg, ui
 extern "C" int rt_assemble_sparse(rt_ctx *ctx, const void *gathered, uint32_t capacity_tiles, void *full, void *stream)
 {
     if (!ctx || !gathered || !full) return fail(RT_ERR_INVALID, "rt_assemble_sparse: null argument");
-    if (ctx->cfg.format != RT_FMT_RGBA8) return fail(RT_ERR_INVALID, "rt_assemble_sparse: the context does not render RGBA8");
-    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows, bg_rgba8(ctx->fa),
-                                                    capacity_tiles, nullptr, 0, 0, (hipStream_t) stream);
+    const BgPixel bg = bg_pixel(ctx);
+    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
+                                                    nullptr, 0, 0, ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "sparse assemble launch failed: %s", hipGetErrorString(e));
     return RT_OK;
 }
@@ -887,10 +911,10 @@ extern "C" int rt_assemble_sparse_incremental(rt_ctx *ctx, const void *gathered,
                                               void *stream)
 {
     if (!ctx || !gathered || !full || !stamps) return fail(RT_ERR_INVALID, "rt_assemble_sparse_incremental: null argument");
-    if (ctx->cfg.format != RT_FMT_RGBA8) return fail(RT_ERR_INVALID, "rt_assemble_sparse_incremental: the context does not render RGBA8");
     const uint32_t max_tiles = ((ctx->fa.width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
-    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows, bg_rgba8(ctx->fa),
-                                                    capacity_tiles, stamps, max_tiles, frame_tag, (hipStream_t) stream);
+    const BgPixel bg = bg_pixel(ctx);
+    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
+                                                    stamps, max_tiles, frame_tag, ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "sparse assemble launch failed: %s", hipGetErrorString(e));
     return RT_OK;
 }

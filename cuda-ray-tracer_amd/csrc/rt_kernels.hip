@@ -316,6 +316,97 @@ __global__ __launch_bounds__(64) void scatter_sparse_kernel(const uint32_t *__re
     if (x + 3u < width) row[x + 3u] = v.w;
 }
 
+// ---- sparse frame transport (RGBA32F) ----------------------------------------------------------------------------------
+// The same message with 16-byte pixels: { count, overflow, 0, 0 } + ids[capacity] (padded to 16 B) + tiles[capacity][256]
+// float4 -- 4 KiB per tile, every tile 16-byte aligned.  One wave per tile as above, one pixel per lane and instruction: 16
+// consecutive lanes cover one 256-byte tile row, one instruction four rows, a tile four instructions per lane.  Background =
+// bit-equal to (bg_color, 1.0f), the value the render kernels store for a pixel without hits.
+__device__ __forceinline__ bool ne16(const uint4 &a, const uint4 &b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u; }
+
+__global__ __launch_bounds__(64) void pack_sparse_f32_kernel(const uint4 *__restrict__ fb, uint32_t width, uint32_t local_rows, uint32_t tiles_x,
+                                                             uint4 bg, uint32_t cap, uint32_t *__restrict__ msg)
+{
+    const uint32_t tile = blockIdx.x, lane = threadIdx.x;
+    const uint32_t x = (tile % tiles_x) * 16u + (lane & 15u), lr0 = (tile / tiles_x) * 16u + (lane >> 4);
+    uint4 v[4];
+    bool diff = false;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        const uint32_t lr = lr0 + 4u * k;
+        v[k] = bg;
+        if (lr < local_rows && x < width) v[k] = fb[(size_t) lr * width + x];
+        diff |= ne16(v[k], bg);
+    }
+    if (__ballot(diff) == 0ull) return; // wave-uniform
+    uint32_t pos = 0;
+    if (lane == 0) pos = atomicAdd(&msg[0], 1u);
+    pos = __builtin_amdgcn_readfirstlane(pos);
+    if (pos >= cap) {
+        if (lane == 0) msg[1] = 1u;
+        return;
+    }
+    const uint32_t off_tiles = (4u + cap + 3u) & ~3u;
+    if (lane == 0) msg[4u + pos] = tile;
+    uint4 *dst = reinterpret_cast<uint4 *>(msg + off_tiles) + (size_t) pos * 256u;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) dst[k * 64u + lane] = v[k];
+}
+
+__global__ __launch_bounds__(256) void fill_f32_kernel(uint4 *__restrict__ full, size_t n, uint4 bg)
+{
+    for (size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) full[i] = bg;
+}
+
+// clear_stale_kernel for 16-byte pixels: the stale tile is repainted with four 16-byte stores per lane
+__global__ __launch_bounds__(64) void clear_stale_f32_kernel(uint4 *__restrict__ full, uint32_t *__restrict__ stamps, uint32_t width, uint32_t height,
+                                                             uint32_t world, uint32_t band_rows, uint32_t tiles_x, uint32_t max_tiles, uint32_t tag, uint4 bg)
+{
+    const uint32_t lane = threadIdx.x;
+    const size_t e = (size_t) blockIdx.x * 64u + lane, n = (size_t) world * max_tiles;
+    uint32_t st = 0;
+    if (e < n) st = stamps[e];
+    unsigned long long stale = __ballot(st != 0u && st != tag);
+    if (st != 0u && st != tag) stamps[e] = 0u;
+    while (stale) { // wave-uniform
+        const uint32_t l = (uint32_t) __builtin_ctzll(stale);
+        stale &= stale - 1ull;
+        const size_t es = (size_t) blockIdx.x * 64u + l;
+        const uint32_t r = (uint32_t) (es / max_tiles), tile = (uint32_t) (es - (size_t) r * max_tiles);
+        const uint32_t x = (tile % tiles_x) * 16u + (lane & 15u), lr0 = (tile / tiles_x) * 16u + (lane >> 4);
+        if (x >= width) continue;
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            const uint32_t lr = lr0 + 4u * k, b = lr / band_rows;
+            const uint64_t y = ((uint64_t) b * world + r) * band_rows + (lr - b * band_rows);
+            if (y < height) full[(size_t) y * width + x] = bg;
+        }
+    }
+}
+
+// scatter_sparse_kernel for 16-byte pixels
+__global__ __launch_bounds__(64) void scatter_sparse_f32_kernel(const uint32_t *__restrict__ gathered, uint4 *__restrict__ full, uint32_t width,
+                                                                uint32_t height, uint32_t world, uint32_t band_rows, uint32_t tiles_x, uint32_t cap,
+                                                                uint32_t *__restrict__ stamps, uint32_t max_tiles, uint32_t tag)
+{
+    const uint32_t r = blockIdx.x / cap, j = blockIdx.x - r * cap, lane = threadIdx.x;
+    const uint32_t off_tiles = (4u + cap + 3u) & ~3u;
+    const size_t msg_words = (size_t) off_tiles + (size_t) cap * 1024u;
+    const uint32_t *msg = gathered + (size_t) r * msg_words;
+    const uint32_t count = msg[0] < cap ? msg[0] : cap;
+    if (j >= count) return;
+    const uint32_t tile = msg[4u + j];
+    if (stamps && lane == 0 && tile < max_tiles) stamps[(size_t) r * max_tiles + tile] = tag; // this frame delivered the tile
+    const uint4 *src = reinterpret_cast<const uint4 *>(msg + off_tiles) + (size_t) j * 256u;
+    const uint32_t x = (tile % tiles_x) * 16u + (lane & 15u), lr0 = (tile / tiles_x) * 16u + (lane >> 4);
+    if (x >= width) return;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        const uint32_t lr = lr0 + 4u * k, b = lr / band_rows;
+        const uint64_t y = ((uint64_t) b * world + r) * band_rows + (lr - b * band_rows);
+        if (y < height) full[(size_t) y * width + x] = src[k * 64u + lane];
+    }
+}
+
 } // namespace RT_SYM(rtk)
 
 extern "C" hipError_t RT_SYM(rt_launch_trace)(const FrameArgs *fa, const DevObject *gobj, const DevLight *glight,
@@ -358,45 +449,63 @@ extern "C" hipError_t RT_SYM(rt_launch_assemble)(const void *gathered, void *ful
     return hipGetLastError();
 }
 
-extern "C" hipError_t RT_SYM(rt_launch_pack_sparse)(const void *fb, void *msg, uint32_t width, uint32_t local_rows, uint32_t bg, uint32_t cap,
-                                                     hipStream_t stream)
+// bg: the background pixel as 4 words (RGBA8: bg[0] only); rgba8 selects the message's pixel format
+extern "C" hipError_t RT_SYM(rt_launch_pack_sparse)(const void *fb, void *msg, uint32_t width, uint32_t local_rows, const uint32_t *bg, uint32_t cap,
+                                                     int rgba8, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     hipError_t e = hipMemsetAsync(msg, 0, 16, stream); // count, overflow
     if (e != hipSuccess) return e;
     const uint32_t tiles_x = (width + 15u) / 16u, tiles_y = (local_rows + 15u) / 16u;
     if (tiles_x * tiles_y == 0u || cap == 0u) return hipSuccess;
-    hipLaunchKernelGGL(pack_sparse_kernel, dim3(tiles_x * tiles_y), dim3(64), 0, stream, (const uint32_t *) fb, width, local_rows, tiles_x, bg, cap,
-                       (uint32_t *) msg);
+    if (rgba8)
+        hipLaunchKernelGGL(pack_sparse_kernel, dim3(tiles_x * tiles_y), dim3(64), 0, stream, (const uint32_t *) fb, width, local_rows, tiles_x, bg[0], cap,
+                           (uint32_t *) msg);
+    else
+        hipLaunchKernelGGL(pack_sparse_f32_kernel, dim3(tiles_x * tiles_y), dim3(64), 0, stream, (const uint4 *) fb, width, local_rows, tiles_x,
+                           make_uint4(bg[0], bg[1], bg[2], bg[3]), cap, (uint32_t *) msg);
     return hipGetLastError();
 }
 
 // stamps == NULL: stateless (fill everything, scatter).  stamps != NULL: incremental -- `full` and `stamps` carry over from
 // the previous call on this buffer (tag 0 = first call: fill everything and clear the stamps), max_tiles entries per rank.
 extern "C" hipError_t RT_SYM(rt_launch_assemble_sparse)(const void *gathered, void *full, uint32_t width, uint32_t height, uint32_t world,
-                                                         uint32_t band_rows, uint32_t bg, uint32_t cap, void *stamps, uint32_t max_tiles, uint32_t tag,
-                                                         hipStream_t stream)
+                                                         uint32_t band_rows, const uint32_t *bg, uint32_t cap, void *stamps, uint32_t max_tiles, uint32_t tag,
+                                                         int rgba8, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     const size_t n = (size_t) width * height;
     if (n == 0) return hipSuccess;
     const uint32_t tiles_x = (width + 15u) / 16u;
+    const uint4 bg4 = make_uint4(bg[0], bg[1], bg[2], bg[3]);
     if (!stamps || tag == 0u) {
         const uint32_t blocks = (uint32_t) ((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192);
-        hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(256), 0, stream, (uint32_t *) full, n, bg);
+        if (rgba8)
+            hipLaunchKernelGGL(fill_kernel, dim3(blocks), dim3(256), 0, stream, (uint32_t *) full, n, bg[0]);
+        else
+            hipLaunchKernelGGL(fill_f32_kernel, dim3(blocks), dim3(256), 0, stream, (uint4 *) full, n, bg4);
         if (stamps) {
             hipError_t e = hipMemsetAsync(stamps, 0, sizeof(uint32_t) * (size_t) world * max_tiles, stream);
             if (e != hipSuccess) return e;
         }
     }
     const uint32_t use_tag = tag == 0u ? 0xFFFFFFFFu : tag; // the first call stamps with a value no later call may use
-    if (cap != 0u && world != 0u)
-        hipLaunchKernelGGL(scatter_sparse_kernel, dim3(world * cap), dim3(64), 0, stream, (const uint32_t *) gathered, (uint32_t *) full, width, height,
-                           world, band_rows, tiles_x, cap, (uint32_t *) stamps, max_tiles, use_tag);
+    if (cap != 0u && world != 0u) {
+        if (rgba8)
+            hipLaunchKernelGGL(scatter_sparse_kernel, dim3(world * cap), dim3(64), 0, stream, (const uint32_t *) gathered, (uint32_t *) full, width, height,
+                               world, band_rows, tiles_x, cap, (uint32_t *) stamps, max_tiles, use_tag);
+        else
+            hipLaunchKernelGGL(scatter_sparse_f32_kernel, dim3(world * cap), dim3(64), 0, stream, (const uint32_t *) gathered, (uint4 *) full, width, height,
+                               world, band_rows, tiles_x, cap, (uint32_t *) stamps, max_tiles, use_tag);
+    }
     if (stamps && tag != 0u && world != 0u && max_tiles != 0u) {
         const size_t entries = (size_t) world * max_tiles;
-        hipLaunchKernelGGL(clear_stale_kernel, dim3((uint32_t) ((entries + 63) / 64)), dim3(64), 0, stream, (uint32_t *) full, (uint32_t *) stamps, width,
-                           height, world, band_rows, tiles_x, max_tiles, use_tag, bg);
+        if (rgba8)
+            hipLaunchKernelGGL(clear_stale_kernel, dim3((uint32_t) ((entries + 63) / 64)), dim3(64), 0, stream, (uint32_t *) full, (uint32_t *) stamps, width,
+                               height, world, band_rows, tiles_x, max_tiles, use_tag, bg[0]);
+        else
+            hipLaunchKernelGGL(clear_stale_f32_kernel, dim3((uint32_t) ((entries + 63) / 64)), dim3(64), 0, stream, (uint4 *) full, (uint32_t *) stamps, width,
+                               height, world, band_rows, tiles_x, max_tiles, use_tag, bg4);
     }
     return hipGetLastError();
 }

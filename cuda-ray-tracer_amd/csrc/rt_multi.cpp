@@ -12,7 +12,9 @@
 //                                           offsets, events, reassembly) on a one-GPU box, without RCCL
 //               one device, SELF_EXCHANGE   RCCL with one rank that sends its rows to itself: the RCCL calls on a one-GPU box
 //
-// Everything is enqueue-only unless timing is requested; rt_multi_wait() / rt_multi_stream() order later work.
+// Everything is enqueue-only unless timing is requested; rt_multi_wait() / rt_multi_stream() order later work.  The exception is
+// RT_MULTI_SPARSE: only tiles that are not pure background travel, and how many there are is only known once a context has
+// rendered, so the host waits for each context's 16-byte message header before it enqueues that message's transfer.
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -69,6 +71,15 @@ struct rt_multi {
     Transport transport = DIRECT;
     bool self_exchange = false;
     bool bandwise = false;            // RT_MULTI_BANDWISE: rows travel band by band straight to their place in the full frame; no rank-major slots, no rt_assemble
+    bool sparse = false;              // RT_MULTI_SPARSE: every context packs its rows into a sparse message; only the used prefix travels
+    uint32_t cap = 0;                 // sparse: tiles per message = the tiles of the largest context (no message can overflow)
+    size_t msg_bytes = 0, head_bytes = 0, tile_bytes = 0; // sparse: message stride in `gathered`, header + id array, one tile
+    std::vector<void *> msg;          // sparse: [world] message of context q on its own device (NULL: it packs straight into its receive slot)
+    std::vector<hipEvent_t> ev_hdr;   // sparse: [world] the message header of context q has reached h_hdr
+    uint32_t *h_hdr = nullptr;        // sparse: pinned host [world][4] message headers of the current frame
+    void *stamps = nullptr;           // sparse: rt_assemble_sparse_incremental's stamps for `full`
+    uint32_t next_tag = 0;            // sparse: frame tag of the next incremental assembly into `full` (0 = repaint everything)
+    uint64_t last_sent = 0, last_dense = 0; // rt_multi_last_transfer
     uint32_t band_rows = 16;
     std::vector<uint32_t> rows;       // [world] local rows of context q (bandwise)
     std::vector<int> dev;              // [n]
@@ -103,10 +114,14 @@ extern "C" int rt_multi_destroy(rt_multi *m)
         if (q < m->local.size() && m->local[q]) (void) hipFree(m->local[q]);
         if (q < m->ev_rendered.size() && m->ev_rendered[q]) (void) hipEventDestroy(m->ev_rendered[q]);
         if (q < m->ev_sent.size() && m->ev_sent[q]) (void) hipEventDestroy(m->ev_sent[q]);
+        if (q < m->msg.size() && m->msg[q]) (void) hipFree(m->msg[q]);
+        if (q < m->ev_hdr.size() && m->ev_hdr[q]) (void) hipEventDestroy(m->ev_hdr[q]);
     }
     if (m->n) (void) hipSetDevice(m->dev[0]);
     if (m->gathered) (void) hipFree(m->gathered);
     if (m->full) (void) hipFree(m->full);
+    if (m->stamps) (void) hipFree(m->stamps);
+    if (m->h_hdr) (void) hipHostFree(m->h_hdr);
     for (hipEvent_t e : {m->ev_gathered, m->ev_assembled, m->ev_t0, m->ev_t1})
         if (e) (void) hipEventDestroy(e);
     for (uint32_t r = 0; r < m->n; r++) {
@@ -128,6 +143,7 @@ static int create_impl(rt_multi *m, const rt_scene_desc *sd, const int *devices,
     m->pixel_bytes = format == RT_FMT_RGBA8 ? 4 : 16;
     m->self_exchange = (flags & RT_MULTI_SELF_EXCHANGE) != 0;
     m->bandwise = (flags & RT_MULTI_BANDWISE) != 0;
+    m->sparse = (flags & RT_MULTI_SPARSE) != 0;
     m->band_rows = band_rows;
     m->dev.assign(devices, devices + n);
     bool all_same = true, all_distinct = true;
@@ -143,6 +159,8 @@ static int create_impl(rt_multi *m, const rt_scene_desc *sd, const int *devices,
     m->local.assign(m->world, nullptr);
     m->ev_rendered.assign(m->world, nullptr);
     m->ev_sent.assign(m->world, nullptr);
+    m->msg.assign(m->world, nullptr);
+    m->ev_hdr.assign(m->world, nullptr);
     m->s_render.assign(n, nullptr);
     m->s_comm.assign(n, nullptr);
     for (uint32_t r = 0; r < n; r++) {
@@ -158,24 +176,45 @@ static int create_impl(rt_multi *m, const rt_scene_desc *sd, const int *devices,
         cfg.rank = q;
         cfg.world = m->world;
         cfg.band_rows = band_rows;
-        cfg.flags = flags & ~(RT_MULTI_SELF_EXCHANGE | RT_MULTI_BANDWISE);
+        cfg.flags = flags & ~(RT_MULTI_SELF_EXCHANGE | RT_MULTI_BANDWISE | RT_MULTI_SPARSE);
         cfg.format = format;
         int rc = rt_create(&m->ctx[q], sd, &cfg);
         if (rc != RT_OK) return rc;
         M_HIP(hipSetDevice(devices[r]));
         M_HIP(hipEventCreateWithFlags(&m->ev_rendered[q], hipEventDisableTiming));
         M_HIP(hipEventCreateWithFlags(&m->ev_sent[q], hipEventDisableTiming));
+        if (m->sparse) M_HIP(hipEventCreateWithFlags(&m->ev_hdr[q], hipEventDisableTiming));
         if (q == 0) rt_max_local_rows(m->ctx[0], &max_rows);
     }
     m->rows.assign(m->world, 0);
     for (uint32_t q = 0; q < m->world; q++) rt_local_rows(m->ctx[q], &m->rows[q]);
     if (m->bandwise && m->world == 1 && m->transport == DIRECT) m->bandwise = false; // (one context renders in place: nothing travels)
+    if (m->sparse && m->world == 1 && m->transport == DIRECT) m->sparse = false;
     m->slot_bytes = (size_t) max_rows * sd->width * m->pixel_bytes;
     m->full_bytes = (size_t) sd->height * sd->width * m->pixel_bytes;
     M_HIP(hipSetDevice(devices[0]));
     M_HIP(hipMalloc(&m->full, m->full_bytes ? m->full_bytes : 16));
-    if ((m->world > 1 || m->transport == RCCL) && !m->bandwise) M_HIP(hipMalloc(&m->gathered, m->slot_bytes * m->world + 16));
-    for (uint32_t q = 0; q < m->world; q++) { // rows that have to travel get a buffer on their own device
+    if (m->sparse) {
+        // one message per context, of one capacity for all (rt_assemble_sparse's stride): the tiles of the largest context
+        m->cap = ((sd->width + 15u) / 16u) * ((max_rows + 15u) / 16u);
+        m->msg_bytes = rt_sparse_msg_bytes(format, m->cap);
+        m->tile_bytes = (size_t) 256u * m->pixel_bytes;
+        m->head_bytes = m->msg_bytes - (size_t) m->cap * m->tile_bytes; // { count, overflow, 0, 0 } + ids[cap], padded to 16 bytes
+        M_HIP(hipMalloc(&m->gathered, m->msg_bytes * m->world));
+        const size_t stamp_bytes = rt_sparse_stamp_bytes(m->ctx[0]);
+        M_HIP(hipMalloc(&m->stamps, stamp_bytes ? stamp_bytes : 16));
+        M_HIP(hipHostMalloc((void **) &m->h_hdr, sizeof(uint32_t) * 4u * m->world, hipHostMallocDefault));
+        for (uint32_t q = 0; q < m->world; q++) { // messages that travel get a buffer on their own device; the others are packed into their receive slot
+            const uint32_t r = q % n;
+            const bool travels = m->transport == RCCL ? (r != 0 || m->self_exchange) : (m->transport == LOCAL_COPY && r != 0);
+            if (!travels) continue;
+            M_HIP(hipSetDevice(devices[r]));
+            M_HIP(hipMalloc(&m->msg[q], m->msg_bytes));
+        }
+        M_HIP(hipSetDevice(devices[0]));
+    }
+    if ((m->world > 1 || m->transport == RCCL) && !m->bandwise && !m->sparse) M_HIP(hipMalloc(&m->gathered, m->slot_bytes * m->world + 16));
+    for (uint32_t q = 0; q < m->world && !m->sparse; q++) { // rows that have to travel get a buffer on their own device
         const uint32_t r = q % n;
         const bool travels = m->bandwise || (m->transport == RCCL ? (r != 0 || m->self_exchange) : (m->transport == LOCAL_COPY && r != 0)); // (bandwise: the root's own rows are strided in the frame too)
         if (!travels) continue;
@@ -203,6 +242,8 @@ extern "C" int rt_create_multi(rt_multi **out, const rt_scene_desc *scene, const
     if (parts == 0) parts = 1;
     if (parts > 16) return fail(RT_ERR_INVALID, "rt_create_multi: %u parts per device (at most 16)", parts);
     if (flags & RT_FLAG_SIMPLE) return fail(RT_ERR_INVALID, "rt_create_multi: not available with RT_FLAG_SIMPLE");
+    if ((flags & RT_MULTI_SPARSE) && (flags & RT_MULTI_BANDWISE))
+        return fail(RT_ERR_INVALID, "rt_create_multi: RT_MULTI_SPARSE and RT_MULTI_BANDWISE exclude each other (tiles travel as messages, or rows band by band)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_ERR_NO_DEVICE, "rt_create_multi: no HIP device available; this library has no CPU fallback");
     for (uint32_t r = 0; r < n_devices; r++)
@@ -240,9 +281,94 @@ extern "C" int rt_render_multi(rt_multi *m, const double cam[16], void *root_ful
     } guard{m};
     M_HIP(hipSetDevice(m->dev[0]));
     if (ms) M_HIP(hipEventRecord(m->ev_t0, m->s_render[0]));
+    uint64_t sent = m->full_bytes; // the dense transports deliver every context's rows
     if (m->world == 1 && m->transport == DIRECT) { // one device, one part: the frame is this context's rows
         int rc = rt_render(m->ctx[0], cam, full, m->s_render[0], nullptr);
         if (rc != RT_OK) return rc;
+    } else if (m->sparse) {
+        // Every context renders into its own buffer (rt_render keeps the wave-per-block schedule, rt_render_sparse would not) and packs it
+        // into a message that holds all of its tiles.  All parts are enqueued first, so the devices keep rendering while the host waits for
+        // the headers; then each part's messages travel, exactly their used prefix, into the root's [world][msg_bytes] receive slots.
+        // Contexts whose rows need not travel pack straight into their slot on the root's render stream, behind the previous frame's
+        // reassembly out of it.
+        if (m->have_assembled) // the receive slots are free again once the previous frame has been reassembled out of them
+            for (uint32_t r = 0; r < n; r++)
+                if (m->transport != RCCL || r == 0) {
+                    M_HIP(hipSetDevice(m->dev[r]));
+                    M_HIP(hipStreamWaitEvent(m->s_comm[r], m->ev_assembled, 0));
+                }
+        for (uint32_t p = 0; p < P; p++)
+            for (uint32_t r = 0; r < n; r++) {
+                const uint32_t q = p * n + r;
+                M_HIP(hipSetDevice(m->dev[r]));
+                if (m->msg[q]) M_HIP(hipStreamWaitEvent(m->s_render[r], m->ev_sent[q], 0)); // the previous frame's message has left this buffer
+                void *dst = m->msg[q] ? m->msg[q] : (char *) m->gathered + (size_t) q * m->msg_bytes;
+                int rc = rt_render(m->ctx[q], cam, nullptr, m->s_render[r], nullptr);
+                if (rc == RT_OK) rc = rt_pack_sparse(m->ctx[q], nullptr, dst, m->cap, m->s_render[r]);
+                if (rc != RT_OK) return rc;
+                M_HIP(hipMemcpyAsync(m->h_hdr + 4u * q, dst, 16, hipMemcpyDeviceToHost, m->s_render[r]));
+                M_HIP(hipEventRecord(m->ev_hdr[q], m->s_render[r]));
+            }
+        sent = 0;
+        std::vector<size_t> bytes(n);
+        for (uint32_t p = 0; p < P; p++) {
+            for (uint32_t r = 0; r < n; r++) { // the host waits for this part's headers (not for the devices)
+                const uint32_t q = p * n + r;
+                M_HIP(hipEventSynchronize(m->ev_hdr[q]));
+                const uint32_t count = m->h_hdr[4u * q], overflow = m->h_hdr[4u * q + 1u];
+                if (overflow || count > m->cap) return fail(RT_ERR_DEVICE, "rt_render_multi: context %u packed %u tiles into a message of %u", q, count, m->cap);
+                bytes[r] = m->head_bytes + (size_t) count * m->tile_bytes;
+                sent += bytes[r];
+                if (m->msg[q]) {
+                    M_HIP(hipSetDevice(m->dev[r]));
+                    M_HIP(hipStreamWaitEvent(m->s_comm[r], m->ev_hdr[q], 0));
+                }
+            }
+            if (m->transport == RCCL) {
+                M_NCCL(ncclGroupStart());
+                ncclResult_t in_group = ncclSuccess; // a failure inside the group still closes it before this call returns
+                for (uint32_t r = 0; r < n && in_group == ncclSuccess; r++) {
+                    const uint32_t q = p * n + r;
+                    if (!m->msg[q]) continue;
+                    in_group = ncclSend(m->msg[q], bytes[r], ncclInt8, 0, m->comm[r], m->s_comm[r]);
+                    if (in_group == ncclSuccess)
+                        in_group = ncclRecv((char *) m->gathered + (size_t) q * m->msg_bytes, bytes[r], ncclInt8, (int) r, m->comm[0], m->s_comm[0]);
+                }
+                const ncclResult_t closed = ncclGroupEnd();
+                if (in_group != ncclSuccess) return fail(RT_ERR_DEVICE, "ncclSend / ncclRecv of part %u failed: %s", p, ncclGetErrorString(in_group));
+                M_NCCL(closed);
+            } else if (m->transport == LOCAL_COPY) {
+                for (uint32_t r = 1; r < n; r++) {
+                    const uint32_t q = p * n + r;
+                    M_HIP(hipSetDevice(m->dev[r]));
+                    M_HIP(hipMemcpyAsync((char *) m->gathered + (size_t) q * m->msg_bytes, m->msg[q], bytes[r], hipMemcpyDeviceToDevice, m->s_comm[r]));
+                }
+            }
+            for (uint32_t r = 0; r < n; r++) {
+                const uint32_t q = p * n + r;
+                if (!m->msg[q]) continue;
+                M_HIP(hipSetDevice(m->dev[r]));
+                M_HIP(hipEventRecord(m->ev_sent[q], m->s_comm[r]));
+                if (m->transport == LOCAL_COPY) { // the copy ran on the sender's comm stream: the root's comm stream waits for it
+                    M_HIP(hipSetDevice(m->dev[0]));
+                    M_HIP(hipStreamWaitEvent(m->s_comm[0], m->ev_sent[q], 0));
+                }
+            }
+        }
+        // root: everything has arrived on its comm stream (the slots packed in place are on the render stream already) -> reassemble there
+        M_HIP(hipSetDevice(m->dev[0]));
+        M_HIP(hipEventRecord(m->ev_gathered, m->s_comm[0]));
+        M_HIP(hipStreamWaitEvent(m->s_render[0], m->ev_gathered, 0));
+        int rc;
+        if (root_full_fb) {
+            rc = rt_assemble_sparse(m->ctx[0], m->gathered, m->cap, full, m->s_render[0]);
+        } else { // the object's own buffer keeps the previous frame: only tiles that lost their content are repainted
+            rc = rt_assemble_sparse_incremental(m->ctx[0], m->gathered, m->cap, full, m->stamps, m->next_tag, m->s_render[0]);
+            if (rc == RT_OK) m->next_tag = m->next_tag >= 0xFFFFFFFEu ? 1u : m->next_tag + 1u;
+        }
+        if (rc != RT_OK) return rc;
+        M_HIP(hipEventRecord(m->ev_assembled, m->s_render[0]));
+        m->have_assembled = true;
     } else if (m->bandwise) {
         // Rows go band by band straight to where they belong in the full frame ("band-wise ncclRecv straight into final row
         // offsets"): band j of context q is rows (j W + q) B ... of the frame.  No rank-major receive slots and no reassembly pass over the
@@ -367,6 +493,8 @@ extern "C" int rt_render_multi(rt_multi *m, const double cam[16], void *root_ful
         M_HIP(hipEventElapsedTime(ms, m->ev_t0, m->ev_t1));
     }
     m->last_full = full;
+    m->last_sent = sent;
+    m->last_dense = m->full_bytes;
     guard.ok = true;
     return RT_OK;
 }
@@ -393,6 +521,14 @@ extern "C" int rt_multi_download(rt_multi *m, void *host_dst, size_t bytes)
     if (!m->last_full) return fail(RT_ERR_INVALID, "rt_multi_download: no frame has been rendered yet");
     M_HIP(hipStreamSynchronize(m->s_render[0]));
     M_HIP(hipMemcpy(host_dst, m->last_full, bytes, hipMemcpyDeviceToHost)); // (the caller's own buffer when the last frame was rendered into one)
+    return RT_OK;
+}
+
+extern "C" int rt_multi_last_transfer(const rt_multi *m, uint64_t *bytes_sent, uint64_t *bytes_dense)
+{
+    if (!m) return fail(RT_ERR_INVALID, "rt_multi_last_transfer: null argument");
+    if (bytes_sent) *bytes_sent = m->last_sent;
+    if (bytes_dense) *bytes_dense = m->last_dense;
     return RT_OK;
 }
 

@@ -1944,13 +1944,18 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
             const uint32_t mslot = s_sparse[0]; // workgroup-uniform
             uint32_t *msg = reinterpret_cast<uint32_t *>(fb);
             if (mslot < fe.sparse_cap) {
-                uchar4 px;
-                px.x = (unsigned char) (int) (res.x * 255.0f + 0.5f);
-                px.y = (unsigned char) (int) (res.y * 255.0f + 0.5f);
-                px.z = (unsigned char) (int) (res.z * 255.0f + 0.5f);
-                px.w = 255;
                 const uint32_t off_tiles = (4u + fe.sparse_cap + 3u) & ~3u;
-                reinterpret_cast<uchar4 *>(msg + off_tiles)[(size_t) mslot * 256u + tile_py(tid_) * 16u + tile_px(tid_)] = px;
+                const size_t mpix = (size_t) mslot * 256u + tile_py(tid_) * 16u + tile_px(tid_);
+                if (fe.rgba8) { // launch-uniform
+                    uchar4 px;
+                    px.x = (unsigned char) (int) (res.x * 255.0f + 0.5f);
+                    px.y = (unsigned char) (int) (res.y * 255.0f + 0.5f);
+                    px.z = (unsigned char) (int) (res.z * 255.0f + 0.5f);
+                    px.w = 255;
+                    reinterpret_cast<uchar4 *>(msg + off_tiles)[mpix] = px;
+                } else { // RGBA32F message: 16-byte pixels, the tiles start 16-byte aligned (off_tiles is a multiple of 4 words)
+                    reinterpret_cast<float4 *>(msg + off_tiles)[mpix] = make_float4(res.x, res.y, res.z, 1.0f);
+                }
                 if (tid == 0) msg[4u + mslot] = tile;
             } else if (mslot != 0xFFFFFFFFu && tid == 0) {
                 msg[1] = 1u; // more tiles with hits than the message holds

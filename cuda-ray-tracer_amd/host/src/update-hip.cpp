@@ -25,6 +25,11 @@
 //                             loaded on demand so that a one-GPU host never needs librccl); default: the current device
 //   MI355RT_PARTS=n           contexts per device in that mode (overlap of transfer and rendering), default 2
 //   MI355RT_BAND_ROWS=n       rows per band in that mode, default 16
+//   MI355RT_MULTI_SELF=1      one device in MI355RT_DEVICES: send its rows to itself through RCCL (RT_MULTI_SELF_EXCHANGE)
+//   MI355RT_MULTI_BANDWISE=1  rows travel band by band straight into their place in the frame (RT_MULTI_BANDWISE)
+//   MI355RT_MULTI_SPARSE=1    only the 16x16 tiles that are not pure background travel (RT_MULTI_SPARSE; update() then waits on the host
+//                             for every context's message header); not together with MI355RT_MULTI_BANDWISE
+//                             (the MI355RT_MULTI_* switches are on when the variable is set, whatever its value)
 //   MI355RT_FORMAT=rgba8      framebuffer = iround(c*255) RGBA8, the format the reference's CUDA back end writes to its display
 //                             surface (src/update-cuda.cu:149-156); default rgba32f, the CPU back end's floats (src/update-cpu.cpp:128-131)
 namespace {
@@ -170,8 +175,11 @@ void init_update(unsigned int texture, const Scene &scene)
     const std::vector<int> devs = device_list();
     if (devs.size() > 1 || (devs.size() == 1 && std::getenv("MI355RT_MULTI_SELF"))) {
         load_multi();
+        if (std::getenv("MI355RT_MULTI_SPARSE") && std::getenv("MI355RT_MULTI_BANDWISE"))
+            die_text("init_update", "MI355RT_MULTI_SPARSE and MI355RT_MULTI_BANDWISE exclude each other (tiles travel as sparse messages, or rows band by band): set one");
         const uint32_t flags = RT_FLAG_STRICT | (std::getenv("MI355RT_MULTI_SELF") ? RT_MULTI_SELF_EXCHANGE : 0u) |
-                               (std::getenv("MI355RT_MULTI_BANDWISE") ? RT_MULTI_BANDWISE : 0u); // (rows band by band into their place in the frame: no reassembly pass)
+                               (std::getenv("MI355RT_MULTI_BANDWISE") ? RT_MULTI_BANDWISE : 0u) | // (rows band by band into their place in the frame: no reassembly pass)
+                               (std::getenv("MI355RT_MULTI_SPARSE") ? RT_MULTI_SPARSE : 0u);     // (only tiles with content travel)
         if (g_mapi.create(&g_multi, &sd, devs.data(), (uint32_t) devs.size(), env_u32("MI355RT_BAND_ROWS", 16), env_u32("MI355RT_PARTS", 2), flags, g_format) != RT_OK)
             die("init_update (MI355RT_DEVICES)");
         return;

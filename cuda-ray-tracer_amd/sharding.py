@@ -57,12 +57,13 @@ def assemble_torch(gathered, height, band_rows, world):
     return flat.index_select(0, idx)
 
 
-# ---- sparse transport (RGBA8): host-side mirror of rt_pack_sparse / rt_assemble_sparse (include/mi355rt.h) ----------
-# message = uint32 {count, overflow, 0, 0}, uint32 ids[capacity] (padded to 16 bytes), capacity x 256 RGBA8 pixels
-# (tile-major, 16 rows of 16 pixels).  Used by the CPU (gloo) tests and to cross-check the device kernels.
+# ---- sparse transport: host-side mirror of rt_pack_sparse / rt_assemble_sparse (include/mi355rt.h) --------------------
+# message = uint32 {count, overflow, 0, 0}, uint32 ids[capacity] (padded to 16 bytes), capacity x 256 pixels (tile-major, 16 rows
+# of 16 pixels).  A pixel is one uint32 word in RGBA8 and four in RGBA32F (the float bits); `bg` is the background pixel in that
+# form (bg_rgba8 / bg_rgba32f).  Used by the CPU (gloo) tests and to cross-check the device kernels.
 
-def sparse_words(capacity):
-    return ((4 + capacity + 3) & ~3) + capacity * 256
+def sparse_words(capacity, pixel_words=1):
+    return ((4 + capacity + 3) & ~3) + capacity * 256 * pixel_words
 
 
 def bg_rgba8(bg_color):
@@ -70,23 +71,37 @@ def bg_rgba8(bg_color):
     return np.uint32(r | (g << 8) | (b << 16) | (255 << 24))
 
 
-def pack_sparse_numpy(local_rgba8, local_rows, bg_word, capacity):
-    """local_rgba8: [>= local_rows, W, 4] uint8 rows of one rank.  Tiles in index order (the device appends in any order)."""
-    w = local_rgba8.shape[1]
-    px = np.ascontiguousarray(local_rgba8[:local_rows]).view(np.uint32).reshape(local_rows, w)
+def bg_rgba32f(bg_color):
+    """The RGBA32F background pixel, (bg_color, 1.0f), as 4 uint32 words."""
+    return np.array([np.float32(c) for c in bg_color] + [np.float32(1.0)], dtype=np.float32).view(np.uint32)
+
+
+def _pixel_words(bg):
+    return int(np.asarray(bg).size)
+
+
+def pack_sparse_numpy(local, local_rows, bg_word, capacity):
+    """local: [>= local_rows, W, 4] rows of one rank, uint8 (RGBA8, bg_word = bg_rgba8) or float32 (RGBA32F, bg_word = bg_rgba32f).
+    Tiles in index order (the device appends in any order)."""
+    k = _pixel_words(bg_word)
+    w = local.shape[1]
+    px = np.ascontiguousarray(local[:local_rows]).view(np.uint32).reshape(local_rows, w, k)
+    bg = np.asarray(bg_word, dtype=np.uint32).reshape(k)
     tiles_x, tiles_y = (w + 15) // 16, (local_rows + 15) // 16
-    msg = np.zeros(sparse_words(capacity), dtype=np.uint32)
+    msg = np.zeros(sparse_words(capacity, k), dtype=np.uint32)
     off = (4 + capacity + 3) & ~3
+    tile_words = 256 * k
     count = 0
     for t in range(tiles_x * tiles_y):
         tx, ty = t % tiles_x, t // tiles_x
-        tile = np.full((16, 16), bg_word, dtype=np.uint32)
+        tile = np.empty((16, 16, k), dtype=np.uint32)
+        tile[...] = bg
         blk = px[ty * 16:ty * 16 + 16, tx * 16:tx * 16 + 16]
         tile[:blk.shape[0], :blk.shape[1]] = blk
-        if np.any(tile != bg_word):
+        if np.any(tile != bg):
             if count < capacity:
                 msg[4 + count] = t
-                msg[off + count * 256: off + (count + 1) * 256] = tile.reshape(-1)
+                msg[off + count * tile_words: off + (count + 1) * tile_words] = tile.reshape(-1)
             else:
                 msg[1] = 1
             count += 1
@@ -95,20 +110,26 @@ def pack_sparse_numpy(local_rgba8, local_rows, bg_word, capacity):
 
 
 def assemble_sparse_numpy(msgs, width, height, band_rows, world, bg_word, capacity):
-    """msgs: [world, sparse_words(capacity)] uint32 in rank order -> [height, width, 4] uint8."""
-    full = np.full((height, width), bg_word, dtype=np.uint32)
+    """msgs: [world, sparse_words(capacity, k)] uint32 in rank order -> [height, width, 4] uint8 (RGBA8) or float32 (RGBA32F),
+    the format following bg_word."""
+    k = _pixel_words(bg_word)
+    full = np.empty((height, width, k), dtype=np.uint32)
+    full[...] = np.asarray(bg_word, dtype=np.uint32).reshape(k)
     tiles_x = (width + 15) // 16
     off = (4 + capacity + 3) & ~3
+    tile_words = 256 * k
     for r in range(world):
         rows = band_rows_of_rank(height, band_rows, world, r)
         for j in range(min(int(msgs[r][0]), capacity)):
             t = int(msgs[r][4 + j])
-            tile = msgs[r][off + j * 256: off + (j + 1) * 256].reshape(16, 16)
+            tile = msgs[r][off + j * tile_words: off + (j + 1) * tile_words].reshape(16, 16, k)
             tx, ty = t % tiles_x, t // tiles_x
-            for k in range(16):
-                lr = ty * 16 + k
+            for i in range(16):
+                lr = ty * 16 + i
                 if lr < len(rows):
                     x0 = tx * 16
                     n = min(16, width - x0)
-                    full[rows[lr], x0:x0 + n] = tile[k, :n]
-    return full.view(np.uint8).reshape(height, width, 4)
+                    full[rows[lr], x0:x0 + n] = tile[i, :n]
+    if k == 1:
+        return full.reshape(height, width).view(np.uint8).reshape(height, width, 4)
+    return full.view(np.float32)

@@ -208,16 +208,23 @@ int rt_download(rt_ctx *ctx, void *host_dst, size_t bytes);
  * Both are device pointers; enqueued on `stream`. */
 int rt_assemble(rt_ctx *ctx, const void *gathered, void *full, void *stream);
 
-/* Sparse transport of an RGBA8 frame (what `rt_assemble` does, with fewer bytes over the links): most 16x16 tiles of a
+/* Sparse transport of a frame (what `rt_assemble` does, with fewer bytes over the links): most 16x16 tiles of a
  * typical frame are pure background, so a rank may send only the others.  rt_pack_sparse turns this rank's rows
- * (dev_fb, or the context's own buffer if NULL) into a fixed-size message of rt_sparse_bytes(capacity_tiles) bytes:
- *   uint32 { count, overflow, 0, 0 }, uint32 ids[capacity] (padded to 16 bytes), capacity x 256 RGBA8 pixels;
- * `overflow` != 0 means more than capacity_tiles tiles had content (send the dense frame instead).  The root gathers
- * the messages ([world][rt_sparse_bytes] in rank order) and rt_assemble_sparse rebuilds [height][width] pixels.
+ * (dev_fb, or the context's own buffer if NULL) into a fixed-size message of rt_sparse_msg_bytes(format, capacity_tiles) bytes:
+ *   uint32 { count, overflow, 0, 0 }, uint32 ids[capacity] (padded to 16 bytes), capacity x 256 pixels of the context's format
+ *   (tile-major, 16 rows of 16 pixels: 1 KiB per RGBA8 tile, 4 KiB per RGBA32F tile; every tile starts 16-byte aligned);
+ * `overflow` != 0 means more than capacity_tiles tiles had content (send the dense frame instead).  A tile is background when
+ * every pixel is bit-equal to the background pixel: RGBA8 iround(bg_color * 255) with alpha 255, RGBA32F (bg_color, 1.0f) --
+ * what the render kernels store where a primary ray hits nothing.  The root gathers the messages ([world][rt_sparse_msg_bytes]
+ * in rank order) and rt_assemble_sparse rebuilds [height][width] pixels.
  * The reference has no counterpart (single GPU); the dense gather + rt_assemble stays the general path. */
-size_t rt_sparse_bytes(uint32_t capacity_tiles);
+size_t rt_sparse_bytes(uint32_t capacity_tiles); /* RGBA8 messages: rt_sparse_msg_bytes(RT_FMT_RGBA8, capacity_tiles) */
+/* Message size for a pixel format (RT_FMT_*); no context needed.  0 for an unknown format. */
+size_t rt_sparse_msg_bytes(uint32_t format, uint32_t capacity_tiles);
 /* rt_render that writes such a message directly (tiles in which a primary ray hit something; background tiles are not
- * stored anywhere): one kernel instead of render + pack, and no local framebuffer.  Arguments as rt_render. */
+ * stored anywhere): one kernel instead of render + pack, and no local framebuffer.  Arguments as rt_render.  Not with
+ * RT_FLAG_SIMPLE.  (It renders with the general schedule: scenes the wave-per-block one would take render slower this way than
+ * with rt_render + rt_pack_sparse.) */
 int rt_render_sparse(rt_ctx *ctx, const double cam[16], void *dev_msg, uint32_t capacity_tiles, void *stream, float *ms);
 int rt_pack_sparse(rt_ctx *ctx, const void *dev_fb, void *dev_msg, uint32_t capacity_tiles, void *stream);
 int rt_assemble_sparse(rt_ctx *ctx, const void *gathered_msgs, uint32_t capacity_tiles, void *full, void *stream);
@@ -258,12 +265,21 @@ int rt_destroy(rt_ctx *ctx);
  *   flags      RT_FLAG_* of every context, plus RT_MULTI_SELF_EXCHANGE
  * rt_render_multi: root_full_fb = device pointer on devices[0] receiving [height][width] pixels, or NULL for the object's
  * own buffer (rt_multi_fb); enqueue-only unless ms is given (then: device time on the root from the start of its render
- * to the end of the reassembly, transfers included).  rt_multi_stream() is the root stream the frame is complete on.
+ * to the end of the reassembly, transfers included) -- except with RT_MULTI_SPARSE, see there.  rt_multi_stream() is the root
+ * stream the frame is complete on; every write of a frame into the full frame is ordered after what the caller enqueued on it before.
  * ------------------------------------------------------------------------------------------------- */
 #define RT_MULTI_SELF_EXCHANGE 0x10000u /* one device: send its rows to itself through RCCL instead of rendering in place
                                            (exercises the RCCL path on a one-GPU box) */
 #define RT_MULTI_BANDWISE 0x20000u      /* rows travel band by band straight into their place in the full frame (one ncclSend / ncclRecv pair per band,
                                          * one strided copy per context on the root device): no rank-major receive slots, no rt_assemble pass */
+#define RT_MULTI_SPARSE 0x40000u        /* only the 16x16 tiles that are not pure background travel to the root (sparse messages, see rt_pack_sparse), in
+                                         * either format.  Every context renders with rt_render into its own buffer and packs it into a message whose
+                                         * capacity is all of its tiles (no overflow is possible); the root copies each message's 16-byte header to the
+                                         * host, and only the used prefix (header, id array, count x tile bytes) travels.  rt_render_multi therefore
+                                         * BLOCKS the calling thread until every context's header of this frame has reached the host (a wait for the
+                                         * renders and packs, not for the whole frame).  The root rebuilds the frame on rt_multi_stream(): incrementally
+                                         * (stamps owned by the object) into the object's own buffer, with a full fill + scatter into a caller's buffer.
+                                         * Not together with RT_MULTI_BANDWISE. */
 typedef struct rt_multi rt_multi;
 int rt_create_multi(rt_multi **out, const rt_scene_desc *scene, const int *devices, uint32_t n_devices, uint32_t band_rows, uint32_t parts,
                     uint32_t flags, uint32_t format);
@@ -273,6 +289,10 @@ void *rt_multi_fb(rt_multi *m);                       /* the object's own full-f
 void *rt_multi_stream(rt_multi *m);                   /* hipStream_t on devices[0] */
 int rt_multi_download(rt_multi *m, void *host_dst, size_t bytes);
 int rt_multi_info(const rt_multi *m, uint32_t *n_contexts, uint32_t *transport /* 0 in place, 1 device copies, 2 RCCL */);
+/* Bytes of the last frame: bytes_sent = what the contexts delivered to the root's reassembly (RT_MULTI_SPARSE: the sum of the used
+ * message prefixes, counted from the headers; the dense transports: every context's rows), bytes_dense = what the dense transport
+ * delivers (height x width pixels).  Either pointer may be NULL.  0 / 0 before the first frame. */
+int rt_multi_last_transfer(const rt_multi *m, uint64_t *bytes_sent, uint64_t *bytes_dense);
 int rt_multi_destroy(rt_multi *m);
 
 #ifdef __cplusplus
