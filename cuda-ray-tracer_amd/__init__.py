@@ -23,6 +23,7 @@ RT_NCOEF = 20
 RT_FLAG_STRICT, RT_FLAG_FAST, RT_FLAG_COUNT, RT_FLAG_SIMPLE, RT_FLAG_NOCULL, RT_FLAG_STATIC_ORDER, RT_FLAG_NOSCAN, RT_FLAG_PLAIN_ORDER = 0, 1, 2, 4, 8, 16, 32, 64
 RT_FLAG_NOSPLIT = 128
 RT_FLAG_NOLEAN = 256
+RT_FLAG_SSAA2, RT_FLAG_SSAA4 = 512, 1024   # k x k supersampling with an exact box-filter resolve (include/mi355rt.h)
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
 
@@ -320,14 +321,20 @@ class Renderer:
         h = C.c_void_p()
         _check(lib().rt_create(C.byref(h), C.byref(d), C.byref(cfg)))
         self._h = h
-        self.width, self.height = d.width, d.height
+        self.width, self.height = d.width, d.height   # the output frame (with supersampling too)
         self.fmt = fmt
+        self.flags = int(flags)
         n = C.c_uint32()
         _check(lib().rt_local_rows(self._h, C.byref(n)))
         self.local_rows = n.value
         _check(lib().rt_max_local_rows(self._h, C.byref(n)))
         self.max_local_rows = n.value
         self.pixel_bytes = lib().rt_pixel_bytes(self._h)
+
+    @property
+    def samples(self):
+        """Supersampling factor k per axis: 1, 2 (RT_FLAG_SSAA2) or 4 (RT_FLAG_SSAA4)."""
+        return 4 if self.flags & RT_FLAG_SSAA4 else (2 if self.flags & RT_FLAG_SSAA2 else 1)
 
     # init_update is the constructor; these two complete the reference's trio
     def update(self, cam=None, dev_fb=None, stream=None, timed=True):
@@ -361,7 +368,8 @@ class Renderer:
         return lib().rt_device_fb(self._h)
 
     def download(self):
-        """Local rows as numpy: float32 [rows, W, 4] (RGBA32F) or uint8 [rows, W, 4] (RGBA8)."""
+        """Local rows of the output frame as numpy: float32 [rows, W, 4] (RGBA32F) or uint8 [rows, W, 4] (RGBA8); with supersampling
+        the resolved pixels, not the samples."""
         dt = np.uint8 if self.fmt == RT_FMT_RGBA8 else np.float32
         out = np.empty((self.local_rows, self.width, 4), dtype=dt)
         if out.size:

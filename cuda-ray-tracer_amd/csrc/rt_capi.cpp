@@ -32,6 +32,8 @@ extern "C" hipError_t rt_launch_assemble_strict(const void *, void *, uint32_t, 
 extern "C" hipError_t rt_launch_pack_sparse_strict(const void *, void *, uint32_t, uint32_t, const uint32_t *, uint32_t, int, hipStream_t);
 extern "C" hipError_t rt_launch_assemble_sparse_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, uint32_t, void *, uint32_t,
                                                        uint32_t, int, hipStream_t);
+// supersampling resolve (rt_resolve.hip, built once without FMA contraction)
+extern "C" hipError_t rt_launch_resolve(const void *, void *, uint32_t, uint32_t, uint32_t, int, int, hipStream_t);
 
 namespace {
 
@@ -93,10 +95,15 @@ struct rt_scene {
 
 struct rt_ctx {
     int device = 0;
-    rt_config cfg{};
-    FrameArgs fa{};
+    rt_config cfg{};   // as the caller passed it (defaults filled in): the OUTPUT frame's bands and format
+    FrameArgs fa{};    // what the render kernels draw: the output frame, or with supersampling the internal k x finer RGBA32F frame
+    // output frame (what every entry point but the render kernels sees; the same as fa's geometry without supersampling)
+    uint32_t width = 0, height = 0;
     uint32_t local_rows = 0, max_local_rows = 0;
     size_t pixel_bytes = 16;
+    uint32_t ssaa = 1;          // samples per axis k (RT_FLAG_SSAA2 / RT_FLAG_SSAA4)
+    void *d_ss = nullptr;       // k > 1: the internal frame's local rows, [k * local_rows][k * width] float4
+    int resolve_nt = 0;         // the resolve reads the internal frame with non-temporal loads (MI355RT_RESOLVE_NT, experiments)
     DevObject *d_obj = nullptr;
     DevLight *d_light = nullptr;
     void *d_fb = nullptr;
@@ -337,7 +344,12 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if (cfg.band_rows == 0) cfg.band_rows = 8;
     if (cfg.rank >= cfg.world) return fail(RT_ERR_INVALID, "rt_create: rank %u >= world %u", cfg.rank, cfg.world);
     if (cfg.format > RT_FMT_RGBA8) return fail(RT_ERR_INVALID, "rt_create: unknown format %u", cfg.format);
+    if ((cfg.flags & RT_FLAG_SSAA2) && (cfg.flags & RT_FLAG_SSAA4))
+        return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA2 and RT_FLAG_SSAA4 exclude each other");
+    const uint32_t k = (cfg.flags & RT_FLAG_SSAA4) ? 4u : ((cfg.flags & RT_FLAG_SSAA2) ? 2u : 1u);
     if (sd->width == 0 || sd->height == 0) return fail(RT_ERR_INVALID, "rt_create: empty image %ux%u", sd->width, sd->height);
+    if (k > 1u && ((uint64_t) k * sd->width > 65536u || (uint64_t) k * sd->height > 65536u))
+        return fail(RT_ERR_INVALID, "rt_create: %ux%u supersampled %ux%u exceeds 65536 samples per axis", sd->width, sd->height, k, k);
     if ((sd->n_objects && (!sd->coefs || !sd->reflection || !sd->albedo)) ||
         (sd->n_lights && (!sd->light_is_spherical || !sd->light_p || !sd->light_color)))
         return fail(RT_ERR_INVALID, "rt_create: null scene array");
@@ -362,6 +374,10 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if (!ctx) return fail(RT_ERR_NOMEM, "out of memory");
     ctx->device = device;
     ctx->cfg = cfg;
+    ctx->width = sd->width;
+    ctx->height = sd->height;
+    ctx->ssaa = k;
+    if (const char *e = std::getenv("MI355RT_RESOLVE_NT")) ctx->resolve_nt = std::atoi(e) != 0; // (experiments)
     ctx->pixel_bytes = cfg.format == RT_FMT_RGBA8 ? 4 : 16;
     ctx->local_rows = rows_of_rank(sd->height, cfg.band_rows, cfg.world, cfg.rank);
     for (uint32_t r = 0; r < cfg.world; r++) {
@@ -369,26 +385,29 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         if (n > ctx->max_local_rows) ctx->max_local_rows = n;
     }
 
+    // the frame the kernels render: with supersampling the unmodified scene at k times the size, into RGBA32F (k is a power of two, so
+    // the aspect ratio is the same double; bands of k * band_rows rows keep each output row's samples with the rank that owns it)
+    const uint32_t rw = k * sd->width, rh = k * sd->height;
     FrameArgs &fa = ctx->fa;
     std::memset(&fa, 0, sizeof(fa));
-    fa.aspect = (double) sd->width / sd->height;       // Scene::aspect_ratio, include/scene.h:32-33
+    fa.aspect = (double) rw / rh;                      // Scene::aspect_ratio, include/scene.h:32-33
     fa.tan_half_fov = std::tan(0.5 * sd->vertical_fov); // init_update, src/update-cpu.cpp:28
     fa.bg[0] = sd->bg_color[0];
     fa.bg[1] = sd->bg_color[1];
     fa.bg[2] = sd->bg_color[2];
     fa.bg[3] = 1.0f;
-    fa.width = sd->width;
-    fa.height = sd->height;
+    fa.width = rw;
+    fa.height = rh;
     fa.n_obj = sd->n_objects;
     fa.n_lights = sd->n_lights;
     fa.max_refl = sd->max_reflections;
     fa.rank = cfg.rank;
     fa.world = cfg.world;
-    fa.band_rows = cfg.band_rows;
-    fa.local_rows = ctx->local_rows;
-    fa.tiles_x = (sd->width + RT_TILE - 1) / RT_TILE;
-    fa.n_tiles = fa.tiles_x * ((ctx->local_rows + RT_TILE - 1) / RT_TILE);
-    fa.rgba8 = cfg.format == RT_FMT_RGBA8 ? 1u : 0u;
+    fa.band_rows = k * cfg.band_rows;
+    fa.local_rows = k * ctx->local_rows; // (= rows_of_rank(rh, k * band_rows, world, rank))
+    fa.tiles_x = (rw + RT_TILE - 1) / RT_TILE;
+    fa.n_tiles = fa.tiles_x * ((fa.local_rows + RT_TILE - 1) / RT_TILE);
+    fa.rgba8 = (k == 1u && cfg.format == RT_FMT_RGBA8) ? 1u : 0u;
     fa.ord_plain = (cfg.flags & RT_FLAG_PLAIN_ORDER) ? 1u : 0u;
     ctx->ord_split = (cfg.flags & RT_FLAG_NOSPLIT) ? 0u : RT_ORD_SPLIT_CLASSES;
     if (const char *e = std::getenv("MI355RT_SPLIT_CLASSES")) ctx->ord_split = (uint32_t) std::atoi(e) & 15u; // (experiments)
@@ -571,25 +590,26 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light, lights.data(), sizeof(DevLight) * lights.size(), hipMemcpyHostToDevice), "hipMemcpy(lights)") &&
         hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light + lights.size(), lightk.data(), sizeof(LightK) * lightk.size(), hipMemcpyHostToDevice), "hipMemcpy(light table)") &&
         hip_ok(hipEventCreate(&ctx->ev0), "hipEventCreate") && hip_ok(hipEventCreate(&ctx->ev1), "hipEventCreate") &&
-        hip_ok(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming), "hipEventCreate");
+        hip_ok(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming), "hipEventCreate") &&
+        hip_ok(k == 1u ? hipSuccess : hipMalloc(&ctx->d_ss, (size_t) (fa.local_rows ? fa.local_rows : 1) * rw * 16u), "hipMalloc(supersampled frame)");
     if (rc != RT_OK) return rc;
     {
         // camera-plane coordinates of every pixel column / row: render_pixel's camera_x / camera_y
         // (src/update-cpu.cpp:84-87) depend only on the pixel index and the scene, so they are evaluated here once,
         // with the same IEEE operations in the same order (this file is compiled with -ffp-contract=off)
-        std::vector<double> cx(sd->width), cy(sd->height);
-        for (uint32_t x = 0; x < sd->width; x++) {
-            const double ndc_x = ((int) x + 0.5) / (int) sd->width;
+        std::vector<double> cx(rw), cy(rh);
+        for (uint32_t x = 0; x < rw; x++) {
+            const double ndc_x = ((int) x + 0.5) / (int) rw;
             cx[x] = (2.0 * ndc_x - 1.0) * fa.aspect * fa.tan_half_fov;
         }
-        for (uint32_t y = 0; y < sd->height; y++) {
-            const double ndc_y = ((int) y + 0.5) / (int) sd->height;
+        for (uint32_t y = 0; y < rh; y++) {
+            const double ndc_y = ((int) y + 0.5) / (int) rh;
             cy[y] = (2.0 * ndc_y - 1.0) * fa.tan_half_fov;
         }
-        hip_ok(hipMalloc((void **) &ctx->d_camx, sizeof(double) * sd->width), "hipMalloc(camx)") &&
-            hip_ok(hipMalloc((void **) &ctx->d_camy, sizeof(double) * sd->height), "hipMalloc(camy)") &&
-            hip_ok(hipMemcpy(ctx->d_camx, cx.data(), sizeof(double) * sd->width, hipMemcpyHostToDevice), "hipMemcpy(camx)") &&
-            hip_ok(hipMemcpy(ctx->d_camy, cy.data(), sizeof(double) * sd->height, hipMemcpyHostToDevice), "hipMemcpy(camy)");
+        hip_ok(hipMalloc((void **) &ctx->d_camx, sizeof(double) * rw), "hipMalloc(camx)") &&
+            hip_ok(hipMalloc((void **) &ctx->d_camy, sizeof(double) * rh), "hipMalloc(camy)") &&
+            hip_ok(hipMemcpy(ctx->d_camx, cx.data(), sizeof(double) * rw, hipMemcpyHostToDevice), "hipMemcpy(camx)") &&
+            hip_ok(hipMemcpy(ctx->d_camy, cy.data(), sizeof(double) * rh, hipMemcpyHostToDevice), "hipMemcpy(camy)");
         if (rc == RT_OK && !(cfg.flags & (RT_FLAG_SIMPLE | RT_FLAG_STATIC_ORDER)) && fa.n_tiles > 0 && fa.n_tiles <= RT_ORD_MAX_TILES) {
             // launch-order feedback: three generations, all empty (first frame = index order)
             fa.ord_stride = (RT_ORD_HDR + 17u * fa.n_tiles + 15u) & ~15u;
@@ -630,12 +650,39 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     return RT_OK;
 }
 
+// background colour as the RGBA8 kernels store it (iround(c * 255), alpha 255), little-endian r | g << 8 | b << 16 | a << 24
+static uint32_t bg_rgba8(const FrameArgs &fa)
+{
+    const uint32_t r = (uint32_t) (unsigned char) (int) (fa.bg[0] * 255.0f + 0.5f), g = (uint32_t) (unsigned char) (int) (fa.bg[1] * 255.0f + 0.5f),
+                   b = (uint32_t) (unsigned char) (int) (fa.bg[2] * 255.0f + 0.5f);
+    return r | (g << 8) | (b << 16) | (255u << 24);
+}
+
+// the background pixel of the context's format as four words (what the sparse kernels compare with and paint): RGBA8 in word 0,
+// RGBA32F the bits of (bg_color, 1.0f) -- what the render kernels store for a pixel without hits
+struct BgPixel {
+    uint32_t w[4];
+};
+static BgPixel bg_pixel(const rt_ctx *ctx)
+{
+    BgPixel p{};
+    if (ctx->cfg.format == RT_FMT_RGBA8) {
+        p.w[0] = bg_rgba8(ctx->fa);
+    } else {
+        const float f[4] = {ctx->fa.bg[0], ctx->fa.bg[1], ctx->fa.bg[2], 1.0f};
+        std::memcpy(p.w, f, sizeof(f));
+    }
+    return p;
+}
+
 static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *stream_, float *ms, bool sparse, uint32_t sparse_cap)
 {
     hipStream_t stream = (hipStream_t) stream_;
     FrameArgs &fa = ctx->fa;
-    fa.sparse = sparse ? 1u : 0u;
-    fa.sparse_cap = sparse ? sparse_cap : 0u;
+    const bool ss = ctx->ssaa > 1u; // supersampled: render the internal frame densely, resolve, and (sparse) pack the resolved rows
+    const bool kernel_sparse = sparse && !ss;
+    fa.sparse = kernel_sparse ? 1u : 0u;
+    fa.sparse_cap = kernel_sparse ? sparse_cap : 0u;
     // Which instantiation renders a scene of unit spheres?  The wave-per-block one ("lean") executes a quarter fewer instructions per
     // frame and wins wherever the GPU is full (4K 120 -> 91 us, 8K 425 -> 306, the 1080p start pose 44 -> 38).  The general one splits
     // costly tiles over two workgroups and every tile's lights over its four waves, which is what counts while few tiles have hits and
@@ -652,7 +699,7 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     if (debug_order && ctx->h_listed)
         std::fprintf(stderr, "mi355rt: frame %llu: tiles with hits %u, list slots wanted %u, census %u, schedule %s\n", (unsigned long long) ctx->frame, ((volatile uint32_t *) ctx->h_listed)[2],
                      ((volatile uint32_t *) ctx->h_listed)[0], ((volatile uint32_t *) ctx->h_listed)[1], ctx->lean_now ? "lean" : "general");
-    fa.lean = (ctx->lean_ok && ctx->lean_now && !sparse) ? 1u : 0u;
+    fa.lean = (ctx->lean_ok && ctx->lean_now && !kernel_sparse) ? 1u : 0u;
     std::memcpy(fa.cam, cam, sizeof(double) * 16);
     // g_ray_origin = camera_matrix * (0,0,0,1), src/update-cpu.cpp:123 -- glm order (m0*x + m1*y) + (m2*z + m3*w)
     for (int r = 0; r < 3; r++) fa.origin[r] = (cam[0 + r] * 0.0 + cam[4 + r] * 0.0) + (cam[8 + r] * 0.0 + cam[12 + r] * 1.0);
@@ -700,10 +747,12 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
                                         "ordered on the device, and a capture cannot be ordered against another stream through an event)");
         RT_HIP(hipStreamWaitEvent(stream, ctx->ev_done, 0));
     }
-    void *fb = dev_fb ? dev_fb : ctx->d_fb;
-    if (sparse) RT_HIP(hipMemsetAsync(fb, 0, 16, stream)); // message header: count, overflow
+    // out: where the frame ends up (a message for sparse calls); fb: what the render kernels write
+    void *out = dev_fb ? dev_fb : ctx->d_fb;
+    void *fb = ss ? ctx->d_ss : out;
+    if (kernel_sparse) RT_HIP(hipMemsetAsync(fb, 0, 16, stream)); // message header: count, overflow
     const int count = (ctx->cfg.flags & RT_FLAG_COUNT) ? 1 : 0;
-    const int rgba8 = ctx->cfg.format == RT_FMT_RGBA8;
+    const int rgba8 = fa.rgba8 != 0u;
     if (count || ctx->zero_counters) {
         RT_HIP(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * 28, stream)); // (word 31 holds the stamp rows' address)
         RT_HIP(hipMemsetAsync(ctx->d_counters + 32, 0, sizeof(unsigned long long) * 32, stream));
@@ -768,6 +817,15 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         e = fast ? rt_launch_wavefront_fast(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream)
                  : rt_launch_wavefront_strict(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    if (ss) {
+        // the next frame's render overwrites the internal frame this reads, so the ordering event below is recorded behind it
+        const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
+        RT_HIP(rt_launch_resolve(ctx->d_ss, sparse ? ctx->d_fb : out, ctx->width, ctx->local_rows, ctx->ssaa, out8, ctx->resolve_nt, stream));
+        if (sparse) {
+            const BgPixel bg = bg_pixel(ctx);
+            RT_HIP(rt_launch_pack_sparse_strict(ctx->d_fb, dev_fb, ctx->width, ctx->local_rows, bg.w, sparse_cap, out8, stream));
+        }
+    }
     ctx->counted = count != 0;
     if (!capturing) RT_HIP(hipEventRecord(ctx->ev_done, stream));
     ctx->captured = capturing;
@@ -826,7 +884,7 @@ extern "C" void *rt_device_fb(rt_ctx *ctx) { return ctx ? ctx->d_fb : nullptr; }
 extern "C" int rt_download(rt_ctx *ctx, void *host_dst, size_t bytes)
 {
     if (!ctx || !host_dst) return fail(RT_ERR_INVALID, "rt_download: null argument");
-    const size_t have = (size_t) ctx->local_rows * ctx->fa.width * ctx->pixel_bytes;
+    const size_t have = (size_t) ctx->local_rows * ctx->width * ctx->pixel_bytes;
     if (bytes > have) return fail(RT_ERR_INVALID, "rt_download: %zu bytes requested, framebuffer holds %zu", bytes, have);
     RT_HIP(hipSetDevice(ctx->device));
     RT_HIP(hipDeviceSynchronize());
@@ -837,35 +895,10 @@ extern "C" int rt_download(rt_ctx *ctx, void *host_dst, size_t bytes)
 extern "C" int rt_assemble(rt_ctx *ctx, const void *gathered, void *full, void *stream)
 {
     if (!ctx || !gathered || !full) return fail(RT_ERR_INVALID, "rt_assemble: null argument");
-    hipError_t e = rt_launch_assemble_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows,
+    hipError_t e = rt_launch_assemble_strict(gathered, full, ctx->width, ctx->height, ctx->cfg.world, ctx->cfg.band_rows,
                                              ctx->max_local_rows, ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "assemble launch failed: %s", hipGetErrorString(e));
     return RT_OK;
-}
-
-// background colour as the RGBA8 kernels store it (iround(c * 255), alpha 255), little-endian r | g << 8 | b << 16 | a << 24
-static uint32_t bg_rgba8(const FrameArgs &fa)
-{
-    const uint32_t r = (uint32_t) (unsigned char) (int) (fa.bg[0] * 255.0f + 0.5f), g = (uint32_t) (unsigned char) (int) (fa.bg[1] * 255.0f + 0.5f),
-                   b = (uint32_t) (unsigned char) (int) (fa.bg[2] * 255.0f + 0.5f);
-    return r | (g << 8) | (b << 16) | (255u << 24);
-}
-
-// the background pixel of the context's format as four words (what the sparse kernels compare with and paint): RGBA8 in word 0,
-// RGBA32F the bits of (bg_color, 1.0f) -- what the render kernels store for a pixel without hits
-struct BgPixel {
-    uint32_t w[4];
-};
-static BgPixel bg_pixel(const rt_ctx *ctx)
-{
-    BgPixel p{};
-    if (ctx->cfg.format == RT_FMT_RGBA8) {
-        p.w[0] = bg_rgba8(ctx->fa);
-    } else {
-        const float f[4] = {ctx->fa.bg[0], ctx->fa.bg[1], ctx->fa.bg[2], 1.0f};
-        std::memcpy(p.w, f, sizeof(f));
-    }
-    return p;
 }
 
 extern "C" size_t rt_sparse_bytes(uint32_t capacity_tiles)
@@ -884,7 +917,7 @@ extern "C" int rt_pack_sparse(rt_ctx *ctx, const void *dev_fb, void *dev_msg, ui
 {
     if (!ctx || !dev_msg) return fail(RT_ERR_INVALID, "rt_pack_sparse: null argument");
     const BgPixel bg = bg_pixel(ctx);
-    hipError_t e = rt_launch_pack_sparse_strict(dev_fb ? dev_fb : ctx->d_fb, dev_msg, ctx->fa.width, ctx->local_rows, bg.w, capacity_tiles,
+    hipError_t e = rt_launch_pack_sparse_strict(dev_fb ? dev_fb : ctx->d_fb, dev_msg, ctx->width, ctx->local_rows, bg.w, capacity_tiles,
                                                 ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pack launch failed: %s", hipGetErrorString(e));
     return RT_OK;
@@ -894,7 +927,7 @@ extern "C" int rt_assemble_sparse(rt_ctx *ctx, const void *gathered, uint32_t ca
 {
     if (!ctx || !gathered || !full) return fail(RT_ERR_INVALID, "rt_assemble_sparse: null argument");
     const BgPixel bg = bg_pixel(ctx);
-    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
+    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->width, ctx->height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
                                                     nullptr, 0, 0, ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "sparse assemble launch failed: %s", hipGetErrorString(e));
     return RT_OK;
@@ -903,7 +936,7 @@ extern "C" int rt_assemble_sparse(rt_ctx *ctx, const void *gathered, uint32_t ca
 extern "C" size_t rt_sparse_stamp_bytes(rt_ctx *ctx)
 {
     if (!ctx) return 0;
-    const size_t max_tiles = (size_t) ((ctx->fa.width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
+    const size_t max_tiles = (size_t) ((ctx->width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
     return sizeof(uint32_t) * (size_t) ctx->cfg.world * max_tiles;
 }
 
@@ -911,9 +944,9 @@ extern "C" int rt_assemble_sparse_incremental(rt_ctx *ctx, const void *gathered,
                                               void *stream)
 {
     if (!ctx || !gathered || !full || !stamps) return fail(RT_ERR_INVALID, "rt_assemble_sparse_incremental: null argument");
-    const uint32_t max_tiles = ((ctx->fa.width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
+    const uint32_t max_tiles = ((ctx->width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
     const BgPixel bg = bg_pixel(ctx);
-    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->fa.width, ctx->fa.height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
+    hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->width, ctx->height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
                                                     stamps, max_tiles, frame_tag, ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "sparse assemble launch failed: %s", hipGetErrorString(e));
     return RT_OK;
@@ -994,6 +1027,7 @@ extern "C" int rt_destroy(rt_ctx *ctx)
     if (ctx->d_obj) (void) hipFree(ctx->d_obj);
     if (ctx->d_light) (void) hipFree(ctx->d_light);
     if (ctx->d_fb) (void) hipFree(ctx->d_fb);
+    if (ctx->d_ss) (void) hipFree(ctx->d_ss);
     if (ctx->d_counters) (void) hipFree(ctx->d_counters);
     if (ctx->d_stamps) (void) hipFree(ctx->d_stamps);
     if (ctx->d_camx) (void) hipFree(ctx->d_camx);

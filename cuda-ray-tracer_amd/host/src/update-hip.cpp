@@ -32,6 +32,8 @@
 //                             (the MI355RT_MULTI_* switches are on when the variable is set, whatever its value)
 //   MI355RT_FORMAT=rgba8      framebuffer = iround(c*255) RGBA8, the format the reference's CUDA back end writes to its display
 //                             surface (src/update-cuda.cu:149-156); default rgba32f, the CPU back end's floats (src/update-cpu.cpp:128-131)
+//   MI355RT_SSAA=2|4          supersampling, k x k rays per pixel box-filtered into the frame (RT_FLAG_SSAA2 / RT_FLAG_SSAA4, include/mi355rt.h),
+//                             one GPU or several; default: one ray per pixel
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -136,6 +138,12 @@ void init_update(unsigned int texture, const Scene &scene)
         if (!std::strcmp(f, "rgba8")) g_format = RT_FMT_RGBA8;
         else if (std::strcmp(f, "rgba32f") && *f) die_text("MI355RT_FORMAT", "expected rgba32f or rgba8");
     }
+    uint32_t ssaa = 0;
+    if (const char *f = std::getenv("MI355RT_SSAA")) {
+        if (!std::strcmp(f, "2")) ssaa = RT_FLAG_SSAA2;
+        else if (!std::strcmp(f, "4")) ssaa = RT_FLAG_SSAA4;
+        else if (*f) die_text("MI355RT_SSAA", "expected 2 or 4");
+    }
 
     // flatten the Scene into the ABI's descriptor (arrays are borrowed only for the call)
     const size_t no = scene.objects.size(), nl = scene.lights.size();
@@ -177,7 +185,7 @@ void init_update(unsigned int texture, const Scene &scene)
         load_multi();
         if (std::getenv("MI355RT_MULTI_SPARSE") && std::getenv("MI355RT_MULTI_BANDWISE"))
             die_text("init_update", "MI355RT_MULTI_SPARSE and MI355RT_MULTI_BANDWISE exclude each other (tiles travel as sparse messages, or rows band by band): set one");
-        const uint32_t flags = RT_FLAG_STRICT | (std::getenv("MI355RT_MULTI_SELF") ? RT_MULTI_SELF_EXCHANGE : 0u) |
+        const uint32_t flags = RT_FLAG_STRICT | ssaa | (std::getenv("MI355RT_MULTI_SELF") ? RT_MULTI_SELF_EXCHANGE : 0u) |
                                (std::getenv("MI355RT_MULTI_BANDWISE") ? RT_MULTI_BANDWISE : 0u) | // (rows band by band into their place in the frame: no reassembly pass)
                                (std::getenv("MI355RT_MULTI_SPARSE") ? RT_MULTI_SPARSE : 0u);     // (only tiles with content travel)
         if (g_mapi.create(&g_multi, &sd, devs.data(), (uint32_t) devs.size(), env_u32("MI355RT_BAND_ROWS", 16), env_u32("MI355RT_PARTS", 2), flags, g_format) != RT_OK)
@@ -187,7 +195,7 @@ void init_update(unsigned int texture, const Scene &scene)
     rt_config cfg{};
     cfg.device = devs.empty() ? -1 : devs[0];
     cfg.world = 1;
-    cfg.flags = RT_FLAG_STRICT;
+    cfg.flags = RT_FLAG_STRICT | ssaa;
     cfg.format = g_format;
     if (rt_create(&g_ctx, &sd, &cfg) != RT_OK) die("init_update");
 }

@@ -81,6 +81,26 @@ typedef struct rt_scene_desc {
 #define RT_FLAG_NOLEAN 256u    /* wavefront kernel: scenes of unit spheres without mirrors are rendered by the general instantiation (hit queue per
                                * tile) instead of the wave-per-block one; same results, for A/B runs and as a cross-check */
 
+/* Supersampling: k x k rays per output pixel (k = 2 or 4; at most one of the two flags).  The context renders the unmodified scene at
+ * (k*width) x (k*height) into an internal RGBA32F frame S with the usual kernels -- sample (X, Y) of S is exactly the reference's pixel
+ * (X, Y) at that size (aspect and tan(fov/2) do not change) -- and a resolve kernel box-filters it: sub-pixel (i, j) of output pixel
+ * (x, y) is S[k*y + j][k*x + i] (row 0 = bottom); per channel, in FP32 without FMA contraction, every sub-row is summed as a pairwise
+ * tree over i (k = 2: s0 + s1; k = 4: (s0 + s1) + (s2 + s3)), the sub-row sums by the same tree over j, the result multiplied by 1/k^2
+ * (exact), alpha 1.0f.  RGBA8 quantises the average as the render kernels do, (unsigned char)(int)(v * 255.0f + 0.5f), alpha 255.  A
+ * pixel whose samples are all equal resolves to exactly that value (a pure background pixel stays bit-equal to the background).
+ * The resolve is the same in every variant (RT_FLAG_FAST included); the flags combine with every other RT_FLAG_*.  rt_create refuses
+ * (RT_ERR_INVALID) both flags together and k*width or k*height above 65536, before it looks for a device.
+ * Everything the caller sees describes the OUTPUT frame: rt_local_rows, rt_max_local_rows, rt_row_map, rt_pixel_bytes, rt_device_fb,
+ * rt_download, rt_assemble, rt_pack_sparse, rt_assemble_sparse[_incremental], rt_sparse_stamp_bytes; bands are band_rows output rows
+ * (the internal frame uses k*band_rows internal rows per band, so output band b comes from internal band b and row ownership does
+ * not change).  rt_render renders into the internal buffer (k^2 * width * local_rows * 16 bytes, allocated by rt_create) and resolves
+ * into dev_fb or the context's own buffer, both kernels on `stream`; `ms` covers both, the ordering event is recorded behind the
+ * resolve, and a frame can be captured into a graph as before (two kernels per frame).  rt_render_sparse renders, resolves into the
+ * context's own buffer and packs it with rt_pack_sparse: the message holds the same tiles as rt_render + rt_pack_sparse.
+ * RT_FLAG_COUNT counts the rays actually traced: primary_rays = k^2 * width * height. */
+#define RT_FLAG_SSAA2 512u
+#define RT_FLAG_SSAA4 1024u
+
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
                                  produces (src/update-cpu.cpp:128-131) plus an alpha lane for 16-byte stores */
