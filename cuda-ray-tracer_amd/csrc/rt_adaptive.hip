@@ -1,0 +1,369 @@
+// rt_adaptive.hip -- edge-adaptive supersampling for gfx950 (include/mi355rt.h, RT_FLAG_SSAA_ADAPTIVE).
+//
+// A frame is: the plain pass P (the usual render kernels, one ray per pixel, RGBA32F), then with several ranks the halo rows
+// (ray_list_kernel<1>: the centre rays of the rows just outside each band), then classify_kernel (which pixels see contrast in
+// their 3x3 neighbourhood: those go to a device list, the others are written out at once), then ray_list_kernel<k> (k x k sample
+// rays per listed pixel, reduced across lanes with the resolve's pairwise tree).  Compiled twice like rt_kernels.hip
+// (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast): the ray kernel shares the simple kernel's
+// shading (rt_shade.hpp).  The resolve's arithmetic -- the sums, 1/k^2 and the RGBA8 quantisation -- uses explicitly rounded
+// operations, so it is the same in both builds and equal to rt_resolve.hip's.
+#include <hip/hip_runtime.h>
+
+#include "rt_shade.hpp"
+#include "rt_wavefront_math.hpp" // Ball, sphere_relevant: the wavefront kernel's conservative shadow culling
+
+namespace RT_SYM(rtk) {
+
+constexpr uint32_t WAVES = 4; // waves per workgroup of the ray kernel
+
+__device__ __forceinline__ double wave_min(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = fmin(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = fmax(v, __shfl_xor(v, m));
+    return v;
+}
+
+// render_ray (rt_shade.hpp) for a wave whose lanes trace nearby rays, with the wavefront kernel's exact shadow culling: after each
+// round of nearest hits the wave forms one ball around its lanes' hit points (Ball, rt_wavefront_math.hpp: box centre, half
+// diagonal plus the 1e-2 shadow bias) and, per light, one wave-wide verdict per object (sphere_relevant, one object per lane); only
+// objects that could block some lane's shadow ray are tested.  A culled object cannot block (that is the culling's contract), so
+// every lane's in_shadow -- and with it every colour -- is what render_ray computes.  Lanes stay resident (a `live` flag instead of
+// break) so that the reductions run on the whole wave.  scull[j] = object j's culling entry (r = +inf: always tested).
+template <bool COUNT>
+__device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevObject *__restrict__ gobj, const DevLight *__restrict__ glight,
+                                                const DevObject *sobj, const UsEntry *scull, const D3 &origin, D3 dir, bool live, Cnt<COUNT> &cnt)
+{
+    const F3 bg{fa.bg[0], fa.bg[1], fa.bg[2]};
+    const uint32_t lane = threadIdx.x & 63u;
+    F3 res = bg;
+    D3 o = origin;
+    float cur_ratio = 1.0f;
+    uint32_t n_refl = 0;
+    bool first = true;
+    while (__ballot(live)) { // wave-uniform
+        // nearest hit: get_color_and_object, src/update-cpu.cpp:45-60 (the loop of trace(), rt_shade.hpp)
+        int best = -1;
+        double best_t = INFINITY;
+        if (live) {
+            Mono m;
+            make_mono(m, o, dir);
+            for (uint32_t k = 0; k < fa.n_obj; k++) {
+                double t = intersect(gobj[k].c, gobj[k].cls, m, MAX_T, false);
+                cnt.test();
+                if (t >= EPS && t < MAX_T && t < best_t) {
+                    best_t = t;
+                    best = (int) k;
+                }
+            }
+        }
+        const bool hit = best >= 0;
+        D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0}, so{0.0, 0.0, 0.0};
+        F3 albedo{0.0f, 0.0f, 0.0f};
+        if (hit) {
+            cnt.hit();
+            sp = D3{o.x + best_t * dir.x, o.y + best_t * dir.y, o.z + best_t * dir.z};
+            const DevObject *bo = &sobj[best];
+            sn = normal_vector(bo->c, sp);
+            albedo = F3{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
+            so = D3{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
+        }
+        F3 acc{0.0f, 0.0f, 0.0f};
+        if (__ballot(hit)) { // wave-uniform
+            bool cull = fa.cull != 0u;
+            Ball ball{0.0, 0.0, 0.0, INFINITY};
+            if (cull) {
+                const bool finite = !hit || (isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z));
+                if (__ballot(!finite)) cull = false; // (a NaN / inf hit point: test everything)
+                const double lx = wave_min(hit ? sp.x : INFINITY), ly = wave_min(hit ? sp.y : INFINITY), lz = wave_min(hit ? sp.z : INFINITY);
+                const double hx = wave_max(hit ? sp.x : -INFINITY), hy = wave_max(hit ? sp.y : -INFINITY), hz = wave_max(hit ? sp.z : -INFINITY);
+                const double dx = hx - lx, dy = hy - ly, dz = hz - lz;
+                ball.cx = 0.5 * (lx + hx);
+                ball.cy = 0.5 * (ly + hy);
+                ball.cz = 0.5 * (lz + hz);
+                ball.R = 0.5 * sqrt(dx * dx + dy * dy + dz * dz) * (1.0 + 1e-9) + 1.01e-2; // as the wavefront kernel forms it
+            }
+            for (uint32_t l = 0; l < fa.n_lights; l++) {
+                const DevLight *lt = &glight[l];
+                const bool spherical = lt->spherical != 0;
+                double max_t = 0.0;
+                D3 sd{0.0, 0.0, 0.0};
+                Mono sm;
+                bool in_shadow = false;
+                if (hit) {
+                    sd = shadow_dir(lt->p, spherical, sp, max_t);
+                    cnt.shadow();
+                    make_mono(sm, so, sd);
+                }
+                for (uint32_t base = 0; base < fa.n_obj; base += 64u) {
+                    unsigned long long mask;
+                    if (cull) {
+                        const uint32_t j = base + lane;
+                        bool rel = false;
+                        if (j < fa.n_obj) rel = spherical ? sphere_relevant<true>(scull[j], ball, *lt) : sphere_relevant<false>(scull[j], ball, *lt);
+                        mask = __ballot(rel);
+                    } else {
+                        const uint32_t n = fa.n_obj - base;
+                        mask = n >= 64u ? ~0ull : ((1ull << n) - 1ull);
+                    }
+                    while (mask && __ballot(hit && !in_shadow)) { // wave-uniform
+                        const uint32_t k = base + (uint32_t) __builtin_ctzll(mask);
+                        mask &= mask - 1ull;
+                        if (hit && !in_shadow) {
+                            const double t = intersect(gobj[k].c, gobj[k].cls, sm, max_t, true);
+                            cnt.test();
+                            if (t > EPS && t < max_t) in_shadow = true;
+                        }
+                    }
+                }
+                if (hit && !in_shadow) {
+                    const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
+                    acc.x += c.x;
+                    acc.y += c.y;
+                    acc.z += c.z;
+                }
+            }
+        }
+        if (live) { // the bounce decision of render_ray
+            if (!hit) {
+                if (!first) RT_SYM(rtk)::blend(res, cur_ratio, bg);
+                live = false;
+            } else {
+                const F3 oc{(acc.x < 1.0f) ? acc.x : 1.0f, (acc.y < 1.0f) ? acc.y : 1.0f, (acc.z < 1.0f) ? acc.z : 1.0f};
+                if (first) res = oc;
+                else RT_SYM(rtk)::blend(res, cur_ratio, oc);
+                first = false;
+                const float refl = sobj[best].refl;
+                if (!((double) refl > EPS)) {
+                    live = false;
+                } else {
+                    cur_ratio *= refl;
+                    if (n_refl == fa.max_refl) {
+                        RT_SYM(rtk)::blend(res, cur_ratio, bg);
+                        live = false;
+                    } else {
+                        n_refl++;
+                        dir = reflect_ray(dir, sn);
+                        cnt.reflect();
+                        o = D3{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
+                    }
+                }
+            }
+        }
+    }
+    return res;
+}
+
+// the RGBA8 store of the render kernels, (unsigned char)(int)(v * 255.0f + 0.5f), with both operations rounded separately in
+// every build (the strict kernels' and rt_resolve.hip's value)
+__device__ __forceinline__ uchar4 quantise(float x, float y, float z)
+{
+    uchar4 px;
+    px.x = (unsigned char) (int) __fadd_rn(__fmul_rn(x, 255.0f), 0.5f);
+    px.y = (unsigned char) (int) __fadd_rn(__fmul_rn(y, 255.0f), 0.5f);
+    px.z = (unsigned char) (int) __fadd_rn(__fmul_rn(z, 255.0f), 0.5f);
+    px.w = 255;
+    return px;
+}
+
+// pairwise float32 sum over the lanes `m` apart (the resolve's tree, one level)
+__device__ __forceinline__ F3 xor_add(const F3 &v, int m)
+{
+    return F3{__fadd_rn(v.x, __shfl_xor(v.x, m)), __fadd_rn(v.y, __shfl_xor(v.y, m)), __fadd_rn(v.z, __shfl_xor(v.z, m))};
+}
+
+// One lane = one sample ray; a wave = 64 / K^2 pixels (K = 4: 4 pixels of 16 lanes; K = 2: 16 pixels of 4 lanes).  Lane bits: i =
+// sub-column (K = 4: bits 0-1, K = 2: bit 0), j = sub-row (the next bits).  Workgroups of four waves stage the scene into LDS once
+// and then take pixels by a grid-stride loop over the device-side count, so the grid size never depends on the frame.
+//   K = 2 / 4: item q is list[q] = (local row << 16) | x; sample (i, j) is the ray of sample (K x + i, K y + j) of the K-times
+//              finer frame (camx / camy: its camera-plane tables); the lanes reduce with the resolve's tree, multiply by 1/K^2 and
+//              store one pixel of the output (RGBA8 quantised as the render kernels do).
+//   K = 1:     halo rows.  Item q = pixel x of halo slot h = q / width: band b = h / 2 of this rank, side 0 = the global row just
+//              below the band, 1 = just above it (nothing when that row lies outside the image); camx / camy: the output frame's
+//              tables.  Stores RGBA32F into halo[h][x].
+template <int K, bool COUNT, bool RGBA8>
+__global__ __launch_bounds__(256) void ray_list_kernel(const FrameArgs fa, const DevObject *__restrict__ gobj, const DevLight *__restrict__ glight,
+                                                       const double *__restrict__ camx, const double *__restrict__ camy,
+                                                       const uint32_t *__restrict__ list, const uint32_t *__restrict__ count_ptr, uint32_t n_items,
+                                                       void *__restrict__ out, unsigned long long *__restrict__ counters)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    DevObject *sobj = reinterpret_cast<DevObject *>(smem);
+    UsEntry *scull = reinterpret_cast<UsEntry *>(smem + (size_t) fa.n_obj * sizeof(DevObject));
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(gobj);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem);
+        const uint32_t n16 = fa.n_obj * (uint32_t) (sizeof(DevObject) / 16);
+        for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) dst[i] = src[i];
+        for (uint32_t i = threadIdx.x; i < fa.n_obj; i += blockDim.x) { // culling entries (UsEntry layout; only kx, ky, kz, r, inv_r are read)
+            const DevObject &g = gobj[i];
+            UsEntry e{};
+            e.kx = g.c[K_X];
+            e.ky = g.c[K_Y];
+            e.kz = g.c[K_Z];
+            e.c = g.c[K_C];
+            e.r = g.bs_radius;
+            e.inv_r = (g.bs_radius < INFINITY) ? 1.0 / g.bs_radius : 0.0;
+            e.orig = i;
+            scull[i] = e;
+        }
+    }
+    __syncthreads();
+
+    constexpr uint32_t LANES = (uint32_t) (K * K), PPW = 64u / LANES; // lanes per pixel, pixels per wave
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t sub = lane % LANES, i = sub % (uint32_t) K, j = sub / (uint32_t) K;
+    const uint32_t n = count_ptr ? *count_ptr : n_items;
+    const D3 origin{fa.origin[0], fa.origin[1], fa.origin[2]};
+    Cnt<COUNT> cnt;
+    for (uint32_t base = (blockIdx.x * WAVES + wave) * PPW; base < n; base += gridDim.x * WAVES * PPW) { // wave-uniform
+        const uint32_t q = base + lane / LANES;
+        bool live = q < n;
+        uint32_t x = 0, lr = 0, y = 0;
+        D3 dir{0.0, 0.0, 1.0};
+        if (K == 1) {
+            if (live) {
+                const uint32_t h = q / fa.width, b = h >> 1;
+                x = q - h * fa.width;
+                lr = h; // (halo slot)
+                const uint32_t start = b * fa.band_rows, rows = min(fa.band_rows, fa.local_rows - start);
+                const int64_t g0 = ((int64_t) b * fa.world + fa.rank) * fa.band_rows;
+                const int64_t gy = (h & 1u) ? g0 + rows : g0 - 1;
+                live = gy >= 0 && gy < (int64_t) fa.height;
+                if (live) dir = primary_dir_tab(fa, camx[x], camy[(uint32_t) gy]);
+            }
+        } else {
+            if (live) {
+                const uint32_t v = list[q];
+                lr = v >> 16;
+                x = v & 0xFFFFu;
+                y = global_row(fa, lr);
+                dir = primary_dir_tab(fa, camx[(size_t) K * x + i], camy[(size_t) K * y + j]);
+            }
+        }
+        if (live) cnt.primary();
+        F3 c = render_ray_culled<COUNT>(fa, gobj, glight, sobj, scull, origin, dir, live, cnt);
+        if (K == 1) {
+            if (live) reinterpret_cast<float4 *>(out)[(size_t) lr * fa.width + x] = make_float4(c.x, c.y, c.z, 1.0f);
+        } else {
+            // (s0 + s1) [+ (s2 + s3)] over i, then the same over j: lanes i ^ 1, i ^ 2, then j's bits
+            c = xor_add(c, 1);
+            if (K == 4) c = xor_add(c, 2);
+            c = xor_add(c, K);
+            if (K == 4) c = xor_add(c, 2 * K);
+            if (live && sub == 0u) {
+                constexpr float inv = 1.0f / (float) (K * K); // exact
+                const float vx = __fmul_rn(c.x, inv), vy = __fmul_rn(c.y, inv), vz = __fmul_rn(c.z, inv);
+                const size_t o = (size_t) lr * fa.width + x;
+                if (RGBA8) reinterpret_cast<uchar4 *>(out)[o] = quantise(vx, vy, vz);
+                else reinterpret_cast<float4 *>(out)[o] = make_float4(vx, vy, vz, 1.0f);
+            }
+        }
+    }
+    cnt.flush(counters);
+}
+
+// One lane per output pixel, a wave per 8 x 8 block (a workgroup per 16 x 16 tile), so that the list keeps locality.  refine(x, y):
+// tau < 0, or some 8-neighbour n inside the image and channel c with !(fabsf(P(x,y).c - P(n).c) <= tau).  Neighbour rows come from
+// P (the same band) or from the halo (a row of another rank).  Unrefined pixels are written to `out` in the context's format
+// (nothing to write when out is P itself); refined ones are appended to the list, one atomicAdd per wave.
+template <bool RGBA8>
+__global__ __launch_bounds__(256) void classify_kernel(const float4 *__restrict__ p, const float4 *__restrict__ halo, uint32_t width, uint32_t height,
+                                                       uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world, uint32_t rank, float tau,
+                                                       void *out, uint32_t *__restrict__ list, uint32_t *__restrict__ count)
+{
+    const uint32_t tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    const bool in = x < width && lr < local_rows;
+    bool refine = false;
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    if (in) {
+        c = p[(size_t) lr * width + x];
+        refine = tau < 0.0f;
+        const uint32_t b = lr / band_rows, t = lr - b * band_rows;
+        const int64_t gy = ((int64_t) b * world + rank) * band_rows + t;
+        for (int dy = -1; dy <= 1 && !refine; dy++) {
+            const int64_t ny = gy + dy;
+            if (ny < 0 || ny >= (int64_t) height) continue;
+            const float4 *row;
+            if (dy == 0) row = p + (size_t) lr * width;
+            else if (world == 1u) row = p + (size_t) (lr + dy) * width;
+            else if (dy < 0) row = t > 0u ? p + (size_t) (lr - 1u) * width : halo + (size_t) (2u * b) * width;
+            else row = (t + 1u < band_rows && lr + 1u < local_rows) ? p + (size_t) (lr + 1u) * width : halo + (size_t) (2u * b + 1u) * width;
+            for (int dx = -1; dx <= 1; dx++) {
+                const int64_t nx = (int64_t) x + dx;
+                if ((dx == 0 && dy == 0) || nx < 0 || nx >= (int64_t) width) continue;
+                const float4 v = row[nx];
+                if (!(fabsf(c.x - v.x) <= tau) || !(fabsf(c.y - v.y) <= tau) || !(fabsf(c.z - v.z) <= tau)) refine = true;
+            }
+        }
+    }
+    const unsigned long long m = __ballot(refine);
+    if (in && !refine) {
+        const size_t o = (size_t) lr * width + x;
+        if (RGBA8) reinterpret_cast<uchar4 *>(out)[o] = quantise(c.x, c.y, c.z);
+        else if (out != (const void *) p) reinterpret_cast<float4 *>(out)[o] = make_float4(c.x, c.y, c.z, 1.0f);
+    }
+    if (m == 0ull) return; // wave-uniform
+    uint32_t base = 0;
+    if (lane == 0u) base = atomicAdd(count, (uint32_t) __popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (refine) list[base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = (lr << 16) | x;
+}
+
+template <int K, bool COUNT>
+hipError_t launch_rays(const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, const double *camx, const double *camy, const uint32_t *list,
+                       const uint32_t *count_ptr, uint32_t n_items, uint32_t grid, void *out, int rgba8, unsigned long long *counters, hipStream_t stream)
+{
+    const size_t lds = (size_t) fa->n_obj * (sizeof(DevObject) + sizeof(UsEntry));
+    if (rgba8)
+        hipLaunchKernelGGL((ray_list_kernel<K, COUNT, true>), dim3(grid), dim3(256), lds, stream, *fa, gobj, glight, camx, camy, list, count_ptr, n_items, out, counters);
+    else
+        hipLaunchKernelGGL((ray_list_kernel<K, COUNT, false>), dim3(grid), dim3(256), lds, stream, *fa, gobj, glight, camx, camy, list, count_ptr, n_items, out, counters);
+    return hipGetLastError();
+}
+
+} // namespace RT_SYM(rtk)
+
+// k = 2 / 4: sample rays of the listed pixels (count_ptr = the device-side list length) into `out` (rgba8: uchar4, else float4);
+// k = 1: the halo rows' centre rays, n_items = 2 * bands * width slots, into `out` = [2 * bands][width] float4.  `grid` workgroups
+// of 256 lanes, fixed per context.
+extern "C" hipError_t RT_SYM(rt_launch_ray_list)(const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, const double *camx, const double *camy,
+                                                  const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out,
+                                                  int rgba8, int count, unsigned long long *counters, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (grid == 0u) return hipSuccess;
+    if (k == 1u) return count ? launch_rays<1, true>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, 0, counters, stream)
+                              : launch_rays<1, false>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, 0, counters, stream);
+    if (k == 2u) return count ? launch_rays<2, true>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream)
+                              : launch_rays<2, false>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream);
+    if (k == 4u) return count ? launch_rays<4, true>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream)
+                              : launch_rays<4, false>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream);
+    return hipErrorInvalidValue;
+}
+
+// p = [local_rows][width] RGBA32F plain frame, halo = [2 * bands][width] (world > 1), out = [local_rows][width] pixels (may be p
+// itself for RGBA32F), list = [local_rows * width] words, count = the list length (cleared by the caller on the stream).
+extern "C" hipError_t RT_SYM(rt_launch_classify)(const void *p, const void *halo, uint32_t width, uint32_t height, uint32_t local_rows, uint32_t band_rows,
+                                                  uint32_t world, uint32_t rank, float tau, void *out, int rgba8, uint32_t *list, uint32_t *count,
+                                                  hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    const uint32_t tiles_x = (width + 15u) / 16u, tiles = tiles_x * ((local_rows + 15u) / 16u);
+    if (tiles == 0u) return hipSuccess;
+    if (rgba8)
+        hipLaunchKernelGGL((classify_kernel<true>), dim3(tiles), dim3(256), 0, stream, (const float4 *) p, (const float4 *) halo, width, height, local_rows,
+                           tiles_x, band_rows, world, rank, tau, out, list, count);
+    else
+        hipLaunchKernelGGL((classify_kernel<false>), dim3(tiles), dim3(256), 0, stream, (const float4 *) p, (const float4 *) halo, width, height, local_rows,
+                           tiles_x, band_rows, world, rank, tau, out, list, count);
+    return hipGetLastError();
+}

@@ -4,6 +4,7 @@
 // RT_ERR_DEVICE when there is no usable GPU.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -34,6 +35,13 @@ extern "C" hipError_t rt_launch_assemble_sparse_strict(const void *, void *, uin
                                                        uint32_t, int, hipStream_t);
 // supersampling resolve (rt_resolve.hip, built once without FMA contraction)
 extern "C" hipError_t rt_launch_resolve(const void *, void *, uint32_t, uint32_t, uint32_t, int, int, hipStream_t);
+// adaptive supersampling (rt_adaptive.hip): the ray-list kernel per contraction mode, and the classify kernel
+extern "C" hipError_t rt_launch_ray_list_strict(const FrameArgs *, const DevObject *, const DevLight *, const double *, const double *, const uint32_t *,
+                                                const uint32_t *, uint32_t, uint32_t, uint32_t, void *, int, int, unsigned long long *, hipStream_t);
+extern "C" hipError_t rt_launch_ray_list_fast(const FrameArgs *, const DevObject *, const DevLight *, const double *, const double *, const uint32_t *,
+                                              const uint32_t *, uint32_t, uint32_t, uint32_t, void *, int, int, unsigned long long *, hipStream_t);
+extern "C" hipError_t rt_launch_classify_strict(const void *, const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, void *, int,
+                                                uint32_t *, uint32_t *, hipStream_t);
 
 namespace {
 
@@ -104,6 +112,16 @@ struct rt_ctx {
     uint32_t ssaa = 1;          // samples per axis k (RT_FLAG_SSAA2 / RT_FLAG_SSAA4)
     void *d_ss = nullptr;       // k > 1: the internal frame's local rows, [k * local_rows][k * width] float4
     int resolve_nt = 0;         // the resolve reads the internal frame with non-temporal loads (MI355RT_RESOLVE_NT, experiments)
+    // RT_FLAG_SSAA_ADAPTIVE (rt_adaptive.hip): fa is the output geometry (as for k = 1); k = ssaa samples per axis where a pixel is refined
+    bool adaptive = false;
+    float tau = 1.0f / 32.0f;   // rt_set_ssaa_threshold
+    void *d_p = nullptr;        // RGBA8 output: the plain frame P, [local_rows][width] float4 (RGBA32F renders P in place)
+    void *d_halo = nullptr;     // world > 1: [halo_slots][width] float4, slot 2b / 2b + 1 = the global row just below / above local band b
+    uint32_t halo_slots = 0;
+    uint64_t halo_rays = 0;     // centre rays the halo pass traces per frame (slots inside the image x width)
+    uint32_t *d_list = nullptr; // [local_rows * width] refined pixels, (local row << 16) | x; d_list[local_rows * width] = their count
+    double *d_camxk = nullptr, *d_camyk = nullptr; // camera-plane tables of the k-times finer sample grid
+    uint32_t ray_grid = 0, halo_grid = 0;          // workgroups of the ray-list kernel (fixed per context)
     DevObject *d_obj = nullptr;
     DevLight *d_light = nullptr;
     void *d_fb = nullptr;
@@ -347,6 +365,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if ((cfg.flags & RT_FLAG_SSAA2) && (cfg.flags & RT_FLAG_SSAA4))
         return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA2 and RT_FLAG_SSAA4 exclude each other");
     const uint32_t k = (cfg.flags & RT_FLAG_SSAA4) ? 4u : ((cfg.flags & RT_FLAG_SSAA2) ? 2u : 1u);
+    const bool adaptive = (cfg.flags & RT_FLAG_SSAA_ADAPTIVE) != 0;
+    if (adaptive && k == 1u) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_ADAPTIVE needs RT_FLAG_SSAA2 or RT_FLAG_SSAA4");
     if (sd->width == 0 || sd->height == 0) return fail(RT_ERR_INVALID, "rt_create: empty image %ux%u", sd->width, sd->height);
     if (k > 1u && ((uint64_t) k * sd->width > 65536u || (uint64_t) k * sd->height > 65536u))
         return fail(RT_ERR_INVALID, "rt_create: %ux%u supersampled %ux%u exceeds 65536 samples per axis", sd->width, sd->height, k, k);
@@ -377,6 +397,7 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     ctx->width = sd->width;
     ctx->height = sd->height;
     ctx->ssaa = k;
+    ctx->adaptive = adaptive;
     if (const char *e = std::getenv("MI355RT_RESOLVE_NT")) ctx->resolve_nt = std::atoi(e) != 0; // (experiments)
     ctx->pixel_bytes = cfg.format == RT_FMT_RGBA8 ? 4 : 16;
     ctx->local_rows = rows_of_rank(sd->height, cfg.band_rows, cfg.world, cfg.rank);
@@ -387,7 +408,9 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
 
     // the frame the kernels render: with supersampling the unmodified scene at k times the size, into RGBA32F (k is a power of two, so
     // the aspect ratio is the same double; bands of k * band_rows rows keep each output row's samples with the rank that owns it)
-    const uint32_t rw = k * sd->width, rh = k * sd->height;
+    // (adaptive: the plain pass renders the output frame itself, k = 1 geometry; the sample rays come from the tables built below)
+    const uint32_t kf = adaptive ? 1u : k;
+    const uint32_t rw = kf * sd->width, rh = kf * sd->height;
     FrameArgs &fa = ctx->fa;
     std::memset(&fa, 0, sizeof(fa));
     fa.aspect = (double) rw / rh;                      // Scene::aspect_ratio, include/scene.h:32-33
@@ -403,11 +426,11 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     fa.max_refl = sd->max_reflections;
     fa.rank = cfg.rank;
     fa.world = cfg.world;
-    fa.band_rows = k * cfg.band_rows;
-    fa.local_rows = k * ctx->local_rows; // (= rows_of_rank(rh, k * band_rows, world, rank))
+    fa.band_rows = kf * cfg.band_rows;
+    fa.local_rows = kf * ctx->local_rows; // (= rows_of_rank(rh, k * band_rows, world, rank))
     fa.tiles_x = (rw + RT_TILE - 1) / RT_TILE;
     fa.n_tiles = fa.tiles_x * ((fa.local_rows + RT_TILE - 1) / RT_TILE);
-    fa.rgba8 = (k == 1u && cfg.format == RT_FMT_RGBA8) ? 1u : 0u;
+    fa.rgba8 = (k == 1u && cfg.format == RT_FMT_RGBA8) ? 1u : 0u; // (adaptive: P is RGBA32F)
     fa.ord_plain = (cfg.flags & RT_FLAG_PLAIN_ORDER) ? 1u : 0u;
     ctx->ord_split = (cfg.flags & RT_FLAG_NOSPLIT) ? 0u : RT_ORD_SPLIT_CLASSES;
     if (const char *e = std::getenv("MI355RT_SPLIT_CLASSES")) ctx->ord_split = (uint32_t) std::atoi(e) & 15u; // (experiments)
@@ -575,6 +598,9 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)",
                     rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub));
     }
+    if (adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
+        return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)",
+                    (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)));
     int rc = RT_OK;
     auto hip_ok = [&](hipError_t err, const char *what) {
         if (err != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(err));
@@ -591,8 +617,42 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light + lights.size(), lightk.data(), sizeof(LightK) * lightk.size(), hipMemcpyHostToDevice), "hipMemcpy(light table)") &&
         hip_ok(hipEventCreate(&ctx->ev0), "hipEventCreate") && hip_ok(hipEventCreate(&ctx->ev1), "hipEventCreate") &&
         hip_ok(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming), "hipEventCreate") &&
-        hip_ok(k == 1u ? hipSuccess : hipMalloc(&ctx->d_ss, (size_t) (fa.local_rows ? fa.local_rows : 1) * rw * 16u), "hipMalloc(supersampled frame)");
+        hip_ok(kf == 1u ? hipSuccess : hipMalloc(&ctx->d_ss, (size_t) (fa.local_rows ? fa.local_rows : 1) * rw * 16u), "hipMalloc(supersampled frame)");
     if (rc != RT_OK) return rc;
+    if (adaptive) {
+        const size_t px = (size_t) ctx->local_rows * sd->width;
+        const uint32_t bands = (ctx->local_rows + cfg.band_rows - 1u) / cfg.band_rows;
+        ctx->halo_slots = cfg.world > 1u ? 2u * bands : 0u;
+        for (uint32_t h = 0; h < ctx->halo_slots; h++) { // (the kernel's own rule, rt_adaptive.hip)
+            const uint32_t b = h >> 1, rows = std::min(cfg.band_rows, ctx->local_rows - b * cfg.band_rows);
+            const int64_t g0 = ((int64_t) b * cfg.world + cfg.rank) * cfg.band_rows, gy = (h & 1u) ? g0 + rows : g0 - 1;
+            if (gy >= 0 && gy < (int64_t) sd->height) ctx->halo_rays += sd->width;
+        }
+        // the ray-list kernel keeps one workgroup per CU resident (it needs all 512 registers of a lane); twice that many keeps every CU
+        // busy while the last workgroups drain
+        const uint64_t ppw = 64u / (k * k), want = (px + ppw * 4u - 1u) / (ppw * 4u), hwant = ((uint64_t) ctx->halo_slots * sd->width + 255u) / 256u;
+        const uint32_t cap = ctx->wg_slots / 3u ? ctx->wg_slots / 3u : 1u;
+        ctx->ray_grid = (uint32_t) std::min<uint64_t>(want, cap);
+        ctx->halo_grid = (uint32_t) std::min<uint64_t>(hwant, cap);
+        std::vector<double> cx((size_t) k * sd->width), cy((size_t) k * sd->height);
+        for (uint32_t x = 0; x < k * sd->width; x++) { // the tables of the k-times finer frame, exactly as a RT_FLAG_SSAAk context forms them below
+            const double ndc_x = ((int) x + 0.5) / (int) (k * sd->width);
+            cx[x] = (2.0 * ndc_x - 1.0) * fa.aspect * fa.tan_half_fov;
+        }
+        for (uint32_t y = 0; y < k * sd->height; y++) {
+            const double ndc_y = ((int) y + 0.5) / (int) (k * sd->height);
+            cy[y] = (2.0 * ndc_y - 1.0) * fa.tan_half_fov;
+        }
+        hip_ok(hipMalloc((void **) &ctx->d_list, sizeof(uint32_t) * (px + 1u)), "hipMalloc(refine list)") &&
+            hip_ok(cfg.format == RT_FMT_RGBA8 ? hipMalloc(&ctx->d_p, (px ? px : 1u) * 16u) : hipSuccess, "hipMalloc(plain frame)") &&
+            hip_ok(ctx->halo_slots ? hipMalloc(&ctx->d_halo, (size_t) ctx->halo_slots * sd->width * 16u) : hipSuccess, "hipMalloc(halo rows)") &&
+            hip_ok(hipMemset(ctx->d_list + px, 0, sizeof(uint32_t)), "hipMemset(refine count)") &&
+            hip_ok(hipMalloc((void **) &ctx->d_camxk, sizeof(double) * cx.size()), "hipMalloc(camx)") &&
+            hip_ok(hipMalloc((void **) &ctx->d_camyk, sizeof(double) * cy.size()), "hipMalloc(camy)") &&
+            hip_ok(hipMemcpy(ctx->d_camxk, cx.data(), sizeof(double) * cx.size(), hipMemcpyHostToDevice), "hipMemcpy(camx)") &&
+            hip_ok(hipMemcpy(ctx->d_camyk, cy.data(), sizeof(double) * cy.size(), hipMemcpyHostToDevice), "hipMemcpy(camy)");
+        if (rc != RT_OK) return rc;
+    }
     {
         // camera-plane coordinates of every pixel column / row: render_pixel's camera_x / camera_y
         // (src/update-cpu.cpp:84-87) depend only on the pixel index and the scene, so they are evaluated here once,
@@ -679,8 +739,8 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
 {
     hipStream_t stream = (hipStream_t) stream_;
     FrameArgs &fa = ctx->fa;
-    const bool ss = ctx->ssaa > 1u; // supersampled: render the internal frame densely, resolve, and (sparse) pack the resolved rows
-    const bool kernel_sparse = sparse && !ss;
+    const bool ss = ctx->ssaa > 1u && !ctx->adaptive; // supersampled: render the internal frame densely, resolve, and (sparse) pack the resolved rows
+    const bool kernel_sparse = sparse && ctx->ssaa == 1u; // (adaptive frames are packed like supersampled ones)
     fa.sparse = kernel_sparse ? 1u : 0u;
     fa.sparse_cap = kernel_sparse ? sparse_cap : 0u;
     // Which instantiation renders a scene of unit spheres?  The wave-per-block one ("lean") executes a quarter fewer instructions per
@@ -750,6 +810,9 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     // out: where the frame ends up (a message for sparse calls); fb: what the render kernels write
     void *out = dev_fb ? dev_fb : ctx->d_fb;
     void *fb = ss ? ctx->d_ss : out;
+    // adaptive: dest = where the output rows go before a sparse pack; the plain frame P is rendered in place for RGBA32F
+    void *dest = sparse ? ctx->d_fb : out;
+    if (ctx->adaptive) fb = ctx->cfg.format == RT_FMT_RGBA8 ? ctx->d_p : dest;
     if (kernel_sparse) RT_HIP(hipMemsetAsync(fb, 0, 16, stream)); // message header: count, overflow
     const int count = (ctx->cfg.flags & RT_FLAG_COUNT) ? 1 : 0;
     const int rgba8 = fa.rgba8 != 0u;
@@ -817,6 +880,25 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         e = fast ? rt_launch_wavefront_fast(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream)
                  : rt_launch_wavefront_strict(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    if (ctx->adaptive) {
+        // halo rows -> clear the list -> classify (unrefined pixels written out) -> the k^2 sample rays of the listed pixels; the next
+        // frame's plain pass overwrites what these read, and the ordering event below is recorded behind the last of them
+        const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
+        auto rays = fast ? rt_launch_ray_list_fast : rt_launch_ray_list_strict;
+        const size_t px = (size_t) ctx->local_rows * ctx->width;
+        if (ctx->halo_slots)
+            RT_HIP(rays(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo, 0,
+                        count, ctx->d_counters, stream));
+        RT_HIP(hipMemsetAsync(ctx->d_list + px, 0, sizeof(uint32_t), stream));
+        RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
+                                         dest, out8, ctx->d_list, ctx->d_list + px, stream));
+        RT_HIP(rays(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
+                    ctx->d_counters, stream));
+        if (sparse) {
+            const BgPixel bg = bg_pixel(ctx);
+            RT_HIP(rt_launch_pack_sparse_strict(ctx->d_fb, dev_fb, ctx->width, ctx->local_rows, bg.w, sparse_cap, out8, stream));
+        }
+    }
     if (ss) {
         // the next frame's render overwrites the internal frame this reads, so the ordering event below is recorded behind it
         const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
@@ -952,6 +1034,27 @@ extern "C" int rt_assemble_sparse_incremental(rt_ctx *ctx, const void *gathered,
     return RT_OK;
 }
 
+extern "C" int rt_set_ssaa_threshold(rt_ctx *ctx, float tau)
+{
+    if (!ctx) return fail(RT_ERR_INVALID, "rt_set_ssaa_threshold: null argument");
+    if (!ctx->adaptive) return fail(RT_ERR_INVALID, "rt_set_ssaa_threshold: the context was not created with RT_FLAG_SSAA_ADAPTIVE");
+    if (std::isnan(tau)) return fail(RT_ERR_INVALID, "rt_set_ssaa_threshold: tau is NaN");
+    ctx->tau = tau;
+    return RT_OK;
+}
+
+extern "C" int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels)
+{
+    if (!ctx || !pixels) return fail(RT_ERR_INVALID, "rt_get_ssaa_refined: null argument");
+    if (!ctx->adaptive) return fail(RT_ERR_INVALID, "rt_get_ssaa_refined: the context was not created with RT_FLAG_SSAA_ADAPTIVE");
+    uint32_t n = 0;
+    RT_HIP(hipSetDevice(ctx->device));
+    RT_HIP(hipDeviceSynchronize());
+    RT_HIP(hipMemcpy(&n, ctx->d_list + (size_t) ctx->local_rows * ctx->width, sizeof(n), hipMemcpyDeviceToHost));
+    *pixels = n;
+    return RT_OK;
+}
+
 extern "C" int rt_get_counters(rt_ctx *ctx, rt_counters *out)
 {
     if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_get_counters: null argument");
@@ -1028,6 +1131,11 @@ extern "C" int rt_destroy(rt_ctx *ctx)
     if (ctx->d_light) (void) hipFree(ctx->d_light);
     if (ctx->d_fb) (void) hipFree(ctx->d_fb);
     if (ctx->d_ss) (void) hipFree(ctx->d_ss);
+    if (ctx->d_p) (void) hipFree(ctx->d_p);
+    if (ctx->d_halo) (void) hipFree(ctx->d_halo);
+    if (ctx->d_list) (void) hipFree(ctx->d_list);
+    if (ctx->d_camxk) (void) hipFree(ctx->d_camxk);
+    if (ctx->d_camyk) (void) hipFree(ctx->d_camyk);
     if (ctx->d_counters) (void) hipFree(ctx->d_counters);
     if (ctx->d_stamps) (void) hipFree(ctx->d_stamps);
     if (ctx->d_camx) (void) hipFree(ctx->d_camx);

@@ -532,6 +532,16 @@ extern "C" int rt_multi_last_transfer(const rt_multi *m, uint64_t *bytes_sent, u
     return RT_OK;
 }
 
+extern "C" int rt_multi_set_ssaa_threshold(rt_multi *m, float tau)
+{
+    if (!m) return fail(RT_ERR_INVALID, "rt_multi_set_ssaa_threshold: null argument");
+    for (rt_ctx *c : m->ctx) { // (every context refuses the same way: NaN, or no RT_FLAG_SSAA_ADAPTIVE -- the first one answers for all)
+        const int rc = rt_set_ssaa_threshold(c, tau);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
 extern "C" int rt_multi_info(const rt_multi *m, uint32_t *n_contexts, uint32_t *transport)
 {
     if (!m) return fail(RT_ERR_INVALID, "rt_multi_info: null argument");

@@ -12,6 +12,7 @@
 
 #include <dlfcn.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,6 +35,8 @@
 //                             surface (src/update-cuda.cu:149-156); default rgba32f, the CPU back end's floats (src/update-cpu.cpp:128-131)
 //   MI355RT_SSAA=2|4          supersampling, k x k rays per pixel box-filtered into the frame (RT_FLAG_SSAA2 / RT_FLAG_SSAA4, include/mi355rt.h),
 //                             one GPU or several; default: one ray per pixel
+//   MI355RT_SSAA_ADAPTIVE=<tau>  with MI355RT_SSAA: supersample only the pixels whose 3x3 neighbourhood differs by more than tau in some
+//                             channel (RT_FLAG_SSAA_ADAPTIVE, rt_set_ssaa_threshold); empty: the default 1/32; tau < 0: every pixel
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -44,6 +47,7 @@ struct MultiApi {
     int (*render)(rt_multi *, const double *, void *, float *) = nullptr;
     int (*download)(rt_multi *, void *, size_t) = nullptr;
     int (*destroy)(rt_multi *) = nullptr;
+    int (*set_threshold)(rt_multi *, float) = nullptr;
 } g_mapi;
 unsigned int g_texture = 0;
 unsigned int g_width = 0, g_height = 0;
@@ -109,7 +113,8 @@ void load_multi()
     g_mapi.render = (decltype(g_mapi.render)) dlsym(g_multi_lib, "rt_render_multi");
     g_mapi.download = (decltype(g_mapi.download)) dlsym(g_multi_lib, "rt_multi_download");
     g_mapi.destroy = (decltype(g_mapi.destroy)) dlsym(g_multi_lib, "rt_multi_destroy");
-    if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy) die_text("libmi355rt_multi.so", "missing entry points");
+    g_mapi.set_threshold = (decltype(g_mapi.set_threshold)) dlsym(g_multi_lib, "rt_multi_set_ssaa_threshold");
+    if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold) die_text("libmi355rt_multi.so", "missing entry points");
 }
 
 } // namespace
@@ -143,6 +148,18 @@ void init_update(unsigned int texture, const Scene &scene)
         if (!std::strcmp(f, "2")) ssaa = RT_FLAG_SSAA2;
         else if (!std::strcmp(f, "4")) ssaa = RT_FLAG_SSAA4;
         else if (*f) die_text("MI355RT_SSAA", "expected 2 or 4");
+    }
+    bool adaptive = false;
+    float tau = 1.0f / 32.0f;
+    if (const char *f = std::getenv("MI355RT_SSAA_ADAPTIVE")) {
+        if (!ssaa) die_text("MI355RT_SSAA_ADAPTIVE", "needs MI355RT_SSAA=2 or 4");
+        adaptive = true;
+        if (*f) {
+            char *end = nullptr;
+            tau = std::strtof(f, &end);
+            if (*end || std::isnan(tau)) die_text("MI355RT_SSAA_ADAPTIVE", "expected a threshold (a number, or empty for the default 1/32)");
+        }
+        ssaa |= RT_FLAG_SSAA_ADAPTIVE;
     }
 
     // flatten the Scene into the ABI's descriptor (arrays are borrowed only for the call)
@@ -190,6 +207,7 @@ void init_update(unsigned int texture, const Scene &scene)
                                (std::getenv("MI355RT_MULTI_SPARSE") ? RT_MULTI_SPARSE : 0u);     // (only tiles with content travel)
         if (g_mapi.create(&g_multi, &sd, devs.data(), (uint32_t) devs.size(), env_u32("MI355RT_BAND_ROWS", 16), env_u32("MI355RT_PARTS", 2), flags, g_format) != RT_OK)
             die("init_update (MI355RT_DEVICES)");
+        if (adaptive && g_mapi.set_threshold(g_multi, tau) != RT_OK) die("init_update (MI355RT_SSAA_ADAPTIVE)");
         return;
     }
     rt_config cfg{};
@@ -198,6 +216,7 @@ void init_update(unsigned int texture, const Scene &scene)
     cfg.flags = RT_FLAG_STRICT | ssaa;
     cfg.format = g_format;
     if (rt_create(&g_ctx, &sd, &cfg) != RT_OK) die("init_update");
+    if (adaptive && rt_set_ssaa_threshold(g_ctx, tau) != RT_OK) die("init_update (MI355RT_SSAA_ADAPTIVE)");
 }
 
 float update(const glm::dmat4 &camera_matrix)

@@ -101,6 +101,22 @@ typedef struct rt_scene_desc {
 #define RT_FLAG_SSAA2 512u
 #define RT_FLAG_SSAA4 1024u
 
+/* Edge-adaptive supersampling: only valid together with exactly one of RT_FLAG_SSAA2 / RT_FLAG_SSAA4 (rt_create
+ * refuses it alone with RT_ERR_INVALID before it looks for a device; the 65536-per-axis limit on k*width and k*height holds).  With
+ * P = the plain frame (the reference's pixels at width x height, what a k = 1 context renders, in RGBA32F), S = the k x k sample frame
+ * above and tau = the threshold (rt_set_ssaa_threshold, default 1/32):
+ *   refine(x, y) = tau < 0, or some 8-neighbour n of (x, y) inside the image and some channel c of R, G, B gives
+ *                  !(fabsf(P(x,y).c - P(n).c) <= tau)   (one float32 subtraction: NaN differences refine; band edges are not image edges)
+ *   output(x, y) = the RT_FLAG_SSAAk resolve of S at (x, y) where refine(x, y), else P(x, y); alpha 1.0f; RGBA8 quantises either value
+ *                  as the render kernels do.
+ * So tau < 0 gives the RT_FLAG_SSAAk frame, tau = +inf the k = 1 frame (scenes without NaN colours), and a pure background pixel stays
+ * the background.  rt_render runs, on `stream`: the plain pass (the usual render kernels, no k^2 frame is allocated), with world > 1 the
+ * centre rays of the rows just outside each band (so every rank's rows equal the single-context frame's), a classify kernel (unrefined
+ * pixels are written out, refined ones appended to a device list) and a kernel that traces the k^2 sample rays of the listed pixels.
+ * Nothing is read back to the host, so frames can be captured into a graph.  `ms` covers all of it; RT_FLAG_COUNT counts every ray:
+ * primary_rays = width * local_rows + halo rays + k^2 * refined (rt_get_counters_detail stays the wavefront kernel's). */
+#define RT_FLAG_SSAA_ADAPTIVE 2048u
+
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
                                  produces (src/update-cpu.cpp:128-131) plus an alpha lane for 16-byte stores */
@@ -268,6 +284,12 @@ int rt_debug_counters(rt_ctx *ctx, uint64_t out[32]);
  * 12 / 13 a 100 MHz clock at the wave's start / end; row = workgroup * 4 + wave.  out = NULL: only the row count. */
 int rt_debug_stamp_rows(rt_ctx *ctx, uint64_t *out, size_t max_rows, size_t *n_rows);
 
+/* RT_FLAG_SSAA_ADAPTIVE contexts only (RT_ERR_INVALID otherwise; a NaN tau is refused too).  The threshold applies from the next
+ * rt_render on; it is a kernel argument, so a frame captured into a graph keeps the tau it was captured with. */
+int rt_set_ssaa_threshold(rt_ctx *ctx, float tau);
+/* The number of refined pixels of this context's last frame (waits for that frame). */
+int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
+
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
 
@@ -313,6 +335,8 @@ int rt_multi_info(const rt_multi *m, uint32_t *n_contexts, uint32_t *transport /
  * message prefixes, counted from the headers; the dense transports: every context's rows), bytes_dense = what the dense transport
  * delivers (height x width pixels).  Either pointer may be NULL.  0 / 0 before the first frame. */
 int rt_multi_last_transfer(const rt_multi *m, uint64_t *bytes_sent, uint64_t *bytes_dense);
+/* rt_set_ssaa_threshold on every context of the object (RT_FLAG_SSAA_ADAPTIVE objects only). */
+int rt_multi_set_ssaa_threshold(rt_multi *m, float tau);
 int rt_multi_destroy(rt_multi *m);
 
 #ifdef __cplusplus
