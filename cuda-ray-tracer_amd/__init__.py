@@ -9,6 +9,7 @@ There is NO CPU fallback: constructing a ``Renderer`` without a usable GPU raise
 PyTorch is optional plumbing here (device tensors can be handed in as raw pointers + a stream handle).
 """
 import ctypes as C
+import fcntl
 import os
 import subprocess
 
@@ -18,6 +19,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI355RT_LIB") or os.path.join(_HERE, "libmi355rt.so")   # MI355RT_LIB: another build of the same ABI, for A/B measurements
 UPDATE_LIB_PATH = os.path.join(_HERE, "libmi355rt_update.so")
 MULTI_LIB_PATH = os.path.join(_HERE, "libmi355rt_multi.so")   # several GPUs behind one call; the only library that links RCCL
+DRIVER_PATH = os.path.join(os.path.dirname(_HERE), "tests", "host_driver", "update_driver")   # headless host of the update.h contract (tests)
+# what `make all` produces, the base library first (the one a caller checks for)
+BUILD_PRODUCTS = (os.path.join(_HERE, "libmi355rt.so"), MULTI_LIB_PATH, UPDATE_LIB_PATH, DRIVER_PATH)
 
 RT_NCOEF = 20
 RT_FLAG_STRICT, RT_FLAG_FAST, RT_FLAG_COUNT, RT_FLAG_SIMPLE, RT_FLAG_NOCULL, RT_FLAG_STATIC_ORDER, RT_FLAG_NOSCAN, RT_FLAG_PLAIN_ORDER = 0, 1, 2, 4, 8, 16, 32, 64
@@ -87,8 +91,12 @@ class Counters(C.Structure):
 
 
 def build(verbose=False):
-    """Compile libmi355rt.so / libmi355rt_update.so in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
-    r = subprocess.run(["make", "-C", _HERE, "-j4", "all"], capture_output=True, text=True)
+    """Compile libmi355rt.so / libmi355rt_update.so in-tree for gfx950 (hipcc cross-compiles without a GPU).  Builds from several
+    processes at once take turns (a lock file in build/): each waits for the one in progress, whose products it then finds up to date."""
+    os.makedirs(os.path.join(_HERE, "build"), exist_ok=True)
+    with open(os.path.join(_HERE, "build", ".lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        r = subprocess.run(["make", "-C", _HERE, "-j4", "all"], capture_output=True, text=True)
     if verbose or r.returncode != 0:
         print(r.stdout[-4000:])
         print(r.stderr[-4000:])
@@ -519,3 +527,10 @@ class MultiRenderer:
             self.cleanup_update()
         except Exception:
             pass
+
+
+# The base library alone does not make a build: a caller that checks for it (tests/conftest.py) must not meet a build that another
+# process is still running, or one that lost a product since (the host driver lives under tests/).  Complete such a build, under
+# the build lock, before anything uses it; a complete build costs a few stat calls here.
+if os.path.exists(BUILD_PRODUCTS[0]) and not all(os.path.exists(p) for p in BUILD_PRODUCTS[1:]):
+    build()

@@ -35,6 +35,9 @@ __device__ __forceinline__ double wave_max(double v)
 // objects that could block some lane's shadow ray are tested.  A culled object cannot block (that is the culling's contract), so
 // every lane's in_shadow -- and with it every colour -- is what render_ray computes.  Lanes stay resident (a `live` flag instead of
 // break) so that the reductions run on the whole wave.  scull[j] = object j's culling entry (r = +inf: always tested).
+// COUNT builds count a shadow ray's tests as the reference does (rt_counters.tests): it stops at the first blocker and tests every
+// object before it, culled or not -- the first blocker's index + 1, or n_obj when nothing blocks.  (The blocker the culled loop
+// finds is that same object: a culled object cannot block.)
 template <bool COUNT>
 __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevObject *__restrict__ gobj, const DevLight *__restrict__ glight,
                                                 const DevObject *sobj, const UsEntry *scull, const D3 &origin, D3 dir, bool live, Cnt<COUNT> &cnt)
@@ -95,6 +98,7 @@ __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevOb
                 D3 sd{0.0, 0.0, 0.0};
                 Mono sm;
                 bool in_shadow = false;
+                uint32_t blocker = fa.n_obj; // (COUNT builds)
                 if (hit) {
                     sd = shadow_dir(lt->p, spherical, sp, max_t);
                     cnt.shadow();
@@ -116,11 +120,14 @@ __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevOb
                         mask &= mask - 1ull;
                         if (hit && !in_shadow) {
                             const double t = intersect(gobj[k].c, gobj[k].cls, sm, max_t, true);
-                            cnt.test();
-                            if (t > EPS && t < max_t) in_shadow = true;
+                            if (t > EPS && t < max_t) {
+                                in_shadow = true;
+                                if (COUNT) blocker = k;
+                            }
                         }
                     }
                 }
+                if (COUNT && hit) cnt.tests(in_shadow ? blocker + 1ull : (unsigned long long) fa.n_obj);
                 if (hit && !in_shadow) {
                     const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
                     acc.x += c.x;

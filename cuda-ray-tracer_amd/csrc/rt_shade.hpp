@@ -27,6 +27,7 @@ struct Cnt {
     __device__ __forceinline__ void shadow() {}
     __device__ __forceinline__ void reflect() {}
     __device__ __forceinline__ void test() {}
+    __device__ __forceinline__ void tests(unsigned long long) {}
     __device__ __forceinline__ void hit() {}
     __device__ __forceinline__ void solve() {}
     __device__ __forceinline__ void flush(unsigned long long *) {}
@@ -38,6 +39,7 @@ struct Cnt<true> {
     __device__ __forceinline__ void shadow() { v[1]++; }
     __device__ __forceinline__ void reflect() { v[2]++; }
     __device__ __forceinline__ void test() { v[3]++; }
+    __device__ __forceinline__ void tests(unsigned long long n) { v[3] += n; }
     __device__ __forceinline__ void hit() { v[4]++; }
     __device__ __forceinline__ void solve() { v[5]++; }
     __device__ __forceinline__ void flush(unsigned long long *g)

@@ -506,13 +506,9 @@ def test_random_mixed_class_scenes_bit_identical(pkg, oracle, seed):
     assert np.array_equal(a[..., :3], want)
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_random_cubic_scenes_within_tolerance(pkg, oracle, seed):
-    """Random degree-3 surfaces next to spheres and a plane (the cubic + mixed instantiations).  Device cbrt / acos / cos
-    differ from glibc's in the last ulp, so the bar is 1e-5 relative with at most 0.2 % of the pixels flipping at solver
-    discontinuities; wavefront and simple kernels must still agree exactly (same device functions)."""
+def random_cubic_scene(pkg, seed, w=128, h=96):
+    """A random degree-3 surface next to a sphere and a plane, two lights; returns (scene, camera)."""
     rng = np.random.default_rng(500 + seed)
-    w, h = 128, 96
     s = pkg.Scene.new(w, h, 40.0, 2, (0.05, 0.1, 0.15))
     q = np.zeros(20)
     q[:10] = rng.uniform(-1, 1, 10) * (rng.random(10) < 0.6)
@@ -526,7 +522,16 @@ def test_random_cubic_scenes_within_tolerance(pkg, oracle, seed):
     s.add_object(pkg.surface_make("plane", [0, -3, 0], [0, 1, 0]), (0.4, 0.5, 0.4))
     s.add_light("directional", [0.3, -1.0, 0.5], (1, 1, 1), 1.5)
     s.add_light("spherical", [2.0, 4.0, -6.0], (1, 0.9, 0.8), 300.0)
-    cam = pkg.camera_matrix(pos=(0.5, 1.0, -9.0), yaw_deg=92.0, pitch_deg=-4.0)
+    return s, pkg.camera_matrix(pos=(0.5, 1.0, -9.0), yaw_deg=92.0, pitch_deg=-4.0)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_random_cubic_scenes_within_tolerance(pkg, oracle, seed):
+    """Random degree-3 surfaces next to spheres and a plane (the cubic + mixed instantiations).  Device cbrt / acos / cos
+    differ from glibc's in the last ulp, so the bar is 1e-5 relative with at most 0.2 % of the pixels flipping at solver
+    discontinuities; wavefront and simple kernels must still agree exactly (same device functions)."""
+    w, h = 128, 96
+    s, cam = random_cubic_scene(pkg, seed, w, h)
     a = render_desc(pkg, s, cam)
     assert np.array_equal(a, render_desc(pkg, s, cam, flags=pkg.RT_FLAG_SIMPLE))
     osc = oracle_from(pkg, oracle, s)
