@@ -1769,7 +1769,9 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
                         // A directional light behind the surface contributes exactly +0 whether or not it is shadowed:
                         // surface_color multiplies by max(0.0f, (float) dot(n, light.p)) (include/light_impl.h:43), and the
                         // colour it scales is finite (checked at rt_create: flag 2).  Such lanes sit the shadow test out AND the shading of this
-                        // light.  (COUNT builds test them anyway: the reference-equivalent test count needs the index of the first blocker.)
+                        // light.  (COUNT builds test them anyway: the reference-equivalent test count needs the index of the first blocker.  They
+                        // also shade them -- the term is +0 -- but book the shading here, for the lanes the product build shades: a lane just
+                        // behind the terminator, or on a plane that faces away, is not blocked.)
                         const bool bfe = (lk.flags & 2u) != 0u;
                         const float lam = (float) dot3(nrm, D3{lk.p[0], lk.p[1], lk.p[2]});
                         const bool wanted = valid && (!bfe || 0.0f < lam); // the lanes the product build traces
@@ -1789,6 +1791,7 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
                                                                                                       own, own_ok && bfe && quad_l && wanted, 0ull, cub_rec0);
                             // the reference stops at the first blocker in index order (src/update-cpu.cpp:66-71)
                             if (valid) cnt.add(3, blocker != NO_BLOCKER ? (unsigned long long) blocker + 1ull : (unsigned long long) fa.n_obj);
+                            if (wanted && blocker == NO_BLOCKER) cnt.shaded();
                             skip |= __ballot(valid && blocker != NO_BLOCKER);
                         } else if (COUNT && valid) {
                             cnt.add(3, fa.n_obj);
@@ -1858,8 +1861,7 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
                     if (!(lk.flags & 1u)) { // directional: ((albedo / pi) * colour) * max(0, n.l), left to right (include/light_impl.h:43)
                         if (lit) {
                             const float lam = (float) dot3(n, D3{lk.p[0], lk.p[1], lk.p[2]});
-                            const float mx = (0.0f < lam) ? lam : 0.0f;
-                            cnt.shaded();
+                            const float mx = (0.0f < lam) ? lam : 0.0f; // (booked in phase B)
                             acc.x += aop.x * lk.color[0] * mx;
                             acc.y += aop.y * lk.color[1] * mx;
                             acc.z += aop.z * lk.color[2] * mx;

@@ -50,8 +50,10 @@ def test_guard_refuses_little_on_clebsch_and_everything_degenerate_on_cayley(pkg
 
 @pytest.mark.parametrize("name", ["clebsch", "cayley", "dingdong", "monkey_saddle", "cubic"])
 def test_counting_render_equals_product_render_and_branch_counts_are_the_oracles(pkg, oracle, name):
-    """The counting instantiation inlines the guarded path, the product calls it out of line: same frame.  The solver-branch counters
-    (classified on the dense coefficients) stay the oracle's whether the guard answered or not."""
+    """The counting instantiation inlines the guarded path, the product calls it out of line: same frame, and the oracle's primary and
+    shadow ray counts.  The solver-branch counters (classified on the dense coefficients whether the guard answered or not) are held to
+    the oracle's in test_counters_fuzz_gpu.py::test_degree_three_counters: shadow rays book only the tests the product build executes,
+    so each branch is bounded by the oracle's, not equal to it."""
     w, h = 240, 180
     sc = pkg.Scene.load_from_file(scene_path(name)).set_size(w, h)
     r = pkg.Renderer(sc, device=0)

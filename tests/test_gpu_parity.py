@@ -581,17 +581,23 @@ def test_row_band_ownership_variants(pkg, h, band, world):
     assert seen.all()
 
 
+def camera_cut_sequence(pkg, mirrors=False):
+    """(scene, views, (away, front, side)): cuts between an empty view, a full view and a partial one, so that the launch-order
+    lists are stale, too short (truncated) and too long in turn."""
+    sc = random_scene(pkg, 4242, 40, 6, w=640, h=360, with_plane=False, mirrors=mirrors)
+    away = pkg.camera_matrix((0.0, 0.0, 0.0), -90.0, 0.0)
+    front = pkg.camera_matrix((0.0, 0.0, 0.0), 90.0, 0.0)
+    side = pkg.camera_matrix((14.0, 2.0, 20.0), 160.0, -5.0)
+    return sc, [away, away, front, front, front, front, side, front, away, side, side, front], (away, front, side)
+
+
 def test_launch_order_feedback_survives_camera_cuts(pkg, oracle):
     """The launch order comes from the previous frame and the number of list slots from an even older one: cut between
     an empty view, a full view and a partial one so that the lists are stale, too short (truncated) and too long in
     turn.  Every frame equals the one an index-order context renders, and the first full one equals the oracle."""
-    sc = random_scene(pkg, 4242, 40, 6, w=640, h=360, with_plane=False)
+    sc, seq, (away, front, side) = camera_cut_sequence(pkg)
     r = pkg.Renderer(sc, device=0)
     ref = pkg.Renderer(sc, device=0, flags=pkg.RT_FLAG_STATIC_ORDER)
-    away = pkg.camera_matrix((0.0, 0.0, 0.0), -90.0, 0.0)
-    front = pkg.camera_matrix((0.0, 0.0, 0.0), 90.0, 0.0)
-    side = pkg.camera_matrix((14.0, 2.0, 20.0), 160.0, -5.0)
-    seq = [away, away, front, front, front, front, side, front, away, side, side, front]
     seen = {}
     for i, cam in enumerate(seq):
         r.update(cam)
@@ -621,10 +627,9 @@ def test_first_kernel_of_a_fresh_process(pkg, name, flags):
     assert out.stdout.strip().splitlines()[-1] == "OK", out.stdout
 
 
-@pytest.mark.parametrize("seed", range(8))
-def test_launch_order_feedback_random_walks(pkg, seed):
-    """Sparse random sphere fields (few tiles with hits, so the launch-order lists stay in use) under a camera that
-    drifts, jumps and comes back: every frame must equal the frame of an index-order context, bit for bit."""
+def random_walk(pkg, seed, frames=14):
+    """(scene, cameras): a sparse random sphere field (few tiles with hits, so the launch-order lists stay in use; mirrors on odd
+    seeds) and a camera that drifts, jumps, looks away for a frame (the lists go stale) and stands still."""
     rng = np.random.default_rng(7000 + seed)
     w, h = int(rng.integers(300, 700)), int(rng.integers(200, 420))
     s = pkg.Scene.new(w, h, float(rng.uniform(40, 75)), 3, (0.2, 0.3, 0.4))
@@ -638,18 +643,28 @@ def test_launch_order_feedback_random_walks(pkg, seed):
             s.add_light("spherical", rng.uniform([-20, 5, -5], [20, 25, 30]), rng.uniform(0, 1, 3), float(rng.uniform(50, 400)))
         else:
             s.add_light("directional", rng.normal(size=3) + np.array([0, -1.5, 0]), rng.uniform(0, 1, 3), float(rng.uniform(0.3, 1.2)))
-    r = pkg.Renderer(s, device=0)
-    ref = pkg.Renderer(s, device=0, flags=pkg.RT_FLAG_STATIC_ORDER)
     pos, yaw, pitch = np.array([0.0, 0.0, 0.0]), 90.0, 0.0
-    hits_seen = 0
-    for frame in range(14):
+    cams = []
+    for frame in range(frames):
         kind = rng.integers(0, 4)
         if kind == 0:      # drift
             pos = pos + rng.normal(scale=0.3, size=3); yaw += float(rng.normal(scale=2.0))
         elif kind == 1:    # jump
             pos = rng.uniform([-10, -4, -5], [10, 6, 8]); yaw = float(rng.uniform(40, 140)); pitch = float(rng.uniform(-15, 15))
         # kind == 2: look away for one frame (empty frame, the lists go stale); kind == 3: stand still
-        cam = pkg.camera_matrix(tuple(pos), -90.0 if kind == 2 else yaw, pitch)
+        cams.append(pkg.camera_matrix(tuple(pos), -90.0 if kind == 2 else yaw, pitch))
+    return s, cams
+
+
+@pytest.mark.parametrize("seed", range(8))
+def test_launch_order_feedback_random_walks(pkg, seed):
+    """Sparse random sphere fields (few tiles with hits, so the launch-order lists stay in use) under a camera that
+    drifts, jumps and comes back: every frame must equal the frame of an index-order context, bit for bit."""
+    s, cams = random_walk(pkg, seed)
+    r = pkg.Renderer(s, device=0)
+    ref = pkg.Renderer(s, device=0, flags=pkg.RT_FLAG_STATIC_ORDER)
+    hits_seen = 0
+    for frame, cam in enumerate(cams):
         r.update(cam)
         ref.update(cam)
         a, b = r.download(), ref.download()
@@ -658,14 +673,13 @@ def test_launch_order_feedback_random_walks(pkg, seed):
     assert hits_seen >= 2, "the walk never saw the scene"
 
 
-@pytest.mark.parametrize("seed", range(6))
-def test_general_camera_matrices_on_sphere_fields(pkg, oracle, seed):
-    """update() takes any dmat4, not only the rigid ones the reference's host builds: scaled, sheared and mirrored
-    camera matrices on all-sphere scenes (where the tile-level pyramid test uses the inverse transpose of the 3x3 part)
-    must still match the oracle bit for bit."""
+def general_camera_case(pkg, seed, max_w=None, max_h=None):
+    """(scene, camera): an all-sphere field under a scaled and sheared camera matrix, mirrored on every third seed; max_w / max_h
+    cap the frame size (the matrix and the spheres stay the same)."""
     rng = np.random.default_rng(9100 + seed)
-    sc = random_scene(pkg, 9100 + seed, int(rng.integers(4, 30)), int(rng.integers(1, 7)), w=int(rng.integers(150, 400)),
-                      h=int(rng.integers(100, 300)), with_plane=False, mirrors=bool(seed % 2))
+    n, lights, w, h = int(rng.integers(4, 30)), int(rng.integers(1, 7)), int(rng.integers(150, 400)), int(rng.integers(100, 300))
+    sc = random_scene(pkg, 9100 + seed, n, lights, w=w if max_w is None else min(w, max_w), h=h if max_h is None else min(h, max_h),
+                      with_plane=False, mirrors=bool(seed % 2))
     base = pkg.camera_matrix((float(rng.uniform(-3, 3)), float(rng.uniform(-2, 2)), float(rng.uniform(-4, 2))),
                              float(rng.uniform(70, 110)), float(rng.uniform(-10, 10))).reshape(4, 4).T.copy()   # row-major view
     lin = np.eye(3) + rng.normal(scale=0.25, size=(3, 3))          # shear + anisotropic scale
@@ -673,7 +687,15 @@ def test_general_camera_matrices_on_sphere_fields(pkg, oracle, seed):
         lin[:, 0] *= -1.0                                           # mirrored
     m = base.copy()
     m[:3, :3] = base[:3, :3] @ lin
-    cam = np.ascontiguousarray(m.T).reshape(16)                     # back to column-major
+    return sc, np.ascontiguousarray(m.T).reshape(16)                # back to column-major
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_general_camera_matrices_on_sphere_fields(pkg, oracle, seed):
+    """update() takes any dmat4, not only the rigid ones the reference's host builds: scaled, sheared and mirrored
+    camera matrices on all-sphere scenes (where the tile-level pyramid test uses the inverse transpose of the 3x3 part)
+    must still match the oracle bit for bit."""
+    sc, cam = general_camera_case(pkg, seed)
     got = render_desc(pkg, sc, cam)
     want = oracle_from(pkg, oracle, sc).render(cam=cam, nthreads=8)
     assert np.array_equal(got[..., :3], want)
