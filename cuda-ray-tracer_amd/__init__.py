@@ -20,8 +20,9 @@ LIB_PATH = os.environ.get("MI355RT_LIB") or os.path.join(_HERE, "libmi355rt.so")
 UPDATE_LIB_PATH = os.path.join(_HERE, "libmi355rt_update.so")
 MULTI_LIB_PATH = os.path.join(_HERE, "libmi355rt_multi.so")   # several GPUs behind one call; the only library that links RCCL
 DRIVER_PATH = os.path.join(os.path.dirname(_HERE), "tests", "host_driver", "update_driver")   # headless host of the update.h contract (tests)
+PICK_DRIVER_PATH = os.path.join(os.path.dirname(_HERE), "tests", "host_driver", "pick_driver")   # ... and of mi355rt_update_pick
 # what `make all` produces, the base library first (the one a caller checks for)
-BUILD_PRODUCTS = (os.path.join(_HERE, "libmi355rt.so"), MULTI_LIB_PATH, UPDATE_LIB_PATH, DRIVER_PATH)
+BUILD_PRODUCTS = (os.path.join(_HERE, "libmi355rt.so"), MULTI_LIB_PATH, UPDATE_LIB_PATH, DRIVER_PATH, PICK_DRIVER_PATH)
 
 RT_NCOEF = 20
 RT_FLAG_STRICT, RT_FLAG_FAST, RT_FLAG_COUNT, RT_FLAG_SIMPLE, RT_FLAG_NOCULL, RT_FLAG_STATIC_ORDER, RT_FLAG_NOSCAN, RT_FLAG_PLAIN_ORDER = 0, 1, 2, 4, 8, 16, 32, 64
@@ -41,6 +42,7 @@ ABI_SYMBOLS = [
     "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_get_ssaa_refined",
+    "rt_render_gbuffer", "rt_pick",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
@@ -88,6 +90,14 @@ class Counters(C.Structure):
         d = {n: int(getattr(self, n)) for n, _ in self._fields_}
         d["rays_total"] = d["primary_rays"] + d["shadow_rays"] + d["reflect_rays"]
         return d
+
+
+class Hit(C.Structure):
+    """rt_hit (include/mi355rt.h): what lies under one pixel's primary ray; 48 bytes."""
+    _fields_ = [("t", C.c_double), ("point", C.c_double * 3), ("normal", C.c_float * 3), ("object", C.c_int32)]
+
+
+HIT_DTYPE = np.dtype([("t", np.float64), ("point", np.float64, 3), ("normal", np.float32, 3), ("object", np.int32)])   # the same record, for numpy
 
 
 def build(verbose=False):
@@ -167,6 +177,8 @@ def lib():
         L.rt_destroy.argtypes = [vp]
         L.rt_set_ssaa_threshold.argtypes = [vp, C.c_float]
         L.rt_get_ssaa_refined.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
+        L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         _lib = L
     return _lib
 
@@ -372,6 +384,38 @@ class Renderer:
         _check(lib().rt_render(self._h, _dptr(cam), C.c_void_p(dev_fb) if dev_fb else None,
                                C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
+
+    def gbuffer(self, cam=None, object=True, t=True, normal=True, stream=None, timed=True):
+        """The primary-hit G-buffer of this rank's rows (rt_render_gbuffer): torch device tensors (object int32 [rows, W], t float64
+        [rows, W], normal float32 [rows, W, 4]; None for a plane not asked for) and the device milliseconds of the pass (None unless
+        timed).  Misses: object -1, t +inf, normal 0."""
+        import torch
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rows, w = self.local_rows, self.width
+        po = torch.empty((rows, w), dtype=torch.int32, device=dev) if object else None
+        pt = torch.empty((rows, w), dtype=torch.float64, device=dev) if t else None
+        pn = torch.empty((rows, w, 4), dtype=torch.float32, device=dev) if normal else None
+        ms = self.gbuffer_into(cam, po.data_ptr() if object else None, pt.data_ptr() if t else None, pn.data_ptr() if normal else None, stream=stream, timed=timed)
+        return po, pt, pn, ms
+
+    def gbuffer_into(self, cam, object_ptr, t_ptr, normal_ptr, stream=None, timed=True):
+        """rt_render_gbuffer into the caller's device memory (raw pointers, None = plane not written)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        ms = C.c_float(0.0)
+        _check(lib().rt_render_gbuffer(self._h, _dptr(cam), C.c_void_p(object_ptr) if object_ptr else None, C.c_void_p(t_ptr) if t_ptr else None,
+                                       C.c_void_p(normal_ptr) if normal_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def pick(self, xy, cam=None, stream=None):
+        """What lies under the pixels xy = [(x, y), ...] (global coordinates, row 0 = bottom): a structured numpy array of HIT_DTYPE
+        records (t, point, normal, object), one per pixel (rt_pick; blocks)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        q = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+        out = np.zeros(q.shape[0], dtype=HIT_DTYPE)
+        _check(lib().rt_pick(self._h, _dptr(cam), q.ctypes.data_as(C.POINTER(C.c_uint32)), q.shape[0], out.ctypes.data_as(C.POINTER(Hit)),
+                             C.c_void_p(stream) if stream else None))
+        return out
 
     def cleanup_update(self):
         if self._h:

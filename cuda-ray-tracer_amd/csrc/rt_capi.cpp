@@ -43,6 +43,13 @@ extern "C" hipError_t rt_launch_ray_list_fast(const FrameArgs *, const DevObject
 extern "C" hipError_t rt_launch_classify_strict(const void *, const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, void *, int,
                                                 uint32_t *, uint32_t *, hipStream_t);
 
+// primary-hit G-buffer and picking (rt_gbuffer.hip), per contraction mode
+extern "C" hipError_t rt_launch_gbuffer_strict(const FrameArgs *, const void *, const double *, const double *, int32_t *, double *, float *, hipStream_t);
+extern "C" hipError_t rt_launch_gbuffer_fast(const FrameArgs *, const void *, const double *, const double *, int32_t *, double *, float *, hipStream_t);
+extern "C" hipError_t rt_launch_pick_strict(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
+extern "C" hipError_t rt_launch_pick_fast(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
+extern "C" size_t rt_gbuffer_lds_bytes_strict(const FrameArgs *);
+
 namespace {
 
 thread_local std::string g_last_error;
@@ -147,6 +154,11 @@ struct rt_ctx {
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
     int lean_force = 0;           // MI355RT_LEAN=always / never (experiments)
     bool ord_on = true;           // launch-order feedback in use (off while most tiles have hits)
+    // G-buffer pass and picking (rt_render_gbuffer / rt_pick): their own events and staging memory, created on first use
+    hipEvent_t gb_ev0 = nullptr, gb_ev1 = nullptr;
+    uint32_t *d_pick_xy = nullptr; // [pick_cap][2] coordinates
+    void *d_pick_out = nullptr;    // [pick_cap] rt_hit
+    uint32_t pick_cap = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -934,6 +946,91 @@ extern "C" int rt_render_sparse(rt_ctx *ctx, const double cam[16], void *dev_msg
     return render_impl(ctx, cam, dev_msg, stream, ms, true, capacity_tiles);
 }
 
+// ---- G-buffer (rt_gbuffer.hip) ---------------------------------------------------------------------------
+// The frame arguments of a G-buffer pass: a COPY of the context's (geometry, scene layout) with this call's camera -- the context's own
+// FrameArgs, which carry the render kernels' frame-to-frame state, are neither read for that state nor written.
+static int gbuffer_args(const char *who, rt_ctx *ctx, const double cam[16], FrameArgs &fa)
+{
+    if (ctx->ssaa > 1u || ctx->adaptive)
+        return fail(RT_ERR_INVALID, "%s: not available for contexts created with RT_FLAG_SSAA2 / RT_FLAG_SSAA4 / RT_FLAG_SSAA_ADAPTIVE", who);
+    fa = ctx->fa;
+    fa.order_state = nullptr;
+    fa.ord_host = nullptr;
+    fa.tile_state = nullptr;
+    std::memcpy(fa.cam, cam, sizeof(double) * 16);
+    for (int r = 0; r < 3; r++) fa.origin[r] = (cam[0 + r] * 0.0 + cam[4 + r] * 0.0) + (cam[8 + r] * 0.0 + cam[12 + r] * 1.0); // as render_impl
+    for (size_t j = 0; j * RT_NCOEF < ctx->cub_coefs.size(); j++) { // degree-3 objects: the Taylor record of the frame's origin, as render_impl forms it
+        const rtm::CubicAt a = rtm::cubic_at(ctx->cub_coefs.data() + j * RT_NCOEF, rtm::D3{fa.origin[0], fa.origin[1], fa.origin[2]});
+        const rtm::CubicAbs ab = rtm::cubic_abs(ctx->cub_coefs.data() + j * RT_NCOEF);
+        const double v[RT_CUB_REC] = {a.f, a.gx, a.gy, a.gz, a.hxx, a.hyy, a.hzz, a.hxy, a.hxz, a.hyz};
+        const double va[4] = {ab.a3, ab.a2, ab.a1, ab.a0};
+        std::memcpy(fa.cub_rec[j], v, sizeof(v));
+        std::memcpy(fa.cub_abs[j], va, sizeof(va));
+    }
+    if (rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
+        return fail(RT_ERR_SCENE, "%s: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", who, rt_gbuffer_lds_bytes_strict(&fa));
+    int cur = -1;
+    RT_HIP(hipGetDevice(&cur));
+    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    return RT_OK;
+}
+
+extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev_object, double *dev_t, float *dev_normal, void *stream_, float *ms)
+{
+    if (!ctx || !cam) return fail(RT_ERR_INVALID, "rt_render_gbuffer: null argument");
+    if (!dev_object && !dev_t && !dev_normal) return fail(RT_ERR_INVALID, "rt_render_gbuffer: all three planes are null");
+    hipStream_t stream = (hipStream_t) stream_;
+    FrameArgs fa;
+    const int rc = gbuffer_args("rt_render_gbuffer", ctx, cam, fa);
+    if (rc != RT_OK) return rc;
+    if (ms) {
+        if (!ctx->gb_ev0) RT_HIP(hipEventCreate(&ctx->gb_ev0));
+        if (!ctx->gb_ev1) RT_HIP(hipEventCreate(&ctx->gb_ev1));
+        RT_HIP(hipEventRecord(ctx->gb_ev0, stream));
+    }
+    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_gbuffer_fast(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream)
+                                                         : rt_launch_gbuffer_strict(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "G-buffer kernel launch failed: %s", hipGetErrorString(e));
+    if (ms) {
+        RT_HIP(hipEventRecord(ctx->gb_ev1, stream));
+        RT_HIP(hipEventSynchronize(ctx->gb_ev1));
+        RT_HIP(hipEventElapsedTime(ms, ctx->gb_ev0, ctx->gb_ev1));
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream_)
+{
+    static_assert(sizeof(rt_hit) == 48, "rt_hit layout");
+    if (!ctx || !cam || !xy || !out_host) return fail(RT_ERR_INVALID, "rt_pick: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_pick: n is 0");
+    for (uint32_t i = 0; i < n; i++)
+        if (xy[2 * (size_t) i] >= ctx->width || xy[2 * (size_t) i + 1] >= ctx->height)
+            return fail(RT_ERR_INVALID, "rt_pick: pixel %u = (%u, %u) lies outside the %u x %u image", i, xy[2 * (size_t) i], xy[2 * (size_t) i + 1], ctx->width, ctx->height);
+    hipStream_t stream = (hipStream_t) stream_;
+    FrameArgs fa;
+    const int rc = gbuffer_args("rt_pick", ctx, cam, fa);
+    if (rc != RT_OK) return rc;
+    if (n > ctx->pick_cap) { // (every earlier call has synchronised: nothing uses the old buffers)
+        if (ctx->d_pick_xy) (void) hipFree(ctx->d_pick_xy);
+        if (ctx->d_pick_out) (void) hipFree(ctx->d_pick_out);
+        ctx->d_pick_xy = nullptr;
+        ctx->d_pick_out = nullptr;
+        ctx->pick_cap = 0;
+        const uint32_t cap = n < 64u ? 64u : n;
+        RT_HIP(hipMalloc((void **) &ctx->d_pick_xy, sizeof(uint32_t) * 2 * (size_t) cap));
+        RT_HIP(hipMalloc(&ctx->d_pick_out, sizeof(rt_hit) * (size_t) cap));
+        ctx->pick_cap = cap;
+    }
+    RT_HIP(hipMemcpyAsync(ctx->d_pick_xy, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_pick_fast(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_pick_xy, n, ctx->d_pick_out, stream)
+                                                         : rt_launch_pick_strict(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_pick_xy, n, ctx->d_pick_out, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pick kernel launch failed: %s", hipGetErrorString(e));
+    RT_HIP(hipMemcpyAsync(out_host, ctx->d_pick_out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
 extern "C" int rt_local_rows(const rt_ctx *ctx, uint32_t *n_rows)
 {
     if (!ctx || !n_rows) return fail(RT_ERR_INVALID, "rt_local_rows: null argument");
@@ -1146,6 +1243,10 @@ extern "C" int rt_destroy(rt_ctx *ctx)
     if (ctx->ev0) (void) hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void) hipEventDestroy(ctx->ev1);
     if (ctx->ev_done) (void) hipEventDestroy(ctx->ev_done);
+    if (ctx->gb_ev0) (void) hipEventDestroy(ctx->gb_ev0);
+    if (ctx->gb_ev1) (void) hipEventDestroy(ctx->gb_ev1);
+    if (ctx->d_pick_xy) (void) hipFree(ctx->d_pick_xy);
+    if (ctx->d_pick_out) (void) hipFree(ctx->d_pick_out);
 
     delete ctx;
     return RT_OK;

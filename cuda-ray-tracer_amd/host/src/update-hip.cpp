@@ -58,6 +58,8 @@ uint32_t g_format = RT_FMT_RGBA32F;
 void (*g_present)(unsigned int texture, unsigned int width, unsigned int height, const float *rgba) = nullptr;
 void (*g_present8)(unsigned int texture, unsigned int width, unsigned int height, const unsigned char *rgba) = nullptr;
 std::vector<unsigned char> g_staging;
+double g_last_cam[16];     // the camera of the last update() call: what mi355rt_update_pick picks with
+bool g_have_cam = false;
 
 [[noreturn]] void die(const char *what)
 {
@@ -131,6 +133,18 @@ extern "C" int mi355rt_update_download(void *host_dst, size_t bytes)
     return RT_ERR_INVALID;
 }
 extern "C" unsigned int mi355rt_update_format(void) { return g_format; }
+// What lies under pixel (x, y) (row 0 = bottom) of the frame the last update() drew: rt_pick with that call's camera.  Single-context
+// back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices, before the first update(), and for supersampling contexts.
+extern "C" int mi355rt_update_pick(unsigned int x, unsigned int y, rt_hit *out)
+{
+    if (!g_ctx || !g_have_cam || !out) {
+        rt_set_last_error(g_multi ? "mi355rt_update_pick: not available with several devices (MI355RT_DEVICES)"
+                                  : (!out ? "mi355rt_update_pick: null argument" : "mi355rt_update_pick: no update() call yet"));
+        return RT_ERR_INVALID;
+    }
+    const uint32_t xy[2] = {x, y};
+    return rt_pick(g_ctx, g_last_cam, xy, 1, out, nullptr);
+}
 
 void init_update(unsigned int texture, const Scene &scene)
 {
@@ -139,6 +153,7 @@ void init_update(unsigned int texture, const Scene &scene)
     g_width = scene.px_width;
     g_height = scene.px_height;
     g_format = RT_FMT_RGBA32F;
+    g_have_cam = false;
     if (const char *f = std::getenv("MI355RT_FORMAT")) {
         if (!std::strcmp(f, "rgba8")) g_format = RT_FMT_RGBA8;
         else if (std::strcmp(f, "rgba32f") && *f) die_text("MI355RT_FORMAT", "expected rgba32f or rgba8");
@@ -228,6 +243,8 @@ float update(const glm::dmat4 &camera_matrix)
     double cam[16];
     for (int c = 0; c < 4; c++)
         for (int r = 0; r < 4; r++) cam[c * 4 + r] = camera_matrix[c][r];
+    std::memcpy(g_last_cam, cam, sizeof(cam));
+    g_have_cam = true;
     float ms = 0.0f;
     if (g_multi) {
         if (g_mapi.render(g_multi, cam, nullptr, &ms) != RT_OK) die("update");
@@ -249,4 +266,5 @@ void cleanup_update()
     g_ctx = nullptr;
     if (g_multi) g_mapi.destroy(g_multi);
     g_multi = nullptr;
+    g_have_cam = false;
 }

@@ -290,6 +290,50 @@ int rt_set_ssaa_threshold(rt_ctx *ctx, float tau);
 /* The number of refined pixels of this context's last frame (waits for that frame). */
 int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
 
+/* ---------------------------------------------------------------------------------------------------
+ * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
+ *
+ * Definition.  For a context of W x H output pixels, camera matrix `cam` and pixel (x, y) (row 0 = bottom, as everywhere): o = the
+ * frame's ray origin (cam * (0,0,0,1)), d = the reference's primary direction of the pixel (src/update-cpu.cpp:82-89).  Run the
+ * reference's nearest-hit loop (src/update-cpu.cpp:50-56): objects in index order, t = intersect_ray(object, o, d), accepted iff
+ * t >= EPS (1e-7) && t < MAX_T (1e6) && t < best_t -- the lowest index wins a tie.  Then per pixel
+ *     object  int32        index of the accepted object                                   miss: -1
+ *     t       float64      best_t: ray parameter along the unit direction d, i.e. the distance from the eye      miss: +inf
+ *     normal  4 x float32  (float) n.x, (float) n.y, (float) n.z, 0.0f with n = normal_vector(object, o + best_t * d)
+ *                          (include/surface_impl.h:157-172: the normalised gradient, never flipped towards the eye), every component
+ *                          rounded once from FP64, to nearest even                         miss: four +0.0f
+ * Only the primary ray counts: a mirror shows itself, not what it reflects.  Each plane is [local_rows][W] in the context's own row
+ * layout (rt_local_rows, rt_row_map), so bands and ranks work as for the framebuffer; the planes do not depend on cfg.format.
+ * Strict contexts compute exactly these values for surfaces of degree <= 2 (degree 3: as the render kernels, within their guard's
+ * 1e-8 of t under the device's cbrt / acos / cos); RT_FLAG_FAST contexts run the FMA-contracted build of the same kernels.
+ * (A unit sphere's normal comes from three of its coefficients; the terms left out are exact zeros, which can only change the sign
+ * of a normal component that is itself an exact zero, and only for a hit point with a negative-zero coordinate.)
+ *
+ * Limits: primary hit only; contexts created with RT_FLAG_SSAA2, RT_FLAG_SSAA4 or RT_FLAG_SSAA_ADAPTIVE are refused (their frame
+ * arguments describe another pixel grid; supporting them is a follow-up); the multi-GPU layer (rt_*_multi) has no G-buffer entry
+ * point -- a rank-level caller gathers the planes itself with rt_row_map.
+ *
+ * The pass reads the context's scene and camera-plane tables (constant after rt_create) and nothing else: no tile words, launch-order
+ * generations, census, counters or frame tag.  Interleaving it with rt_render, on the same or another stream, changes no image and no
+ * later G-buffer; it needs no ordering against the context's frames.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt_hit {
+    double t;         /* distance from the eye, +inf on a miss */
+    double point[3];  /* o[i] + t * d[i] (multiply and add rounded separately in strict contexts); 0 on a miss */
+    float normal[3];  /* as the normal plane; 0 on a miss */
+    int32_t object;   /* -1 on a miss */
+} rt_hit;             /* 48 bytes */
+
+/* Enqueue one G-buffer pass for this rank's rows on `stream`.  Any of the three device pointers may be NULL (that plane is not
+ * written), not all three.  ms as in rt_render: NULL = enqueue only (capturable into a graph), else synchronise and report the
+ * device time of the pass.  RT_ERR_INVALID for a NULL context / camera, three NULL planes and supersampling contexts. */
+int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev_object, double *dev_t, float *dev_normal, void *stream, float *ms);
+/* n pixels by GLOBAL coordinates xy[2*i], xy[2*i+1] (any row, whatever this rank owns); blocks and writes n records to host memory.
+ * Same per-ray function as the planes: a picked pixel is bit-equal to the planes' entry.  RT_ERR_INVALID for NULL arguments, n == 0,
+ * a coordinate outside W x H (all n are checked before anything is enqueued) and supersampling contexts.  The staging buffers are the
+ * context's own (allocated on the first call, freed by rt_destroy); calls on one context must not overlap in time. */
+int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream);
+
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
 
