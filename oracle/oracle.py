@@ -55,6 +55,28 @@ def build(force=False):
     return so
 
 
+REFERENCE_DIR = os.environ.get("RT_REFERENCE_DIR", "/root/reference")
+REF_DIR = os.path.join(_HERE, "_ref")
+REF_PROGRAMS = ("ref_frames_O2", "ref_frames_O0", "ref_units_O2", "ref_units_O0")
+
+
+def reference_present():
+    """The reference tree is here and readable (it is not on a GPU box)."""
+    return os.access(os.path.join(REFERENCE_DIR, "src", "update-cpu.cpp"), os.R_OK)
+
+
+def build_ref():
+    """Compile the reference's own CPU path into oracle/_ref/ with oracle/Makefile.ref (g++ -O2 and -O0, -ffp-contract=off; the
+    reference's sources unmodified, against oracle/ref_shim/): the programs tests/test_oracle_vs_reference.py and
+    tests/test_reference_gpu.py hold the oracle and the kernels to.  Where the reference tree is absent (a GPU box) nothing is
+    built and oracle/_ref/ stays as it arrived.  Returns oracle/_ref/ when all four programs are there, else None."""
+    if reference_present():
+        p = subprocess.run(["make", "-C", _HERE, "-f", "Makefile.ref", "REF=" + REFERENCE_DIR, "OUT=_ref", "all"], capture_output=True, text=True)
+        if p.returncode != 0:
+            raise RuntimeError("oracle/Makefile.ref failed:\n" + p.stdout[-2000:] + p.stderr[-4000:])
+    return REF_DIR if all(os.access(os.path.join(REF_DIR, p), os.X_OK) for p in REF_PROGRAMS) else None
+
+
 def lib():
     global _LIB
     if _LIB is None:

@@ -1,6 +1,6 @@
 /*
  * rt_oracle.c -- CPU ORACLE (test infrastructure, NOT product code; see rt_oracle.h for the rules and
- * for the "parity unpinned" statement).
+ * for what pins it to the reference: tests/test_oracle_vs_reference.py, bit for bit).
  *
  * Plain-C restatement of the reference CPU back end.  Arithmetic type and operation ORDER follow the
  * reference exactly (FP64 geometry, FP32 colour, one FP64->FP32->FP64 round trip on the shadow
@@ -24,8 +24,8 @@ static const double K_MAX_T = 1e6;
 static const float K_PI_F = 3.14159274101257324219f;
 
 /* ------------------------------------------------------------------------------------------------
- * glm operations the reference relies on, written out (glm is an unpinned dependency;
- * this operation order defines parity at that boundary).
+ * glm operations the reference relies on, written out (glm is not vendored by the
+ * reference; this operation order -- also oracle/ref_shim/glm/glm.hpp's -- is assumed at that boundary).
  * ---------------------------------------------------------------------------------------------- */
 static inline double dot3(const double a[3], const double b[3])
 {

@@ -13,13 +13,16 @@
  * with the glm vector operations it relies on (dot, normalize, mat4*vec4, min, max, radians) written
  * out explicitly.  Every function cites the reference file:line it follows.
  *
- * PARITY UNPINNED (formally): the reference ships no tests, golden vectors or rendered outputs, and
- * its CPU path cannot be built in this image (glm, GLFW and yaml-cpp are absent and un-vendored; a
- * build against stand-in headers is not allowed).  The only cross-checks available are the
- * survey-time anchors recorded in SURVEY.md section 8(c)/8 work table (frame checksums, sample pixels, ray and
- * intersection-test counts); tests/test_oracle_anchors.py asserts the oracle reproduces all of them.
- * glm itself is an unpinned third-party dependency of the reference: the explicit operation order
- * used here ("third-party arithmetic") DEFINES parity at that boundary.
+ * PARITY: pinned bit for bit to a build of the reference's own CPU path.  oracle/Makefile.ref compiles
+ * the four sources and two headers above, unmodified, against the stand-in glm / GLFW headers of
+ * oracle/ref_shim/ into oracle/_ref/ (never committed), and tests/test_oracle_vs_reference.py holds every
+ * function below and whole frames to those programs with array_equal on the bits: shipped, random and
+ * edge scenes, every solver branch, inf / NaN inputs.  tests/test_reference_gpu.py holds the kernels to
+ * them directly.  Still assumed: glm's operation order is the stand-in's, not a
+ * real glm's ("third-party arithmetic"); glibc's cbrt / acos / cos stand on both
+ * sides; the host compiler (the reference at -O0 renders the frames it renders at -O2); and the
+ * reference's YAML loader (src/scene.cpp, yaml-cpp) is not built -- orc_radians restates Scene::Scene.
+ * The survey-time anchors of SURVEY.md section 8(c) (tests/test_oracle_anchors.py) remain a second tie.
  *
  * Build: see oracle/Makefile (gcc -O2 -ffp-contract=off, no -ffast-math: the reference's x86-64
  * default has no FMA contraction).

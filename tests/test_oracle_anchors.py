@@ -1,5 +1,7 @@
-"""The oracle against the only reference-derived numbers that exist: SURVEY.md's survey-time anchors
-(tests/golden/survey_anchors.json).  Formal status: "parity unpinned" -- see oracle/rt_oracle.h."""
+"""The oracle against SURVEY.md's survey-time anchors (tests/golden/survey_anchors.json): checksums printed with 2-6 decimals,
+work counts and sample pixels taken from the reference at native resolution with the identity camera.  They are a coarse second
+tie; what pins the oracle to the reference bit for bit is tests/test_oracle_vs_reference.py, against the programs oracle/Makefile.ref
+builds from the reference's own CPU sources (oracle/rt_oracle.h)."""
 import json
 import os
 

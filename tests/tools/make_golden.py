@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/frames_96x72.npz: float-RGB frames of all 8 scenes at 96x72 for two cameras, rendered by
-the CPU ORACLE (oracle/rt_oracle.c).  These are regression fixtures of the oracle -- the reference ships no
-rendered outputs and cannot be built here (see oracle/rt_oracle.h) -- kept so that a silent change of the
-oracle or of the HIP path shows up against committed data."""
+the CPU ORACLE (oracle/rt_oracle.c).  These are regression fixtures of the oracle, kept so that a silent change of the
+oracle or of the HIP path shows up against committed data; tests/test_oracle_vs_reference.py checks that a build of the
+reference's own CPU path renders the same 16 frames bit for bit."""
 import os
 import sys
 
