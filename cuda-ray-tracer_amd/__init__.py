@@ -30,6 +30,7 @@ RT_FLAG_NOSPLIT = 128
 RT_FLAG_NOLEAN = 256
 RT_FLAG_SSAA2, RT_FLAG_SSAA4 = 512, 1024   # k x k supersampling with an exact box-filter resolve (include/mi355rt.h)
 RT_FLAG_SSAA_ADAPTIVE = 2048                # ... only where the plain frame shows contrast (with RT_FLAG_SSAA2 or RT_FLAG_SSAA4)
+RT_FLAG_SSAA_GEOMETRY = 4096                # ... and where the primary hit changes object or its normal turns (with RT_FLAG_SSAA_ADAPTIVE)
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -41,13 +42,13 @@ ABI_SYMBOLS = [
     "rt_scene_get_desc", "rt_scene_free", "rt_camera_matrix", "rt_create", "rt_render", "rt_local_rows", "rt_max_local_rows",
     "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
-    "rt_set_ssaa_threshold", "rt_get_ssaa_refined",
+    "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined",
     "rt_render_gbuffer", "rt_pick",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
 MULTI_ABI_SYMBOLS = ["rt_create_multi", "rt_render_multi", "rt_multi_wait", "rt_multi_fb", "rt_multi_stream", "rt_multi_download", "rt_multi_info",
-                     "rt_multi_last_transfer", "rt_multi_set_ssaa_threshold", "rt_multi_destroy"]
+                     "rt_multi_last_transfer", "rt_multi_set_ssaa_threshold", "rt_multi_set_ssaa_geometry", "rt_multi_destroy"]
 RT_MULTI_SELF_EXCHANGE = 0x10000
 RT_MULTI_BANDWISE = 0x20000
 RT_MULTI_SPARSE = 0x40000
@@ -176,6 +177,7 @@ def lib():
         L.rt_debug_stamp_rows.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_destroy.argtypes = [vp]
         L.rt_set_ssaa_threshold.argtypes = [vp, C.c_float]
+        L.rt_set_ssaa_geometry.argtypes = [vp, C.c_float]
         L.rt_get_ssaa_refined.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
@@ -223,6 +225,7 @@ def multi_lib():
         M.rt_multi_last_transfer.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         M.rt_multi_destroy.argtypes = [vp]
         M.rt_multi_set_ssaa_threshold.argtypes = [vp, C.c_float]
+        M.rt_multi_set_ssaa_geometry.argtypes = [vp, C.c_float]
         _mlib = M
     return _mlib
 
@@ -339,7 +342,7 @@ from .sharding import (band_rows_of_rank, max_local_rows, assemble_index, gather
 class Renderer:
     """init_update / update / cleanup_update (reference include/update.h:6-8) as an object."""
 
-    def __init__(self, scene, device=-1, rank=0, world=1, band_rows=8, flags=RT_FLAG_STRICT, fmt=RT_FMT_RGBA32F, ssaa_threshold=None):
+    def __init__(self, scene, device=-1, rank=0, world=1, band_rows=8, flags=RT_FLAG_STRICT, fmt=RT_FMT_RGBA32F, ssaa_threshold=None, ssaa_min_cos=None):
         self._h = None
         d = scene.desc() if isinstance(scene, Scene) else scene
         self._desc = d
@@ -358,11 +361,18 @@ class Renderer:
         self.pixel_bytes = lib().rt_pixel_bytes(self._h)
         if ssaa_threshold is not None:
             self.set_ssaa_threshold(ssaa_threshold)
+        if ssaa_min_cos is not None:
+            self.set_ssaa_geometry(ssaa_min_cos)
 
     def set_ssaa_threshold(self, tau):
         """RT_FLAG_SSAA_ADAPTIVE: refine pixels whose 3x3 neighbourhood differs by more than tau in some channel (tau < 0: every
         pixel).  Applies from the next update(); a captured graph keeps the tau it was captured with."""
         _check(lib().rt_set_ssaa_threshold(self._h, float(tau)))
+
+    def set_ssaa_geometry(self, min_cos):
+        """RT_FLAG_SSAA_GEOMETRY: also refine pixels with an 8-neighbour on the same object whose normal makes a cosine below min_cos
+        with theirs (-inf, the default: object boundaries only).  Applies from the next update(), like set_ssaa_threshold."""
+        _check(lib().rt_set_ssaa_geometry(self._h, float(min_cos)))
 
     @property
     def refined(self):
@@ -521,7 +531,7 @@ class Renderer:
 class MultiRenderer:
     """init_update / update / cleanup_update over several GPUs of one node (rt_create_multi ...): the frame ends up on devices[0]."""
 
-    def __init__(self, scene, devices, band_rows=16, parts=1, flags=RT_FLAG_STRICT, fmt=RT_FMT_RGBA32F):
+    def __init__(self, scene, devices, band_rows=16, parts=1, flags=RT_FLAG_STRICT, fmt=RT_FMT_RGBA32F, ssaa_min_cos=None):
         self._h = None
         d = scene.desc() if isinstance(scene, Scene) else scene
         self._desc = d
@@ -533,6 +543,8 @@ class MultiRenderer:
         n, t = C.c_uint32(), C.c_uint32()
         _check(multi_lib().rt_multi_info(self._h, C.byref(n), C.byref(t)))
         self.n_contexts, self.transport = n.value, {0: "in place", 1: "device copies", 2: "rccl"}[t.value]
+        if ssaa_min_cos is not None:
+            self.set_ssaa_geometry(ssaa_min_cos)
 
     def last_transfer(self):
         """(bytes_sent, bytes_dense) of the last frame: what travelled to the root, and what the dense transport moves."""
@@ -543,6 +555,10 @@ class MultiRenderer:
     def set_ssaa_threshold(self, tau):
         """Renderer.set_ssaa_threshold on every context (RT_FLAG_SSAA_ADAPTIVE objects only)."""
         _check(multi_lib().rt_multi_set_ssaa_threshold(self._h, float(tau)))
+
+    def set_ssaa_geometry(self, min_cos):
+        """Renderer.set_ssaa_geometry on every context (RT_FLAG_SSAA_GEOMETRY objects only)."""
+        _check(multi_lib().rt_multi_set_ssaa_geometry(self._h, float(min_cos)))
 
     def update(self, cam=None, full_ptr=None, timed=True):
         cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)

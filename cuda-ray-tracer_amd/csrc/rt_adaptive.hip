@@ -325,6 +325,96 @@ __global__ __launch_bounds__(256) void classify_kernel(const float4 *__restrict_
     if (refine) list[base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = (lr << 16) | x;
 }
 
+// One rt_hit record as gbuffer_kernel's coordinate-list mode writes it (rt_gbuffer.hip, GbRecord): the halo rows' object and normal
+struct GeoHalo {
+    double t, p[3];
+    float n[3];
+    int32_t object;
+};
+static_assert(sizeof(GeoHalo) == 48, "rt_hit layout");
+
+// dotf of include/mi355rt.h (RT_FLAG_SSAA_GEOMETRY): float32, every operation rounded separately in every build
+__device__ __forceinline__ float geo_dot(float ax, float ay, float az, float bx, float by, float bz)
+{
+    return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
+}
+
+// classify_kernel with the geometric term of RT_FLAG_SSAA_GEOMETRY: refine(x, y) also when some 8-neighbour inside the image has
+// another primary-hit object, or the same object (>= 0) and !(dotf(N(x, y), N(n)) >= min_cos).  obj / nrm: this rank's planes
+// ([local_rows][width], gbuffer_kernel's plane mode; nrm = NULL: ids only, launch-uniform), ghalo: [2 * bands][width] records of the
+// halo rows (world > 1; the slots of `halo`).  Every neighbour is read where it lies: with bands of any height a block's
+// neighbour rows are per lane (a plane row or a halo slot), so there is no rectangular apron to stage.
+template <bool RGBA8>
+__global__ __launch_bounds__(256) void classify_geometry_kernel(const float4 *__restrict__ p, const float4 *__restrict__ halo, const int32_t *__restrict__ obj,
+                                                                const float4 *__restrict__ nrm, const GeoHalo *__restrict__ ghalo, uint32_t width,
+                                                                uint32_t height, uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world,
+                                                                uint32_t rank, float tau, float min_cos, void *out, uint32_t *__restrict__ list,
+                                                                uint32_t *__restrict__ count)
+{
+    const uint32_t tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
+    const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
+    const bool in = x < width && lr < local_rows;
+    const bool normals = nrm != nullptr; // launch-uniform
+    bool refine = false;
+    float4 c = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    if (in) {
+        const size_t at = (size_t) lr * width + x;
+        c = p[at];
+        refine = tau < 0.0f;
+        const int32_t id = obj[at];
+        float4 n0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (normals && id >= 0) n0 = nrm[at];
+        const uint32_t b = lr / band_rows, t = lr - b * band_rows;
+        const int64_t gy = ((int64_t) b * world + rank) * band_rows + t;
+        for (int dy = -1; dy <= 1 && !refine; dy++) {
+            const int64_t ny = gy + dy;
+            if (ny < 0 || ny >= (int64_t) height) continue;
+            // the neighbour row: local row r of the planes, or halo slot r (the existing classifier's rule)
+            bool from_halo = false;
+            uint32_t r = lr;
+            if (dy != 0) {
+                if (world == 1u) r = lr + dy;
+                else if (dy < 0) { from_halo = t == 0u; r = from_halo ? 2u * b : lr - 1u; }
+                else { from_halo = !(t + 1u < band_rows && lr + 1u < local_rows); r = from_halo ? 2u * b + 1u : lr + 1u; }
+            }
+            const size_t row = (size_t) r * width;
+            for (int dx = -1; dx <= 1; dx++) {
+                const int64_t nx = (int64_t) x + dx;
+                if ((dx == 0 && dy == 0) || nx < 0 || nx >= (int64_t) width) continue;
+                const float4 v = from_halo ? halo[row + nx] : p[row + nx];
+                if (!(fabsf(c.x - v.x) <= tau) || !(fabsf(c.y - v.y) <= tau) || !(fabsf(c.z - v.z) <= tau)) refine = true;
+                const int32_t idn = from_halo ? ghalo[row + nx].object : obj[row + nx];
+                if (idn != id) {
+                    refine = true;
+                } else if (normals && id >= 0) {
+                    float bx, by, bz;
+                    if (from_halo) {
+                        const GeoHalo *g = &ghalo[row + nx];
+                        bx = g->n[0]; by = g->n[1]; bz = g->n[2];
+                    } else {
+                        const float4 n1 = nrm[row + nx];
+                        bx = n1.x; by = n1.y; bz = n1.z;
+                    }
+                    if (!(geo_dot(n0.x, n0.y, n0.z, bx, by, bz) >= min_cos)) refine = true;
+                }
+            }
+        }
+    }
+    const unsigned long long m = __ballot(refine);
+    if (in && !refine) {
+        const size_t o = (size_t) lr * width + x;
+        if (RGBA8) reinterpret_cast<uchar4 *>(out)[o] = quantise(c.x, c.y, c.z);
+        else if (out != (const void *) p) reinterpret_cast<float4 *>(out)[o] = make_float4(c.x, c.y, c.z, 1.0f);
+    }
+    if (m == 0ull) return; // wave-uniform
+    uint32_t base = 0;
+    if (lane == 0u) base = atomicAdd(count, (uint32_t) __popcll(m));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (refine) list[base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = (lr << 16) | x;
+}
+
 template <int K, bool COUNT>
 hipError_t launch_rays(const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, const double *camx, const double *camy, const uint32_t *list,
                        const uint32_t *count_ptr, uint32_t n_items, uint32_t grid, void *out, int rgba8, unsigned long long *counters, hipStream_t stream)
@@ -372,5 +462,23 @@ extern "C" hipError_t RT_SYM(rt_launch_classify)(const void *p, const void *halo
     else
         hipLaunchKernelGGL((classify_kernel<false>), dim3(tiles), dim3(256), 0, stream, (const float4 *) p, (const float4 *) halo, width, height, local_rows,
                            tiles_x, band_rows, world, rank, tau, out, list, count);
+    return hipGetLastError();
+}
+
+// The same with the geometric term (RT_FLAG_SSAA_GEOMETRY): obj / nrm = this rank's id and normal planes (nrm = NULL: ids only),
+// ghalo = [2 * bands][width] rt_hit records of the halo rows (world > 1).
+extern "C" hipError_t RT_SYM(rt_launch_classify_geometry)(const void *p, const void *halo, const int32_t *obj, const float *nrm, const void *ghalo, uint32_t width,
+                                                           uint32_t height, uint32_t local_rows, uint32_t band_rows, uint32_t world, uint32_t rank, float tau,
+                                                           float min_cos, void *out, int rgba8, uint32_t *list, uint32_t *count, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    const uint32_t tiles_x = (width + 15u) / 16u, tiles = tiles_x * ((local_rows + 15u) / 16u);
+    if (tiles == 0u) return hipSuccess;
+    if (rgba8)
+        hipLaunchKernelGGL((classify_geometry_kernel<true>), dim3(tiles), dim3(256), 0, stream, (const float4 *) p, (const float4 *) halo, obj, (const float4 *) nrm,
+                           (const GeoHalo *) ghalo, width, height, local_rows, tiles_x, band_rows, world, rank, tau, min_cos, out, list, count);
+    else
+        hipLaunchKernelGGL((classify_geometry_kernel<false>), dim3(tiles), dim3(256), 0, stream, (const float4 *) p, (const float4 *) halo, obj, (const float4 *) nrm,
+                           (const GeoHalo *) ghalo, width, height, local_rows, tiles_x, band_rows, world, rank, tau, min_cos, out, list, count);
     return hipGetLastError();
 }

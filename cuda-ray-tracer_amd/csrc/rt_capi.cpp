@@ -49,6 +49,13 @@ extern "C" hipError_t rt_launch_gbuffer_fast(const FrameArgs *, const void *, co
 extern "C" hipError_t rt_launch_pick_strict(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
 extern "C" hipError_t rt_launch_pick_fast(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
 extern "C" size_t rt_gbuffer_lds_bytes_strict(const FrameArgs *);
+// RT_FLAG_SSAA_GEOMETRY: the G pass of an adaptive frame (rt_gbuffer.hip) and the classifier that reads it (rt_adaptive.hip)
+extern "C" hipError_t rt_launch_gbuffer_edges_strict(const FrameArgs *, const void *, const double *, const double *, int32_t *, float *, const uint32_t *, uint32_t,
+                                                     void *, hipStream_t);
+extern "C" hipError_t rt_launch_gbuffer_edges_fast(const FrameArgs *, const void *, const double *, const double *, int32_t *, float *, const uint32_t *, uint32_t,
+                                                   void *, hipStream_t);
+extern "C" hipError_t rt_launch_classify_geometry_strict(const void *, const void *, const int32_t *, const float *, const void *, uint32_t, uint32_t, uint32_t,
+                                                         uint32_t, uint32_t, uint32_t, float, float, void *, int, uint32_t *, uint32_t *, hipStream_t);
 
 namespace {
 
@@ -129,6 +136,13 @@ struct rt_ctx {
     uint32_t *d_list = nullptr; // [local_rows * width] refined pixels, (local row << 16) | x; d_list[local_rows * width] = their count
     double *d_camxk = nullptr, *d_camyk = nullptr; // camera-plane tables of the k-times finer sample grid
     uint32_t ray_grid = 0, halo_grid = 0;          // workgroups of the ray-list kernel (fixed per context)
+    // RT_FLAG_SSAA_GEOMETRY: the primary-hit planes of this rank's rows and the halo rows' records
+    bool geometry = false;
+    float min_cos = -INFINITY;    // rt_set_ssaa_geometry; -inf: object ids only, the normal plane is not formed
+    int32_t *d_geo_obj = nullptr; // [local_rows][width]
+    float *d_geo_nrm = nullptr;   // [local_rows][width] float4
+    uint32_t *d_geo_xy = nullptr; // world > 1: [halo_slots * width][2] global coordinates of the halo rows' pixels (constant)
+    void *d_geo_halo = nullptr;   // world > 1: [halo_slots][width] rt_hit
     DevObject *d_obj = nullptr;
     DevLight *d_light = nullptr;
     void *d_fb = nullptr;
@@ -379,6 +393,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     const uint32_t k = (cfg.flags & RT_FLAG_SSAA4) ? 4u : ((cfg.flags & RT_FLAG_SSAA2) ? 2u : 1u);
     const bool adaptive = (cfg.flags & RT_FLAG_SSAA_ADAPTIVE) != 0;
     if (adaptive && k == 1u) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_ADAPTIVE needs RT_FLAG_SSAA2 or RT_FLAG_SSAA4");
+    const bool geometry = (cfg.flags & RT_FLAG_SSAA_GEOMETRY) != 0;
+    if (geometry && !adaptive) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_GEOMETRY needs RT_FLAG_SSAA_ADAPTIVE");
     if (sd->width == 0 || sd->height == 0) return fail(RT_ERR_INVALID, "rt_create: empty image %ux%u", sd->width, sd->height);
     if (k > 1u && ((uint64_t) k * sd->width > 65536u || (uint64_t) k * sd->height > 65536u))
         return fail(RT_ERR_INVALID, "rt_create: %ux%u supersampled %ux%u exceeds 65536 samples per axis", sd->width, sd->height, k, k);
@@ -410,6 +426,7 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     ctx->height = sd->height;
     ctx->ssaa = k;
     ctx->adaptive = adaptive;
+    ctx->geometry = geometry;
     if (const char *e = std::getenv("MI355RT_RESOLVE_NT")) ctx->resolve_nt = std::atoi(e) != 0; // (experiments)
     ctx->pixel_bytes = cfg.format == RT_FMT_RGBA8 ? 4 : 16;
     ctx->local_rows = rows_of_rank(sd->height, cfg.band_rows, cfg.world, cfg.rank);
@@ -613,6 +630,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if (adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)",
                     (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)));
+    if (geometry && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
+        return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
     int rc = RT_OK;
     auto hip_ok = [&](hipError_t err, const char *what) {
         if (err != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(err));
@@ -664,6 +683,27 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
             hip_ok(hipMemcpy(ctx->d_camxk, cx.data(), sizeof(double) * cx.size(), hipMemcpyHostToDevice), "hipMemcpy(camx)") &&
             hip_ok(hipMemcpy(ctx->d_camyk, cy.data(), sizeof(double) * cy.size(), hipMemcpyHostToDevice), "hipMemcpy(camy)");
         if (rc != RT_OK) return rc;
+        if (geometry) {
+            // the halo rows' pixels by global coordinates, slot-major like d_halo; a slot outside the image is never read by the
+            // classifier: it traces the nearest image row, so that every query is a valid one
+            const size_t hpx = (size_t) ctx->halo_slots * sd->width;
+            std::vector<uint32_t> xy(2u * hpx);
+            for (uint32_t h = 0; h < ctx->halo_slots; h++) {
+                const uint32_t b = h >> 1, rows = std::min(cfg.band_rows, ctx->local_rows - b * cfg.band_rows);
+                const int64_t g0 = ((int64_t) b * cfg.world + cfg.rank) * cfg.band_rows, gy = (h & 1u) ? g0 + rows : g0 - 1;
+                const uint32_t row = (uint32_t) std::min<int64_t>(std::max<int64_t>(gy, 0), (int64_t) sd->height - 1);
+                for (uint32_t x = 0; x < sd->width; x++) {
+                    xy[2u * ((size_t) h * sd->width + x)] = x;
+                    xy[2u * ((size_t) h * sd->width + x) + 1u] = row;
+                }
+            }
+            hip_ok(hipMalloc((void **) &ctx->d_geo_obj, (px ? px : 1u) * sizeof(int32_t)), "hipMalloc(object plane)") &&
+                hip_ok(hipMalloc((void **) &ctx->d_geo_nrm, (px ? px : 1u) * 16u), "hipMalloc(normal plane)") &&
+                hip_ok(hpx ? hipMalloc((void **) &ctx->d_geo_xy, sizeof(uint32_t) * 2u * hpx) : hipSuccess, "hipMalloc(halo coordinates)") &&
+                hip_ok(hpx ? hipMalloc(&ctx->d_geo_halo, sizeof(rt_hit) * hpx) : hipSuccess, "hipMalloc(halo records)") &&
+                hip_ok(hpx ? hipMemcpy(ctx->d_geo_xy, xy.data(), sizeof(uint32_t) * 2u * hpx, hipMemcpyHostToDevice) : hipSuccess, "hipMemcpy(halo coordinates)");
+            if (rc != RT_OK) return rc;
+        }
     }
     {
         // camera-plane coordinates of every pixel column / row: render_pixel's camera_x / camera_y
@@ -902,8 +942,19 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             RT_HIP(rays(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo, 0,
                         count, ctx->d_counters, stream));
         RT_HIP(hipMemsetAsync(ctx->d_list + px, 0, sizeof(uint32_t), stream));
-        RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
-                                         dest, out8, ctx->d_list, ctx->d_list + px, stream));
+        if (ctx->geometry) {
+            // the primary-hit object (and, for a finite min_cos, normal) of this rank's rows and of the halo rows: gbuffer_kernel itself, which
+            // reads no frame state and books no rays; then the classifier with the geometric term
+            float *nrm = ctx->min_cos == -INFINITY ? nullptr : ctx->d_geo_nrm;
+            auto edges = fast ? rt_launch_gbuffer_edges_fast : rt_launch_gbuffer_edges_strict;
+            RT_HIP(edges(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nrm, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
+            RT_HIP(rt_launch_classify_geometry_strict(fb, ctx->d_halo, ctx->d_geo_obj, nrm, ctx->d_geo_halo, ctx->width, ctx->height, ctx->local_rows,
+                                                      ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau, ctx->min_cos, dest, out8, ctx->d_list,
+                                                      ctx->d_list + px, stream));
+        } else {
+            RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
+                                             dest, out8, ctx->d_list, ctx->d_list + px, stream));
+        }
         RT_HIP(rays(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
                     ctx->d_counters, stream));
         if (sparse) {
@@ -1140,6 +1191,15 @@ extern "C" int rt_set_ssaa_threshold(rt_ctx *ctx, float tau)
     return RT_OK;
 }
 
+extern "C" int rt_set_ssaa_geometry(rt_ctx *ctx, float min_cos)
+{
+    if (!ctx) return fail(RT_ERR_INVALID, "rt_set_ssaa_geometry: null argument");
+    if (!ctx->geometry) return fail(RT_ERR_INVALID, "rt_set_ssaa_geometry: the context was not created with RT_FLAG_SSAA_GEOMETRY");
+    if (std::isnan(min_cos)) return fail(RT_ERR_INVALID, "rt_set_ssaa_geometry: min_cos is NaN");
+    ctx->min_cos = min_cos;
+    return RT_OK;
+}
+
 extern "C" int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels)
 {
     if (!ctx || !pixels) return fail(RT_ERR_INVALID, "rt_get_ssaa_refined: null argument");
@@ -1230,6 +1290,10 @@ extern "C" int rt_destroy(rt_ctx *ctx)
     if (ctx->d_ss) (void) hipFree(ctx->d_ss);
     if (ctx->d_p) (void) hipFree(ctx->d_p);
     if (ctx->d_halo) (void) hipFree(ctx->d_halo);
+    if (ctx->d_geo_obj) (void) hipFree(ctx->d_geo_obj);
+    if (ctx->d_geo_nrm) (void) hipFree(ctx->d_geo_nrm);
+    if (ctx->d_geo_xy) (void) hipFree(ctx->d_geo_xy);
+    if (ctx->d_geo_halo) (void) hipFree(ctx->d_geo_halo);
     if (ctx->d_list) (void) hipFree(ctx->d_list);
     if (ctx->d_camxk) (void) hipFree(ctx->d_camxk);
     if (ctx->d_camyk) (void) hipFree(ctx->d_camyk);

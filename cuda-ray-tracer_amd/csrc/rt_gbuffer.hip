@@ -297,3 +297,17 @@ extern "C" hipError_t RT_SYM(rt_launch_pick)(const FrameArgs *fa, const void *sc
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::launch(fa, scene, camx, camy, (n + 255u) / 256u, nullptr, nullptr, nullptr, xy, n, out, stream);
 }
+
+// RT_FLAG_SSAA_GEOMETRY (rt_adaptive.hip): the object and normal planes of this rank's rows (out_normal may be
+// NULL) and, with several ranks, one record per pixel of the halo rows (halo_xy = n_halo global coordinate pairs) -- both from
+// gbuffer_kernel itself, so the adaptive frame's edges are the ones rt_render_gbuffer / rt_pick report, in the FAST build too.
+extern "C" hipError_t RT_SYM(rt_launch_gbuffer_edges)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object,
+                                                       float *out_normal, const uint32_t *halo_xy, uint32_t n_halo, void *halo_rec, hipStream_t stream)
+{
+    if (fa->n_tiles != 0u) {
+        const hipError_t e = RT_SYM(rtk)::launch(fa, scene, camx, camy, fa->n_tiles, out_object, nullptr, out_normal, nullptr, 0u, nullptr, stream);
+        if (e != hipSuccess) return e;
+    }
+    if (n_halo == 0u) return hipSuccess;
+    return RT_SYM(rtk)::launch(fa, scene, camx, camy, (n_halo + 255u) / 256u, nullptr, nullptr, nullptr, halo_xy, n_halo, halo_rec, stream);
+}

@@ -542,6 +542,16 @@ extern "C" int rt_multi_set_ssaa_threshold(rt_multi *m, float tau)
     return RT_OK;
 }
 
+extern "C" int rt_multi_set_ssaa_geometry(rt_multi *m, float min_cos)
+{
+    if (!m) return fail(RT_ERR_INVALID, "rt_multi_set_ssaa_geometry: null argument");
+    for (rt_ctx *c : m->ctx) { // (as above: NaN, or no RT_FLAG_SSAA_GEOMETRY -- the first context answers for all)
+        const int rc = rt_set_ssaa_geometry(c, min_cos);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
 extern "C" int rt_multi_info(const rt_multi *m, uint32_t *n_contexts, uint32_t *transport)
 {
     if (!m) return fail(RT_ERR_INVALID, "rt_multi_info: null argument");

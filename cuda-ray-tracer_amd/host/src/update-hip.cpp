@@ -37,6 +37,9 @@
 //                             one GPU or several; default: one ray per pixel
 //   MI355RT_SSAA_ADAPTIVE=<tau>  with MI355RT_SSAA: supersample only the pixels whose 3x3 neighbourhood differs by more than tau in some
 //                             channel (RT_FLAG_SSAA_ADAPTIVE, rt_set_ssaa_threshold); empty: the default 1/32; tau < 0: every pixel
+//   MI355RT_SSAA_GEOMETRY=<min_cos>  with MI355RT_SSAA_ADAPTIVE: also supersample the pixels next to one whose primary ray hits another
+//                             object (RT_FLAG_SSAA_GEOMETRY, rt_set_ssaa_geometry); empty: object boundaries only; a number: also where the
+//                             normals of one object make a cosine below it
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -48,6 +51,7 @@ struct MultiApi {
     int (*download)(rt_multi *, void *, size_t) = nullptr;
     int (*destroy)(rt_multi *) = nullptr;
     int (*set_threshold)(rt_multi *, float) = nullptr;
+    int (*set_geometry)(rt_multi *, float) = nullptr;
 } g_mapi;
 unsigned int g_texture = 0;
 unsigned int g_width = 0, g_height = 0;
@@ -116,7 +120,8 @@ void load_multi()
     g_mapi.download = (decltype(g_mapi.download)) dlsym(g_multi_lib, "rt_multi_download");
     g_mapi.destroy = (decltype(g_mapi.destroy)) dlsym(g_multi_lib, "rt_multi_destroy");
     g_mapi.set_threshold = (decltype(g_mapi.set_threshold)) dlsym(g_multi_lib, "rt_multi_set_ssaa_threshold");
-    if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold) die_text("libmi355rt_multi.so", "missing entry points");
+    g_mapi.set_geometry = (decltype(g_mapi.set_geometry)) dlsym(g_multi_lib, "rt_multi_set_ssaa_geometry");
+    if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold || !g_mapi.set_geometry) die_text("libmi355rt_multi.so", "missing entry points");
 }
 
 } // namespace
@@ -176,6 +181,19 @@ void init_update(unsigned int texture, const Scene &scene)
         }
         ssaa |= RT_FLAG_SSAA_ADAPTIVE;
     }
+    bool geometry = false, have_min_cos = false;
+    float min_cos = 0.0f;
+    if (const char *f = std::getenv("MI355RT_SSAA_GEOMETRY")) {
+        if (!adaptive) die_text("MI355RT_SSAA_GEOMETRY", "needs MI355RT_SSAA_ADAPTIVE");
+        geometry = true;
+        if (*f) {
+            char *end = nullptr;
+            min_cos = std::strtof(f, &end);
+            if (*end || std::isnan(min_cos)) die_text("MI355RT_SSAA_GEOMETRY", "expected a cosine (a number, or empty for object boundaries only)");
+            have_min_cos = true;
+        }
+        ssaa |= RT_FLAG_SSAA_GEOMETRY;
+    }
 
     // flatten the Scene into the ABI's descriptor (arrays are borrowed only for the call)
     const size_t no = scene.objects.size(), nl = scene.lights.size();
@@ -223,6 +241,7 @@ void init_update(unsigned int texture, const Scene &scene)
         if (g_mapi.create(&g_multi, &sd, devs.data(), (uint32_t) devs.size(), env_u32("MI355RT_BAND_ROWS", 16), env_u32("MI355RT_PARTS", 2), flags, g_format) != RT_OK)
             die("init_update (MI355RT_DEVICES)");
         if (adaptive && g_mapi.set_threshold(g_multi, tau) != RT_OK) die("init_update (MI355RT_SSAA_ADAPTIVE)");
+        if (geometry && have_min_cos && g_mapi.set_geometry(g_multi, min_cos) != RT_OK) die("init_update (MI355RT_SSAA_GEOMETRY)");
         return;
     }
     rt_config cfg{};
@@ -232,6 +251,7 @@ void init_update(unsigned int texture, const Scene &scene)
     cfg.format = g_format;
     if (rt_create(&g_ctx, &sd, &cfg) != RT_OK) die("init_update");
     if (adaptive && rt_set_ssaa_threshold(g_ctx, tau) != RT_OK) die("init_update (MI355RT_SSAA_ADAPTIVE)");
+    if (geometry && have_min_cos && rt_set_ssaa_geometry(g_ctx, min_cos) != RT_OK) die("init_update (MI355RT_SSAA_GEOMETRY)");
 }
 
 float update(const glm::dmat4 &camera_matrix)

@@ -117,6 +117,36 @@ typedef struct rt_scene_desc {
  * primary_rays = width * local_rows + halo rays + k^2 * refined (rt_get_counters_detail stays the wavefront kernel's). */
 #define RT_FLAG_SSAA_ADAPTIVE 2048u
 
+/* Geometric edges for the adaptive classifier: only valid together with RT_FLAG_SSAA_ADAPTIVE, and therefore with
+ * exactly one of RT_FLAG_SSAA2 / RT_FLAG_SSAA4 (rt_create refuses it without RT_FLAG_SSAA_ADAPTIVE with RT_ERR_INVALID before it looks
+ * for a device).  The colour term above cannot see a boundary between two surfaces that are lit alike (equal albedo under a head-on
+ * light, an object of the background's colour, a scene without lights, the fold of a cubic over itself); this flag adds what the
+ * primary ray hits.  In the notation above, with obj(x, y) and N(x, y) = the `object` entry and the first three `normal` floats of the
+ * G-buffer definition below (the primary hit on the output frame's W x H grid; a miss gives -1 and three +0.0f) and c = the normal
+ * threshold (rt_set_ssaa_geometry, default -inf):
+ *   geo(x, y)    = some 8-neighbour n of (x, y) inside the image gives
+ *                      obj(n) != obj(x, y)
+ *                   or (obj(n) == obj(x, y) >= 0  and  !(dotf(N(x, y), N(n)) >= c))
+ *   dotf(a, b)   = ((a.x * b.x) + (a.y * b.y)) + (a.z * b.z)   float32, every operation rounded separately, no FMA, identical in the
+ *                  strict and RT_FLAG_FAST builds (as the resolve's sums are)
+ *   refine(x, y) = refine of RT_FLAG_SSAA_ADAPTIVE (tau, colour)  or  geo(x, y)
+ * The output rule is unchanged: the RT_FLAG_SSAAk resolve of S where refine(x, y), else P(x, y).  A NaN dot product refines, as a NaN
+ * colour difference does; band edges are not image edges; only the primary hit counts (an edge seen in a mirror stays the colour
+ * term's business).  tau < 0 still gives the full RT_FLAG_SSAAk frame, tau = +inf now means "geometric edges only", and a pure
+ * background pixel whose eight neighbours are background stays the background pixel (so a sparse message holds the same tiles).
+ * With c = -inf the normal term can only fire on a NaN normal (a hit exactly where a surface's gradient vanishes), and the library
+ * does not form the normals at all then: object ids only, and such a pixel is not seen.  Any finite c <= -2 forms them and has
+ * exactly the meaning the definition gives c = -inf.  No default crease angle is chosen: nobody has measured one.
+ * In strict contexts obj and N are the G-buffer definition's values for surfaces of degree <= 2; in RT_FLAG_FAST contexts (and for
+ * degree 3) they are bit for bit what rt_render_gbuffer / rt_pick report on a context without supersampling and otherwise equal flags
+ * (the same kernel computes them).  rt_render adds, on `stream`, that kernel for this rank's rows (and, world > 1, for the rows just
+ * outside each band) in front of the classify kernel; still nothing is read back and frames can be captured into a graph.
+ * rt_get_ssaa_refined and rt_render_sparse work as in every adaptive context.  RT_FLAG_COUNT does not book the rays of that pass (as
+ * rt_render_gbuffer books none): primary_rays = width * local_rows + halo rays + k^2 * refined, with the new refined count.
+ * Known limits: two sheets of ONE object at different depths whose normals agree are not told apart (there is no depth term), and a
+ * mirror shows only itself.  rt_render_gbuffer and rt_pick keep refusing every supersampling context. */
+#define RT_FLAG_SSAA_GEOMETRY 4096u
+
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
                                  produces (src/update-cpu.cpp:128-131) plus an alpha lane for 16-byte stores */
@@ -287,6 +317,10 @@ int rt_debug_stamp_rows(rt_ctx *ctx, uint64_t *out, size_t max_rows, size_t *n_r
 /* RT_FLAG_SSAA_ADAPTIVE contexts only (RT_ERR_INVALID otherwise; a NaN tau is refused too).  The threshold applies from the next
  * rt_render on; it is a kernel argument, so a frame captured into a graph keeps the tau it was captured with. */
 int rt_set_ssaa_threshold(rt_ctx *ctx, float tau);
+/* RT_FLAG_SSAA_GEOMETRY contexts only (RT_ERR_INVALID for a NULL context, a context without the flag and a NaN min_cos): the normal
+ * threshold c of the geometric term, default -inf (object ids only).  Like tau it applies from the next rt_render on and is a kernel
+ * argument, so a frame captured into a graph keeps the value it was captured with. */
+int rt_set_ssaa_geometry(rt_ctx *ctx, float min_cos);
 /* The number of refined pixels of this context's last frame (waits for that frame). */
 int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
 
@@ -381,6 +415,8 @@ int rt_multi_info(const rt_multi *m, uint32_t *n_contexts, uint32_t *transport /
 int rt_multi_last_transfer(const rt_multi *m, uint64_t *bytes_sent, uint64_t *bytes_dense);
 /* rt_set_ssaa_threshold on every context of the object (RT_FLAG_SSAA_ADAPTIVE objects only). */
 int rt_multi_set_ssaa_threshold(rt_multi *m, float tau);
+/* rt_set_ssaa_geometry on every context of the object (RT_FLAG_SSAA_GEOMETRY objects only). */
+int rt_multi_set_ssaa_geometry(rt_multi *m, float min_cos);
 int rt_multi_destroy(rt_multi *m);
 
 #ifdef __cplusplus
