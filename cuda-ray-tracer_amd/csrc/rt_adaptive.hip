@@ -106,7 +106,7 @@ __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevOb
                 }
                 for (uint32_t base = 0; base < fa.n_obj; base += 64u) {
                     unsigned long long mask;
-                    if (cull) {
+                    if (cull && (spherical || fabs(lt->u2) > EPS)) { // (a directional light with |d|^2 <= EPS: the reference's linear branch, t = -t0 / t1, is not geometry -- test everything)
                         const uint32_t j = base + lane;
                         bool rel = false;
                         if (j < fa.n_obj) rel = spherical ? sphere_relevant<true>(scull[j], ball, *lt) : sphere_relevant<false>(scull[j], ball, *lt);

@@ -571,6 +571,7 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         std::memcpy(blob.data() + fa.off_mat + i * sizeof(MatEntry), &m, sizeof(m));
     }
     std::vector<DevLight> lights(sd->n_lights);
+    std::vector<char> term_finite(sd->n_lights, 0); // this light's colour and every albedo are finite: a factor max(0, n.l) = 0 makes its term exactly +0
     for (uint32_t i = 0; i < sd->n_lights; i++) {
         DevLight &l = lights[i];
         std::memset(&l, 0, sizeof(l));
@@ -592,6 +593,7 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         bool finite = std::isfinite(l.color[0]) && std::isfinite(l.color[1]) && std::isfinite(l.color[2]);
         for (uint32_t k = 0; k < sd->n_objects * 3u && finite; k++) finite = std::isfinite(sd->albedo[k]);
         l.backface_exact = (!l.spherical && finite) ? 1u : 0u;
+        term_finite[i] = finite ? 1 : 0;
     }
     fa.lights_plain = 1u;
     std::vector<LightK> lightk(sd->n_lights); // the same lights as the lean path reads them (rt_scene_dev.h)
@@ -605,7 +607,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         k.s_yz = std::fabs(l.sdir[1]) + std::fabs(l.sdir[2]);
         k.s_xz = std::fabs(l.sdir[0]) + std::fabs(l.sdir[2]);
         k.s_xy = std::fabs(l.sdir[0]) + std::fabs(l.sdir[1]);
-        k.flags = (l.spherical ? 1u : 0u) | (l.backface_exact ? 2u : 0u) | (std::fabs(l.u2) > 1e-7 ? 4u : 0u); // EPS of include/surface_impl.h:16,138
+        k.flags = (l.spherical ? 1u : 0u) | (l.backface_exact ? 2u : 0u) | (std::fabs(l.u2) > 1e-7 ? 4u : 0u) | // EPS of include/surface_impl.h:16,138
+                  ((l.spherical && term_finite[i]) ? 8u : 0u);
         if (!l.spherical && (k.flags & 6u) != 6u) fa.lights_plain = 0u;
     }
 

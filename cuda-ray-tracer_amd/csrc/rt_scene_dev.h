@@ -101,7 +101,7 @@ struct alignas(64) LightK {
     double four_u2;     // 4.0 * u2: the factor of t0 in the discriminant (include/surface_impl.h:139)
     double s_yz, s_xz, s_xy; // |sdir.y| + |sdir.z|, |sdir.x| + |sdir.z|, |sdir.x| + |sdir.y|: the box stage of the culling
     float color[3];     // LightSource::light_color
-    uint32_t flags;     // 1 spherical   2 backface_exact (DevLight)   4 |sdir|^2 > EPS (the reference solves a quadratic for this light's rays)
+    uint32_t flags;     // 1 spherical   2 backface_exact (DevLight)   4 |sdir|^2 > EPS (the reference solves a quadratic for this light's rays)   8 spherical, its colour and every albedo finite (behind the surface its term is exactly +0)
     uint32_t pad[2];
 };                      // 128 B: two 64-byte scalar loads
 static_assert(sizeof(LightK) == 128, "LightK layout");

@@ -771,7 +771,11 @@ __device__ __forceinline__ int shadow_blocker(const FrameArgs &fa, const SceneLd
         unsigned long long cand = 0;
         if (fa.cull) {
             unsigned long long it;
-            if (!SPHERICAL && base == 0) {
+            if (!SPHERICAL && !quad) {
+                // |d|^2 <= EPS: the reference takes its linear branch, t = -t0 / t1, which is not where the ray meets the sphere -- the
+                // culling tests, which are geometry, say nothing about it: every sphere is a candidate (wave-uniform: quad is a scalar here)
+                it = __ballot(base + lane < end);
+            } else if (!SPHERICAL && base == 0) {
                 it = relevant_mask_directional(crec, end, sm.d, lt.inv_uu, lt.len_u, lane); // sm.d is this light's FP32-rounded direction
                 if (__popcll(it) >= BOX_STAGE_MIN) { // wave-uniform: many got through the ball -- look again with the box
                     if constexpr (OWN) it &= __ballot(lane < end && crec_in_box_shadow(crec[lane], *boxp, sm.d, lt.s_yz, lt.s_xz, lt.s_xy));
@@ -780,7 +784,7 @@ __device__ __forceinline__ int shadow_blocker(const FrameArgs &fa, const SceneLd
                 }
             }
             else it = relevant_mask<SPHERICAL>(S.us, base, end, *ballp, lt, lane); // (the ball is read from LDS here, not kept)
-            if (lane == 0 && prod_any) cnt.cull(SPHERICAL ? C_SHADOW_SPH : C_SHADOW_DIR, end - base);
+            if (lane == 0 && prod_any && (SPHERICAL || quad)) cnt.cull(SPHERICAL ? C_SHADOW_SPH : C_SHADOW_DIR, end - base);
             if (OWN && base == 0) it &= ~own_excl;
             if (!OWN && prod) cnt.exec(K_US, (unsigned long long) __popcll(it));
             while (it) { // wave-uniform loop over the spheres that survived the culling
@@ -1082,7 +1086,9 @@ __device__ __forceinline__ void lean_block(const FrameArgs &fa, const SceneLds &
                     const double dx = lk.p[0] - spl.x, dy = lk.p[1] - spl.y, dz = lk.p[2] - spl.z;
                     const double q = dot3(sn, D3{dx, dy, dz});
                     const double mag = fabs(sn.x * dx) + fabs(sn.y * dy) + fabs(sn.z * dz);
-                    const bool wanted = hit && !(q < -1e-9 * mag); // behind the surface by a margin 10^7 times the rounding: the term is +0 (as in the other path)
+                    // behind the surface by a margin 10^7 times the rounding: the term is +0 (as in the other path) -- with finite colours (flag 8);
+                    // inf * 0 is NaN, which the clamp turns into 1 unless the ray is blocked
+                    const bool wanted = hit && !((lk.flags & 8u) != 0u && q < -1e-9 * mag);
                     if (COUNT || __any(wanted)) {
                         Mono sd;
                         sd.o = sm.o; sd.u0 = sm.u0;
@@ -1805,7 +1811,8 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
                         const double dx = lk.p[0] - p.x, dy = lk.p[1] - p.y, dz = lk.p[2] - p.z;
                         const double q = dot3(nrm, D3{dx, dy, dz});
                         const double mag = fabs(nrm.x * dx) + fabs(nrm.y * dy) + fabs(nrm.z * dz);
-                        const bool wanted = valid && !(q < -1e-9 * mag);
+                        // (flag 8: colour and albedos finite -- otherwise the term is NaN, not +0, unless the ray is blocked)
+                        const bool wanted = valid && !((lk.flags & 8u) != 0u && q < -1e-9 * mag);
                         skip = 0ull;
                         if (COUNT || __any(wanted)) {
                             Mono sd = sm;

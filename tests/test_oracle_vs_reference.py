@@ -188,6 +188,42 @@ def test_random_and_edge_scenes_of_the_gpu_suites(pkg, oracle, key):
     bits_equal(osc.render(cam=cam, nthreads=4), R.render(osc, [cam])[0], str(key))
 
 
+def _raw():
+    return _tool("raw_desc_scenes")
+
+
+def _raw_names():
+    import raw_desc_scenes as S
+    return list(S.NAMED)
+
+
+def _raw_seeds():
+    import raw_desc_scenes as S
+    return list(range(S.N_SEEDS))
+
+
+@pytest.mark.parametrize("name", _raw_names())
+def test_raw_descriptor_named_scenes(oracle, name):
+    """tests/tools/raw_desc_scenes.py: directional lights of any length (short, zero, long, NaN, inf), colours, albedos, reflection
+    ratios and backgrounds that are not finite or not in [0, 1] -- inputs only a raw scene description holds, lights as stored records.
+    The GPU tests (tests/test_raw_descriptor_gpu.py) take the oracle's word on them; here the reference renders them, two cameras."""
+    s, twin, cams = _raw().named(name)
+    ref = R.render(s, cams)
+    for i, cam in enumerate(cams):
+        bits_equal(s.render(cam=cam, nthreads=4), ref[i], f"{name} camera {i}")
+    bits_equal(twin.render(cam=cams[0], nthreads=4), R.render(twin, cams[:1])[0], f"{name}, the twin")
+
+
+@pytest.mark.parametrize("seed", _raw_seeds())
+def test_raw_descriptor_generated_scenes(oracle, seed):
+    """The seeded generator of the same module: the scene's own camera and the identity."""
+    s, cam = _raw().scene(seed)
+    cams = [cam, None]
+    ref = R.render(s, cams)
+    for i, c in enumerate(cams):
+        bits_equal(s.render(cam=c, nthreads=4), ref[i], f"seed {seed} camera {i}")
+
+
 def _own_edge_scenes(O):
     """Edges no builder above has: lights behind and on the surface, reflection_ratio at and around EPS, coincident objects,
     a scene with nothing in it, a hit exactly at EPS and at MAX_T."""
