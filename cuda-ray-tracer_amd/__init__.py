@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined",
     "rt_render_gbuffer", "rt_pick",
+    "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
@@ -99,6 +100,14 @@ class Hit(C.Structure):
 
 
 HIT_DTYPE = np.dtype([("t", np.float64), ("point", np.float64, 3), ("normal", np.float32, 3), ("object", np.int32)])   # the same record, for numpy
+
+
+class Ray(C.Structure):
+    """rt_ray (include/mi355rt.h): origin and direction of one ray query, the direction used as given; 48 bytes."""
+    _fields_ = [("o", C.c_double * 3), ("d", C.c_double * 3)]
+
+
+RAY_DTYPE = np.dtype([("o", np.float64, 3), ("d", np.float64, 3)])   # the same record, for numpy
 
 
 def build(verbose=False):
@@ -181,6 +190,9 @@ def lib():
         L.rt_get_ssaa_refined.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
+        L.rt_trace_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, fp]
+        L.rt_occluded_rays.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, fp]
+        L.rt_trace_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.POINTER(Hit), vp]
         _lib = L
     return _lib
 
@@ -426,6 +438,54 @@ class Renderer:
         _check(lib().rt_pick(self._h, _dptr(cam), q.ctypes.data_as(C.POINTER(C.c_uint32)), q.shape[0], out.ctypes.data_as(C.POINTER(Hit)),
                              C.c_void_p(stream) if stream else None))
         return out
+
+    @staticmethod
+    def rays(origins, dirs):
+        """RAY_DTYPE records from origins and directions ([n, 3] each, or one of them a single vector for all rays)."""
+        o, d = np.asarray(origins, dtype=np.float64), np.asarray(dirs, dtype=np.float64)
+        n = max(o.size, d.size) // 3
+        out = np.zeros(n, dtype=RAY_DTYPE)
+        out["o"] = o.reshape(-1, 3)
+        out["d"] = d.reshape(-1, 3)
+        return out
+
+    def trace(self, origins, dirs, stream=None):
+        """The closest hit of every ray (rt_trace_rays_host; blocks): a structured numpy array of HIT_DTYPE records.  Directions are
+        used as given (t is in units of |d|); a miss is object -1, t +inf, point and normal 0.  Works in every context kind."""
+        rays = self.rays(origins, dirs)
+        out = np.zeros(len(rays), dtype=HIT_DTYPE)
+        _check(lib().rt_trace_rays_host(self._h, rays.ctypes.data_as(C.POINTER(Ray)), len(rays), out.ctypes.data_as(C.POINTER(Hit)),
+                                        C.c_void_p(stream) if stream else None))
+        return out
+
+    def trace_into(self, ray_ptr, n, hit_ptr, stream=None, timed=True):
+        """rt_trace_rays on the caller's device memory (raw pointers to n rt_ray / n rt_hit, 16-byte aligned): device milliseconds, or
+        None unless timed (then the call only enqueues one kernel)."""
+        ms = C.c_float(0.0)
+        _check(lib().rt_trace_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, int(n), C.c_void_p(hit_ptr) if hit_ptr else None,
+                                   C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def occluded(self, origins, dirs, t_max=None, stream=None, timed=True):
+        """Is each ray blocked by some object at EPS < t < t_max (rt_occluded_rays; t_max: one value per ray, None = 1e6 for all)?
+        Returns (torch int32 device tensor [n] of 1 / 0, device milliseconds or None)."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        rays = self.rays(origins, dirs)
+        d_rays = torch.from_numpy(rays.view(np.float64).reshape(-1, 6)).to(dev)
+        d_tmax = None if t_max is None else torch.from_numpy(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (len(rays),)).copy()).to(dev)
+        out = torch.empty((len(rays),), dtype=torch.int32, device=dev)
+        if stream:   # the uploads above ran on torch's current stream
+            torch.cuda.current_stream().synchronize()
+        ms = self.occluded_into(d_rays.data_ptr(), None if d_tmax is None else d_tmax.data_ptr(), len(rays), out.data_ptr(), stream=stream, timed=timed)
+        return out, ms
+
+    def occluded_into(self, ray_ptr, t_max_ptr, n, blocked_ptr, stream=None, timed=True):
+        """rt_occluded_rays on the caller's device memory (raw pointers; t_max_ptr None = 1e6 for every ray)."""
+        ms = C.c_float(0.0)
+        _check(lib().rt_occluded_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, C.c_void_p(t_max_ptr) if t_max_ptr else None, int(n),
+                                      C.c_void_p(blocked_ptr) if blocked_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
 
     def cleanup_update(self):
         if self._h:

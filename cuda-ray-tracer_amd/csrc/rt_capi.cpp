@@ -49,6 +49,12 @@ extern "C" hipError_t rt_launch_gbuffer_fast(const FrameArgs *, const void *, co
 extern "C" hipError_t rt_launch_pick_strict(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
 extern "C" hipError_t rt_launch_pick_fast(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
 extern "C" size_t rt_gbuffer_lds_bytes_strict(const FrameArgs *);
+// ray queries (rt_rays.hip), per contraction mode
+extern "C" hipError_t rt_launch_trace_rays_strict(const FrameArgs *, const void *, const void *, uint32_t, void *, uint32_t, hipStream_t);
+extern "C" hipError_t rt_launch_trace_rays_fast(const FrameArgs *, const void *, const void *, uint32_t, void *, uint32_t, hipStream_t);
+extern "C" hipError_t rt_launch_occluded_rays_strict(const FrameArgs *, const void *, const void *, const double *, uint32_t, int32_t *, uint32_t, hipStream_t);
+extern "C" hipError_t rt_launch_occluded_rays_fast(const FrameArgs *, const void *, const void *, const double *, uint32_t, int32_t *, uint32_t, hipStream_t);
+extern "C" size_t rt_rays_lds_bytes_strict(const FrameArgs *);
 // RT_FLAG_SSAA_GEOMETRY: the G pass of an adaptive frame (rt_gbuffer.hip) and the classifier that reads it (rt_adaptive.hip)
 extern "C" hipError_t rt_launch_gbuffer_edges_strict(const FrameArgs *, const void *, const double *, const double *, int32_t *, float *, const uint32_t *, uint32_t,
                                                      void *, hipStream_t);
@@ -173,6 +179,11 @@ struct rt_ctx {
     uint32_t *d_pick_xy = nullptr; // [pick_cap][2] coordinates
     void *d_pick_out = nullptr;    // [pick_cap] rt_hit
     uint32_t pick_cap = 0;
+    // ray queries (rt_trace_rays / rt_occluded_rays / rt_trace_rays_host): their own events and staging memory, created on first use
+    hipEvent_t rq_ev0 = nullptr, rq_ev1 = nullptr;
+    void *d_rq_rays = nullptr; // [rq_cap] rt_ray
+    void *d_rq_hits = nullptr; // [rq_cap] rt_hit
+    uint32_t rq_cap = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -1085,6 +1096,108 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
     return RT_OK;
 }
 
+// ---- ray queries (rt_rays.hip) ----------------------------------------------------------------------------
+// A ray query reads the scene blob only: of the context's FrameArgs it takes the scene-layout words (the same in every context kind,
+// supersampling included) and nothing of the frame.
+static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    const uintptr_t pa = (uintptr_t) a, pb = (uintptr_t) b;
+    return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+
+static int rays_ready(const char *who, rt_ctx *ctx)
+{
+    if (rt_rays_lds_bytes_strict(&ctx->fa) > 160u * 1024u)
+        return fail(RT_ERR_SCENE, "%s: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", who, rt_rays_lds_bytes_strict(&ctx->fa));
+    int cur = -1;
+    RT_HIP(hipGetDevice(&cur));
+    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    return RT_OK;
+}
+
+// workgroups of one ray-query launch: four per CU (the kernels' registers allow three to four resident ones), fewer for few rays
+static uint32_t rays_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
+
+static int rays_timed(rt_ctx *ctx, hipStream_t stream, float *ms, bool begin)
+{
+    if (!ms) return RT_OK;
+    if (begin) {
+        if (!ctx->rq_ev0) RT_HIP(hipEventCreate(&ctx->rq_ev0));
+        if (!ctx->rq_ev1) RT_HIP(hipEventCreate(&ctx->rq_ev1));
+        RT_HIP(hipEventRecord(ctx->rq_ev0, stream));
+    } else {
+        RT_HIP(hipEventRecord(ctx->rq_ev1, stream));
+        RT_HIP(hipEventSynchronize(ctx->rq_ev1));
+        RT_HIP(hipEventElapsedTime(ms, ctx->rq_ev0, ctx->rq_ev1));
+    }
+    return RT_OK;
+}
+
+extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_hit *dev_hits, void *stream_, float *ms)
+{
+    static_assert(sizeof(rt_ray) == 48 && sizeof(rt_hit) == 48, "rt_ray / rt_hit layout");
+    if (!ctx || !dev_rays || !dev_hits) return fail(RT_ERR_INVALID, "rt_trace_rays: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_trace_rays: n is 0");
+    if (((uintptr_t) dev_rays | (uintptr_t) dev_hits) & 15u) return fail(RT_ERR_INVALID, "rt_trace_rays: rays and hits must be 16-byte aligned");
+    if (ranges_overlap(dev_rays, sizeof(rt_ray) * (size_t) n, dev_hits, sizeof(rt_hit) * (size_t) n))
+        return fail(RT_ERR_INVALID, "rt_trace_rays: the rays and the hits overlap");
+    hipStream_t stream = (hipStream_t) stream_;
+    int rc = rays_ready("rt_trace_rays", ctx);
+    if (rc != RT_OK) return rc;
+    if ((rc = rays_timed(ctx, stream, ms, true)) != RT_OK) return rc;
+    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_trace_rays_fast(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream)
+                                                         : rt_launch_trace_rays_strict(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
+    return rays_timed(ctx, stream, ms, false);
+}
+
+extern "C" int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const double *dev_t_max, uint32_t n, int32_t *dev_blocked, void *stream_, float *ms)
+{
+    if (!ctx || !dev_rays || !dev_blocked) return fail(RT_ERR_INVALID, "rt_occluded_rays: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_occluded_rays: n is 0");
+    if ((uintptr_t) dev_rays & 15u) return fail(RT_ERR_INVALID, "rt_occluded_rays: rays must be 16-byte aligned");
+    if (((uintptr_t) dev_t_max & 7u) || ((uintptr_t) dev_blocked & 3u)) return fail(RT_ERR_INVALID, "rt_occluded_rays: t_max / flags are not aligned to their type");
+    if (ranges_overlap(dev_rays, sizeof(rt_ray) * (size_t) n, dev_blocked, sizeof(int32_t) * (size_t) n) ||
+        (dev_t_max && ranges_overlap(dev_t_max, sizeof(double) * (size_t) n, dev_blocked, sizeof(int32_t) * (size_t) n)))
+        return fail(RT_ERR_INVALID, "rt_occluded_rays: the flags overlap the rays or t_max");
+    hipStream_t stream = (hipStream_t) stream_;
+    int rc = rays_ready("rt_occluded_rays", ctx);
+    if (rc != RT_OK) return rc;
+    if ((rc = rays_timed(ctx, stream, ms, true)) != RT_OK) return rc;
+    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_occluded_rays_fast(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream)
+                                                         : rt_launch_occluded_rays_strict(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
+    return rays_timed(ctx, stream, ms, false);
+}
+
+extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, rt_hit *out, void *stream_)
+{
+    if (!ctx || !rays || !out) return fail(RT_ERR_INVALID, "rt_trace_rays_host: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_trace_rays_host: n is 0");
+    if (ranges_overlap(rays, sizeof(rt_ray) * (size_t) n, out, sizeof(rt_hit) * (size_t) n)) return fail(RT_ERR_INVALID, "rt_trace_rays_host: the rays and the hits overlap");
+    hipStream_t stream = (hipStream_t) stream_;
+    const int rc = rays_ready("rt_trace_rays_host", ctx);
+    if (rc != RT_OK) return rc;
+    if (n > ctx->rq_cap) { // (every earlier call has synchronised: nothing uses the old buffers)
+        if (ctx->d_rq_rays) (void) hipFree(ctx->d_rq_rays);
+        if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
+        ctx->d_rq_rays = nullptr;
+        ctx->d_rq_hits = nullptr;
+        ctx->rq_cap = 0;
+        const uint32_t cap = n < 64u ? 64u : n;
+        RT_HIP(hipMalloc(&ctx->d_rq_rays, sizeof(rt_ray) * (size_t) cap));
+        RT_HIP(hipMalloc(&ctx->d_rq_hits, sizeof(rt_hit) * (size_t) cap));
+        ctx->rq_cap = cap;
+    }
+    RT_HIP(hipMemcpyAsync(ctx->d_rq_rays, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_trace_rays_fast(&ctx->fa, ctx->d_obj, ctx->d_rq_rays, n, ctx->d_rq_hits, rays_max_grid(ctx), stream)
+                                                         : rt_launch_trace_rays_strict(&ctx->fa, ctx->d_obj, ctx->d_rq_rays, n, ctx->d_rq_hits, rays_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
+    RT_HIP(hipMemcpyAsync(out, ctx->d_rq_hits, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
 extern "C" int rt_local_rows(const rt_ctx *ctx, uint32_t *n_rows)
 {
     if (!ctx || !n_rows) return fail(RT_ERR_INVALID, "rt_local_rows: null argument");
@@ -1314,6 +1427,10 @@ extern "C" int rt_destroy(rt_ctx *ctx)
     if (ctx->gb_ev1) (void) hipEventDestroy(ctx->gb_ev1);
     if (ctx->d_pick_xy) (void) hipFree(ctx->d_pick_xy);
     if (ctx->d_pick_out) (void) hipFree(ctx->d_pick_out);
+    if (ctx->d_rq_rays) (void) hipFree(ctx->d_rq_rays);
+    if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
+    if (ctx->rq_ev0) (void) hipEventDestroy(ctx->rq_ev0);
+    if (ctx->rq_ev1) (void) hipEventDestroy(ctx->rq_ev1);
 
     delete ctx;
     return RT_OK;

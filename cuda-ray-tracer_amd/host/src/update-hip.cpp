@@ -151,6 +151,18 @@ extern "C" int mi355rt_update_pick(unsigned int x, unsigned int y, rt_hit *out)
     return rt_pick(g_ctx, g_last_cam, xy, 1, out, nullptr);
 }
 
+// The closest hit of n caller-supplied rays against the scene init_update() loaded (rt_trace_rays_host; include/mi355rt.h, "Ray
+// queries").  Valid after init_update(): unlike picking it needs no earlier update() call, a ray query uses no camera.  Single-context
+// back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices and before init_update().
+extern "C" int mi355rt_update_trace(const rt_ray *rays, unsigned int n, rt_hit *out)
+{
+    if (!g_ctx) {
+        rt_set_last_error(g_multi ? "mi355rt_update_trace: not available with several devices (MI355RT_DEVICES)" : "mi355rt_update_trace: no init_update() call yet");
+        return RT_ERR_INVALID;
+    }
+    return rt_trace_rays_host(g_ctx, rays, n, out, nullptr);
+}
+
 void init_update(unsigned int texture, const Scene &scene)
 {
     if (g_ctx || g_multi) cleanup_update();

@@ -368,6 +368,62 @@ int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev_object, do
  * context's own (allocated on the first call, freed by rt_destroy); calls on one context must not overlap in time. */
 int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream);
 
+/* ---------------------------------------------------------------------------------------------------
+ * Ray queries: closest hit and occlusion for rays the caller supplies (csrc/rt_rays.hip)
+ *
+ * The G-buffer and rt_pick answer "what does the primary ray of this pixel hit"; these answer it for ANY ray: a reflection followed
+ * from a hit point, a shadow ray towards a light, another camera (orthographic, fisheye, stereo, cube map), a line-of-sight or
+ * collision probe.  A ray is an origin and a direction; the direction is used exactly as given, never normalised, so t is in units
+ * of |d| as in intersect_ray (include/surface_impl.h:21).
+ *
+ * Closest hit.  The reference's nearest-hit loop (src/update-cpu.cpp:50-56) over the scene's objects in index order:
+ * t = intersect_ray(object, o, d), accepted iff t >= EPS (1e-7) && t < MAX_T (1e6) && t < best_t -- the lowest index wins a tie.  One
+ * rt_hit per ray: object; t = best_t; point[i] = o[i] + t * d[i] (multiply and add rounded separately in strict contexts);
+ * normal = (float) normal_vector(object, point) (include/surface_impl.h:157-172), never flipped.  A miss gives object = -1, t = +inf
+ * and +0.0 in point and normal: exactly what rt_pick writes.
+ *
+ * Occlusion.  The reference's shadow loop (src/update-cpu.cpp:66-72): ray i is blocked iff some object gives
+ * t > EPS && t < t_max[i] -- both comparisons strict, and `>` where the closest hit has `>=`.  t_max is a device array of n doubles;
+ * NULL means MAX_T (1e6) for every ray; a NaN t_max blocks nothing.  One int32 per ray, 1 (blocked) or 0.
+ *
+ * Nothing is skipped on the caller's behalf in either query: no own-sphere rule, no shadow bias, no round trip of the direction
+ * through float.  A caller that wants the reference's shadow decision for a hit (point sp, normal n in FP64) and a light forms the
+ * ray itself, as include/light_impl.h:17-27 and src/update-cpu.cpp:67 do:
+ *     o = sp + SHADOW_BIAS * n          SHADOW_BIAS = 1e-2 (include/surface_impl.h:18)
+ *     directional light:  d = (double) (float) light.p,         t_max = 1e6
+ *     point light:        d = (double) (float) (light.p - sp),   t_max = 1.0       (the difference in FP64, then rounded to float)
+ * and lights the hit where the ray is not blocked.  (rt_hit carries the normal in float; the reference's own decision uses the FP64
+ * normal, which a caller recomputes from the surface's coefficients at `point` when it needs the reference's bits.)
+ *
+ * Accuracy.  Strict contexts compute exactly these values for surfaces of degree <= 2, for every ray: zero directions, |d|^2 <= EPS
+ * (the reference's linear branch) and non-finite components included; a NaN t is never accepted.  The class tables and the deferred
+ * root solves are used where they are proven -- every component of o and d at most 1e100 in magnitude, so that no monomial
+ * overflows -- and every other ray goes through the reference's dense 20-term expansion, object by object.  Degree 3 behaves as the
+ * render kernels do: the same guarded Taylor form with the dense fallback, within the guard's 1e-8 of t under the device's cbrt /
+ * acos / cos.  RT_FLAG_FAST contexts run the FMA-contracted build of the same kernel; their results are their own arithmetic and are
+ * not promised equal to rt_pick's (two kernels cannot promise that under contraction).
+ *
+ * Ray queries carry no frame state, so they work in EVERY context: plain, RT_FLAG_SSAA2 / RT_FLAG_SSAA4, adaptive, any rank or world,
+ * any format.  They read the scene blob and nothing else -- no camera tables, tile words, launch-order generations, census, counters
+ * or frame tag -- and need no ordering against rt_render.  Scenes whose class tables exceed the LDS limit are refused as
+ * rt_render_gbuffer refuses them.  Limits: no colour for arbitrary rays; the multi-GPU layer (rt_*_multi) has no ray-query entry point.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt_ray {
+    double o[3]; /* origin */
+    double d[3]; /* direction, used as given */
+} rt_ray;        /* 48 bytes; 16-byte aligned in device memory */
+
+/* n rays -> n rt_hit, both in device memory, on `stream`.  ms as in rt_render_gbuffer: NULL = enqueue only (one kernel, capturable
+ * into a graph), else synchronise and report the device time of the pass.  RT_ERR_INVALID for a NULL context or pointer, n == 0, a
+ * ray or hit pointer that is not 16-byte aligned, and input and output ranges that overlap. */
+int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_hit *dev_hits, void *stream, float *ms);
+/* n rays (and n t_max values, or NULL) -> n int32 flags, all in device memory.  Refusals as rt_trace_rays (dev_t_max may be NULL; the
+ * flags must overlap neither the rays nor t_max). */
+int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const double *dev_t_max, uint32_t n, int32_t *dev_blocked, void *stream, float *ms);
+/* rt_trace_rays for rays and records in HOST memory; blocks.  The staging buffers are the context's own (they grow as rt_pick's do,
+ * rt_destroy frees them); calls on one context must not overlap in time. */
+int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, rt_hit *out, void *stream);
+
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
 
