@@ -376,6 +376,29 @@ static uint32_t rows_of_rank(uint32_t height, uint32_t band, uint32_t world, uin
 
 static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *cfg_in);
 
+// MI355RT_DEBUG_FRAME0 / MI355RT_DEBUG_TAG0 (tests: a context that starts late in its life, just in front of a counter's restart):
+// an unsigned number, decimal or 0x hex, nothing behind it, at most `max`.  Unset: *value is left alone.
+static int debug_start_value(const char *name, uint64_t max, uint64_t *value)
+{
+    const char *e = std::getenv(name);
+    if (!e) return RT_OK;
+    const bool hex = e[0] == '0' && (e[1] == 'x' || e[1] == 'X');
+    const char *p = hex ? e + 2 : e;
+    uint64_t v = 0;
+    bool ok = *p != '\0';
+    for (; ok && *p; p++) {
+        const int c = (unsigned char) *p;
+        const int d = (c >= '0' && c <= '9') ? c - '0' : ((hex && c >= 'a' && c <= 'f') ? c - 'a' + 10 : ((hex && c >= 'A' && c <= 'F') ? c - 'A' + 10 : -1));
+        const uint64_t base = hex ? 16u : 10u;
+        ok = d >= 0 && v <= (UINT64_MAX - (uint64_t) d) / base;
+        if (ok) v = v * base + (uint64_t) d;
+    }
+    if (!ok) return fail(RT_ERR_INVALID, "rt_create: %s=\"%s\" is not an unsigned decimal or 0x hexadecimal number", name, e);
+    if (v > max) return fail(RT_ERR_INVALID, "rt_create: %s=%s exceeds 0x%llX", name, e, (unsigned long long) max);
+    *value = v;
+    return RT_OK;
+}
+
 extern "C" int rt_create(rt_ctx **out, const rt_scene_desc *sd, const rt_config *cfg_in)
 {
     try { // host-side packing allocates; nothing may propagate through the C ABI
@@ -412,6 +435,11 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if ((sd->n_objects && (!sd->coefs || !sd->reflection || !sd->albedo)) ||
         (sd->n_lights && (!sd->light_is_spherical || !sd->light_p || !sd->light_color)))
         return fail(RT_ERR_INVALID, "rt_create: null scene array");
+    // (tests) the frame number and the tile-word tag the context starts from; the device state starts zeroed whatever they say: tile words
+    // with tag 0 never equal a live tag and all three launch-order generations are empty, so any starting frame % 3 is consistent
+    uint64_t frame0 = 0, tag0 = 0;
+    if (int rc = debug_start_value("MI355RT_DEBUG_FRAME0", UINT64_MAX, &frame0)) return rc;
+    if (int rc = debug_start_value("MI355RT_DEBUG_TAG0", 0x1FFFFFF0u, &tag0)) return rc;
 
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
@@ -438,6 +466,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     ctx->ssaa = k;
     ctx->adaptive = adaptive;
     ctx->geometry = geometry;
+    ctx->frame = frame0;
+    ctx->tag = (uint32_t) tag0;
     if (const char *e = std::getenv("MI355RT_RESOLVE_NT")) ctx->resolve_nt = std::atoi(e) != 0; // (experiments)
     ctx->pixel_bytes = cfg.format == RT_FMT_RGBA8 ? 4 : 16;
     ctx->local_rows = rows_of_rank(sd->height, cfg.band_rows, cfg.world, cfg.rank);

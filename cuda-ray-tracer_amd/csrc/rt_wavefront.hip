@@ -1409,8 +1409,13 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
                     uint32_t k, idx;
                     ord_locate(oh, rank, k, idx);
                     d_tile = ord_rd[RT_ORD_HDR + (1u + k) * hot_n_tiles + idx];
-                    d_flags |= (d_tile >= hot_n_tiles || ord_last_position(oh, rank) >= n_eff) ? 8u : 1u; // (>= n_tiles: never true for lists this kernel wrote;
-                                                             // a pair cut in two by the end of the slots: the tile's index slot renders all of it)
+                    // The entry counts only if the tile's own word names it -- the very test by which the tile's index slot (and its classifier)
+                    // decides that a list slot renders the tile, so that exactly one of them does.  A generation that a replayed graph appended
+                    // to again without its having been cleared holds a tile once per replay, and its header may count more entries than were
+                    // written (stale or zero words behind them): the word names the last entry only, the other list slots leave.
+                    const uint32_t back = ord_rd[RT_ORD_HDR + (d_tile < hot_n_tiles ? d_tile : 0u)];
+                    d_flags |= (d_tile >= hot_n_tiles || back != ((idx << 5) | (k + 1u)) || ord_last_position(oh, rank) >= n_eff) ? 8u : 1u; // (>= n_tiles: never true for
+                                                             // lists this kernel wrote; a pair cut in two by the end of the slots: the tile's index slot renders all of it)
                 }
             } else {
                 d_tile = idx_tile;

@@ -255,7 +255,9 @@ int rt_create(rt_ctx **out, const rt_scene_desc *scene, const rt_config *cfg);
  * command processor needs between two dependent launches disappear: 42 instead of 45 us per 1080p frame).  Every captured call
  * carries its own arguments (camera, launch-order generation, frame tag): launched once, in place of the K calls, the graph is
  * exactly those K frames; REPLAYING it renders correctly too but repeats frame tags and generations, i.e. without the benefit of
- * the ordering (use RT_FLAG_STATIC_ORDER for contexts whose graphs are replayed). */
+ * the ordering (use RT_FLAG_STATIC_ORDER for contexts whose graphs are replayed).  Tested (tests/test_graph_replay_gpu.py): a graph
+ * may be replayed any number of times, also several graphs of one context in turn and with uncaptured frames in between, and the
+ * counters and sparse messages of the frame that follows are unaffected. */
 int rt_render(rt_ctx *ctx, const double cam[16], void *dev_fb, void *stream, float *ms);
 
 /* Row ownership: number of local rows, and for local row i its global y (row 0 = bottom of the image,

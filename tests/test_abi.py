@@ -75,6 +75,33 @@ def test_bad_arguments_are_reported_not_crashed(pkg):
     assert lib.rt_destroy(None) == 0
 
 
+@pytest.mark.parametrize("name,value", [("MI355RT_DEBUG_FRAME0", "12x"), ("MI355RT_DEBUG_FRAME0", "abc"), ("MI355RT_DEBUG_FRAME0", ""), ("MI355RT_DEBUG_FRAME0", "-1"),
+                                        ("MI355RT_DEBUG_FRAME0", "0x"), ("MI355RT_DEBUG_FRAME0", "7 "), ("MI355RT_DEBUG_FRAME0", "0x1G"),
+                                        ("MI355RT_DEBUG_FRAME0", "18446744073709551616"), ("MI355RT_DEBUG_TAG0", "1e3"), ("MI355RT_DEBUG_TAG0", "0x10 0"),
+                                        ("MI355RT_DEBUG_TAG0", "0x1FFFFFF1"), ("MI355RT_DEBUG_TAG0", "536870897"), ("MI355RT_DEBUG_TAG0", "0xFFFFFFFFFFFFFFFF")])
+def test_debug_start_values_are_checked(pkg, monkeypatch, name, value):
+    """MI355RT_DEBUG_FRAME0 / MI355RT_DEBUG_TAG0 (tests/test_frame_wrap_gpu.py): a malformed value, trailing text or a tag above
+    0x1FFFFFF0 is refused by rt_create with RT_ERR_INVALID and the variable's name -- before the device lookup, so also without a GPU."""
+    sc = pkg.Scene.load_from_file(scene_path("quadratic"))
+    monkeypatch.setenv(name, value)
+    with pytest.raises(pkg.RtError) as e:
+        pkg.Renderer(sc)
+    assert e.value.code == -1 and name in e.value.message, e.value
+    assert name in pkg.lib().rt_last_error().decode()
+
+
+@pytest.mark.parametrize("frame0,tag0", [("0", "0"), ("4294967277", "0x1FFFFFF0"), ("0xFFFFFFFFFFFFFFFF", "536870896"), ("0Xffffffed", "0x1fffffed")])
+def test_debug_start_values_are_accepted(pkg, monkeypatch, frame0, tag0):
+    """Decimal or 0x hex, up to the limits: rt_create gets as far as the device (a context with a GPU, RT_ERR_NO_DEVICE without one)."""
+    sc = pkg.Scene.load_from_file(scene_path("quadratic")).set_size(32, 24)
+    monkeypatch.setenv("MI355RT_DEBUG_FRAME0", frame0)
+    monkeypatch.setenv("MI355RT_DEBUG_TAG0", tag0)
+    try:
+        pkg.Renderer(sc).cleanup_update()
+    except pkg.RtError as e:
+        assert e.code == pkg.RT_ERR_NO_DEVICE, e
+
+
 def test_product_does_not_link_or_import_the_oracle(pkg):
     """The oracle is test infrastructure: nothing under cuda-ray-tracer_amd/ or include/ may reference it."""
     bad = []

@@ -107,12 +107,18 @@ def test_band_sharding_reassembles_bit_identical(pkg):
 
 
 def test_rgba8_within_one_lsb(pkg, oracle):
+    """The quantisation is defined exactly -- (unsigned char) (int) (v * 255.0f + 0.5f) in FP32 -- so the RGBA8 frame is held to
+    that rule applied to the RGBA32F frame of the same configuration and to the oracle's frame, not to one LSB."""
+    from test_raw_descriptor_gpu import check_rgba8, rgba8_of
     w, h = 320, 240
     got, _, _ = render_gpu(pkg, "20spheres", w, h, fmt=pkg.RT_FMT_RGBA8)
+    v32, _, _ = render_gpu(pkg, "20spheres", w, h)
     want = render_cpu(oracle, "20spheres", w, h)
-    q = np.floor(want * 255.0 + 0.5).astype(np.int32)
     assert got.dtype == np.uint8 and np.all(got[..., 3] == 255)
-    assert np.abs(got[..., :3].astype(np.int32) - q).max() <= 1
+    check_rgba8(got, v32, "20spheres against its RGBA32F frame")
+    q, ok = rgba8_of(want)
+    assert ok.all() and np.array_equal(got, q)
+    assert np.abs(got[..., :3].astype(np.int32) - np.floor(want * 255.0 + 0.5).astype(np.int32)).max() <= 1
 
 
 def test_fast_variant_statistics(pkg, oracle):
