@@ -44,7 +44,7 @@ ABI_SYMBOLS = [
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined",
     "rt_render_gbuffer", "rt_pick",
-    "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host",
+    "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
@@ -193,6 +193,8 @@ def lib():
         L.rt_trace_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, fp]
         L.rt_occluded_rays.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, fp]
         L.rt_trace_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.POINTER(Hit), vp]
+        L.rt_shade_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, fp]
+        L.rt_shade_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, fp, vp]
         _lib = L
     return _lib
 
@@ -485,6 +487,23 @@ class Renderer:
         ms = C.c_float(0.0)
         _check(lib().rt_occluded_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, C.c_void_p(t_max_ptr) if t_max_ptr else None, int(n),
                                       C.c_void_p(blocked_ptr) if blocked_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def shade(self, origins, dirs, stream=None):
+        """The reference's colour of every ray (rt_shade_rays_host; blocks): an [n, 4] float32 numpy array of (r, g, b, 1) -- what an
+        RGBA32F pixel holds whose primary ray this is.  Directions are used as given.  Works in every context kind and format."""
+        rays = self.rays(origins, dirs)
+        out = np.zeros((len(rays), 4), dtype=np.float32)
+        _check(lib().rt_shade_rays_host(self._h, rays.ctypes.data_as(C.POINTER(Ray)), len(rays), out.ctypes.data_as(C.POINTER(C.c_float)),
+                                        C.c_void_p(stream) if stream else None))
+        return out
+
+    def shade_into(self, ray_ptr, n, rgba_ptr, hit_ptr=None, stream=None, timed=True):
+        """rt_shade_rays on the caller's device memory (raw pointers to n rt_ray / n x 4 float32 / optionally n rt_hit, 16-byte
+        aligned): device milliseconds, or None unless timed (then the call only enqueues one kernel)."""
+        ms = C.c_float(0.0)
+        _check(lib().rt_shade_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, int(n), C.c_void_p(rgba_ptr) if rgba_ptr else None,
+                                   C.c_void_p(hit_ptr) if hit_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
 
     def cleanup_update(self):

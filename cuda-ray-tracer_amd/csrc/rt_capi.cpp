@@ -55,6 +55,9 @@ extern "C" hipError_t rt_launch_trace_rays_fast(const FrameArgs *, const void *,
 extern "C" hipError_t rt_launch_occluded_rays_strict(const FrameArgs *, const void *, const void *, const double *, uint32_t, int32_t *, uint32_t, hipStream_t);
 extern "C" hipError_t rt_launch_occluded_rays_fast(const FrameArgs *, const void *, const void *, const double *, uint32_t, int32_t *, uint32_t, hipStream_t);
 extern "C" size_t rt_rays_lds_bytes_strict(const FrameArgs *);
+// colour of caller-supplied rays (rt_shade_rays.hip), per contraction mode
+extern "C" hipError_t rt_launch_shade_rays_strict(const FrameArgs *, const void *, const void *, const void *, uint32_t, float *, void *, uint32_t, hipStream_t);
+extern "C" hipError_t rt_launch_shade_rays_fast(const FrameArgs *, const void *, const void *, const void *, uint32_t, float *, void *, uint32_t, hipStream_t);
 // RT_FLAG_SSAA_GEOMETRY: the G pass of an adaptive frame (rt_gbuffer.hip) and the classifier that reads it (rt_adaptive.hip)
 extern "C" hipError_t rt_launch_gbuffer_edges_strict(const FrameArgs *, const void *, const double *, const double *, int32_t *, float *, const uint32_t *, uint32_t,
                                                      void *, hipStream_t);
@@ -179,10 +182,11 @@ struct rt_ctx {
     uint32_t *d_pick_xy = nullptr; // [pick_cap][2] coordinates
     void *d_pick_out = nullptr;    // [pick_cap] rt_hit
     uint32_t pick_cap = 0;
-    // ray queries (rt_trace_rays / rt_occluded_rays / rt_trace_rays_host): their own events and staging memory, created on first use
+    // ray queries (rt_trace_rays / rt_occluded_rays / rt_shade_rays and the _host entry points): their own events and staging memory,
+    // created on first use
     hipEvent_t rq_ev0 = nullptr, rq_ev1 = nullptr;
     void *d_rq_rays = nullptr; // [rq_cap] rt_ray
-    void *d_rq_hits = nullptr; // [rq_cap] rt_hit
+    void *d_rq_hits = nullptr; // [rq_cap] rt_hit (rt_shade_rays_host: its 4 x float32 pixels)
     uint32_t rq_cap = 0;
 };
 
@@ -1163,6 +1167,23 @@ static int rays_timed(rt_ctx *ctx, hipStream_t stream, float *ms, bool begin)
     return RT_OK;
 }
 
+// the staging buffers of the _host entry points, for n rays
+static int rays_staging(rt_ctx *ctx, uint32_t n)
+{
+    if (n > ctx->rq_cap) { // (every earlier call has synchronised: nothing uses the old buffers)
+        if (ctx->d_rq_rays) (void) hipFree(ctx->d_rq_rays);
+        if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
+        ctx->d_rq_rays = nullptr;
+        ctx->d_rq_hits = nullptr;
+        ctx->rq_cap = 0;
+        const uint32_t cap = n < 64u ? 64u : n;
+        RT_HIP(hipMalloc(&ctx->d_rq_rays, sizeof(rt_ray) * (size_t) cap));
+        RT_HIP(hipMalloc(&ctx->d_rq_hits, sizeof(rt_hit) * (size_t) cap));
+        ctx->rq_cap = cap;
+    }
+    return RT_OK;
+}
+
 extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_hit *dev_hits, void *stream_, float *ms)
 {
     static_assert(sizeof(rt_ray) == 48 && sizeof(rt_hit) == 48, "rt_ray / rt_hit layout");
@@ -1206,24 +1227,58 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
     if (n == 0) return fail(RT_ERR_INVALID, "rt_trace_rays_host: n is 0");
     if (ranges_overlap(rays, sizeof(rt_ray) * (size_t) n, out, sizeof(rt_hit) * (size_t) n)) return fail(RT_ERR_INVALID, "rt_trace_rays_host: the rays and the hits overlap");
     hipStream_t stream = (hipStream_t) stream_;
-    const int rc = rays_ready("rt_trace_rays_host", ctx);
+    int rc = rays_ready("rt_trace_rays_host", ctx);
     if (rc != RT_OK) return rc;
-    if (n > ctx->rq_cap) { // (every earlier call has synchronised: nothing uses the old buffers)
-        if (ctx->d_rq_rays) (void) hipFree(ctx->d_rq_rays);
-        if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
-        ctx->d_rq_rays = nullptr;
-        ctx->d_rq_hits = nullptr;
-        ctx->rq_cap = 0;
-        const uint32_t cap = n < 64u ? 64u : n;
-        RT_HIP(hipMalloc(&ctx->d_rq_rays, sizeof(rt_ray) * (size_t) cap));
-        RT_HIP(hipMalloc(&ctx->d_rq_hits, sizeof(rt_hit) * (size_t) cap));
-        ctx->rq_cap = cap;
-    }
+    if ((rc = rays_staging(ctx, n)) != RT_OK) return rc;
     RT_HIP(hipMemcpyAsync(ctx->d_rq_rays, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
     const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_trace_rays_fast(&ctx->fa, ctx->d_obj, ctx->d_rq_rays, n, ctx->d_rq_hits, rays_max_grid(ctx), stream)
                                                          : rt_launch_trace_rays_strict(&ctx->fa, ctx->d_obj, ctx->d_rq_rays, n, ctx->d_rq_hits, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out, ctx->d_rq_hits, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+// ---- colour of caller-supplied rays (rt_shade_rays.hip) ----------------------------------------------------
+// Like the ray queries it reads the scene (blob and lights) and nothing of the frame; always 4 x float32 per ray, whatever cfg.format.
+static hipError_t shade_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, float *dev_rgba, void *dev_hits, hipStream_t stream)
+{
+    return (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_shade_rays_fast(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream)
+                                           : rt_launch_shade_rays_strict(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
+}
+
+extern "C" int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits, void *stream_, float *ms)
+{
+    if (!ctx || !dev_rays || !dev_rgba) return fail(RT_ERR_INVALID, "rt_shade_rays: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_shade_rays: n is 0");
+    if (((uintptr_t) dev_rays | (uintptr_t) dev_rgba | (uintptr_t) dev_hits) & 15u) return fail(RT_ERR_INVALID, "rt_shade_rays: rays, rgba and hits must be 16-byte aligned");
+    const size_t ray_bytes = sizeof(rt_ray) * (size_t) n, px_bytes = 4 * sizeof(float) * (size_t) n, hit_bytes = sizeof(rt_hit) * (size_t) n;
+    if (ranges_overlap(dev_rays, ray_bytes, dev_rgba, px_bytes)) return fail(RT_ERR_INVALID, "rt_shade_rays: the rays and the rgba output overlap");
+    if (dev_hits && (ranges_overlap(dev_rays, ray_bytes, dev_hits, hit_bytes) || ranges_overlap(dev_rgba, px_bytes, dev_hits, hit_bytes)))
+        return fail(RT_ERR_INVALID, "rt_shade_rays: the hits overlap the rays or the rgba output");
+    hipStream_t stream = (hipStream_t) stream_;
+    int rc = rays_ready("rt_shade_rays", ctx);
+    if (rc != RT_OK) return rc;
+    if ((rc = rays_timed(ctx, stream, ms, true)) != RT_OK) return rc;
+    const hipError_t e = shade_launch(ctx, dev_rays, n, dev_rgba, dev_hits, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_shade_rays: kernel launch failed: %s", hipGetErrorString(e));
+    return rays_timed(ctx, stream, ms, false);
+}
+
+extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_out, void *stream_)
+{
+    if (!ctx || !rays || !rgba_out) return fail(RT_ERR_INVALID, "rt_shade_rays_host: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_shade_rays_host: n is 0");
+    if (ranges_overlap(rays, sizeof(rt_ray) * (size_t) n, rgba_out, 4 * sizeof(float) * (size_t) n)) return fail(RT_ERR_INVALID, "rt_shade_rays_host: the rays and the rgba output overlap");
+    hipStream_t stream = (hipStream_t) stream_;
+    int rc = rays_ready("rt_shade_rays_host", ctx);
+    if (rc != RT_OK) return rc;
+    if ((rc = rays_staging(ctx, n)) != RT_OK) return rc;
+    float *d_rgba = reinterpret_cast<float *>(ctx->d_rq_hits); // (48 bytes per ray there, 16 needed)
+    RT_HIP(hipMemcpyAsync(ctx->d_rq_rays, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = shade_launch(ctx, ctx->d_rq_rays, n, d_rgba, nullptr, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_shade_rays_host: kernel launch failed: %s", hipGetErrorString(e));
+    RT_HIP(hipMemcpyAsync(rgba_out, d_rgba, 4 * sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
 }

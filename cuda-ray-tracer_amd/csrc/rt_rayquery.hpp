@@ -1,0 +1,200 @@
+// rt_rayquery.hpp -- what the kernels for caller-supplied rays share (rt_rays.hip: closest hit and occlusion; rt_shade_rays.hip: the
+// reference's colour): the scene-layout argument words, the class tables in LDS, the object loops for one ray per lane -- through the
+// tables where they are proven, through the dense expansion elsewhere -- and the 48-byte ray / record layouts of include/mi355rt.h.
+// Included by files that are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
+#ifndef RT_RAYQUERY_HPP
+#define RT_RAYQUERY_HPP
+
+#include <hip/hip_runtime.h>
+
+#include "rt_shade.hpp"          // RT_SYM and the variant's namespace
+#include "rt_wavefront_math.hpp" // class-table coefficients, us_needs_solve, needs_solve, accept
+
+namespace RT_SYM(rtk) {
+
+// the scene-layout words of FrameArgs (all a ray query needs of it), the number of rays and what a NULL t_max array stands for
+struct RayQueryArgs {
+    uint32_t n_obj, n_us, n_gq, n_lin, n_cub;
+    uint32_t off_gq, off_lin, off_cub; // byte offsets into the staged tables (i.e. relative to FrameArgs::off_us)
+    uint32_t off_us, tab_bytes;        // the tables in the scene blob: [UsEntry][GqEntry][LinEntry][uint32 cubic indices], each padded to 16 bytes
+    uint32_t n;
+};
+
+struct RqTables {
+    const UsEntry *us;
+    const GqEntry *gq;
+    const LinEntry *lin;
+    const uint32_t *cub;
+};
+
+// Above this magnitude a product of three components (times 3) can overflow, and a coefficient that is exactly zero then no longer
+// contributes an exact zero to the reference's 20-term sums (0 * inf = NaN): the class tables, which leave those terms out, are only
+// proven for rays below it.  NaN and +-inf components fail the comparison too.
+constexpr double RQ_PLAIN_ABOVE = 1e100;
+
+__device__ __forceinline__ bool rq_tables_proven(const D3 &o, const D3 &d)
+{
+    // (every component on its own: fmax would drop a NaN operand)
+    return fabs(o.x) <= RQ_PLAIN_ABOVE && fabs(o.y) <= RQ_PLAIN_ABOVE && fabs(o.z) <= RQ_PLAIN_ABOVE && fabs(d.x) <= RQ_PLAIN_ABOVE &&
+           fabs(d.y) <= RQ_PLAIN_ABOVE && fabs(d.z) <= RQ_PLAIN_ABOVE;
+}
+
+// One candidate's root against the query's acceptance rule.  Closest hit: rtm::accept (t >= EPS, t < MAX_T, nearest, lowest index on a
+// tie).  Occlusion: t > EPS && t < t_max, both strict; a NaN on either side blocks nothing.
+template <bool OCCLUSION>
+__device__ __forceinline__ void rq_take(double t, int k, double t_max, double &best_t, int &best)
+{
+    if (OCCLUSION) {
+        if (t > EPS && t < t_max) best = 1;
+    } else {
+        accept(t, k, best_t, best);
+    }
+}
+
+// The object loops for one ray per lane, wave-uniform as the non-cone branch of the G-buffer's nearest_hit: t1 / t0 and the sign of
+// the discriminant first, the root and the division only in the lanes that need them (us_needs_solve / needs_solve say when the
+// reference's solver returns nothing that `t >= EPS`, hence `t > EPS`, can accept); planes take their one division; degree 3 goes
+// through the guarded Taylor test with the surface's data at the lane's own origin.  `use`: the lane has a ray whose answer comes from
+// the tables.  OCCLUSION: best = 1 once something blocks; the wave leaves as soon as no lane is left undecided.
+template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+__device__ __forceinline__ void rq_tables(const RayQueryArgs &qa, const RqTables &S, const DevObject *__restrict__ gobj, const Mono &m, bool use, double t_max,
+                                          double &best_t, int &best)
+{
+#define RQ_ALL_DECIDED() (OCCLUSION && __ballot(use && best == 0) == 0ull)
+    const bool quad = fabs(m.u2) > EPS; // unit spheres share t2 = u2: one degree decision per ray
+    const double four_t2 = 4.0 * m.u2;
+    for (uint32_t base = 0; base < qa.n_us; base += 64) {
+        const uint32_t end = (base + 64 < qa.n_us) ? base + 64 : qa.n_us;
+        unsigned long long cand = 0;
+#pragma unroll 4
+        for (uint32_t j = base; j < end; j++) {
+            const UsEntry e = S.us[j];
+            const bool need = us_needs_solve(quad, four_t2, us_t1(e, m), us_t0(e, m));
+            cand |= need ? (1ull << (j - base)) : 0ull;
+        }
+        if (!use) cand = 0;
+        while (cand && !(OCCLUSION && best != 0)) { // per lane: the few spheres whose root must actually be computed
+            const int b = __builtin_ctzll(cand);
+            cand &= cand - 1;
+            const UsEntry e = S.us[base + b];
+            rq_take<OCCLUSION>(solve_quadlin(m.u2, us_t1(e, m), us_t0(e, m)), (int) e.orig, t_max, best_t, best);
+        }
+        if (RQ_ALL_DECIDED()) return;
+    }
+    for (uint32_t base = 0; HAS_GQ && base < qa.n_gq; base += 64) {
+        const uint32_t end = (base + 64 < qa.n_gq) ? base + 64 : qa.n_gq;
+        unsigned long long cand = 0;
+#pragma unroll 2
+        for (uint32_t j = base; j < end; j++) {
+            const GqEntry e = S.gq[j];
+            cand |= needs_solve(gq_t2(e, m), gq_t1(e, m), gq_t0(e, m)) ? (1ull << (j - base)) : 0ull;
+        }
+        if (!use) cand = 0;
+        while (cand && !(OCCLUSION && best != 0)) {
+            const int b = __builtin_ctzll(cand);
+            cand &= cand - 1;
+            const GqEntry e = S.gq[base + b];
+            rq_take<OCCLUSION>(solve_quadlin(gq_t2(e, m), gq_t1(e, m), gq_t0(e, m)), (int) e.orig, t_max, best_t, best);
+        }
+        if (RQ_ALL_DECIDED()) return;
+    }
+    for (uint32_t j = 0; j < qa.n_lin; j++) { // planes: every lane needs the one division, nothing to defer
+        const LinEntry e = S.lin[j];
+        const double t1 = lin_t1(e, m);
+        const double t0 = lin_t0(e, m);
+        const double t = (fabs(t1) > EPS) ? -t0 / t1 : -1.0;
+        if (use) rq_take<OCCLUSION>(t, (int) e.orig, t_max, best_t, best);
+    }
+    if (HAS_CUBIC) {
+        if (RQ_ALL_DECIDED()) return;
+        for (uint32_t j = 0; j < qa.n_cub; j++) {
+            const uint32_t k = (uint32_t) __builtin_amdgcn_readfirstlane((int) S.cub[j]);
+            if (use && !(OCCLUSION && best != 0)) {
+                // the guarded Taylor test of the render kernels (rt_math.hpp: cubic_guarded, dense expansion where it refuses); the surface's
+                // data at the ray's origin is formed per lane: there is no host record for arbitrary origins
+                const CubicAt ca = cubic_at(gobj[k].c, m.o);
+                const CubicAbs ab = cubic_abs(gobj[k].c);
+                bool refused;
+                const double t = intersect_cubic_taylor<false>(gobj[k].c, ca, cubic_mag_origin(ab, m.o), m.o, m.d, OCCLUSION ? t_max : MAX_T, OCCLUSION, refused);
+                rq_take<OCCLUSION>(t, (int) k, t_max, best_t, best);
+            }
+            if (RQ_ALL_DECIDED()) return;
+        }
+    }
+#undef RQ_ALL_DECIDED
+}
+
+// The plain path: every object in index order through the reference's own expression, the dense 20-term expansion and its solver
+// (rtm::intersect_cubic = intersect_ray, include/surface_impl.h:21-155, whatever the object's degree).  For rays the class tables are
+// not proven for (rq_tables_proven): non-finite or astronomically large components.  Rare, so nothing here is tuned; the solver stays
+// out of line (inlined, its expansion would set the register count of the whole kernel: 215 VGPRs instead of the callee's 152).
+template <bool OCCLUSION>
+__device__ __forceinline__ void rq_plain(const RayQueryArgs &qa, const DevObject *__restrict__ gobj, const D3 &o, const D3 &d, bool use, double t_max, double &best_t,
+                                         int &best)
+{
+    for (uint32_t k = 0; k < qa.n_obj; k++) {
+        if (use && !(OCCLUSION && best != 0)) {
+            const double t = intersect_cubic(gobj[k].c, o.x, o.y, o.z, d.x, d.y, d.z);
+            rq_take<OCCLUSION>(t, (int) k, t_max, best_t, best);
+        }
+    }
+}
+
+// One rt_ray / rt_hit (include/mi355rt.h) as three 16-byte words
+struct alignas(16) RqRay {
+    double o[3], d[3];
+};
+struct alignas(16) RqRecord {
+    double t, p[3];
+    float n[3];
+    int32_t object;
+};
+static_assert(sizeof(RqRay) == 48 && sizeof(RqRecord) == 48, "rt_ray / rt_hit layout");
+
+// The class tables of the scene blob, copied to LDS by the whole 256-thread workgroup (ends with a barrier)
+__device__ __forceinline__ RqTables rq_stage_tables(const RayQueryArgs &qa, const unsigned char *__restrict__ scene, unsigned char *smem)
+{
+    const uint4 *src = reinterpret_cast<const uint4 *>(scene + qa.off_us);
+    uint4 *dst = reinterpret_cast<uint4 *>(smem);
+    for (uint32_t i = threadIdx.x; i < (qa.tab_bytes >> 4); i += 256u) dst[i] = src[i];
+    __syncthreads();
+    RqTables S;
+    S.us = reinterpret_cast<const UsEntry *>(smem);
+    S.gq = reinterpret_cast<const GqEntry *>(smem + qa.off_gq);
+    S.lin = reinterpret_cast<const LinEntry *>(smem + qa.off_lin);
+    S.cub = reinterpret_cast<const uint32_t *>(smem + qa.off_cub);
+    return S;
+}
+
+// the scene-layout words of a context's FrameArgs for n rays
+static inline RayQueryArgs rq_args(const FrameArgs *fa, uint32_t n)
+{
+    RayQueryArgs qa;
+    qa.n_obj = fa->n_obj; qa.n_us = fa->n_us; qa.n_gq = fa->n_gq; qa.n_lin = fa->n_lin; qa.n_cub = fa->n_cub;
+    qa.off_us = fa->off_us;
+    qa.off_gq = fa->off_gq - fa->off_us; qa.off_lin = fa->off_lin - fa->off_us; qa.off_cub = fa->off_cub - fa->off_us;
+    qa.tab_bytes = fa->off_mat - fa->off_us;
+    qa.n = n;
+    return qa;
+}
+
+// the hit record of a ray (o, d) whose nearest hit is object `best` at best_t with normal nv at point p; a miss for best < 0
+__device__ __forceinline__ void rq_store_record(RqRecord *__restrict__ dst_rec, int best, double best_t, const D3 &p, const D3 &nv)
+{
+    RqRecord r{INFINITY, {0.0, 0.0, 0.0}, {0.0f, 0.0f, 0.0f}, -1};
+    if (best >= 0) {
+        r.t = best_t;
+        r.p[0] = p.x; r.p[1] = p.y; r.p[2] = p.z;
+        r.n[0] = (float) nv.x; r.n[1] = (float) nv.y; r.n[2] = (float) nv.z;
+        r.object = best;
+    }
+    uint4 *dst = reinterpret_cast<uint4 *>(dst_rec); // three 16-byte stores
+    const uint4 *srcw = reinterpret_cast<const uint4 *>(&r);
+    dst[0] = srcw[0];
+    dst[1] = srcw[1];
+    dst[2] = srcw[2];
+}
+
+} // namespace RT_SYM(rtk)
+
+#endif

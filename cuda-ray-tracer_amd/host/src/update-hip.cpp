@@ -163,6 +163,17 @@ extern "C" int mi355rt_update_trace(const rt_ray *rays, unsigned int n, rt_hit *
     return rt_trace_rays_host(g_ctx, rays, n, out, nullptr);
 }
 
+// The reference's colour of n caller-supplied rays (rt_shade_rays_host; include/mi355rt.h, "Ray queries"): n x 4 float32, (r, g, b, 1).
+// Valid after init_update() like mi355rt_update_trace, and refused where that is.
+extern "C" int mi355rt_update_shade(const rt_ray *rays, unsigned int n, float *rgba_out)
+{
+    if (!g_ctx) {
+        rt_set_last_error(g_multi ? "mi355rt_update_shade: not available with several devices (MI355RT_DEVICES)" : "mi355rt_update_shade: no init_update() call yet");
+        return RT_ERR_INVALID;
+    }
+    return rt_shade_rays_host(g_ctx, rays, n, rgba_out, nullptr);
+}
+
 void init_update(unsigned int texture, const Scene &scene)
 {
     if (g_ctx || g_multi) cleanup_update();

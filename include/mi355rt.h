@@ -371,7 +371,8 @@ int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev_object, do
 int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
- * Ray queries: closest hit and occlusion for rays the caller supplies (csrc/rt_rays.hip)
+ * Ray queries: closest hit, occlusion and colour for rays the caller supplies (csrc/rt_rays.hip, csrc/rt_shade_rays.hip; DESIGN.md
+ * sections 15 and 16)
  *
  * The G-buffer and rt_pick answer "what does the primary ray of this pixel hit"; these answer it for ANY ray: a reflection followed
  * from a hit point, a shadow ray towards a light, another camera (orthographic, fisheye, stereo, cube map), a line-of-sight or
@@ -408,7 +409,28 @@ int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, r
  * Ray queries carry no frame state, so they work in EVERY context: plain, RT_FLAG_SSAA2 / RT_FLAG_SSAA4, adaptive, any rank or world,
  * any format.  They read the scene blob and nothing else -- no camera tables, tile words, launch-order generations, census, counters
  * or frame tag -- and need no ordering against rt_render.  Scenes whose class tables exceed the LDS limit are refused as
- * rt_render_gbuffer refuses them.  Limits: no colour for arbitrary rays; the multi-GPU layer (rt_*_multi) has no ray-query entry point.
+ * rt_render_gbuffer refuses them.  Limits: the multi-GPU layer (rt_*_multi) has no ray-query entry point.
+ *
+ * Colour (rt_shade_rays; csrc/rt_shade_rays.hip).  The reference's render_pixel (src/update-cpu.cpp:82-119) with
+ * ray_origin := o and dir := d, d used exactly as given, never normalised.  The first segment is get_color_and_object
+ * (src/update-cpu.cpp:45-80): the closest hit above; sp = o + t * d; sn = normal_vector(sp) in FP64, never flipped; every light in index
+ * order with shadow_ray (include/light_impl.h:17-27: the direction through float, max_t 1 or 1e6) from sp + SHADOW_BIAS * sn, blocked
+ * iff some object gives t > EPS && t < max_t; the unblocked lights add surface_color (include/light_impl.h:29-44) in float32; each
+ * component is clamped with (x < 1.0f) ? x : 1.0f.  Then the reflection loop of lines 96-117: reflection_ratio > EPS compared in double,
+ * cur_ratio *= ratio in float, reflect_ray of the direction as it is, the new origin sp + SHADOW_BIAS * sn, UPDATE_COLOR as
+ * (1.0f - r) * res + r * c; the scene's max_reflections cap and a bounce that leaves the scene both blend the background; a
+ * first-segment miss is the background colour.  A scene without lights gives black hits, not the background.
+ * Output is four float32 per ray, (r, g, b, 1.0f), whatever cfg.format is (as the G-buffer planes do not depend on the format): exactly
+ * what an RT_FMT_RGBA32F pixel of rt_render holds when the ray is that pixel's primary ray.  dev_hits, when not NULL, receives the
+ * rt_hit of the first segment, bit-equal to what rt_trace_rays writes for the same ray.
+ * Accuracy as above: strict contexts compute exactly these values for surfaces of degree <= 2, for every ray -- zero directions,
+ * non-finite components and components beyond 1e100 included -- and the FP32 colour operations are not contracted; degree 3 behaves as
+ * the render kernels do; RT_FLAG_FAST contexts run the FMA-contracted build, whose colours are its own arithmetic.  Whether the class
+ * tables are proven is decided for EVERY ray the kernel traces, not only the caller's: a hit at t < 1e6 along |d| <= 1e100 can put sp
+ * beyond 1e100 and a vanishing gradient makes sn NaN, and the shadow and bounce rays derived from them then take the dense expansion.
+ * None of the render kernels' work removal (facing-away skip, own-sphere rule, bounding-volume culling) is applied.
+ * No frame state, as the other ray queries: every context kind, no ordering against rt_render, one kernel with ms == NULL (capturable
+ * into a graph), and RT_FLAG_COUNT books none of its rays.
  * ------------------------------------------------------------------------------------------------- */
 typedef struct rt_ray {
     double o[3]; /* origin */
@@ -425,6 +447,13 @@ int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const double *dev_t_ma
 /* rt_trace_rays for rays and records in HOST memory; blocks.  The staging buffers are the context's own (they grow as rt_pick's do,
  * rt_destroy frees them); calls on one context must not overlap in time. */
 int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, rt_hit *out, void *stream);
+/* n rays -> n pixels of 4 x float32 (r, g, b, 1.0f), optionally n rt_hit of the rays themselves (dev_hits may be NULL); all in device
+ * memory, on `stream`; ms as in rt_trace_rays.  RT_ERR_INVALID for a NULL context, dev_rays or dev_rgba and for n == 0 (both before a
+ * device is looked for), rays, rgba or hits that are not 16-byte aligned, and any overlap between input and output ranges or between
+ * the two outputs.  Scenes beyond the LDS limit are refused as by rt_trace_rays. */
+int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits /* may be NULL */, void *stream, float *ms);
+/* rt_shade_rays for rays and pixels in HOST memory; blocks.  Staging buffers as rt_trace_rays_host. */
+int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_out, void *stream); /* host memory, blocks */
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
