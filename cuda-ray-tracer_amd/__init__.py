@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined",
     "rt_render_gbuffer", "rt_pick",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
+    "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
@@ -108,6 +109,15 @@ class Ray(C.Structure):
 
 
 RAY_DTYPE = np.dtype([("o", np.float64, 3), ("d", np.float64, 3)])   # the same record, for numpy
+
+
+class SceneUpdate(C.Structure):
+    """rt_scene_update (include/mi355rt.h): five raw descriptor arrays, any of them NULL = keep what the context holds; 40 bytes."""
+    _fields_ = [("coefs", C.c_void_p), ("reflection", C.c_void_p), ("albedo", C.c_void_p), ("light_p", C.c_void_p), ("light_color", C.c_void_p)]
+
+
+SCENE_UPDATE_FIELDS = (("coefs", np.float64), ("reflection", np.float32), ("albedo", np.float32), ("light_p", np.float64), ("light_color", np.float32))
+RT_SCENE_REJECT_CLASS, RT_SCENE_REJECT_BOUND, RT_SCENE_REJECT_MIRROR, RT_SCENE_REJECT_CUBIC, RT_SCENE_REJECT_LIGHT = 1, 2, 3, 4, 5
 
 
 def build(verbose=False):
@@ -195,6 +205,10 @@ def lib():
         L.rt_trace_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_shade_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, fp]
         L.rt_shade_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, fp, vp]
+        L.rt_set_scene.argtypes = [vp, C.POINTER(SceneUpdate), vp]
+        L.rt_set_scene_host.argtypes = [vp, C.POINTER(SceneUpdate), vp]
+        L.rt_set_scene_status.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.rt_debug_scene_blob.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 
@@ -505,6 +519,40 @@ class Renderer:
         _check(lib().rt_shade_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, int(n), C.c_void_p(rgba_ptr) if rgba_ptr else None,
                                    C.c_void_p(hit_ptr) if hit_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
+
+    def set_scene(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None):
+        """Replace the scene's raw descriptor arrays (numpy, rt_scene_desc layout; None = keep what the context holds) without a new
+        context (rt_set_scene_host; blocks).  Raises SceneException when the update would change the scene's layout (include/mi355rt.h,
+        "Scene updates"): nothing was written then."""
+        given = dict(coefs=coefs, reflection=reflection, albedo=albedo, light_p=light_p, light_color=light_color)
+        keep = {n: np.ascontiguousarray(given[n], dtype=dt) for n, dt in SCENE_UPDATE_FIELDS if given[n] is not None}
+        no, nl = self._desc.n_objects, self._desc.n_lights
+        want = dict(coefs=no * RT_NCOEF, reflection=no, albedo=3 * no, light_p=3 * nl, light_color=3 * nl)
+        for n, a in keep.items():
+            if a.size != want[n]:
+                raise ValueError(f"set_scene: {n} has {a.size} values, the scene takes {want[n]}")
+        u = SceneUpdate(**{n: (a.ctypes.data if a.size else None) for n, a in keep.items()})
+        _check(lib().rt_set_scene_host(self._h, C.byref(u), C.c_void_p(stream) if stream else None))
+
+    def set_scene_into(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None):
+        """rt_set_scene on the caller's device memory (raw pointers, for example tensor.data_ptr(); None = keep): enqueues one kernel
+        and returns -- capturable into a graph; whether it was applied is on the device (set_scene_status)."""
+        u = SceneUpdate(coefs or None, reflection or None, albedo or None, light_p or None, light_color or None)
+        _check(lib().rt_set_scene(self._h, C.byref(u), C.c_void_p(stream) if stream else None))
+
+    def set_scene_status(self):
+        """Updates applied / rejected since the context was created and the reason / index of the last rejection (waits)."""
+        a, r, why, idx = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        _check(lib().rt_set_scene_status(self._h, C.byref(a), C.byref(r), C.byref(why), C.byref(idx)))
+        return dict(applied=int(a.value), rejected=int(r.value), reason=int(why.value), index=int(idx.value))
+
+    def debug_scene_blob(self):
+        """Diagnostics: the scene as the device holds it (blob, DevLight[], LightK[]) as bytes (rt_debug_scene_blob; waits)."""
+        n = C.c_size_t()
+        _check(lib().rt_debug_scene_blob(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        _check(lib().rt_debug_scene_blob(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
+        return out
 
     def cleanup_update(self):
         if self._h:

@@ -16,6 +16,8 @@
 
 #include "mi355rt.h"
 #include "rt_scene_dev.h"
+#include "rt_scene_pack.hpp" // (the derived scene data per record: shared with rt_set_scene.hip)
+#include "rt_set_scene.h"
 #include "rt_math.hpp" // (rtm::cubic_at, host side: the Taylor data of degree-3 objects at the frame's ray origin)
 #include "scene-exception.h"
 #include "scene.h"
@@ -65,6 +67,9 @@ extern "C" hipError_t rt_launch_gbuffer_edges_fast(const FrameArgs *, const void
                                                    void *, hipStream_t);
 extern "C" hipError_t rt_launch_classify_geometry_strict(const void *, const void *, const int32_t *, const float *, const void *, uint32_t, uint32_t, uint32_t,
                                                          uint32_t, uint32_t, uint32_t, float, float, void *, int, uint32_t *, uint32_t *, hipStream_t);
+
+// scene update (rt_set_scene.hip, built once without FMA contraction: the derived scene data is the same in every variant)
+extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *, hipStream_t);
 
 namespace {
 
@@ -188,6 +193,9 @@ struct rt_ctx {
     void *d_rq_rays = nullptr; // [rq_cap] rt_ray
     void *d_rq_hits = nullptr; // [rq_cap] rt_hit (rt_shade_rays_host: its 4 x float32 pixels)
     uint32_t rq_cap = 0;
+    // scene updates (rt_set_scene): the kernel's status block, and the staging memory of rt_set_scene_host, created on first use
+    SetSceneStatus *d_ss_status = nullptr;
+    unsigned char *d_ss_stage = nullptr;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -355,18 +363,6 @@ extern "C" int rt_camera_matrix(const double pos[3], double yaw_deg, double pitc
 }
 
 // ---- render -------------------------------------------------------------------------------------------
-static uint32_t classify(const double *c)
-{
-    uint32_t cls = 0;
-    for (int i = K_X3; i <= K_XYZ; i++)
-        if (c[i] != 0.0) cls |= RT_CLS_CUBIC;
-    if (cls & RT_CLS_CUBIC) return RT_CLS_CUBIC; // dense path handles everything
-    if (c[K_X2] != 0.0 || c[K_Y2] != 0.0 || c[K_Z2] != 0.0) cls |= RT_CLS_SQUARE;
-    if (c[K_XY] != 0.0 || c[K_XZ] != 0.0 || c[K_YZ] != 0.0) cls |= RT_CLS_CROSS;
-    if (!(cls & RT_CLS_CROSS) && c[K_X2] == 1.0 && c[K_Y2] == 1.0 && c[K_Z2] == 1.0) cls |= RT_CLS_UNITSQ;
-    return cls;
-}
-
 static uint32_t rows_of_rank(uint32_t height, uint32_t band, uint32_t world, uint32_t rank)
 {
     // bands b = rank, rank + world, ... ; the last band of the image may be partial
@@ -510,31 +506,14 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if (const char *e = std::getenv("MI355RT_SPLIT_CLASSES")) ctx->ord_split = (uint32_t) std::atoi(e) & 15u; // (experiments)
     fa.has_mirror = 0;
     for (uint32_t i = 0; i < sd->n_objects; i++)
-        if ((double) sd->reflection[i] > 1e-7) fa.has_mirror = 1; // EPS of the reflection loop, src/update-cpu.cpp:101
+        if (rtp::is_mirror(sd->reflection[i])) fa.has_mirror = 1;
     std::vector<DevObject> objs(sd->n_objects);
     uint32_t n_cullable = 0;
-    for (uint32_t i = 0; i < sd->n_objects; i++) {
-        DevObject &o = objs[i];
-        std::memset(&o, 0, sizeof(o));
-        std::memcpy(o.c, sd->coefs + (size_t) i * RT_NCOEF, sizeof(double) * RT_NCOEF);
-        o.albedo[0] = sd->albedo[3 * i + 0];
-        o.albedo[1] = sd->albedo[3 * i + 1];
-        o.albedo[2] = sd->albedo[3 * i + 2];
-        o.refl = sd->reflection[i];
-        o.cls = classify(o.c);
-        // bounding sphere of a sphere: centre -k/2, r^2 = |centre|^2 - c (src/surface.cpp:4-15 inverted)
-        o.bs_radius = INFINITY;
-        if (o.cls & RT_CLS_UNITSQ) {
-            const double cx = -0.5 * o.c[K_X], cy = -0.5 * o.c[K_Y], cz = -0.5 * o.c[K_Z];
-            const double r2 = cx * cx + cy * cy + cz * cz - o.c[K_C];
-            if (r2 > 0.0 && std::isfinite(r2)) {
-                o.bs_center[0] = cx;
-                o.bs_center[1] = cy;
-                o.bs_center[2] = cz;
-                o.bs_radius = std::sqrt(r2);
-                n_cullable++;
-            }
-        }
+    bool albedos_finite = true;
+    for (uint32_t i = 0; i < sd->n_objects; i++) { // (rt_scene_pack.hpp: class word, bounding sphere)
+        rtp::pack_object(objs[i], sd->coefs + (size_t) i * RT_NCOEF, sd->albedo + 3 * (size_t) i, sd->reflection[i]);
+        if (rtp::cullable(objs[i])) n_cullable++;
+        albedos_finite = albedos_finite && rtp::albedo_finite(objs[i].albedo);
     }
     // culling costs one bounding-volume decision per (object, light, 64-hit chunk); worth it from a handful
     // of bounded objects upwards
@@ -552,39 +531,16 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
             if (t_cub.size() < RT_CUB_AT_MAX) ctx->cub_coefs.insert(ctx->cub_coefs.end(), o.c, o.c + RT_NCOEF);
             t_cub.push_back(i);
         } else if (o.cls & RT_CLS_UNITSQ) {
-            UsEntry e{};
-            e.kx = o.c[K_X]; e.ky = o.c[K_Y]; e.kz = o.c[K_Z]; e.c = o.c[K_C];
-            e.r = o.bs_radius;
-            e.inv_r = (o.bs_radius < INFINITY) ? 1.0 / o.bs_radius : 0.0;
-            e.orig = i;
-            // window of the reference's own t0 inside which a shadow ray leaving this sphere towards a directional light in front of the
-            // surface cannot be blocked by this sphere (rt_wavefront.hip, own_sphere_skippable): (1e-10 (r^2 + 1) + 1e-20 S^2, (r + 1)^2),
-            // S = 2 |centre|_1 + 3 r + 3; rounded inwards to FP32.  No window (+inf, 0) for spheres without a real radius.
-            e.own_lo = INFINITY;
-            e.own_hi = 0.0f;
-            if (o.bs_radius < INFINITY && o.bs_radius > 0.0) {
-                const double r = o.bs_radius, S = 2.0 * (std::fabs(o.bs_center[0]) + std::fabs(o.bs_center[1]) + std::fabs(o.bs_center[2])) + 3.0 * r + 3.0;
-                const double lo = 1e-10 * (r * r + 1.0) + 1e-20 * S * S, hi = (r + 1.0) * (r + 1.0);
-                float flo = (float) lo, fhi = (float) hi;
-                if (!((double) flo > lo)) flo = std::nextafterf(flo, INFINITY);
-                if (!((double) fhi < hi)) fhi = std::nextafterf(fhi, -INFINITY);
-                if (std::isfinite(lo) && std::isfinite(hi) && (double) flo > lo && (double) fhi < hi && flo < fhi) {
-                    e.own_lo = flo;
-                    e.own_hi = fhi;
-                }
-            }
+            UsEntry e;
+            rtp::pack_us(e, o, i); // (with the own-sphere window of the lean path)
             t_us.push_back(e);
         } else if (o.cls & (RT_CLS_SQUARE | RT_CLS_CROSS)) {
-            GqEntry e{};
-            e.x2 = o.c[K_X2]; e.y2 = o.c[K_Y2]; e.z2 = o.c[K_Z2];
-            e.xy = o.c[K_XY]; e.xz = o.c[K_XZ]; e.yz = o.c[K_YZ];
-            e.kx = o.c[K_X]; e.ky = o.c[K_Y]; e.kz = o.c[K_Z]; e.c = o.c[K_C];
-            e.orig = i;
+            GqEntry e;
+            rtp::pack_gq(e, o, i);
             t_gq.push_back(e);
         } else {
-            LinEntry e{};
-            e.kx = o.c[K_X]; e.ky = o.c[K_Y]; e.kz = o.c[K_Z]; e.c = o.c[K_C];
-            e.orig = i;
+            LinEntry e;
+            rtp::pack_lin(e, o, i);
             t_lin.push_back(e);
         }
     }
@@ -608,53 +564,17 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if (!t_lin.empty()) std::memcpy(blob.data() + fa.off_lin, t_lin.data(), sizeof(LinEntry) * t_lin.size());
     if (!t_cub.empty()) std::memcpy(blob.data() + fa.off_cub, t_cub.data(), sizeof(uint32_t) * t_cub.size());
     for (size_t i = 0; i < objs.size(); i++) {
-        MatEntry m{};
-        m.albedo[0] = objs[i].albedo[0];
-        m.albedo[1] = objs[i].albedo[1];
-        m.albedo[2] = objs[i].albedo[2];
-        m.refl = objs[i].refl;
+        MatEntry m;
+        rtp::pack_mat(m, objs[i]);
         std::memcpy(blob.data() + fa.off_mat + i * sizeof(MatEntry), &m, sizeof(m));
     }
     std::vector<DevLight> lights(sd->n_lights);
-    std::vector<char> term_finite(sd->n_lights, 0); // this light's colour and every albedo are finite: a factor max(0, n.l) = 0 makes its term exactly +0
-    for (uint32_t i = 0; i < sd->n_lights; i++) {
-        DevLight &l = lights[i];
-        std::memset(&l, 0, sizeof(l));
-        for (int k = 0; k < 3; k++) {
-            l.p[k] = sd->light_p[3 * i + k];
-            l.color[k] = sd->light_color[3 * i + k];
-        }
-        l.spherical = sd->light_is_spherical[i] ? 1u : 0u;
-        for (int k = 0; k < 3; k++) l.sdir[k] = (double) (float) l.p[k];
-        l.dxx = l.sdir[0] * l.sdir[0];
-        l.dyy = l.sdir[1] * l.sdir[1];
-        l.dzz = l.sdir[2] * l.sdir[2];
-        l.dxy = l.sdir[0] * l.sdir[1];
-        l.dxz = l.sdir[0] * l.sdir[2];
-        l.dyz = l.sdir[1] * l.sdir[2];
-        l.u2 = (l.dxx + l.dyy) + l.dzz;
-        l.inv_uu = l.u2 > 0.0 ? 1.0 / l.u2 : 0.0;
-        l.len_u = 1.001 * std::sqrt(l.u2);
-        bool finite = std::isfinite(l.color[0]) && std::isfinite(l.color[1]) && std::isfinite(l.color[2]);
-        for (uint32_t k = 0; k < sd->n_objects * 3u && finite; k++) finite = std::isfinite(sd->albedo[k]);
-        l.backface_exact = (!l.spherical && finite) ? 1u : 0u;
-        term_finite[i] = finite ? 1 : 0;
-    }
-    fa.lights_plain = 1u;
     std::vector<LightK> lightk(sd->n_lights); // the same lights as the lean path reads them (rt_scene_dev.h)
+    fa.lights_plain = 1u;
     for (uint32_t i = 0; i < sd->n_lights; i++) {
-        const DevLight &l = lights[i];
-        LightK &k = lightk[i];
-        std::memset(&k, 0, sizeof(k));
-        for (int c = 0; c < 3; c++) { k.p[c] = l.p[c]; k.sdir[c] = l.sdir[c]; k.color[c] = l.color[c]; }
-        k.u2 = l.u2; k.inv_uu = l.inv_uu; k.len_u = l.len_u;
-        k.four_u2 = 4.0 * l.u2;
-        k.s_yz = std::fabs(l.sdir[1]) + std::fabs(l.sdir[2]);
-        k.s_xz = std::fabs(l.sdir[0]) + std::fabs(l.sdir[2]);
-        k.s_xy = std::fabs(l.sdir[0]) + std::fabs(l.sdir[1]);
-        k.flags = (l.spherical ? 1u : 0u) | (l.backface_exact ? 2u : 0u) | (std::fabs(l.u2) > 1e-7 ? 4u : 0u) | // EPS of include/surface_impl.h:16,138
-                  ((l.spherical && term_finite[i]) ? 8u : 0u);
-        if (!l.spherical && (k.flags & 6u) != 6u) fa.lights_plain = 0u;
+        const bool term_finite = rtp::pack_light(lights[i], sd->light_p + 3 * (size_t) i, sd->light_color + 3 * (size_t) i, sd->light_is_spherical[i], albedos_finite);
+        rtp::pack_lightk(lightk[i], lights[i], term_finite);
+        if (!lights[i].spherical && (lightk[i].flags & 6u) != 6u) fa.lights_plain = 0u;
     }
 
     // the wave-per-block instantiation: unit spheres only, every one with a bounding radius, no mirror (sparse frames take the other one)
@@ -691,6 +611,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         hip_ok(hipMalloc(&ctx->d_fb, fb_bytes), "hipMalloc(framebuffer)") &&
         hip_ok(hipMalloc((void **) &ctx->d_counters, sizeof(unsigned long long) * 64), "hipMalloc(counters)") &&
         hip_ok(hipMemset(ctx->d_counters, 0, sizeof(unsigned long long) * 64), "hipMemset(counters)") &&
+        hip_ok(hipMalloc((void **) &ctx->d_ss_status, sizeof(SetSceneStatus)), "hipMalloc(scene-update status)") &&
+        hip_ok(hipMemset(ctx->d_ss_status, 0, sizeof(SetSceneStatus)), "hipMemset(scene-update status)") &&
         hip_ok(hipMemcpy(ctx->d_obj, blob.data(), blob.size(), hipMemcpyHostToDevice), "hipMemcpy(scene)") &&
         hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light, lights.data(), sizeof(DevLight) * lights.size(), hipMemcpyHostToDevice), "hipMemcpy(lights)") &&
         hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light + lights.size(), lightk.data(), sizeof(LightK) * lightk.size(), hipMemcpyHostToDevice), "hipMemcpy(light table)") &&
@@ -1283,6 +1205,163 @@ extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, f
     return RT_OK;
 }
 
+// ---- scene updates (rt_set_scene.hip) -----------------------------------------------------------------------
+static const char *reject_text(uint32_t reason)
+{
+    switch (reason) {
+    case RT_SCENE_REJECT_CLASS: return "the object would move to another class table";
+    case RT_SCENE_REJECT_BOUND: return "the unit sphere would gain or lose its bounding radius";
+    case RT_SCENE_REJECT_MIRROR: return "the scene would gain its first mirror or lose its last (object)";
+    case RT_SCENE_REJECT_CUBIC: return "a coefficient of the degree-3 object differs";
+    case RT_SCENE_REJECT_LIGHT: return "the light's table flags would change (|direction|^2 against 1e-7, or finite colours / albedos)";
+    default: return "unknown reason";
+    }
+}
+
+// Copy `bytes` from device memory behind everything the context has enqueued, and wait for that alone: the copy runs on the stream of
+// the context's last call (frames and updates of a context are ordered on it), so no other stream of the device is stalled.  Refused
+// while that stream is capturing -- nothing can be waited for inside a capture.
+static int read_behind_last_call(const char *who, rt_ctx *ctx, void *dst, const void *src, size_t bytes, void *dst2 = nullptr, const void *src2 = nullptr, size_t bytes2 = 0)
+{
+    int cur = -1;
+    RT_HIP(hipGetDevice(&cur));
+    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->last_stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(RT_ERR_INVALID, "%s: the context's stream is capturing; end the capture first", who);
+    RT_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream));
+    if (bytes2) RT_HIP(hipMemcpyAsync(dst2, src2, bytes2, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+static int set_scene_check(const char *who, const rt_ctx *ctx, const rt_scene_update *u)
+{
+    if (!u->coefs && !u->reflection && !u->albedo && !u->light_p && !u->light_color) return fail(RT_ERR_INVALID, "%s: all five arrays are null", who);
+    if (((uintptr_t) u->coefs | (uintptr_t) u->light_p) & 7u) return fail(RT_ERR_INVALID, "%s: coefs / light_p must be 8-byte aligned", who);
+    if (((uintptr_t) u->reflection | (uintptr_t) u->albedo | (uintptr_t) u->light_color) & 3u)
+        return fail(RT_ERR_INVALID, "%s: reflection / albedo / light_color must be 4-byte aligned", who);
+    if (ctx->fa.n_obj == 0u && (u->coefs || u->reflection || u->albedo)) return fail(RT_ERR_INVALID, "%s: an object array for a scene without objects", who);
+    if (ctx->fa.n_lights == 0u && (u->light_p || u->light_color)) return fail(RT_ERR_INVALID, "%s: a light array for a scene without lights", who);
+    return RT_OK;
+}
+
+// enqueue the kernel on `stream`, in the context's frame order (the rule of render_impl)
+static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update *dev, hipStream_t stream)
+{
+    int cur = -1;
+    RT_HIP(hipGetDevice(&cur));
+    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    if (ctx->rendered && stream != ctx->last_stream) {
+        if (ctx->captured || capturing)
+            return fail(RT_ERR_INVALID, "%s: a context whose calls were captured into a graph on one stream must stay on that stream (frames and scene updates of a "
+                                        "context are ordered on the device, and a capture cannot be ordered against another stream through an event)", who);
+        RT_HIP(hipStreamWaitEvent(stream, ctx->ev_done, 0));
+    }
+    const FrameArgs &fa = ctx->fa;
+    SetSceneArgs a{};
+    a.blob = reinterpret_cast<unsigned char *>(ctx->d_obj);
+    a.lights = ctx->d_light;
+    a.status = ctx->d_ss_status;
+    a.coefs = dev->coefs;
+    a.reflection = dev->reflection;
+    a.albedo = dev->albedo;
+    a.light_p = dev->light_p;
+    a.light_color = dev->light_color;
+    a.n_obj = fa.n_obj;
+    a.n_lights = fa.n_lights;
+    a.n_us = fa.n_us;
+    a.n_gq = fa.n_gq;
+    a.n_lin = fa.n_lin;
+    a.off_us = fa.off_us;
+    a.off_gq = fa.off_gq;
+    a.off_lin = fa.off_lin;
+    a.off_mat = fa.off_mat;
+    a.has_mirror = fa.has_mirror;
+    const hipError_t e = rt_launch_set_scene(&a, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    if (!capturing) RT_HIP(hipEventRecord(ctx->ev_done, stream));
+    ctx->captured = capturing;
+    ctx->last_stream = stream;
+    ctx->rendered = true;
+    return RT_OK;
+}
+
+extern "C" int rt_set_scene(rt_ctx *ctx, const rt_scene_update *dev, void *stream)
+{
+    if (!ctx || !dev) return fail(RT_ERR_INVALID, "rt_set_scene: null argument");
+    if (int rc = set_scene_check("rt_set_scene", ctx, dev)) return rc;
+    return set_scene_enqueue("rt_set_scene", ctx, dev, (hipStream_t) stream);
+}
+
+extern "C" int rt_set_scene_host(rt_ctx *ctx, const rt_scene_update *host, void *stream_)
+{
+    if (!ctx || !host) return fail(RT_ERR_INVALID, "rt_set_scene_host: null argument");
+    if (int rc = set_scene_check("rt_set_scene_host", ctx, host)) return rc;
+    hipStream_t stream = (hipStream_t) stream_;
+    int cur = -1;
+    RT_HIP(hipGetDevice(&cur));
+    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(RT_ERR_INVALID, "rt_set_scene_host: the stream is capturing, and this call allocates and waits; capture rt_set_scene (device arrays) instead");
+    // staging: the five arrays back to back, the FP64 ones first (n_objects and n_lights are fixed, so one allocation serves every call)
+    const size_t no = ctx->fa.n_obj, nl = ctx->fa.n_lights;
+    const size_t b_coefs = sizeof(double) * RT_NCOEF * no, b_lp = sizeof(double) * 3 * nl, b_refl = sizeof(float) * no, b_alb = sizeof(float) * 3 * no,
+                 b_lc = sizeof(float) * 3 * nl;
+    if (!ctx->d_ss_stage) RT_HIP(hipMalloc((void **) &ctx->d_ss_stage, b_coefs + b_lp + b_refl + b_alb + b_lc));
+    unsigned char *p = ctx->d_ss_stage;
+    rt_scene_update dev{};
+    auto put = [&](const void *src, size_t bytes) -> const void * {
+        unsigned char *dst = p;
+        p += bytes;
+        if (!src) return nullptr;
+        return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) == hipSuccess ? dst : nullptr;
+    };
+    dev.coefs = (const double *) put(host->coefs, b_coefs);
+    dev.light_p = (const double *) put(host->light_p, b_lp);
+    dev.reflection = (const float *) put(host->reflection, b_refl);
+    dev.albedo = (const float *) put(host->albedo, b_alb);
+    dev.light_color = (const float *) put(host->light_color, b_lc);
+    if ((!dev.coefs != !host->coefs) || (!dev.light_p != !host->light_p) || (!dev.reflection != !host->reflection) || (!dev.albedo != !host->albedo) ||
+        (!dev.light_color != !host->light_color))
+        return fail(RT_ERR_DEVICE, "rt_set_scene_host: hipMemcpyAsync failed: %s", hipGetErrorString(hipGetLastError()));
+    if (int rc = set_scene_enqueue("rt_set_scene_host", ctx, &dev, stream)) return rc;
+    SetSceneStatus st{};
+    RT_HIP(hipMemcpyAsync(&st, ctx->d_ss_status, sizeof(st), hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    if (st.last == 2u)
+        return fail(RT_ERR_SCENE, "rt_set_scene_host: update rejected, nothing was written: reason %u at index %u: %s", st.reason, st.index, reject_text(st.reason));
+    return RT_OK;
+}
+
+extern "C" int rt_set_scene_status(rt_ctx *ctx, uint64_t *applied, uint64_t *rejected, uint32_t *reason, uint32_t *index)
+{
+    if (!ctx) return fail(RT_ERR_INVALID, "rt_set_scene_status: null argument");
+    SetSceneStatus st{};
+    if (int rc = read_behind_last_call("rt_set_scene_status", ctx, &st, ctx->d_ss_status, sizeof(st))) return rc;
+    if (applied) *applied = st.applied;
+    if (rejected) *rejected = st.rejected;
+    if (reason) *reason = st.reason;
+    if (index) *index = st.index;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_scene_blob(rt_ctx *ctx, void *out, size_t cap, size_t *bytes)
+{
+    if (!ctx || !bytes) return fail(RT_ERR_INVALID, "rt_debug_scene_blob: null argument");
+    const size_t light_bytes = (sizeof(DevLight) + sizeof(LightK)) * (size_t) ctx->fa.n_lights, need = (size_t) ctx->fa.scene_bytes + light_bytes;
+    *bytes = need;
+    if (!out) return RT_OK;
+    if (cap < need) return fail(RT_ERR_INVALID, "rt_debug_scene_blob: %zu bytes offered, the scene takes %zu", cap, need);
+    return read_behind_last_call("rt_debug_scene_blob", ctx, out, ctx->d_obj, ctx->fa.scene_bytes, (unsigned char *) out + ctx->fa.scene_bytes, ctx->d_light, light_bytes);
+}
+
 extern "C" int rt_local_rows(const rt_ctx *ctx, uint32_t *n_rows)
 {
     if (!ctx || !n_rows) return fail(RT_ERR_INVALID, "rt_local_rows: null argument");
@@ -1516,6 +1595,8 @@ extern "C" int rt_destroy(rt_ctx *ctx)
     if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
     if (ctx->rq_ev0) (void) hipEventDestroy(ctx->rq_ev0);
     if (ctx->rq_ev1) (void) hipEventDestroy(ctx->rq_ev1);
+    if (ctx->d_ss_status) (void) hipFree(ctx->d_ss_status);
+    if (ctx->d_ss_stage) (void) hipFree(ctx->d_ss_stage);
 
     delete ctx;
     return RT_OK;

@@ -124,6 +124,40 @@ void load_multi()
     if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold || !g_mapi.set_geometry) die_text("libmi355rt_multi.so", "missing entry points");
 }
 
+// the Scene's objects and lights as the ABI's flat arrays
+struct FlatScene {
+    std::vector<double> coefs, light_p;
+    std::vector<float> refl, albedo, light_c;
+    std::vector<uint8_t> kind;
+    explicit FlatScene(const Scene &scene)
+    {
+        const size_t no = scene.objects.size(), nl = scene.lights.size();
+        coefs.resize(no * RT_NCOEF);
+        light_p.resize(nl * 3);
+        refl.resize(no);
+        albedo.resize(no * 3);
+        light_c.resize(nl * 3);
+        kind.resize(nl);
+        for (size_t i = 0; i < no; i++) {
+            const Object &o = scene.objects[i];
+            const double *c = &o.surface.x3; // 20 packed doubles in SurfaceCoefs order (include/surface.h:12-14)
+            for (int k = 0; k < RT_NCOEF; k++) coefs[i * RT_NCOEF + k] = c[k];
+            refl[i] = o.reflection_ratio;
+            for (int k = 0; k < 3; k++) albedo[3 * i + k] = o.color[k];
+        }
+        for (size_t i = 0; i < nl; i++) {
+            const LightSource &l = scene.lights[i];
+            kind[i] = l.is_spherical ? 1 : 0;
+            for (int k = 0; k < 3; k++) {
+                light_p[3 * i + k] = l.p[k];
+                light_c[3 * i + k] = l.light_color[k];
+            }
+        }
+    }
+};
+size_t g_n_objects = 0, g_n_lights = 0; // of the scene init_update() loaded: what mi355rt_update_scene may replace
+std::vector<uint8_t> g_light_kind;
+
 } // namespace
 
 // Exported so a host can install / query without new headers.
@@ -174,6 +208,36 @@ extern "C" int mi355rt_update_shade(const rt_ray *rays, unsigned int n, float *r
     return rt_shade_rays_host(g_ctx, rays, n, rgba_out, nullptr);
 }
 
+// Move the objects and lights of the scene init_update() loaded: the same number of objects and lights, every light of its kind, the new
+// coefficients, materials, light vectors and colours (rt_set_scene_host; include/mi355rt.h, "Scene updates").  Valid after init_update();
+// the next update() draws the new scene.  RT_ERR_SCENE when the update would change the scene's layout (nothing is written then),
+// RT_ERR_INVALID for other counts or kinds, before init_update() and with MI355RT_DEVICES naming several devices: the multi-GPU layer
+// has no scene-update entry point.  Image size, background, field of view and max_reflections of `scene` are not looked at.
+extern "C" int mi355rt_update_scene(const Scene &scene)
+{
+    if (!g_ctx) {
+        rt_set_last_error(g_multi ? "mi355rt_update_scene: not available with several devices (MI355RT_DEVICES)" : "mi355rt_update_scene: no init_update() call yet");
+        return RT_ERR_INVALID;
+    }
+    const FlatScene flat(scene);
+    if (scene.objects.size() != g_n_objects || scene.lights.size() != g_n_lights || flat.kind != g_light_kind) {
+        rt_set_last_error("mi355rt_update_scene: the number of objects and lights and every light's kind must stay what init_update() loaded");
+        return RT_ERR_INVALID;
+    }
+    if (g_n_objects == 0 && g_n_lights == 0) return RT_OK;
+    rt_scene_update u{};
+    if (g_n_objects) {
+        u.coefs = flat.coefs.data();
+        u.reflection = flat.refl.data();
+        u.albedo = flat.albedo.data();
+    }
+    if (g_n_lights) {
+        u.light_p = flat.light_p.data();
+        u.light_color = flat.light_c.data();
+    }
+    return rt_set_scene_host(g_ctx, &u, nullptr);
+}
+
 void init_update(unsigned int texture, const Scene &scene)
 {
     if (g_ctx || g_multi) cleanup_update();
@@ -220,24 +284,13 @@ void init_update(unsigned int texture, const Scene &scene)
 
     // flatten the Scene into the ABI's descriptor (arrays are borrowed only for the call)
     const size_t no = scene.objects.size(), nl = scene.lights.size();
-    std::vector<double> coefs(no * RT_NCOEF), light_p(nl * 3);
-    std::vector<float> refl(no), albedo(no * 3), light_c(nl * 3);
-    std::vector<uint8_t> kind(nl);
-    for (size_t i = 0; i < no; i++) {
-        const Object &o = scene.objects[i];
-        const double *c = &o.surface.x3; // 20 packed doubles in SurfaceCoefs order (include/surface.h:12-14)
-        for (int k = 0; k < RT_NCOEF; k++) coefs[i * RT_NCOEF + k] = c[k];
-        refl[i] = o.reflection_ratio;
-        for (int k = 0; k < 3; k++) albedo[3 * i + k] = o.color[k];
-    }
-    for (size_t i = 0; i < nl; i++) {
-        const LightSource &l = scene.lights[i];
-        kind[i] = l.is_spherical ? 1 : 0;
-        for (int k = 0; k < 3; k++) {
-            light_p[3 * i + k] = l.p[k];
-            light_c[3 * i + k] = l.light_color[k];
-        }
-    }
+    const FlatScene flat(scene);
+    const std::vector<double> &coefs = flat.coefs, &light_p = flat.light_p;
+    const std::vector<float> &refl = flat.refl, &albedo = flat.albedo, &light_c = flat.light_c;
+    const std::vector<uint8_t> &kind = flat.kind;
+    g_n_objects = no;
+    g_n_lights = nl;
+    g_light_kind = kind;
     rt_scene_desc sd{};
     sd.width = scene.px_width;
     sd.height = scene.px_height;

@@ -349,9 +349,9 @@ int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
  * arguments describe another pixel grid; supporting them is a follow-up); the multi-GPU layer (rt_*_multi) has no G-buffer entry
  * point -- a rank-level caller gathers the planes itself with rt_row_map.
  *
- * The pass reads the context's scene and camera-plane tables (constant after rt_create) and nothing else: no tile words, launch-order
- * generations, census, counters or frame tag.  Interleaving it with rt_render, on the same or another stream, changes no image and no
- * later G-buffer; it needs no ordering against the context's frames.
+ * The pass reads the context's scene (constant between rt_set_scene calls) and camera-plane tables (constant after rt_create) and
+ * nothing else: no tile words, launch-order generations, census, counters or frame tag.  Interleaving it with rt_render, on the same or another stream, changes no image and no
+ * later G-buffer; it needs no ordering against the context's frames -- only against rt_set_scene, see "Scene updates".
  * ------------------------------------------------------------------------------------------------- */
 typedef struct rt_hit {
     double t;         /* distance from the eye, +inf on a miss */
@@ -408,8 +408,8 @@ int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, r
  *
  * Ray queries carry no frame state, so they work in EVERY context: plain, RT_FLAG_SSAA2 / RT_FLAG_SSAA4, adaptive, any rank or world,
  * any format.  They read the scene blob and nothing else -- no camera tables, tile words, launch-order generations, census, counters
- * or frame tag -- and need no ordering against rt_render.  Scenes whose class tables exceed the LDS limit are refused as
- * rt_render_gbuffer refuses them.  Limits: the multi-GPU layer (rt_*_multi) has no ray-query entry point.
+ * or frame tag -- and need no ordering against rt_render (against rt_set_scene they do: "Scene updates").  Scenes whose class
+ * tables exceed the LDS limit are refused as rt_render_gbuffer refuses them.  Limits: the multi-GPU layer (rt_*_multi) has no ray-query entry point.
  *
  * Colour (rt_shade_rays; csrc/rt_shade_rays.hip).  The reference's render_pixel (src/update-cpu.cpp:82-119) with
  * ray_origin := o and dir := d, d used exactly as given, never normalised.  The first segment is get_color_and_object
@@ -454,6 +454,71 @@ int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, rt_hit *out,
 int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits /* may be NULL */, void *stream, float *ms);
 /* rt_shade_rays for rays and pixels in HOST memory; blocks.  Staging buffers as rt_trace_rays_host. */
 int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_out, void *stream); /* host memory, blocks */
+
+/* ---------------------------------------------------------------------------------------------------
+ * Scene updates: move objects and lights of a live context (csrc/rt_set_scene.hip)
+ *
+ * rt_create uploads the scene once; rt_set_scene rewrites it in stream order, without a new context: one kernel of one workgroup reads
+ * raw descriptor arrays from DEVICE memory -- the layout and meaning of the rt_scene_desc arrays of the same names -- and rebuilds the
+ * scene blob and both light tables with the very functions rt_create packs them with (csrc/rt_scene_pack.hpp), so the device holds,
+ * byte for byte, what a fresh rt_create of the new scene with the same rt_config would have uploaded (rt_debug_scene_blob shows it).
+ * Any of the five pointers may be NULL = "keep what the context holds" (the kernel takes those raw values from its own records), not all
+ * five.  n_objects, n_lights and every light's kind are fixed, and so are the background, field of view and max_reflections.
+ *
+ * The layout rule.  Everything the host chose at rt_create (kernel instantiation, table sizes and offsets, LDS sizes, culling, the lean
+ * path) stays valid without the host seeing the data, because an update is ACCEPTED if and only if a fresh rt_create would derive
+ *   - the same class table (unit sphere / other quadric / plane / degree 3) for every object, hence the same slot;
+ *   - the same cullability for every object (a unit sphere with finite r^2 > 0, or not);
+ *   - the same "some object has reflection_ratio > 1e-7" for the scene;
+ *   - the same light-table flags for every light: its direction keeps |(float) p|^2 > 1e-7 or keeps failing it, and "this light's
+ *     colour and every albedo of the scene are finite" keeps its truth value;
+ *   - bit-identical 20 coefficients for every degree-3 object (their per-frame Taylor data is formed on the host: cubic surfaces are
+ *     frozen in this version; their albedo and reflection may change within the rule).
+ * Otherwise it is REJECTED and the kernel writes nothing to the scene: all or nothing.  Either way the kernel bumps a counter in a
+ * small device block of the context: `applied`, or `rejected` together with the reason (RT_SCENE_REJECT_*) and the index of the
+ * first offender -- objects come before lights, the lowest index first, and for one object the lowest reason code;
+ * RT_SCENE_REJECT_MIRROR names the first object that became a mirror in a scene without one, or the first that stopped being one when
+ * no mirror is left; RT_SCENE_REJECT_LIGHT names the light (a non-finite albedo shows as the first light with finite colour).
+ *
+ * Ordering.  rt_set_scene takes part in the context's frame order exactly as rt_render does: same stream as the previous call = enqueue
+ * only (one kernel, nothing else: `(rt_set_scene, rt_render) x K` can be captured into one graph, and a replay reads the device arrays
+ * again, so rewriting them between replays animates the scene); another stream first waits for the event recorded behind the previous
+ * call; the event is not recorded while capturing, and after a captured call a call on another stream is refused (RT_ERR_INVALID).
+ * The arrays must stay unchanged until the kernel has run.  The passes that READ the scene -- rt_render_gbuffer, rt_pick, rt_trace_rays,
+ * rt_occluded_rays, rt_shade_rays and their _host forms -- need no ordering against rt_render, but they DO need ordering against
+ * rt_set_scene when issued on another stream, and that ordering is the caller's to establish (on one stream it is automatic).
+ * Frame-to-frame state (launch order, census, tile words) survives an update: it affects speed only, never the image, exactly as under
+ * a moving camera.  Works in every context kind.  The multi-GPU layer (rt_*_multi) has no scene-update entry point.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt_scene_update {
+    const double *coefs;       /* [n_objects][RT_NCOEF]  or NULL */
+    const float *reflection;   /* [n_objects]            or NULL */
+    const float *albedo;       /* [n_objects][3]         or NULL */
+    const double *light_p;     /* [n_lights][3]          or NULL */
+    const float *light_color;  /* [n_lights][3]          or NULL */
+} rt_scene_update;             /* 40 bytes */
+
+#define RT_SCENE_REJECT_CLASS 1u  /* an object would move to another class table */
+#define RT_SCENE_REJECT_BOUND 2u  /* a unit sphere would gain or lose its bounding radius (r^2 <= 0 or not finite) */
+#define RT_SCENE_REJECT_MIRROR 3u /* the scene would gain its first mirror or lose its last */
+#define RT_SCENE_REJECT_CUBIC 4u  /* a coefficient of a degree-3 object differs */
+#define RT_SCENE_REJECT_LIGHT 5u  /* a light's table flags would change */
+
+/* Device pointers; enqueues one kernel on `stream` and returns.  RT_ERR_INVALID for a NULL context or struct (both before a device is
+ * looked for), five NULL arrays, a pointer not aligned to its type (8 bytes for coefs / light_p, 4 for the others) and a non-NULL
+ * array of a kind the scene has none of (objects / lights).  Whether the update was applied is on the device: rt_set_scene_status. */
+int rt_set_scene(rt_ctx *ctx, const rt_scene_update *dev, void *stream);
+/* The same for arrays in HOST memory; blocks.  The staging buffer is the context's own (allocated on first use, freed by rt_destroy);
+ * calls on one context must not overlap in time.  RT_ERR_SCENE when the kernel rejected the update: rt_last_error() then names the
+ * reason and the index.  RT_ERR_INVALID on a capturing stream (the call allocates and waits: capture rt_set_scene instead). */
+int rt_set_scene_host(rt_ctx *ctx, const rt_scene_update *host, void *stream);
+/* Waits for the context's last call (on that call's stream; no other stream of the device is stalled), then: updates applied and
+ * rejected since rt_create, and the reason / index of the most recent rejection (0 / 0 before the first).  Any output pointer may be
+ * NULL.  RT_ERR_INVALID while that stream is capturing. */
+int rt_set_scene_status(rt_ctx *ctx, uint64_t *applied, uint64_t *rejected, uint32_t *reason, uint32_t *index);
+/* Diagnostics: the scene as the device holds it -- the blob, then DevLight[n_lights], then LightK[n_lights] (csrc/rt_scene_dev.h).
+ * *bytes receives the size; out may be NULL (size only), else cap must be at least that.  Waits as rt_set_scene_status does. */
+int rt_debug_scene_blob(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
