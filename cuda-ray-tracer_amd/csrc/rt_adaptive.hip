@@ -8,7 +8,7 @@
 // shading (rt_shade.hpp).  The resolve's arithmetic -- the sums, 1/k^2 and the RGBA8 quantisation -- uses explicitly rounded
 // operations, so it is the same in both builds and equal to rt_resolve.hip's.
 #include <hip/hip_runtime.h>
-
+#include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_shade.hpp"
 #include "rt_wavefront_math.hpp" // Ball, sphere_relevant: the wavefront kernel's conservative shadow culling
 

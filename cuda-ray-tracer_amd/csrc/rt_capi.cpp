@@ -10,66 +10,26 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
 
 #include "mi355rt.h"
+#include "rt_launch.h"       // every launcher of the kernel files, and struct Kernels
 #include "rt_scene_dev.h"
-#include "rt_scene_pack.hpp" // (the derived scene data per record: shared with rt_set_scene.hip)
+#include "rt_scene_image.hpp" // the scene image (blob, light tables, FrameArgs' scene words): shared with the test tools
+#include "rt_frame_host.hpp"  // camera tables, per-frame camera words, halo rows: shared with the test tools
 #include "rt_set_scene.h"
-#include "rt_math.hpp" // (rtm::cubic_at, host side: the Taylor data of degree-3 objects at the frame's ray origin)
 #include "scene-exception.h"
 #include "scene.h"
 #include "camera.h"
 
-// kernels, one set per floating-point contraction mode (rt_kernels.hip)
-extern "C" hipError_t rt_launch_trace_strict(const FrameArgs *, const DevObject *, const DevLight *, void *, unsigned long long *, int, int, hipStream_t);
-extern "C" hipError_t rt_launch_trace_fast(const FrameArgs *, const DevObject *, const DevLight *, void *, unsigned long long *, int, int, hipStream_t);
-extern "C" hipError_t rt_launch_wavefront_strict(const FrameArgs *, const DevObject *, const DevLight *, void *, unsigned long long *, int, const double *, const double *, hipStream_t);
-extern "C" hipError_t rt_launch_wavefront_fast(const FrameArgs *, const DevObject *, const DevLight *, void *, unsigned long long *, int, const double *, const double *, hipStream_t);
-
-extern "C" size_t rt_wavefront_lds_bytes_strict(uint32_t, uint32_t, int, uint32_t, int, uint32_t);
-
-extern "C" hipError_t rt_launch_assemble_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, hipStream_t);
-extern "C" hipError_t rt_launch_pack_sparse_strict(const void *, void *, uint32_t, uint32_t, const uint32_t *, uint32_t, int, hipStream_t);
-extern "C" hipError_t rt_launch_assemble_sparse_strict(const void *, void *, uint32_t, uint32_t, uint32_t, uint32_t, const uint32_t *, uint32_t, void *, uint32_t,
-                                                       uint32_t, int, hipStream_t);
-// supersampling resolve (rt_resolve.hip, built once without FMA contraction)
-extern "C" hipError_t rt_launch_resolve(const void *, void *, uint32_t, uint32_t, uint32_t, int, int, hipStream_t);
-// adaptive supersampling (rt_adaptive.hip): the ray-list kernel per contraction mode, and the classify kernel
-extern "C" hipError_t rt_launch_ray_list_strict(const FrameArgs *, const DevObject *, const DevLight *, const double *, const double *, const uint32_t *,
-                                                const uint32_t *, uint32_t, uint32_t, uint32_t, void *, int, int, unsigned long long *, hipStream_t);
-extern "C" hipError_t rt_launch_ray_list_fast(const FrameArgs *, const DevObject *, const DevLight *, const double *, const double *, const uint32_t *,
-                                              const uint32_t *, uint32_t, uint32_t, uint32_t, void *, int, int, unsigned long long *, hipStream_t);
-extern "C" hipError_t rt_launch_classify_strict(const void *, const void *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, void *, int,
-                                                uint32_t *, uint32_t *, hipStream_t);
-
-// primary-hit G-buffer and picking (rt_gbuffer.hip), per contraction mode
-extern "C" hipError_t rt_launch_gbuffer_strict(const FrameArgs *, const void *, const double *, const double *, int32_t *, double *, float *, hipStream_t);
-extern "C" hipError_t rt_launch_gbuffer_fast(const FrameArgs *, const void *, const double *, const double *, int32_t *, double *, float *, hipStream_t);
-extern "C" hipError_t rt_launch_pick_strict(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
-extern "C" hipError_t rt_launch_pick_fast(const FrameArgs *, const void *, const double *, const double *, const uint32_t *, uint32_t, void *, hipStream_t);
-extern "C" size_t rt_gbuffer_lds_bytes_strict(const FrameArgs *);
-// ray queries (rt_rays.hip), per contraction mode
-extern "C" hipError_t rt_launch_trace_rays_strict(const FrameArgs *, const void *, const void *, uint32_t, void *, uint32_t, hipStream_t);
-extern "C" hipError_t rt_launch_trace_rays_fast(const FrameArgs *, const void *, const void *, uint32_t, void *, uint32_t, hipStream_t);
-extern "C" hipError_t rt_launch_occluded_rays_strict(const FrameArgs *, const void *, const void *, const double *, uint32_t, int32_t *, uint32_t, hipStream_t);
-extern "C" hipError_t rt_launch_occluded_rays_fast(const FrameArgs *, const void *, const void *, const double *, uint32_t, int32_t *, uint32_t, hipStream_t);
-extern "C" size_t rt_rays_lds_bytes_strict(const FrameArgs *);
-// colour of caller-supplied rays (rt_shade_rays.hip), per contraction mode
-extern "C" hipError_t rt_launch_shade_rays_strict(const FrameArgs *, const void *, const void *, const void *, uint32_t, float *, void *, uint32_t, hipStream_t);
-extern "C" hipError_t rt_launch_shade_rays_fast(const FrameArgs *, const void *, const void *, const void *, uint32_t, float *, void *, uint32_t, hipStream_t);
-// RT_FLAG_SSAA_GEOMETRY: the G pass of an adaptive frame (rt_gbuffer.hip) and the classifier that reads it (rt_adaptive.hip)
-extern "C" hipError_t rt_launch_gbuffer_edges_strict(const FrameArgs *, const void *, const double *, const double *, int32_t *, float *, const uint32_t *, uint32_t,
-                                                     void *, hipStream_t);
-extern "C" hipError_t rt_launch_gbuffer_edges_fast(const FrameArgs *, const void *, const double *, const double *, int32_t *, float *, const uint32_t *, uint32_t,
-                                                   void *, hipStream_t);
-extern "C" hipError_t rt_launch_classify_geometry_strict(const void *, const void *, const int32_t *, const float *, const void *, uint32_t, uint32_t, uint32_t,
-                                                         uint32_t, uint32_t, uint32_t, float, float, void *, int, uint32_t *, uint32_t *, hipStream_t);
-
-// scene update (rt_set_scene.hip, built once without FMA contraction: the derived scene data is the same in every variant)
-extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *, hipStream_t);
+// the launchers a context calls per floating-point contraction mode (rt_launch.h, struct Kernels); rt_create picks one from RT_FLAG_FAST
+#define RT_KERNELS(V)                                                                                                                              \
+    {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
+     RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V)}
+static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 
 namespace {
 
@@ -86,11 +46,74 @@ int fail(int code, const char *fmt, ...)
     return code;
 }
 
-#define RT_HIP(call)                                                                                         \
+// a failed HIP call is RT_ERR_DEVICE, named `what` in the message ("hipMalloc(scene) failed: ...") or by its own text
+#define RT_TRY(what, call)                                                                                   \
     do {                                                                                                     \
         hipError_t e_ = (call);                                                                              \
-        if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s failed: %s", #call, hipGetErrorString(e_));      \
+        if (e_ != hipSuccess) return fail(RT_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(e_));       \
     } while (0)
+#define RT_HIP(call) RT_TRY(#call, call)
+
+// What a context owns on the device, one wrapper per kind: released when the context is deleted (rt_destroy makes the context's device
+// current first).  They convert to the raw handle, so the code that uses them reads like code on raw pointers.
+struct NoCopy {
+    NoCopy() = default;
+    NoCopy(const NoCopy &) = delete;
+    NoCopy &operator=(const NoCopy &) = delete;
+};
+template <typename T>
+struct DevMem : NoCopy { // device memory
+    T *p = nullptr;
+    ~DevMem() { reset(); }
+    void reset() { if (p) (void) hipFree(p); p = nullptr; }
+    hipError_t alloc(size_t bytes) { reset(); return hipMalloc((void **) &p, bytes); }
+    operator T *() const { return p; }
+};
+struct MappedWords : NoCopy { // host memory the device writes through a mapping
+    uint32_t *p = nullptr;
+    ~MappedWords() { reset(); }
+    void reset() { if (p) (void) hipHostFree(p); p = nullptr; }
+    operator uint32_t *() const { return p; }
+};
+struct Event : NoCopy {
+    hipEvent_t e = nullptr;
+    ~Event() { if (e) (void) hipEventDestroy(e); }
+    hipError_t create(unsigned flags = hipEventDefault) { return hipEventCreateWithFlags(&e, flags); }
+    operator hipEvent_t() const { return e; }
+};
+
+// the staging buffers of an entry point that takes host arrays: an input and an output array that only grow, n elements each
+struct Staging {
+    DevMem<void> in, out;
+    uint32_t cap = 0;
+    int reserve(uint32_t n, size_t in_each, size_t out_each)
+    {
+        if (n <= cap) return RT_OK; // (every earlier call has synchronised: nothing uses the old buffers)
+        in.reset();
+        out.reset();
+        cap = 0;
+        const uint32_t want = n < 64u ? 64u : n;
+        RT_HIP(in.alloc(in_each * (size_t) want));
+        RT_HIP(out.alloc(out_each * (size_t) want));
+        cap = want;
+        return RT_OK;
+    }
+};
+
+// the C ABI's exception boundary of the scene entry points: a SceneException is RT_ERR_SCENE, anything else `other`
+template <typename F>
+int guarded(int other, F &&body)
+{
+    try {
+        return body();
+    } catch (const SceneException &e) {
+        return fail(RT_ERR_SCENE, "%s", e.what());
+    } catch (const std::bad_alloc &) {
+        return fail(RT_ERR_NOMEM, "out of memory");
+    } catch (const std::exception &e) {
+        return fail(other, "%s", e.what());
+    }
+}
 
 } // namespace
 
@@ -131,6 +154,7 @@ struct rt_scene {
 
 struct rt_ctx {
     int device = 0;
+    const Kernels *kern = &kernels_strict; // RT_FLAG_FAST: &kernels_fast
     rt_config cfg{};   // as the caller passed it (defaults filled in): the OUTPUT frame's bands and format
     FrameArgs fa{};    // what the render kernels draw: the output frame, or with supersampling the internal k x finer RGBA32F frame
     // output frame (what every entry point but the render kernels sees; the same as fa's geometry without supersampling)
@@ -138,64 +162,56 @@ struct rt_ctx {
     uint32_t local_rows = 0, max_local_rows = 0;
     size_t pixel_bytes = 16;
     uint32_t ssaa = 1;          // samples per axis k (RT_FLAG_SSAA2 / RT_FLAG_SSAA4)
-    void *d_ss = nullptr;       // k > 1: the internal frame's local rows, [k * local_rows][k * width] float4
+    DevMem<void> d_ss;          // k > 1: the internal frame's local rows, [k * local_rows][k * width] float4
     int resolve_nt = 0;         // the resolve reads the internal frame with non-temporal loads (MI355RT_RESOLVE_NT, experiments)
     // RT_FLAG_SSAA_ADAPTIVE (rt_adaptive.hip): fa is the output geometry (as for k = 1); k = ssaa samples per axis where a pixel is refined
     bool adaptive = false;
     float tau = 1.0f / 32.0f;   // rt_set_ssaa_threshold
-    void *d_p = nullptr;        // RGBA8 output: the plain frame P, [local_rows][width] float4 (RGBA32F renders P in place)
-    void *d_halo = nullptr;     // world > 1: [halo_slots][width] float4, slot 2b / 2b + 1 = the global row just below / above local band b
+    DevMem<void> d_p;           // RGBA8 output: the plain frame P, [local_rows][width] float4 (RGBA32F renders P in place)
+    DevMem<void> d_halo;        // world > 1: [halo_slots][width] float4, slot 2b / 2b + 1 = the global row just below / above local band b
     uint32_t halo_slots = 0;
     uint64_t halo_rays = 0;     // centre rays the halo pass traces per frame (slots inside the image x width)
-    uint32_t *d_list = nullptr; // [local_rows * width] refined pixels, (local row << 16) | x; d_list[local_rows * width] = their count
-    double *d_camxk = nullptr, *d_camyk = nullptr; // camera-plane tables of the k-times finer sample grid
-    uint32_t ray_grid = 0, halo_grid = 0;          // workgroups of the ray-list kernel (fixed per context)
+    DevMem<uint32_t> d_list;    // [local_rows * width] refined pixels, (local row << 16) | x; d_list[local_rows * width] = their count
+    DevMem<double> d_camxk, d_camyk;      // camera-plane tables of the k-times finer sample grid
+    uint32_t ray_grid = 0, halo_grid = 0; // workgroups of the ray-list kernel (fixed per context)
     // RT_FLAG_SSAA_GEOMETRY: the primary-hit planes of this rank's rows and the halo rows' records
     bool geometry = false;
-    float min_cos = -INFINITY;    // rt_set_ssaa_geometry; -inf: object ids only, the normal plane is not formed
-    int32_t *d_geo_obj = nullptr; // [local_rows][width]
-    float *d_geo_nrm = nullptr;   // [local_rows][width] float4
-    uint32_t *d_geo_xy = nullptr; // world > 1: [halo_slots * width][2] global coordinates of the halo rows' pixels (constant)
-    void *d_geo_halo = nullptr;   // world > 1: [halo_slots][width] rt_hit
-    DevObject *d_obj = nullptr;
-    DevLight *d_light = nullptr;
-    void *d_fb = nullptr;
-    unsigned long long *d_counters = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t ev_done = nullptr;      // recorded behind every render: a render on ANOTHER stream waits for it (frames of a context are ordered)
+    float min_cos = -INFINITY;   // rt_set_ssaa_geometry; -inf: object ids only, the normal plane is not formed
+    DevMem<int32_t> d_geo_obj;   // [local_rows][width]
+    DevMem<float> d_geo_nrm;     // [local_rows][width] float4
+    DevMem<uint32_t> d_geo_xy;   // world > 1: [halo_slots * width][2] global coordinates of the halo rows' pixels (constant)
+    DevMem<void> d_geo_halo;     // world > 1: [halo_slots][width] rt_hit
+    DevMem<DevObject> d_obj;     // the scene blob (rt_scene_dev.h)
+    DevMem<DevLight> d_light;    // [DevLight x n_lights][LightK x n_lights]
+    DevMem<void> d_fb;
+    DevMem<unsigned long long> d_counters;
+    Event ev0, ev1;  // the pair behind `ms` of every timed entry point (a context belongs to one thread at a time, and a timed call has waited for ev1 when it returns)
+    Event ev_done;   // recorded behind every render: a render on ANOTHER stream waits for it (frames of a context are ordered)
 
     hipStream_t last_stream = nullptr;
     bool rendered = false;
     bool captured = false;      // the last render was recorded into a stream capture: ev_done was not (an event recorded inside a capture orders nothing outside it)
     bool counted = false;
     bool zero_counters = false; // diagnostic builds: clear counters[] before every render
-    uint64_t *d_stamps = nullptr;
-    double *d_camx = nullptr, *d_camy = nullptr; // per-column / per-row camera-plane coordinates
+    DevMem<uint64_t> d_stamps;
+    DevMem<double> d_camx, d_camy; // per-column / per-row camera-plane coordinates
     size_t n_stamp_rows = 0;
     uint64_t frame = 0; // renders so far: selects the launch-order generation (FrameArgs::order_state); 64 bits: frame % 3 must never skip
     uint32_t tag = 0;   // frame tag of the scan workgroups' tile words (FrameArgs::tile_state); unique per render, never 0
-    uint32_t *h_listed = nullptr; // host-mapped words the kernel writes (FrameArgs::ord_host)
+    DevMem<uint32_t> d_order, d_tiles; // what FrameArgs::order_state / tile_state point at
+    MappedWords h_listed;         // host-mapped words the kernel writes (FrameArgs::ord_host)
     uint32_t ord_split = 0;       // FrameArgs::ord_split of non-sparse frames
     std::vector<double> cub_coefs; // the 20 coefficients of the first RT_CUB_AT_MAX degree-3 objects (FrameArgs::cub_at is formed from them every frame)
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
-    bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see render_impl)
+    bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
     int lean_force = 0;           // MI355RT_LEAN=always / never (experiments)
     bool ord_on = true;           // launch-order feedback in use (off while most tiles have hits)
-    // G-buffer pass and picking (rt_render_gbuffer / rt_pick): their own events and staging memory, created on first use
-    hipEvent_t gb_ev0 = nullptr, gb_ev1 = nullptr;
-    uint32_t *d_pick_xy = nullptr; // [pick_cap][2] coordinates
-    void *d_pick_out = nullptr;    // [pick_cap] rt_hit
-    uint32_t pick_cap = 0;
-    // ray queries (rt_trace_rays / rt_occluded_rays / rt_shade_rays and the _host entry points): their own events and staging memory,
-    // created on first use
-    hipEvent_t rq_ev0 = nullptr, rq_ev1 = nullptr;
-    void *d_rq_rays = nullptr; // [rq_cap] rt_ray
-    void *d_rq_hits = nullptr; // [rq_cap] rt_hit (rt_shade_rays_host: its 4 x float32 pixels)
-    uint32_t rq_cap = 0;
+    Staging pick;  // rt_pick: [cap][2] coordinates in, [cap] rt_hit out; created on first use
+    Staging rq;    // the _host ray entry points: [cap] rt_ray in, [cap] rt_hit out (rt_shade_rays_host: its 4 x float32 pixels); created on first use
     // scene updates (rt_set_scene): the kernel's status block, and the staging memory of rt_set_scene_host, created on first use
-    SetSceneStatus *d_ss_status = nullptr;
-    unsigned char *d_ss_stage = nullptr;
+    DevMem<SetSceneStatus> d_ss_status;
+    DevMem<unsigned char> d_ss_stage;
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -210,28 +226,22 @@ extern "C" const char *rt_last_error(void) { return g_last_error.c_str(); }
 extern "C" void rt_set_last_error(const char *message) { g_last_error = message ? message : ""; }
 
 // ---- scene --------------------------------------------------------------------------------------------
+// a new scene handle around `make()`'s Scene
+template <typename F>
+static int scene_handle(rt_scene **out, F &&make)
+{
+    std::unique_ptr<rt_scene> s(new rt_scene());
+    s->scene = make();
+    s->flatten();
+    *out = s.release();
+    return RT_OK;
+}
+
 extern "C" int rt_scene_load_file(const char *path, rt_scene **out)
 {
     if (!path || !out) return fail(RT_ERR_INVALID, "rt_scene_load_file: null argument");
     *out = nullptr;
-    try {
-        rt_scene *s = new rt_scene();
-        try {
-            s->scene = Scene::load_from_file(path);
-        } catch (...) {
-            delete s;
-            throw;
-        }
-        s->flatten();
-        *out = s;
-        return RT_OK;
-    } catch (const SceneException &e) {
-        return fail(RT_ERR_SCENE, "%s", e.what());
-    } catch (const std::bad_alloc &) {
-        return fail(RT_ERR_NOMEM, "out of memory");
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_SCENE, "%s", e.what());
-    }
+    return guarded(RT_ERR_SCENE, [&]() -> int { return scene_handle(out, [&] { return Scene::load_from_file(path); }); });
 }
 
 extern "C" int rt_scene_new(uint32_t width, uint32_t height, double fov_deg, uint32_t max_reflections,
@@ -239,61 +249,40 @@ extern "C" int rt_scene_new(uint32_t width, uint32_t height, double fov_deg, uin
 {
     if (!out || !bg_color) return fail(RT_ERR_INVALID, "rt_scene_new: null argument");
     *out = nullptr;
-    try {
-        rt_scene *s = new rt_scene();
-        try {
-            s->scene = Scene(width, height, fov_deg, max_reflections, glm::vec3(bg_color[0], bg_color[1], bg_color[2]));
-        } catch (...) {
-            delete s;
-            throw;
-        }
-        s->flatten();
-        *out = s;
-        return RT_OK;
-    } catch (const SceneException &e) {
-        return fail(RT_ERR_SCENE, "%s", e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_NOMEM, "%s", e.what());
-    }
+    return guarded(RT_ERR_NOMEM, [&]() -> int {
+        return scene_handle(out, [&] { return Scene(width, height, fov_deg, max_reflections, glm::vec3(bg_color[0], bg_color[1], bg_color[2])); });
+    });
 }
 
 extern "C" int rt_scene_add_object(rt_scene *s, const double coefs[RT_NCOEF], float reflection_ratio, const float color[3])
 {
     if (!s || !coefs || !color) return fail(RT_ERR_INVALID, "rt_scene_add_object: null argument");
-    try {
+    return guarded(RT_ERR_NOMEM, [&]() -> int {
         SurfaceCoefs sc{};
         std::memcpy(sc.data(), coefs, sizeof(double) * RT_NCOEF);
         s->scene.objects.push_back(Object(sc, reflection_ratio, glm::vec3(color[0], color[1], color[2])));
         s->flatten();
         return RT_OK;
-    } catch (const SceneException &e) {
-        return fail(RT_ERR_SCENE, "%s", e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_NOMEM, "%s", e.what());
-    }
+    });
 }
 
 extern "C" int rt_scene_add_light(rt_scene *s, int is_spherical, float intensity, const double v[3], const float color[3])
 {
     if (!s || !v || !color) return fail(RT_ERR_INVALID, "rt_scene_add_light: null argument");
-    try {
+    return guarded(RT_ERR_NOMEM, [&]() -> int {
         const glm::dvec3 dv(v[0], v[1], v[2]);
         const glm::vec3 c(color[0], color[1], color[2]);
         s->scene.lights.push_back(is_spherical ? LightSource::spherical(intensity, dv, c) : LightSource::directional(intensity, dv, c));
         s->flatten();
         return RT_OK;
-    } catch (const SceneException &e) {
-        return fail(RT_ERR_SCENE, "%s", e.what());
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_NOMEM, "%s", e.what());
-    }
+    });
 }
 
 extern "C" int rt_surface_make(int kind, const double a[3], const double b[3], double out_coefs[RT_NCOEF])
 {
     if (!out_coefs) return fail(RT_ERR_INVALID, "rt_surface_make: null output");
     if ((kind <= 2 && !a) || (kind <= 1 && !b)) return fail(RT_ERR_INVALID, "rt_surface_make: null argument");
-    try {
+    return guarded(RT_ERR_NOMEM, [&]() -> int {
         SurfaceCoefs sc{};
         switch (kind) {
         case 0: sc = SurfaceCoefs::sphere(glm::dvec3(a[0], a[1], a[2]), b[0]); break;
@@ -305,9 +294,7 @@ extern "C" int rt_surface_make(int kind, const double a[3], const double b[3], d
         }
         std::memcpy(out_coefs, sc.data(), sizeof(double) * RT_NCOEF);
         return RT_OK;
-    } catch (const SceneException &e) {
-        return fail(RT_ERR_SCENE, "%s", e.what());
-    }
+    });
 }
 
 extern "C" int rt_scene_set_size(rt_scene *s, uint32_t width, uint32_t height)
@@ -374,8 +361,6 @@ static uint32_t rows_of_rank(uint32_t height, uint32_t band, uint32_t world, uin
     return rows;
 }
 
-static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *cfg_in);
-
 // MI355RT_DEBUG_FRAME0 / MI355RT_DEBUG_TAG0 (tests: a context that starts late in its life, just in front of a counter's restart):
 // an unsigned number, decimal or 0x hex, nothing behind it, at most `max`.  Unset: *value is left alone.
 static int debug_start_value(const char *name, uint64_t max, uint64_t *value)
@@ -399,22 +384,22 @@ static int debug_start_value(const char *name, uint64_t max, uint64_t *value)
     return RT_OK;
 }
 
-extern "C" int rt_create(rt_ctx **out, const rt_scene_desc *sd, const rt_config *cfg_in)
+// ---- rt_create, step by step ------------------------------------------------------------------------------
+// a table the context keeps on the device: hipMalloc, then hipMemcpy from src or, without one, hipMemset to zero
+template <typename T>
+static int device_table(DevMem<T> &d, const void *src, size_t bytes, const char *what)
 {
-    try { // host-side packing allocates; nothing may propagate through the C ABI
-        return create_impl(out, sd, cfg_in);
-    } catch (const std::bad_alloc &) {
-        return fail(RT_ERR_NOMEM, "rt_create: out of host memory");
-    } catch (const std::exception &e) {
-        return fail(RT_ERR_INVALID, "rt_create: %s", e.what());
-    }
+    hipError_t e = d.alloc(bytes);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "hipMalloc(%s) failed: %s", what, hipGetErrorString(e));
+    e = src ? hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) : hipMemset(d, 0, bytes);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s(%s) failed: %s", src ? "hipMemcpy" : "hipMemset", what, hipGetErrorString(e));
+    return RT_OK;
 }
 
-static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *cfg_in)
+// 1. everything that can be refused without a device, in this order (a machine without a GPU sees the same refusals)
+static int create_checks(rt_ctx *ctx, const rt_scene_desc *sd, const rt_config *cfg_in)
 {
-    if (!out || !sd) return fail(RT_ERR_INVALID, "rt_create: null argument");
-    *out = nullptr;
-    rt_config cfg{};
+    rt_config &cfg = ctx->cfg;
     cfg.device = -1;
     cfg.world = 1;
     if (cfg_in) cfg = *cfg_in;
@@ -424,11 +409,11 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     if (cfg.format > RT_FMT_RGBA8) return fail(RT_ERR_INVALID, "rt_create: unknown format %u", cfg.format);
     if ((cfg.flags & RT_FLAG_SSAA2) && (cfg.flags & RT_FLAG_SSAA4))
         return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA2 and RT_FLAG_SSAA4 exclude each other");
-    const uint32_t k = (cfg.flags & RT_FLAG_SSAA4) ? 4u : ((cfg.flags & RT_FLAG_SSAA2) ? 2u : 1u);
-    const bool adaptive = (cfg.flags & RT_FLAG_SSAA_ADAPTIVE) != 0;
-    if (adaptive && k == 1u) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_ADAPTIVE needs RT_FLAG_SSAA2 or RT_FLAG_SSAA4");
-    const bool geometry = (cfg.flags & RT_FLAG_SSAA_GEOMETRY) != 0;
-    if (geometry && !adaptive) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_GEOMETRY needs RT_FLAG_SSAA_ADAPTIVE");
+    const uint32_t k = ctx->ssaa = (cfg.flags & RT_FLAG_SSAA4) ? 4u : ((cfg.flags & RT_FLAG_SSAA2) ? 2u : 1u);
+    ctx->adaptive = (cfg.flags & RT_FLAG_SSAA_ADAPTIVE) != 0;
+    if (ctx->adaptive && k == 1u) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_ADAPTIVE needs RT_FLAG_SSAA2 or RT_FLAG_SSAA4");
+    ctx->geometry = (cfg.flags & RT_FLAG_SSAA_GEOMETRY) != 0;
+    if (ctx->geometry && !ctx->adaptive) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_GEOMETRY needs RT_FLAG_SSAA_ADAPTIVE");
     if (sd->width == 0 || sd->height == 0) return fail(RT_ERR_INVALID, "rt_create: empty image %ux%u", sd->width, sd->height);
     if (k > 1u && ((uint64_t) k * sd->width > 65536u || (uint64_t) k * sd->height > 65536u))
         return fail(RT_ERR_INVALID, "rt_create: %ux%u supersampled %ux%u exceeds 65536 samples per axis", sd->width, sd->height, k, k);
@@ -437,37 +422,21 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
         return fail(RT_ERR_INVALID, "rt_create: null scene array");
     // (tests) the frame number and the tile-word tag the context starts from; the device state starts zeroed whatever they say: tile words
     // with tag 0 never equal a live tag and all three launch-order generations are empty, so any starting frame % 3 is consistent
-    uint64_t frame0 = 0, tag0 = 0;
-    if (int rc = debug_start_value("MI355RT_DEBUG_FRAME0", UINT64_MAX, &frame0)) return rc;
+    uint64_t tag0 = 0;
+    if (int rc = debug_start_value("MI355RT_DEBUG_FRAME0", UINT64_MAX, &ctx->frame)) return rc;
     if (int rc = debug_start_value("MI355RT_DEBUG_TAG0", 0x1FFFFFF0u, &tag0)) return rc;
+    ctx->tag = (uint32_t) tag0;
+    return RT_OK;
+}
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev == 0)
-        return fail(RT_ERR_NO_DEVICE, "rt_create: no HIP device available (%s); this library has no CPU fallback",
-                    e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-    int device = cfg.device;
-    if (device < 0) RT_HIP(hipGetDevice(&device));
-    if (device >= ndev) return fail(RT_ERR_INVALID, "rt_create: device %d out of range (%d devices)", device, ndev);
-    RT_HIP(hipSetDevice(device));
-
-    // owned by a guard until the very end: whatever throws or fails on the way (host-side packing allocates), rt_destroy releases
-    // the context and every device buffer it already holds
-    struct Guard {
-        rt_ctx *p;
-        ~Guard() { if (p) { std::string keep = g_last_error; rt_destroy(p); g_last_error = keep; } }
-    } guard{new (std::nothrow) rt_ctx()};
-    rt_ctx *ctx = guard.p;
-    if (!ctx) return fail(RT_ERR_NOMEM, "out of memory");
+// 2. the context's own words and the geometry of the frame the kernels render (host only)
+static void create_frame(rt_ctx *ctx, const rt_scene_desc *sd, int device)
+{
+    const rt_config &cfg = ctx->cfg;
     ctx->device = device;
-    ctx->cfg = cfg;
+    ctx->kern = (cfg.flags & RT_FLAG_FAST) ? &kernels_fast : &kernels_strict;
     ctx->width = sd->width;
     ctx->height = sd->height;
-    ctx->ssaa = k;
-    ctx->adaptive = adaptive;
-    ctx->geometry = geometry;
-    ctx->frame = frame0;
-    ctx->tag = (uint32_t) tag0;
     if (const char *e = std::getenv("MI355RT_RESOLVE_NT")) ctx->resolve_nt = std::atoi(e) != 0; // (experiments)
     ctx->pixel_bytes = cfg.format == RT_FMT_RGBA8 ? 4 : 16;
     ctx->local_rows = rows_of_rank(sd->height, cfg.band_rows, cfg.world, cfg.rank);
@@ -478,8 +447,8 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
 
     // the frame the kernels render: with supersampling the unmodified scene at k times the size, into RGBA32F (k is a power of two, so
     // the aspect ratio is the same double; bands of k * band_rows rows keep each output row's samples with the rank that owns it)
-    // (adaptive: the plain pass renders the output frame itself, k = 1 geometry; the sample rays come from the tables built below)
-    const uint32_t kf = adaptive ? 1u : k;
+    // (adaptive: the plain pass renders the output frame itself, k = 1 geometry; the sample rays come from the tables of create_adaptive)
+    const uint32_t kf = ctx->adaptive ? 1u : ctx->ssaa;
     const uint32_t rw = kf * sd->width, rh = kf * sd->height;
     FrameArgs &fa = ctx->fa;
     std::memset(&fa, 0, sizeof(fa));
@@ -491,8 +460,6 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     fa.bg[3] = 1.0f;
     fa.width = rw;
     fa.height = rh;
-    fa.n_obj = sd->n_objects;
-    fa.n_lights = sd->n_lights;
     fa.max_refl = sd->max_reflections;
     fa.rank = cfg.rank;
     fa.world = cfg.world;
@@ -500,236 +467,172 @@ static int create_impl(rt_ctx **out, const rt_scene_desc *sd, const rt_config *c
     fa.local_rows = kf * ctx->local_rows; // (= rows_of_rank(rh, k * band_rows, world, rank))
     fa.tiles_x = (rw + RT_TILE - 1) / RT_TILE;
     fa.n_tiles = fa.tiles_x * ((fa.local_rows + RT_TILE - 1) / RT_TILE);
-    fa.rgba8 = (k == 1u && cfg.format == RT_FMT_RGBA8) ? 1u : 0u; // (adaptive: P is RGBA32F)
+    fa.rgba8 = (ctx->ssaa == 1u && cfg.format == RT_FMT_RGBA8) ? 1u : 0u; // (adaptive: P is RGBA32F)
     fa.ord_plain = (cfg.flags & RT_FLAG_PLAIN_ORDER) ? 1u : 0u;
     ctx->ord_split = (cfg.flags & RT_FLAG_NOSPLIT) ? 0u : RT_ORD_SPLIT_CLASSES;
     if (const char *e = std::getenv("MI355RT_SPLIT_CLASSES")) ctx->ord_split = (uint32_t) std::atoi(e) & 15u; // (experiments)
-    fa.has_mirror = 0;
-    for (uint32_t i = 0; i < sd->n_objects; i++)
-        if (rtp::is_mirror(sd->reflection[i])) fa.has_mirror = 1;
-    std::vector<DevObject> objs(sd->n_objects);
-    uint32_t n_cullable = 0;
-    bool albedos_finite = true;
-    for (uint32_t i = 0; i < sd->n_objects; i++) { // (rt_scene_pack.hpp: class word, bounding sphere)
-        rtp::pack_object(objs[i], sd->coefs + (size_t) i * RT_NCOEF, sd->albedo + 3 * (size_t) i, sd->reflection[i]);
-        if (rtp::cullable(objs[i])) n_cullable++;
-        albedos_finite = albedos_finite && rtp::albedo_finite(objs[i].albedo);
-    }
-    // culling costs one bounding-volume decision per (object, light, 64-hit chunk); worth it from a handful
-    // of bounded objects upwards
-    fa.cull = (!(cfg.flags & RT_FLAG_NOCULL) && n_cullable >= 4) ? 1u : 0u;
-    fa.all_cullable = (fa.cull && n_cullable == sd->n_objects) ? 1u : 0u;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) ctx->wg_slots = 6u * (uint32_t) cus;
+    if (const char *e = std::getenv("MI355RT_LEAN")) ctx->lean_force = (e[0] == 'a') ? 1 : ((e[0] == 'n') ? -1 : 0);
+}
 
-    // per-class tables behind the object array (rt_scene_dev.h)
-    std::vector<UsEntry> t_us;
-    std::vector<GqEntry> t_gq;
-    std::vector<LinEntry> t_lin;
-    std::vector<uint32_t> t_cub;
-    for (uint32_t i = 0; i < sd->n_objects; i++) {
-        const DevObject &o = objs[i];
-        if (o.cls & RT_CLS_CUBIC) {
-            if (t_cub.size() < RT_CUB_AT_MAX) ctx->cub_coefs.insert(ctx->cub_coefs.end(), o.c, o.c + RT_NCOEF);
-            t_cub.push_back(i);
-        } else if (o.cls & RT_CLS_UNITSQ) {
-            UsEntry e;
-            rtp::pack_us(e, o, i); // (with the own-sphere window of the lean path)
-            t_us.push_back(e);
-        } else if (o.cls & (RT_CLS_SQUARE | RT_CLS_CROSS)) {
-            GqEntry e;
-            rtp::pack_gq(e, o, i);
-            t_gq.push_back(e);
-        } else {
-            LinEntry e;
-            rtp::pack_lin(e, o, i);
-            t_lin.push_back(e);
-        }
+// 3. the scene image (rt_scene_image.hpp) and what it means for this context: the schedule it may take, the LDS it needs
+static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &im)
+{
+    FrameArgs &fa = ctx->fa;
+    im = rtp::scene_image(*sd, ctx->cfg.flags, fa);
+    ctx->cub_coefs = im.cub_coefs;
+    ctx->lean_ok = im.lean_ok && !std::getenv("MI355RT_NOLEAN"); // (experiments)
+    if (!(ctx->cfg.flags & RT_FLAG_SIMPLE)) {
+        const size_t lds = rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub);
+        if (lds > 160u * 1024u) return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", lds);
     }
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t) 15; };
-    fa.n_us = (uint32_t) t_us.size();
-    fa.n_gq = (uint32_t) t_gq.size();
-    fa.n_lin = (uint32_t) t_lin.size();
-    fa.n_cub = (uint32_t) t_cub.size();
-    size_t off = up16(sizeof(DevObject) * objs.size());
-    fa.off_us = (uint32_t) off; off = up16(off + sizeof(UsEntry) * t_us.size());
-    fa.off_gq = (uint32_t) off; off = up16(off + sizeof(GqEntry) * t_gq.size());
-    fa.off_lin = (uint32_t) off; off = up16(off + sizeof(LinEntry) * t_lin.size());
-    fa.off_cub = (uint32_t) off; off = up16(off + sizeof(uint32_t) * t_cub.size());
-    fa.off_mat = (uint32_t) off; off = up16(off + sizeof(MatEntry) * objs.size());
-    fa.scene_bytes = (uint32_t) (off ? off : 16);
-    fa.stage_bytes = fa.scene_bytes - fa.off_us;
-    std::vector<unsigned char> blob(fa.scene_bytes, 0);
-    if (!objs.empty()) std::memcpy(blob.data(), objs.data(), sizeof(DevObject) * objs.size());
-    if (!t_us.empty()) std::memcpy(blob.data() + fa.off_us, t_us.data(), sizeof(UsEntry) * t_us.size());
-    if (!t_gq.empty()) std::memcpy(blob.data() + fa.off_gq, t_gq.data(), sizeof(GqEntry) * t_gq.size());
-    if (!t_lin.empty()) std::memcpy(blob.data() + fa.off_lin, t_lin.data(), sizeof(LinEntry) * t_lin.size());
-    if (!t_cub.empty()) std::memcpy(blob.data() + fa.off_cub, t_cub.data(), sizeof(uint32_t) * t_cub.size());
-    for (size_t i = 0; i < objs.size(); i++) {
-        MatEntry m;
-        rtp::pack_mat(m, objs[i]);
-        std::memcpy(blob.data() + fa.off_mat + i * sizeof(MatEntry), &m, sizeof(m));
-    }
-    std::vector<DevLight> lights(sd->n_lights);
-    std::vector<LightK> lightk(sd->n_lights); // the same lights as the lean path reads them (rt_scene_dev.h)
-    fa.lights_plain = 1u;
-    for (uint32_t i = 0; i < sd->n_lights; i++) {
-        const bool term_finite = rtp::pack_light(lights[i], sd->light_p + 3 * (size_t) i, sd->light_color + 3 * (size_t) i, sd->light_is_spherical[i], albedos_finite);
-        rtp::pack_lightk(lightk[i], lights[i], term_finite);
-        if (!lights[i].spherical && (lightk[i].flags & 6u) != 6u) fa.lights_plain = 0u;
-    }
-
-    // the wave-per-block instantiation: unit spheres only, every one with a bounding radius, no mirror (sparse frames take the other one)
-    ctx->lean_ok = !(cfg.flags & (RT_FLAG_SIMPLE | RT_FLAG_NOLEAN)) && fa.all_cullable && fa.n_us == sd->n_objects && !fa.has_mirror && fa.n_gq == 0 && fa.n_lin == 0 &&
-                   fa.n_cub == 0;
-    if (sd->n_lights > 64u) ctx->lean_ok = false; // (its point-light pass keeps one bit per light and lane)
-    fa.pt_mask[0] = fa.pt_mask[1] = 0u;
-    for (uint32_t i = 0; i < sd->n_lights && i < 64u; i++)
-        if (sd->light_is_spherical[i]) fa.pt_mask[i >> 5] |= 1u << (i & 31u);
-    if (std::getenv("MI355RT_NOLEAN")) ctx->lean_ok = false; // (experiments)
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) == hipSuccess && cus > 0) ctx->wg_slots = 6u * (uint32_t) cus;
-        if (const char *e = std::getenv("MI355RT_LEAN")) ctx->lean_force = (e[0] == 'a') ? 1 : ((e[0] == 'n') ? -1 : 0);
-    }
-
-    if (!(cfg.flags & RT_FLAG_SIMPLE) && rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub) > 160u * 1024u) {
-        return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)",
-                    rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub));
-    }
-    if (adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
+    if (ctx->adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)",
                     (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)));
-    if (geometry && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
+    if (ctx->geometry && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
-    int rc = RT_OK;
-    auto hip_ok = [&](hipError_t err, const char *what) {
-        if (err != hipSuccess && rc == RT_OK) rc = fail(RT_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString(err));
-        return err == hipSuccess;
-    };
-    const size_t fb_bytes = (size_t) (ctx->local_rows ? ctx->local_rows : 1) * sd->width * ctx->pixel_bytes;
-    hip_ok(hipMalloc((void **) &ctx->d_obj, blob.size()), "hipMalloc(scene)") &&
-        hip_ok(hipMalloc((void **) &ctx->d_light, (sizeof(DevLight) + sizeof(LightK)) * (lights.size() ? lights.size() : 1)), "hipMalloc(lights)") &&
-        hip_ok(hipMalloc(&ctx->d_fb, fb_bytes), "hipMalloc(framebuffer)") &&
-        hip_ok(hipMalloc((void **) &ctx->d_counters, sizeof(unsigned long long) * 64), "hipMalloc(counters)") &&
-        hip_ok(hipMemset(ctx->d_counters, 0, sizeof(unsigned long long) * 64), "hipMemset(counters)") &&
-        hip_ok(hipMalloc((void **) &ctx->d_ss_status, sizeof(SetSceneStatus)), "hipMalloc(scene-update status)") &&
-        hip_ok(hipMemset(ctx->d_ss_status, 0, sizeof(SetSceneStatus)), "hipMemset(scene-update status)") &&
-        hip_ok(hipMemcpy(ctx->d_obj, blob.data(), blob.size(), hipMemcpyHostToDevice), "hipMemcpy(scene)") &&
-        hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light, lights.data(), sizeof(DevLight) * lights.size(), hipMemcpyHostToDevice), "hipMemcpy(lights)") &&
-        hip_ok(lights.empty() ? hipSuccess : hipMemcpy(ctx->d_light + lights.size(), lightk.data(), sizeof(LightK) * lightk.size(), hipMemcpyHostToDevice), "hipMemcpy(light table)") &&
-        hip_ok(hipEventCreate(&ctx->ev0), "hipEventCreate") && hip_ok(hipEventCreate(&ctx->ev1), "hipEventCreate") &&
-        hip_ok(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming), "hipEventCreate") &&
-        hip_ok(kf == 1u ? hipSuccess : hipMalloc(&ctx->d_ss, (size_t) (fa.local_rows ? fa.local_rows : 1) * rw * 16u), "hipMalloc(supersampled frame)");
-    if (rc != RT_OK) return rc;
-    if (adaptive) {
-        const size_t px = (size_t) ctx->local_rows * sd->width;
-        const uint32_t bands = (ctx->local_rows + cfg.band_rows - 1u) / cfg.band_rows;
-        ctx->halo_slots = cfg.world > 1u ? 2u * bands : 0u;
-        for (uint32_t h = 0; h < ctx->halo_slots; h++) { // (the kernel's own rule, rt_adaptive.hip)
-            const uint32_t b = h >> 1, rows = std::min(cfg.band_rows, ctx->local_rows - b * cfg.band_rows);
-            const int64_t g0 = ((int64_t) b * cfg.world + cfg.rank) * cfg.band_rows, gy = (h & 1u) ? g0 + rows : g0 - 1;
-            if (gy >= 0 && gy < (int64_t) sd->height) ctx->halo_rays += sd->width;
-        }
-        // the ray-list kernel keeps one workgroup per CU resident (it needs all 512 registers of a lane); twice that many keeps every CU
-        // busy while the last workgroups drain
-        const uint64_t ppw = 64u / (k * k), want = (px + ppw * 4u - 1u) / (ppw * 4u), hwant = ((uint64_t) ctx->halo_slots * sd->width + 255u) / 256u;
-        const uint32_t cap = ctx->wg_slots / 3u ? ctx->wg_slots / 3u : 1u;
-        ctx->ray_grid = (uint32_t) std::min<uint64_t>(want, cap);
-        ctx->halo_grid = (uint32_t) std::min<uint64_t>(hwant, cap);
-        std::vector<double> cx((size_t) k * sd->width), cy((size_t) k * sd->height);
-        for (uint32_t x = 0; x < k * sd->width; x++) { // the tables of the k-times finer frame, exactly as a RT_FLAG_SSAAk context forms them below
-            const double ndc_x = ((int) x + 0.5) / (int) (k * sd->width);
-            cx[x] = (2.0 * ndc_x - 1.0) * fa.aspect * fa.tan_half_fov;
-        }
-        for (uint32_t y = 0; y < k * sd->height; y++) {
-            const double ndc_y = ((int) y + 0.5) / (int) (k * sd->height);
-            cy[y] = (2.0 * ndc_y - 1.0) * fa.tan_half_fov;
-        }
-        hip_ok(hipMalloc((void **) &ctx->d_list, sizeof(uint32_t) * (px + 1u)), "hipMalloc(refine list)") &&
-            hip_ok(cfg.format == RT_FMT_RGBA8 ? hipMalloc(&ctx->d_p, (px ? px : 1u) * 16u) : hipSuccess, "hipMalloc(plain frame)") &&
-            hip_ok(ctx->halo_slots ? hipMalloc(&ctx->d_halo, (size_t) ctx->halo_slots * sd->width * 16u) : hipSuccess, "hipMalloc(halo rows)") &&
-            hip_ok(hipMemset(ctx->d_list + px, 0, sizeof(uint32_t)), "hipMemset(refine count)") &&
-            hip_ok(hipMalloc((void **) &ctx->d_camxk, sizeof(double) * cx.size()), "hipMalloc(camx)") &&
-            hip_ok(hipMalloc((void **) &ctx->d_camyk, sizeof(double) * cy.size()), "hipMalloc(camy)") &&
-            hip_ok(hipMemcpy(ctx->d_camxk, cx.data(), sizeof(double) * cx.size(), hipMemcpyHostToDevice), "hipMemcpy(camx)") &&
-            hip_ok(hipMemcpy(ctx->d_camyk, cy.data(), sizeof(double) * cy.size(), hipMemcpyHostToDevice), "hipMemcpy(camy)");
-        if (rc != RT_OK) return rc;
-        if (geometry) {
-            // the halo rows' pixels by global coordinates, slot-major like d_halo; a slot outside the image is never read by the
-            // classifier: it traces the nearest image row, so that every query is a valid one
-            const size_t hpx = (size_t) ctx->halo_slots * sd->width;
-            std::vector<uint32_t> xy(2u * hpx);
-            for (uint32_t h = 0; h < ctx->halo_slots; h++) {
-                const uint32_t b = h >> 1, rows = std::min(cfg.band_rows, ctx->local_rows - b * cfg.band_rows);
-                const int64_t g0 = ((int64_t) b * cfg.world + cfg.rank) * cfg.band_rows, gy = (h & 1u) ? g0 + rows : g0 - 1;
-                const uint32_t row = (uint32_t) std::min<int64_t>(std::max<int64_t>(gy, 0), (int64_t) sd->height - 1);
-                for (uint32_t x = 0; x < sd->width; x++) {
-                    xy[2u * ((size_t) h * sd->width + x)] = x;
-                    xy[2u * ((size_t) h * sd->width + x) + 1u] = row;
-                }
-            }
-            hip_ok(hipMalloc((void **) &ctx->d_geo_obj, (px ? px : 1u) * sizeof(int32_t)), "hipMalloc(object plane)") &&
-                hip_ok(hipMalloc((void **) &ctx->d_geo_nrm, (px ? px : 1u) * 16u), "hipMalloc(normal plane)") &&
-                hip_ok(hpx ? hipMalloc((void **) &ctx->d_geo_xy, sizeof(uint32_t) * 2u * hpx) : hipSuccess, "hipMalloc(halo coordinates)") &&
-                hip_ok(hpx ? hipMalloc(&ctx->d_geo_halo, sizeof(rt_hit) * hpx) : hipSuccess, "hipMalloc(halo records)") &&
-                hip_ok(hpx ? hipMemcpy(ctx->d_geo_xy, xy.data(), sizeof(uint32_t) * 2u * hpx, hipMemcpyHostToDevice) : hipSuccess, "hipMemcpy(halo coordinates)");
-            if (rc != RT_OK) return rc;
+    return RT_OK;
+}
+
+// 4. what every context holds on the device: scene, framebuffer, counters, events, the camera-plane tables
+static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
+{
+    const FrameArgs &fa = ctx->fa;
+    const size_t nl = im.lights.size();
+    if (int rc = device_table(ctx->d_obj, im.blob.data(), im.blob.size(), "scene")) return rc;
+    RT_TRY("hipMalloc(lights)", ctx->d_light.alloc((sizeof(DevLight) + sizeof(LightK)) * (nl ? nl : 1)));
+    if (nl) {
+        RT_TRY("hipMemcpy(lights)", hipMemcpy(ctx->d_light, im.lights.data(), sizeof(DevLight) * nl, hipMemcpyHostToDevice));
+        RT_TRY("hipMemcpy(light table)", hipMemcpy(ctx->d_light + nl, im.lightk.data(), sizeof(LightK) * nl, hipMemcpyHostToDevice));
+    }
+    RT_TRY("hipMalloc(framebuffer)", ctx->d_fb.alloc((size_t) (ctx->local_rows ? ctx->local_rows : 1) * ctx->width * ctx->pixel_bytes));
+    if (int rc = device_table(ctx->d_counters, nullptr, sizeof(unsigned long long) * 64, "counters")) return rc;
+    if (int rc = device_table(ctx->d_ss_status, nullptr, sizeof(SetSceneStatus), "scene-update status")) return rc;
+    RT_TRY("hipEventCreate", ctx->ev0.create());
+    RT_TRY("hipEventCreate", ctx->ev1.create());
+    RT_TRY("hipEventCreate", ctx->ev_done.create(hipEventDisableTiming));
+    if (ctx->ssaa > 1u && !ctx->adaptive) RT_TRY("hipMalloc(supersampled frame)", ctx->d_ss.alloc((size_t) (fa.local_rows ? fa.local_rows : 1) * fa.width * 16u));
+    std::vector<double> cx, cy;
+    rtf::camera_tables(fa.width, fa.height, fa.aspect, fa.tan_half_fov, cx, cy);
+    if (int rc = device_table(ctx->d_camx, cx.data(), sizeof(double) * cx.size(), "camx")) return rc;
+    return device_table(ctx->d_camy, cy.data(), sizeof(double) * cy.size(), "camy");
+}
+
+// 5. RT_FLAG_SSAA_ADAPTIVE / RT_FLAG_SSAA_GEOMETRY: the refine list, the halo rows, the sample grid's tables, the primary-hit planes
+static int create_adaptive(rt_ctx *ctx)
+{
+    const rt_config &cfg = ctx->cfg;
+    const FrameArgs &fa = ctx->fa;
+    const uint32_t k = ctx->ssaa, width = ctx->width, height = ctx->height;
+    const size_t px = (size_t) ctx->local_rows * width;
+    const uint32_t bands = (ctx->local_rows + cfg.band_rows - 1u) / cfg.band_rows;
+    ctx->halo_slots = cfg.world > 1u ? 2u * bands : 0u;
+    for (uint32_t h = 0; h < ctx->halo_slots; h++) {
+        const int64_t gy = rtf::halo_global_row(h, cfg.band_rows, cfg.world, cfg.rank, ctx->local_rows);
+        if (gy >= 0 && gy < (int64_t) height) ctx->halo_rays += width;
+    }
+    // the ray-list kernel keeps one workgroup per CU resident (it needs all 512 registers of a lane); twice that many keeps every CU
+    // busy while the last workgroups drain
+    const uint64_t ppw = 64u / (k * k), want = (px + ppw * 4u - 1u) / (ppw * 4u), hwant = ((uint64_t) ctx->halo_slots * width + 255u) / 256u;
+    const uint32_t cap = ctx->wg_slots / 3u ? ctx->wg_slots / 3u : 1u;
+    ctx->ray_grid = (uint32_t) std::min<uint64_t>(want, cap);
+    ctx->halo_grid = (uint32_t) std::min<uint64_t>(hwant, cap);
+    RT_TRY("hipMalloc(refine list)", ctx->d_list.alloc(sizeof(uint32_t) * (px + 1u)));
+    if (cfg.format == RT_FMT_RGBA8) RT_TRY("hipMalloc(plain frame)", ctx->d_p.alloc((px ? px : 1u) * 16u));
+    if (ctx->halo_slots) RT_TRY("hipMalloc(halo rows)", ctx->d_halo.alloc((size_t) ctx->halo_slots * width * 16u));
+    RT_TRY("hipMemset(refine count)", hipMemset(ctx->d_list + px, 0, sizeof(uint32_t)));
+    std::vector<double> cx, cy; // the tables of the k-times finer frame, exactly as a RT_FLAG_SSAAk context forms its own
+    rtf::camera_tables(k * width, k * height, fa.aspect, fa.tan_half_fov, cx, cy);
+    if (int rc = device_table(ctx->d_camxk, cx.data(), sizeof(double) * cx.size(), "camx")) return rc;
+    if (int rc = device_table(ctx->d_camyk, cy.data(), sizeof(double) * cy.size(), "camy")) return rc;
+    if (!ctx->geometry) return RT_OK;
+    // the halo rows' pixels by global coordinates, slot-major like d_halo; a slot outside the image is never read by the
+    // classifier: it traces the nearest image row, so that every query is a valid one
+    const size_t hpx = (size_t) ctx->halo_slots * width;
+    std::vector<uint32_t> xy(2u * hpx);
+    for (uint32_t h = 0; h < ctx->halo_slots; h++) {
+        const int64_t gy = rtf::halo_global_row(h, cfg.band_rows, cfg.world, cfg.rank, ctx->local_rows);
+        const uint32_t row = (uint32_t) std::min<int64_t>(std::max<int64_t>(gy, 0), (int64_t) height - 1);
+        for (uint32_t x = 0; x < width; x++) {
+            xy[2u * ((size_t) h * width + x)] = x;
+            xy[2u * ((size_t) h * width + x) + 1u] = row;
         }
     }
-    {
-        // camera-plane coordinates of every pixel column / row: render_pixel's camera_x / camera_y
-        // (src/update-cpu.cpp:84-87) depend only on the pixel index and the scene, so they are evaluated here once,
-        // with the same IEEE operations in the same order (this file is compiled with -ffp-contract=off)
-        std::vector<double> cx(rw), cy(rh);
-        for (uint32_t x = 0; x < rw; x++) {
-            const double ndc_x = ((int) x + 0.5) / (int) rw;
-            cx[x] = (2.0 * ndc_x - 1.0) * fa.aspect * fa.tan_half_fov;
-        }
-        for (uint32_t y = 0; y < rh; y++) {
-            const double ndc_y = ((int) y + 0.5) / (int) rh;
-            cy[y] = (2.0 * ndc_y - 1.0) * fa.tan_half_fov;
-        }
-        hip_ok(hipMalloc((void **) &ctx->d_camx, sizeof(double) * rw), "hipMalloc(camx)") &&
-            hip_ok(hipMalloc((void **) &ctx->d_camy, sizeof(double) * rh), "hipMalloc(camy)") &&
-            hip_ok(hipMemcpy(ctx->d_camx, cx.data(), sizeof(double) * rw, hipMemcpyHostToDevice), "hipMemcpy(camx)") &&
-            hip_ok(hipMemcpy(ctx->d_camy, cy.data(), sizeof(double) * rh, hipMemcpyHostToDevice), "hipMemcpy(camy)");
-        if (rc == RT_OK && !(cfg.flags & (RT_FLAG_SIMPLE | RT_FLAG_STATIC_ORDER)) && fa.n_tiles > 0 && fa.n_tiles <= RT_ORD_MAX_TILES) {
-            // launch-order feedback: three generations, all empty (first frame = index order)
-            fa.ord_stride = (RT_ORD_HDR + 17u * fa.n_tiles + 15u) & ~15u;
-            // ... and behind them one word per tile, the last frame in which one of a split tile's two workgroups entered the tile (FrameArgs::ord_frame)
-            const size_t bytes = sizeof(uint32_t) * (3u * (size_t) fa.ord_stride + fa.n_tiles);
-            hip_ok(hipMalloc((void **) &fa.order_state, bytes), "hipMalloc(order)") && hip_ok(hipMemset(fa.order_state, 0, bytes), "hipMemset(order)");
-            // the kernel reports the number of listed tiles through one host-mapped word; without it (allocation
-            // refused) every launch simply carries n_tiles list slots
-            if (rc == RT_OK && hipHostMalloc((void **) &ctx->h_listed, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess) {
-                ctx->h_listed[0] = 0;
-                ctx->h_listed[1] = 0;
-                ctx->h_listed[2] = 0xFFFFFFFFu; // (nothing known yet: the wave-per-block instantiation starts)
-                if (hipHostGetDevicePointer((void **) &fa.ord_host, ctx->h_listed, 0) != hipSuccess) {
-                    (void) hipHostFree(ctx->h_listed);
-                    ctx->h_listed = nullptr;
-                    fa.ord_host = nullptr;
-                }
-            } else {
-                ctx->h_listed = nullptr;
-                (void) hipGetLastError();
+    RT_TRY("hipMalloc(object plane)", ctx->d_geo_obj.alloc((px ? px : 1u) * sizeof(int32_t)));
+    RT_TRY("hipMalloc(normal plane)", ctx->d_geo_nrm.alloc((px ? px : 1u) * 16u));
+    if (!hpx) return RT_OK;
+    RT_TRY("hipMalloc(halo records)", ctx->d_geo_halo.alloc(sizeof(rt_hit) * hpx));
+    return device_table(ctx->d_geo_xy, xy.data(), sizeof(uint32_t) * 2u * hpx, "halo coordinates");
+}
+
+// 6. the frame-to-frame state of the wavefront kernel: launch-order generations, the host-mapped words, tile words (and stamp rows)
+static int create_order_state(rt_ctx *ctx)
+{
+    FrameArgs &fa = ctx->fa;
+    const uint32_t flags = ctx->cfg.flags;
+    if (!(flags & (RT_FLAG_SIMPLE | RT_FLAG_STATIC_ORDER)) && fa.n_tiles > 0 && fa.n_tiles <= RT_ORD_MAX_TILES) {
+        // launch-order feedback: three generations, all empty (first frame = index order)
+        fa.ord_stride = (RT_ORD_HDR + 17u * fa.n_tiles + 15u) & ~15u;
+        // ... and behind them one word per tile, the last frame in which one of a split tile's two workgroups entered the tile (FrameArgs::ord_frame)
+        if (int rc = device_table(ctx->d_order, nullptr, sizeof(uint32_t) * (3u * (size_t) fa.ord_stride + fa.n_tiles), "order")) return rc;
+        fa.order_state = ctx->d_order;
+        // the kernel reports the number of listed tiles through one host-mapped word; without it (allocation
+        // refused) every launch simply carries n_tiles list slots
+        if (hipHostMalloc((void **) &ctx->h_listed.p, 64, hipHostMallocMapped | hipHostMallocPortable) == hipSuccess) {
+            ctx->h_listed[0] = 0;
+            ctx->h_listed[1] = 0;
+            ctx->h_listed[2] = 0xFFFFFFFFu; // (nothing known yet: the wave-per-block instantiation starts)
+            if (hipHostGetDevicePointer((void **) &fa.ord_host, ctx->h_listed, 0) != hipSuccess) {
+                ctx->h_listed.reset();
+                fa.ord_host = nullptr;
             }
+        } else {
+            ctx->h_listed.p = nullptr;
+            (void) hipGetLastError();
         }
-        if (rc == RT_OK && !(cfg.flags & RT_FLAG_SIMPLE) && fa.all_cullable && fa.n_tiles > 0) {
-            // one word per tile for the scan workgroups (rt_wavefront.hip, scan_tiles); all zero = "no frame has classified it"
-            hip_ok(hipMalloc((void **) &fa.tile_state, sizeof(uint32_t) * fa.n_tiles), "hipMalloc(tile state)") &&
-                hip_ok(hipMemset(fa.tile_state, 0, sizeof(uint32_t) * fa.n_tiles), "hipMemset(tile state)");
-        }
-        if (rc != RT_OK) return rc;
+    }
+    if (!(flags & RT_FLAG_SIMPLE) && fa.all_cullable && fa.n_tiles > 0) {
+        // one word per tile for the scan workgroups (rt_wavefront.hip, scan_tiles); all zero = "no frame has classified it"
+        if (int rc = device_table(ctx->d_tiles, nullptr, sizeof(uint32_t) * fa.n_tiles, "tile state")) return rc;
+        fa.tile_state = ctx->d_tiles;
     }
     ctx->zero_counters = std::getenv("MI355RT_DEBUG_COUNTERS") != nullptr;
     if (ctx->zero_counters) { // room for the stamp rows of a diagnostic (STAMPS=1) build: one per wave
         ctx->n_stamp_rows = (size_t) fa.n_tiles * 9 + 96; // one row per wave of the (up to) 2 * n_tiles + n_tiles / 16 + n_tiles / 64 + 2 workgroups of a launch
-        if (hipMalloc((void **) &ctx->d_stamps, ctx->n_stamp_rows * 16 * sizeof(uint64_t) + 8) != hipSuccess) ctx->d_stamps = nullptr;
+        if (ctx->d_stamps.alloc(ctx->n_stamp_rows * 16 * sizeof(uint64_t) + 8) != hipSuccess) ctx->d_stamps.p = nullptr;
         else (void) hipMemset(ctx->d_stamps, 0, ctx->n_stamp_rows * 16 * sizeof(uint64_t));
     }
-    guard.p = nullptr;
-    *out = ctx;
     return RT_OK;
+}
+
+extern "C" int rt_create(rt_ctx **out, const rt_scene_desc *sd, const rt_config *cfg_in)
+{
+    if (!out || !sd) return fail(RT_ERR_INVALID, "rt_create: null argument");
+    *out = nullptr;
+    return guarded(RT_ERR_INVALID, [&]() -> int { // host-side packing allocates; nothing may propagate through the C ABI
+        // owned here until the very end: whatever throws or fails on the way, the context goes, and with it every device buffer it
+        // already holds (its device is current from the first allocation on)
+        std::unique_ptr<rt_ctx> ctx(new rt_ctx());
+        if (int rc = create_checks(ctx.get(), sd, cfg_in)) return rc;
+        int ndev = 0, device = ctx->cfg.device;
+        hipError_t e = hipGetDeviceCount(&ndev);
+        if (e != hipSuccess || ndev == 0)
+            return fail(RT_ERR_NO_DEVICE, "rt_create: no HIP device available (%s); this library has no CPU fallback",
+                        e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
+        if (device < 0) RT_HIP(hipGetDevice(&device));
+        if (device >= ndev) return fail(RT_ERR_INVALID, "rt_create: device %d out of range (%d devices)", device, ndev);
+        RT_HIP(hipSetDevice(device));
+        rtp::SceneImage im;
+        create_frame(ctx.get(), sd, device);
+        if (int rc = create_scene(ctx.get(), sd, im)) return rc;
+        if (int rc = create_device_state(ctx.get(), im)) return rc;
+        if (ctx->adaptive)
+            if (int rc = create_adaptive(ctx.get())) return rc;
+        if (int rc = create_order_state(ctx.get())) return rc;
+        *out = ctx.release();
+        return RT_OK;
+    });
 }
 
 // background colour as the RGBA8 kernels store it (iround(c * 255), alpha 255), little-endian r | g << 8 | b << 16 | a << 24
@@ -757,6 +660,128 @@ static BgPixel bg_pixel(const rt_ctx *ctx)
     return p;
 }
 
+// ---- what every entry point on a context shares ----------------------------------------------------------------
+static int use_device(const rt_ctx *ctx) // make the context's device the calling thread's current one
+{
+    int cur = -1;
+    RT_HIP(hipGetDevice(&cur));
+    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    return RT_OK;
+}
+
+// wait for everything the device has been given, then copy back (the getters)
+static int read_synced(const rt_ctx *ctx, void *dst, const void *src, size_t bytes)
+{
+    if (int rc = use_device(ctx)) return rc;
+    RT_HIP(hipDeviceSynchronize());
+    RT_HIP(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// A context's frames depend on each other on the device (launch-order generations: read k, append k + 1, clear k + 2; tile words
+// tagged per frame), and a scene update belongs between two of them, so its calls must run in the order they were issued.  On one
+// stream they do; when the caller switches streams, the new stream first waits for the previous call (order_begin), and every call
+// leaves the event the next one may have to wait for (order_end).
+static int order_begin(const char *who, rt_ctx *ctx, hipStream_t stream, bool *capturing)
+{
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
+    *capturing = cap != hipStreamCaptureStatusNone;
+    if (ctx->rendered && stream != ctx->last_stream) {
+        if (ctx->captured || *capturing)
+            return fail(RT_ERR_INVALID, "%s: a context whose calls were captured into a graph on one stream must stay on that stream (frames and scene updates of a "
+                                        "context are ordered on the device, and a capture cannot be ordered against another stream through an event)", who);
+        RT_HIP(hipStreamWaitEvent(stream, ctx->ev_done, 0));
+    }
+    return RT_OK;
+}
+
+static int order_end(rt_ctx *ctx, hipStream_t stream, bool capturing)
+{
+    if (!capturing) RT_HIP(hipEventRecord(ctx->ev_done, stream));
+    ctx->captured = capturing;
+    ctx->last_stream = stream;
+    ctx->rendered = true;
+    return RT_OK;
+}
+
+// `ms` of a timed entry point: the device time between the two calls (timer_end waits for it); nothing when ms is null
+static int timer_begin(rt_ctx *ctx, hipStream_t stream, const float *ms)
+{
+    if (ms) RT_HIP(hipEventRecord(ctx->ev0, stream));
+    return RT_OK;
+}
+
+static int timer_end(rt_ctx *ctx, hipStream_t stream, float *ms)
+{
+    if (!ms) return RT_OK;
+    RT_HIP(hipEventRecord(ctx->ev1, stream));
+    RT_HIP(hipEventSynchronize(ctx->ev1));
+    RT_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
+    return RT_OK;
+}
+
+// ---- rt_render ----------------------------------------------------------------------------------------------
+// Which instantiation renders a scene of unit spheres?  The wave-per-block one ("lean") executes a quarter fewer instructions per
+// frame and wins wherever the GPU is full (4K 120 -> 91 us, 8K 425 -> 306, the 1080p start pose 44 -> 38).  The general one splits
+// costly tiles over two workgroups and every tile's lights over its four waves, which is what counts while few tiles have hits and
+// the frame ends with its slowest wave (orbit poses 5 / 6 at 1080p: 40 us against 54).  The previous frames' count of tiles with
+// hits decides, with a hysteresis: lean from 0.66 of the workgroup slots up, back below 0.62 (the orbit of tools/flythrough_bench.py: the
+// general one wins every pose below 950 tiles for 1536 slots and loses every pose above 975; a wider band kept poses 3 and 4 on the wrong side).
+static void choose_schedule(rt_ctx *ctx, FrameArgs &fa)
+{
+    if (ctx->lean_ok && ctx->h_listed && ctx->lean_force == 0) {
+        const uint32_t tiles = ((volatile uint32_t *) ctx->h_listed.p)[2]; // tiles with hits a few frames ago (listed, or the census' estimate while the lists are off)
+        if (ctx->lean_now ? (uint64_t) tiles * 100u < (uint64_t) ctx->wg_slots * 62u : (uint64_t) tiles * 100u >= (uint64_t) ctx->wg_slots * 66u) ctx->lean_now = !ctx->lean_now;
+    } else {
+        ctx->lean_now = ctx->lean_force >= 0;
+    }
+    static const bool debug_order = std::getenv("MI355RT_DEBUG_ORDER") != nullptr; // (diagnostics: what the previous frames' kernels reported back)
+    if (debug_order && ctx->h_listed)
+        std::fprintf(stderr, "mi355rt: frame %llu: tiles with hits %u, list slots wanted %u, census %u, schedule %s\n", (unsigned long long) ctx->frame, ((volatile uint32_t *) ctx->h_listed.p)[2],
+                     ((volatile uint32_t *) ctx->h_listed.p)[0], ((volatile uint32_t *) ctx->h_listed.p)[1], ctx->lean_now ? "lean" : "general");
+    fa.lean = (ctx->lean_ok && ctx->lean_now && !fa.sparse) ? 1u : 0u;
+}
+
+// rotate the launch-order generations: read k, write k+1, clear k+2 (contexts with FrameArgs::order_state)
+static int rotate_launch_order(rt_ctx *ctx, FrameArgs &fa, hipStream_t stream)
+{
+    fa.ord_read = (uint32_t) (ctx->frame % 3u);
+    fa.ord_write = (uint32_t) ((ctx->frame + 1u) % 3u);
+    fa.ord_zero = (uint32_t) ((ctx->frame + 2u) % 3u);
+    // list slots of this launch: what an earlier frame reported (the host runs ahead of the device, so the words
+    // are a few frames old) plus a quarter and 64; too few only means that the surplus tiles start in index order.
+    // The ordering is switched off while the census says that >= 25 % of the tiles have hits (back on below 20 %).
+    uint32_t cap = fa.n_tiles;
+    if (ctx->h_listed) {
+        const uint32_t seen = ((volatile uint32_t *) ctx->h_listed.p)[0], census = ((volatile uint32_t *) ctx->h_listed.p)[1];
+        const uint64_t want = (uint64_t) seen + seen / 4u + 64u;
+        if (want < cap) cap = (uint32_t) want;
+        const uint64_t with_hits = (uint64_t) census * 16u;
+        // ... and while so many tiles have hits that the launch is many rounds of workgroups deep anyway: there the order buys nothing any
+        // more and the lists only cost their upkeep -- the decode in front of every list slot.  Measured with the lean schedule (index
+        // order against lists): 2 rounds (4K orbit pose 5) 81 -> 69 us with the lists, 3.7 rounds (4K pose 19) 117 -> 109, 4.3 rounds (4K pose
+        // 16) 119 / 120, 7.5 - 8 rounds (8K poses 5 / 6) 206 -> 243 and 197 -> 233, 12.7 rounds (8K start pose) 288 / 293.  Off from 16 / 3
+        // rounds, back on below 4.
+        const uint64_t slots = ctx->wg_slots ? ctx->wg_slots : 1536u;
+        const bool too_many = ctx->ord_on ? with_hits * 3u >= slots * 16u : with_hits >= slots * 4u;
+        const bool too_dense = ctx->ord_on ? with_hits * 4u >= fa.n_tiles : with_hits * 5u >= fa.n_tiles;
+        ctx->ord_on = !(too_many || too_dense);
+    }
+    fa.ord_cap = cap;
+    fa.ord_on = ctx->ord_on ? 1u : 0u;
+    fa.ord_split = (fa.sparse || fa.lean) ? 0u : ctx->ord_split; // (a sparse message has one slot per tile; the lean instantiation's waves are independent:
+                                                                 // a second workgroup per tile would shorten nothing)
+    // this frame's number for the per-tile "entered by" words of split tiles: 1 .. 0xFFFFFFF0, never 0 (the words start out 0).  The
+    // election is an atomicMax, so when the number starts over (every 2^32 - 16 frames) the words are cleared first -- the same
+    // guard the tile-word tag has in render_impl.
+    fa.ord_frame = (uint32_t) (ctx->frame % 0xFFFFFFF0ull) + 1u;
+    if (fa.ord_frame == 1u && ctx->frame != 0u)
+        RT_HIP(hipMemsetAsync(fa.order_state + 3u * (size_t) fa.ord_stride, 0, sizeof(uint32_t) * fa.n_tiles, stream));
+    ctx->frame++;
+    return RT_OK;
+}
+
 static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *stream_, float *ms, bool sparse, uint32_t sparse_cap)
 {
     hipStream_t stream = (hipStream_t) stream_;
@@ -765,86 +790,26 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     const bool kernel_sparse = sparse && ctx->ssaa == 1u; // (adaptive frames are packed like supersampled ones)
     fa.sparse = kernel_sparse ? 1u : 0u;
     fa.sparse_cap = kernel_sparse ? sparse_cap : 0u;
-    // Which instantiation renders a scene of unit spheres?  The wave-per-block one ("lean") executes a quarter fewer instructions per
-    // frame and wins wherever the GPU is full (4K 120 -> 91 us, 8K 425 -> 306, the 1080p start pose 44 -> 38).  The general one splits
-    // costly tiles over two workgroups and every tile's lights over its four waves, which is what counts while few tiles have hits and
-    // the frame ends with its slowest wave (orbit poses 5 / 6 at 1080p: 40 us against 54).  The previous frames' count of tiles with
-    // hits decides, with a hysteresis: lean from 0.66 of the workgroup slots up, back below 0.62 (the orbit of tools/flythrough_bench.py: the
-    // general one wins every pose below 950 tiles for 1536 slots and loses every pose above 975; a wider band kept poses 3 and 4 on the wrong side).
-    if (ctx->lean_ok && ctx->h_listed && ctx->lean_force == 0) {
-        const uint32_t tiles = ((volatile uint32_t *) ctx->h_listed)[2]; // tiles with hits a few frames ago (listed, or the census' estimate while the lists are off)
-        if (ctx->lean_now ? (uint64_t) tiles * 100u < (uint64_t) ctx->wg_slots * 62u : (uint64_t) tiles * 100u >= (uint64_t) ctx->wg_slots * 66u) ctx->lean_now = !ctx->lean_now;
-    } else {
-        ctx->lean_now = ctx->lean_force >= 0;
-    }
-    static const bool debug_order = std::getenv("MI355RT_DEBUG_ORDER") != nullptr; // (diagnostics: what the previous frames' kernels reported back)
-    if (debug_order && ctx->h_listed)
-        std::fprintf(stderr, "mi355rt: frame %llu: tiles with hits %u, list slots wanted %u, census %u, schedule %s\n", (unsigned long long) ctx->frame, ((volatile uint32_t *) ctx->h_listed)[2],
-                     ((volatile uint32_t *) ctx->h_listed)[0], ((volatile uint32_t *) ctx->h_listed)[1], ctx->lean_now ? "lean" : "general");
-    fa.lean = (ctx->lean_ok && ctx->lean_now && !kernel_sparse) ? 1u : 0u;
-    std::memcpy(fa.cam, cam, sizeof(double) * 16);
-    // g_ray_origin = camera_matrix * (0,0,0,1), src/update-cpu.cpp:123 -- glm order (m0*x + m1*y) + (m2*z + m3*w)
-    for (int r = 0; r < 3; r++) fa.origin[r] = (cam[0 + r] * 0.0 + cam[4 + r] * 0.0) + (cam[8 + r] * 0.0 + cam[12 + r] * 1.0);
-
-    for (size_t j = 0; j * RT_NCOEF < ctx->cub_coefs.size(); j++) { // degree-3 objects: F, grad F, half Hessian at the frame's ray origin (rt_math.hpp, cubic_at)
-        const rtm::CubicAt a = rtm::cubic_at(ctx->cub_coefs.data() + j * RT_NCOEF, rtm::D3{fa.origin[0], fa.origin[1], fa.origin[2]});
-        const rtm::CubicAbs ab = rtm::cubic_abs(ctx->cub_coefs.data() + j * RT_NCOEF); // what cubic_guarded's error bounds follow from (same function as on the device)
-        const double v[RT_CUB_REC] = {a.f, a.gx, a.gy, a.gz, a.hxx, a.hyy, a.hzz, a.hxy, a.hxz, a.hyz};
-        const double va[4] = {ab.a3, ab.a2, ab.a1, ab.a0};
-        std::memcpy(fa.cub_rec[j], v, sizeof(v));
-        std::memcpy(fa.cub_abs[j], va, sizeof(va));
-    }
-    { // tile pyramids of the early-out test (FrameArgs::tile_nt): inverse transpose of the camera's 3x3 part
-        const double a = cam[0], b = cam[4], c = cam[8], d = cam[1], e = cam[5], f = cam[9], g = cam[2], h = cam[6], i = cam[10];
-        const double co00 = e * i - f * h, co01 = -(d * i - f * g), co02 = d * h - e * g;
-        const double co10 = -(b * i - c * h), co11 = a * i - c * g, co12 = -(a * h - b * g);
-        const double co20 = b * f - c * e, co21 = -(a * f - c * d), co22 = a * e - b * d;
-        const double det = a * co00 + b * co01 + c * co02;
-        const double amax = std::fabs(a) + std::fabs(b) + std::fabs(c) + std::fabs(d) + std::fabs(e) + std::fabs(f) + std::fabs(g) + std::fabs(h) + std::fabs(i);
-        fa.tile_planes_ok = (std::isfinite(det) && std::isfinite(amax) && std::fabs(det) > 1e-9 * amax * amax * amax) ? 1u : 0u;
-        if (fa.tile_planes_ok) { // (M^-1)^T = cofactor matrix / det; stored column-major: element (row r, col k) at [3 * k + r]
-            const double inv = 1.0 / det;
-            const double nt[9] = {co00 * inv, co10 * inv, co20 * inv, co01 * inv, co11 * inv, co21 * inv, co02 * inv, co12 * inv, co22 * inv};
-            for (int k = 0; k < 9; k++) fa.tile_nt[k] = nt[k];
-        }
-        fa.cx_a = 2.0 * fa.aspect * fa.tan_half_fov / (double) fa.width;
-        fa.cx_b = (1.0 / (double) fa.width - 1.0) * fa.aspect * fa.tan_half_fov;
-        fa.cy_a = 2.0 * fa.tan_half_fov / (double) fa.height;
-        fa.cy_b = (1.0 / (double) fa.height - 1.0) * fa.tan_half_fov;
-        if (!(fa.cx_a > 0.0) || !(fa.cy_a > 0.0) || !std::isfinite(fa.cx_a) || !std::isfinite(fa.cy_a)) fa.tile_planes_ok = 0;
-    }
-    int cur = -1;
-    RT_HIP(hipGetDevice(&cur));
-    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
-
-    // A context's frames depend on each other on the device (launch-order generations: read k, append k + 1, clear k + 2; tile words
-    // tagged per frame), so they must run in the order they were issued.  On one stream they do; when the caller switches streams,
-    // the new stream first waits for the previous frame.
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    if (ctx->rendered && stream != ctx->last_stream) {
-        if (ctx->captured || capturing)
-            return fail(RT_ERR_INVALID, "rt_render: a context whose frames were captured into a graph on one stream must stay on that stream (frames of a context are "
-                                        "ordered on the device, and a capture cannot be ordered against another stream through an event)");
-        RT_HIP(hipStreamWaitEvent(stream, ctx->ev_done, 0));
-    }
+    choose_schedule(ctx, fa);
+    rtf::frame_camera(fa, cam, ctx->cub_coefs);
+    if (int rc = use_device(ctx)) return rc;
+    bool capturing = false;
+    if (int rc = order_begin("rt_render", ctx, stream, &capturing)) return rc;
     // out: where the frame ends up (a message for sparse calls); fb: what the render kernels write
-    void *out = dev_fb ? dev_fb : ctx->d_fb;
-    void *fb = ss ? ctx->d_ss : out;
-    // adaptive: dest = where the output rows go before a sparse pack; the plain frame P is rendered in place for RGBA32F
-    void *dest = sparse ? ctx->d_fb : out;
-    if (ctx->adaptive) fb = ctx->cfg.format == RT_FMT_RGBA8 ? ctx->d_p : dest;
+    void *out = dev_fb ? dev_fb : ctx->d_fb.p;
+    void *fb = ss ? ctx->d_ss.p : out;
+    // dest: where the output rows of a supersampled or adaptive frame go before a sparse pack; the plain frame P is rendered in place for RGBA32F
+    void *dest = sparse ? ctx->d_fb.p : out;
+    if (ctx->adaptive) fb = ctx->cfg.format == RT_FMT_RGBA8 ? ctx->d_p.p : dest;
     if (kernel_sparse) RT_HIP(hipMemsetAsync(fb, 0, 16, stream)); // message header: count, overflow
     const int count = (ctx->cfg.flags & RT_FLAG_COUNT) ? 1 : 0;
-    const int rgba8 = fa.rgba8 != 0u;
     if (count || ctx->zero_counters) {
         RT_HIP(hipMemsetAsync(ctx->d_counters, 0, sizeof(unsigned long long) * 28, stream)); // (word 31 holds the stamp rows' address)
         RT_HIP(hipMemsetAsync(ctx->d_counters + 32, 0, sizeof(unsigned long long) * 32, stream));
     }
     if (ctx->d_stamps) {
         RT_HIP(hipMemsetAsync(ctx->d_stamps, 0, ctx->n_stamp_rows * 16 * sizeof(uint64_t), stream)); // rows of this frame only
-        const unsigned long long ptr = (unsigned long long) (uintptr_t) ctx->d_stamps;
+        const unsigned long long ptr = (unsigned long long) (uintptr_t) ctx->d_stamps.p;
         RT_HIP(hipMemcpyAsync(ctx->d_counters + 31, &ptr, sizeof(ptr), hipMemcpyHostToDevice, stream));
         RT_HIP(hipStreamSynchronize(stream));
     }
@@ -857,67 +822,26 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         fa.frame_tag = ++ctx->tag;
         fa.n_scan = (fa.n_tiles + RT_SCAN_TILES - 1) / RT_SCAN_TILES;
     }
-    if (fa.order_state) { // rotate the launch-order generations: read k, write k+1, clear k+2
-        fa.ord_read = (uint32_t) (ctx->frame % 3u);
-        fa.ord_write = (uint32_t) ((ctx->frame + 1u) % 3u);
-        fa.ord_zero = (uint32_t) ((ctx->frame + 2u) % 3u);
-        // list slots of this launch: what an earlier frame reported (the host runs ahead of the device, so the words
-        // are a few frames old) plus a quarter and 64; too few only means that the surplus tiles start in index order.
-        // The ordering is switched off while the census says that >= 25 % of the tiles have hits (back on below 20 %).
-        uint32_t cap = fa.n_tiles;
-        if (ctx->h_listed) {
-            const uint32_t seen = ((volatile uint32_t *) ctx->h_listed)[0], census = ((volatile uint32_t *) ctx->h_listed)[1];
-            const uint64_t want = (uint64_t) seen + seen / 4u + 64u;
-            if (want < cap) cap = (uint32_t) want;
-            const uint64_t with_hits = (uint64_t) census * 16u;
-            // ... and while so many tiles have hits that the launch is many rounds of workgroups deep anyway: there the order buys nothing any
-            // more and the lists only cost their upkeep -- the decode in front of every list slot.  Measured with the lean schedule (index
-            // order against lists): 2 rounds (4K orbit pose 5) 81 -> 69 us with the lists, 3.7 rounds (4K pose 19) 117 -> 109, 4.3 rounds (4K pose
-            // 16) 119 / 120, 7.5 - 8 rounds (8K poses 5 / 6) 206 -> 243 and 197 -> 233, 12.7 rounds (8K start pose) 288 / 293.  Off from 16 / 3
-            // rounds, back on below 4.
-            const uint64_t slots = ctx->wg_slots ? ctx->wg_slots : 1536u;
-            const bool too_many = ctx->ord_on ? with_hits * 3u >= slots * 16u : with_hits >= slots * 4u;
-            const bool too_dense = ctx->ord_on ? with_hits * 4u >= fa.n_tiles : with_hits * 5u >= fa.n_tiles;
-            ctx->ord_on = !(too_many || too_dense);
-        }
-        fa.ord_cap = cap;
-        fa.ord_on = ctx->ord_on ? 1u : 0u;
-        fa.ord_split = (fa.sparse || fa.lean) ? 0u : ctx->ord_split; // (a sparse message has one slot per tile; the lean instantiation's waves are independent:
-                                                                     // a second workgroup per tile would shorten nothing)
-        // this frame's number for the per-tile "entered by" words of split tiles: 1 .. 0xFFFFFFF0, never 0 (the words start out 0).  The
-        // election is an atomicMax, so when the number starts over (every 2^32 - 16 frames) the words are cleared first -- the same
-        // guard the tile-word tag has above.
-        fa.ord_frame = (uint32_t) (ctx->frame % 0xFFFFFFF0ull) + 1u;
-        if (fa.ord_frame == 1u && ctx->frame != 0u)
-            RT_HIP(hipMemsetAsync(fa.order_state + 3u * (size_t) fa.ord_stride, 0, sizeof(uint32_t) * fa.n_tiles, stream));
-        ctx->frame++;
-    }
-    if (ms) RT_HIP(hipEventRecord(ctx->ev0, stream));
-    const bool fast = (ctx->cfg.flags & RT_FLAG_FAST) != 0;
-    hipError_t e;
-    if (ctx->cfg.flags & RT_FLAG_SIMPLE)
-        e = fast ? rt_launch_trace_fast(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, rgba8, count, stream)
-                 : rt_launch_trace_strict(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, rgba8, count, stream);
-    else
-        e = fast ? rt_launch_wavefront_fast(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream)
-                 : rt_launch_wavefront_strict(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
+    if (fa.order_state)
+        if (int rc = rotate_launch_order(ctx, fa, stream)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
+                                                           : ctx->kern->wavefront(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
+    const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
     if (ctx->adaptive) {
         // halo rows -> clear the list -> classify (unrefined pixels written out) -> the k^2 sample rays of the listed pixels; the next
         // frame's plain pass overwrites what these read, and the ordering event below is recorded behind the last of them
-        const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
-        auto rays = fast ? rt_launch_ray_list_fast : rt_launch_ray_list_strict;
         const size_t px = (size_t) ctx->local_rows * ctx->width;
         if (ctx->halo_slots)
-            RT_HIP(rays(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo, 0,
-                        count, ctx->d_counters, stream));
+            RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo,
+                                       0, count, ctx->d_counters, stream));
         RT_HIP(hipMemsetAsync(ctx->d_list + px, 0, sizeof(uint32_t), stream));
         if (ctx->geometry) {
             // the primary-hit object (and, for a finite min_cos, normal) of this rank's rows and of the halo rows: gbuffer_kernel itself, which
             // reads no frame state and books no rays; then the classifier with the geometric term
-            float *nrm = ctx->min_cos == -INFINITY ? nullptr : ctx->d_geo_nrm;
-            auto edges = fast ? rt_launch_gbuffer_edges_fast : rt_launch_gbuffer_edges_strict;
-            RT_HIP(edges(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nrm, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
+            float *nrm = ctx->min_cos == -INFINITY ? nullptr : ctx->d_geo_nrm.p;
+            RT_HIP(ctx->kern->gbuffer_edges(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nrm, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
             RT_HIP(rt_launch_classify_geometry_strict(fb, ctx->d_halo, ctx->d_geo_obj, nrm, ctx->d_geo_halo, ctx->width, ctx->height, ctx->local_rows,
                                                       ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau, ctx->min_cos, dest, out8, ctx->d_list,
                                                       ctx->d_list + px, stream));
@@ -925,33 +849,18 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
                                              dest, out8, ctx->d_list, ctx->d_list + px, stream));
         }
-        RT_HIP(rays(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
-                    ctx->d_counters, stream));
-        if (sparse) {
-            const BgPixel bg = bg_pixel(ctx);
-            RT_HIP(rt_launch_pack_sparse_strict(ctx->d_fb, dev_fb, ctx->width, ctx->local_rows, bg.w, sparse_cap, out8, stream));
-        }
+        RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
+                                   ctx->d_counters, stream));
     }
-    if (ss) {
-        // the next frame's render overwrites the internal frame this reads, so the ordering event below is recorded behind it
-        const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
-        RT_HIP(rt_launch_resolve(ctx->d_ss, sparse ? ctx->d_fb : out, ctx->width, ctx->local_rows, ctx->ssaa, out8, ctx->resolve_nt, stream));
-        if (sparse) {
-            const BgPixel bg = bg_pixel(ctx);
-            RT_HIP(rt_launch_pack_sparse_strict(ctx->d_fb, dev_fb, ctx->width, ctx->local_rows, bg.w, sparse_cap, out8, stream));
-        }
+    if (ss) // the next frame's render overwrites the internal frame this reads, so the ordering event below is recorded behind it
+        RT_HIP(rt_launch_resolve(ctx->d_ss, dest, ctx->width, ctx->local_rows, ctx->ssaa, out8, ctx->resolve_nt, stream));
+    if (sparse && !kernel_sparse) { // supersampled and adaptive frames: pack the finished rows into the message
+        const BgPixel bg = bg_pixel(ctx);
+        RT_HIP(rt_launch_pack_sparse_strict(ctx->d_fb, dev_fb, ctx->width, ctx->local_rows, bg.w, sparse_cap, out8, stream));
     }
     ctx->counted = count != 0;
-    if (!capturing) RT_HIP(hipEventRecord(ctx->ev_done, stream));
-    ctx->captured = capturing;
-    ctx->last_stream = stream;
-    ctx->rendered = true;
-    if (ms) {
-        RT_HIP(hipEventRecord(ctx->ev1, stream));
-        RT_HIP(hipEventSynchronize(ctx->ev1));
-        RT_HIP(hipEventElapsedTime(ms, ctx->ev0, ctx->ev1));
-    }
-    return RT_OK;
+    if (int rc = order_end(ctx, stream, capturing)) return rc;
+    return timer_end(ctx, stream, ms);
 }
 
 extern "C" int rt_render(rt_ctx *ctx, const double cam[16], void *dev_fb, void *stream, float *ms)
@@ -978,22 +887,10 @@ static int gbuffer_args(const char *who, rt_ctx *ctx, const double cam[16], Fram
     fa.order_state = nullptr;
     fa.ord_host = nullptr;
     fa.tile_state = nullptr;
-    std::memcpy(fa.cam, cam, sizeof(double) * 16);
-    for (int r = 0; r < 3; r++) fa.origin[r] = (cam[0 + r] * 0.0 + cam[4 + r] * 0.0) + (cam[8 + r] * 0.0 + cam[12 + r] * 1.0); // as render_impl
-    for (size_t j = 0; j * RT_NCOEF < ctx->cub_coefs.size(); j++) { // degree-3 objects: the Taylor record of the frame's origin, as render_impl forms it
-        const rtm::CubicAt a = rtm::cubic_at(ctx->cub_coefs.data() + j * RT_NCOEF, rtm::D3{fa.origin[0], fa.origin[1], fa.origin[2]});
-        const rtm::CubicAbs ab = rtm::cubic_abs(ctx->cub_coefs.data() + j * RT_NCOEF);
-        const double v[RT_CUB_REC] = {a.f, a.gx, a.gy, a.gz, a.hxx, a.hyy, a.hzz, a.hxy, a.hxz, a.hyz};
-        const double va[4] = {ab.a3, ab.a2, ab.a1, ab.a0};
-        std::memcpy(fa.cub_rec[j], v, sizeof(v));
-        std::memcpy(fa.cub_abs[j], va, sizeof(va));
-    }
+    rtf::frame_origin(fa, cam, ctx->cub_coefs);
     if (rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "%s: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", who, rt_gbuffer_lds_bytes_strict(&fa));
-    int cur = -1;
-    RT_HIP(hipGetDevice(&cur));
-    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
-    return RT_OK;
+    return use_device(ctx);
 }
 
 extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev_object, double *dev_t, float *dev_normal, void *stream_, float *ms)
@@ -1002,22 +899,11 @@ extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev
     if (!dev_object && !dev_t && !dev_normal) return fail(RT_ERR_INVALID, "rt_render_gbuffer: all three planes are null");
     hipStream_t stream = (hipStream_t) stream_;
     FrameArgs fa;
-    const int rc = gbuffer_args("rt_render_gbuffer", ctx, cam, fa);
-    if (rc != RT_OK) return rc;
-    if (ms) {
-        if (!ctx->gb_ev0) RT_HIP(hipEventCreate(&ctx->gb_ev0));
-        if (!ctx->gb_ev1) RT_HIP(hipEventCreate(&ctx->gb_ev1));
-        RT_HIP(hipEventRecord(ctx->gb_ev0, stream));
-    }
-    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_gbuffer_fast(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream)
-                                                         : rt_launch_gbuffer_strict(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
+    if (int rc = gbuffer_args("rt_render_gbuffer", ctx, cam, fa)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = ctx->kern->gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "G-buffer kernel launch failed: %s", hipGetErrorString(e));
-    if (ms) {
-        RT_HIP(hipEventRecord(ctx->gb_ev1, stream));
-        RT_HIP(hipEventSynchronize(ctx->gb_ev1));
-        RT_HIP(hipEventElapsedTime(ms, ctx->gb_ev0, ctx->gb_ev1));
-    }
-    return RT_OK;
+    return timer_end(ctx, stream, ms);
 }
 
 extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream_)
@@ -1030,24 +916,12 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
             return fail(RT_ERR_INVALID, "rt_pick: pixel %u = (%u, %u) lies outside the %u x %u image", i, xy[2 * (size_t) i], xy[2 * (size_t) i + 1], ctx->width, ctx->height);
     hipStream_t stream = (hipStream_t) stream_;
     FrameArgs fa;
-    const int rc = gbuffer_args("rt_pick", ctx, cam, fa);
-    if (rc != RT_OK) return rc;
-    if (n > ctx->pick_cap) { // (every earlier call has synchronised: nothing uses the old buffers)
-        if (ctx->d_pick_xy) (void) hipFree(ctx->d_pick_xy);
-        if (ctx->d_pick_out) (void) hipFree(ctx->d_pick_out);
-        ctx->d_pick_xy = nullptr;
-        ctx->d_pick_out = nullptr;
-        ctx->pick_cap = 0;
-        const uint32_t cap = n < 64u ? 64u : n;
-        RT_HIP(hipMalloc((void **) &ctx->d_pick_xy, sizeof(uint32_t) * 2 * (size_t) cap));
-        RT_HIP(hipMalloc(&ctx->d_pick_out, sizeof(rt_hit) * (size_t) cap));
-        ctx->pick_cap = cap;
-    }
-    RT_HIP(hipMemcpyAsync(ctx->d_pick_xy, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_pick_fast(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_pick_xy, n, ctx->d_pick_out, stream)
-                                                         : rt_launch_pick_strict(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_pick_xy, n, ctx->d_pick_out, stream);
+    if (int rc = gbuffer_args("rt_pick", ctx, cam, fa)) return rc;
+    if (int rc = ctx->pick.reserve(n, sizeof(uint32_t) * 2, sizeof(rt_hit))) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->pick.in, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = ctx->kern->pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pick kernel launch failed: %s", hipGetErrorString(e));
-    RT_HIP(hipMemcpyAsync(out_host, ctx->d_pick_out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipMemcpyAsync(out_host, ctx->pick.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
 }
@@ -1065,46 +939,11 @@ static int rays_ready(const char *who, rt_ctx *ctx)
 {
     if (rt_rays_lds_bytes_strict(&ctx->fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "%s: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", who, rt_rays_lds_bytes_strict(&ctx->fa));
-    int cur = -1;
-    RT_HIP(hipGetDevice(&cur));
-    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
-    return RT_OK;
+    return use_device(ctx);
 }
 
 // workgroups of one ray-query launch: four per CU (the kernels' registers allow three to four resident ones), fewer for few rays
 static uint32_t rays_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
-
-static int rays_timed(rt_ctx *ctx, hipStream_t stream, float *ms, bool begin)
-{
-    if (!ms) return RT_OK;
-    if (begin) {
-        if (!ctx->rq_ev0) RT_HIP(hipEventCreate(&ctx->rq_ev0));
-        if (!ctx->rq_ev1) RT_HIP(hipEventCreate(&ctx->rq_ev1));
-        RT_HIP(hipEventRecord(ctx->rq_ev0, stream));
-    } else {
-        RT_HIP(hipEventRecord(ctx->rq_ev1, stream));
-        RT_HIP(hipEventSynchronize(ctx->rq_ev1));
-        RT_HIP(hipEventElapsedTime(ms, ctx->rq_ev0, ctx->rq_ev1));
-    }
-    return RT_OK;
-}
-
-// the staging buffers of the _host entry points, for n rays
-static int rays_staging(rt_ctx *ctx, uint32_t n)
-{
-    if (n > ctx->rq_cap) { // (every earlier call has synchronised: nothing uses the old buffers)
-        if (ctx->d_rq_rays) (void) hipFree(ctx->d_rq_rays);
-        if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
-        ctx->d_rq_rays = nullptr;
-        ctx->d_rq_hits = nullptr;
-        ctx->rq_cap = 0;
-        const uint32_t cap = n < 64u ? 64u : n;
-        RT_HIP(hipMalloc(&ctx->d_rq_rays, sizeof(rt_ray) * (size_t) cap));
-        RT_HIP(hipMalloc(&ctx->d_rq_hits, sizeof(rt_hit) * (size_t) cap));
-        ctx->rq_cap = cap;
-    }
-    return RT_OK;
-}
 
 extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_hit *dev_hits, void *stream_, float *ms)
 {
@@ -1115,13 +954,11 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt
     if (ranges_overlap(dev_rays, sizeof(rt_ray) * (size_t) n, dev_hits, sizeof(rt_hit) * (size_t) n))
         return fail(RT_ERR_INVALID, "rt_trace_rays: the rays and the hits overlap");
     hipStream_t stream = (hipStream_t) stream_;
-    int rc = rays_ready("rt_trace_rays", ctx);
-    if (rc != RT_OK) return rc;
-    if ((rc = rays_timed(ctx, stream, ms, true)) != RT_OK) return rc;
-    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_trace_rays_fast(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream)
-                                                         : rt_launch_trace_rays_strict(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
+    if (int rc = rays_ready("rt_trace_rays", ctx)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = ctx->kern->trace_rays(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
-    return rays_timed(ctx, stream, ms, false);
+    return timer_end(ctx, stream, ms);
 }
 
 extern "C" int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const double *dev_t_max, uint32_t n, int32_t *dev_blocked, void *stream_, float *ms)
@@ -1134,13 +971,11 @@ extern "C" int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const doubl
         (dev_t_max && ranges_overlap(dev_t_max, sizeof(double) * (size_t) n, dev_blocked, sizeof(int32_t) * (size_t) n)))
         return fail(RT_ERR_INVALID, "rt_occluded_rays: the flags overlap the rays or t_max");
     hipStream_t stream = (hipStream_t) stream_;
-    int rc = rays_ready("rt_occluded_rays", ctx);
-    if (rc != RT_OK) return rc;
-    if ((rc = rays_timed(ctx, stream, ms, true)) != RT_OK) return rc;
-    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_occluded_rays_fast(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream)
-                                                         : rt_launch_occluded_rays_strict(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
+    if (int rc = rays_ready("rt_occluded_rays", ctx)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = ctx->kern->occluded_rays(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
-    return rays_timed(ctx, stream, ms, false);
+    return timer_end(ctx, stream, ms);
 }
 
 extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, rt_hit *out, void *stream_)
@@ -1149,14 +984,12 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
     if (n == 0) return fail(RT_ERR_INVALID, "rt_trace_rays_host: n is 0");
     if (ranges_overlap(rays, sizeof(rt_ray) * (size_t) n, out, sizeof(rt_hit) * (size_t) n)) return fail(RT_ERR_INVALID, "rt_trace_rays_host: the rays and the hits overlap");
     hipStream_t stream = (hipStream_t) stream_;
-    int rc = rays_ready("rt_trace_rays_host", ctx);
-    if (rc != RT_OK) return rc;
-    if ((rc = rays_staging(ctx, n)) != RT_OK) return rc;
-    RT_HIP(hipMemcpyAsync(ctx->d_rq_rays, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_trace_rays_fast(&ctx->fa, ctx->d_obj, ctx->d_rq_rays, n, ctx->d_rq_hits, rays_max_grid(ctx), stream)
-                                                         : rt_launch_trace_rays_strict(&ctx->fa, ctx->d_obj, ctx->d_rq_rays, n, ctx->d_rq_hits, rays_max_grid(ctx), stream);
+    if (int rc = rays_ready("rt_trace_rays_host", ctx)) return rc;
+    if (int rc = ctx->rq.reserve(n, sizeof(rt_ray), sizeof(rt_hit))) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->rq.in, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = ctx->kern->trace_rays(&ctx->fa, ctx->d_obj, ctx->rq.in, n, ctx->rq.out, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
-    RT_HIP(hipMemcpyAsync(out, ctx->d_rq_hits, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipMemcpyAsync(out, ctx->rq.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
 }
@@ -1165,8 +998,7 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
 // Like the ray queries it reads the scene (blob and lights) and nothing of the frame; always 4 x float32 per ray, whatever cfg.format.
 static hipError_t shade_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, float *dev_rgba, void *dev_hits, hipStream_t stream)
 {
-    return (ctx->cfg.flags & RT_FLAG_FAST) ? rt_launch_shade_rays_fast(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream)
-                                           : rt_launch_shade_rays_strict(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
+    return ctx->kern->shade_rays(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
 }
 
 extern "C" int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits, void *stream_, float *ms)
@@ -1179,12 +1011,11 @@ extern "C" int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, fl
     if (dev_hits && (ranges_overlap(dev_rays, ray_bytes, dev_hits, hit_bytes) || ranges_overlap(dev_rgba, px_bytes, dev_hits, hit_bytes)))
         return fail(RT_ERR_INVALID, "rt_shade_rays: the hits overlap the rays or the rgba output");
     hipStream_t stream = (hipStream_t) stream_;
-    int rc = rays_ready("rt_shade_rays", ctx);
-    if (rc != RT_OK) return rc;
-    if ((rc = rays_timed(ctx, stream, ms, true)) != RT_OK) return rc;
+    if (int rc = rays_ready("rt_shade_rays", ctx)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
     const hipError_t e = shade_launch(ctx, dev_rays, n, dev_rgba, dev_hits, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_shade_rays: kernel launch failed: %s", hipGetErrorString(e));
-    return rays_timed(ctx, stream, ms, false);
+    return timer_end(ctx, stream, ms);
 }
 
 extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_out, void *stream_)
@@ -1193,12 +1024,11 @@ extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, f
     if (n == 0) return fail(RT_ERR_INVALID, "rt_shade_rays_host: n is 0");
     if (ranges_overlap(rays, sizeof(rt_ray) * (size_t) n, rgba_out, 4 * sizeof(float) * (size_t) n)) return fail(RT_ERR_INVALID, "rt_shade_rays_host: the rays and the rgba output overlap");
     hipStream_t stream = (hipStream_t) stream_;
-    int rc = rays_ready("rt_shade_rays_host", ctx);
-    if (rc != RT_OK) return rc;
-    if ((rc = rays_staging(ctx, n)) != RT_OK) return rc;
-    float *d_rgba = reinterpret_cast<float *>(ctx->d_rq_hits); // (48 bytes per ray there, 16 needed)
-    RT_HIP(hipMemcpyAsync(ctx->d_rq_rays, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = shade_launch(ctx, ctx->d_rq_rays, n, d_rgba, nullptr, stream);
+    if (int rc = rays_ready("rt_shade_rays_host", ctx)) return rc;
+    if (int rc = ctx->rq.reserve(n, sizeof(rt_ray), sizeof(rt_hit))) return rc;
+    float *d_rgba = static_cast<float *>(ctx->rq.out.p); // (48 bytes per ray there, 16 needed)
+    RT_HIP(hipMemcpyAsync(ctx->rq.in, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = shade_launch(ctx, ctx->rq.in, n, d_rgba, nullptr, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_shade_rays_host: kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(rgba_out, d_rgba, 4 * sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1223,9 +1053,7 @@ static const char *reject_text(uint32_t reason)
 // while that stream is capturing -- nothing can be waited for inside a capture.
 static int read_behind_last_call(const char *who, rt_ctx *ctx, void *dst, const void *src, size_t bytes, void *dst2 = nullptr, const void *src2 = nullptr, size_t bytes2 = 0)
 {
-    int cur = -1;
-    RT_HIP(hipGetDevice(&cur));
-    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    if (int rc = use_device(ctx)) return rc;
     hipStream_t stream = ctx->last_stream;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
@@ -1247,24 +1075,15 @@ static int set_scene_check(const char *who, const rt_ctx *ctx, const rt_scene_up
     return RT_OK;
 }
 
-// enqueue the kernel on `stream`, in the context's frame order (the rule of render_impl)
+// enqueue the kernel on `stream`, in the context's frame order (order_begin / order_end, as a render)
 static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update *dev, hipStream_t stream)
 {
-    int cur = -1;
-    RT_HIP(hipGetDevice(&cur));
-    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    if (ctx->rendered && stream != ctx->last_stream) {
-        if (ctx->captured || capturing)
-            return fail(RT_ERR_INVALID, "%s: a context whose calls were captured into a graph on one stream must stay on that stream (frames and scene updates of a "
-                                        "context are ordered on the device, and a capture cannot be ordered against another stream through an event)", who);
-        RT_HIP(hipStreamWaitEvent(stream, ctx->ev_done, 0));
-    }
+    if (int rc = use_device(ctx)) return rc;
+    bool capturing = false;
+    if (int rc = order_begin(who, ctx, stream, &capturing)) return rc;
     const FrameArgs &fa = ctx->fa;
     SetSceneArgs a{};
-    a.blob = reinterpret_cast<unsigned char *>(ctx->d_obj);
+    a.blob = reinterpret_cast<unsigned char *>(ctx->d_obj.p);
     a.lights = ctx->d_light;
     a.status = ctx->d_ss_status;
     a.coefs = dev->coefs;
@@ -1284,11 +1103,7 @@ static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update
     a.has_mirror = fa.has_mirror;
     const hipError_t e = rt_launch_set_scene(&a, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
-    if (!capturing) RT_HIP(hipEventRecord(ctx->ev_done, stream));
-    ctx->captured = capturing;
-    ctx->last_stream = stream;
-    ctx->rendered = true;
-    return RT_OK;
+    return order_end(ctx, stream, capturing);
 }
 
 extern "C" int rt_set_scene(rt_ctx *ctx, const rt_scene_update *dev, void *stream)
@@ -1303,9 +1118,7 @@ extern "C" int rt_set_scene_host(rt_ctx *ctx, const rt_scene_update *host, void 
     if (!ctx || !host) return fail(RT_ERR_INVALID, "rt_set_scene_host: null argument");
     if (int rc = set_scene_check("rt_set_scene_host", ctx, host)) return rc;
     hipStream_t stream = (hipStream_t) stream_;
-    int cur = -1;
-    RT_HIP(hipGetDevice(&cur));
-    if (cur != ctx->device) RT_HIP(hipSetDevice(ctx->device));
+    if (int rc = use_device(ctx)) return rc;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
     if (cap != hipStreamCaptureStatusNone)
@@ -1314,7 +1127,7 @@ extern "C" int rt_set_scene_host(rt_ctx *ctx, const rt_scene_update *host, void 
     const size_t no = ctx->fa.n_obj, nl = ctx->fa.n_lights;
     const size_t b_coefs = sizeof(double) * RT_NCOEF * no, b_lp = sizeof(double) * 3 * nl, b_refl = sizeof(float) * no, b_alb = sizeof(float) * 3 * no,
                  b_lc = sizeof(float) * 3 * nl;
-    if (!ctx->d_ss_stage) RT_HIP(hipMalloc((void **) &ctx->d_ss_stage, b_coefs + b_lp + b_refl + b_alb + b_lc));
+    if (!ctx->d_ss_stage) RT_HIP(ctx->d_ss_stage.alloc(b_coefs + b_lp + b_refl + b_alb + b_lc));
     unsigned char *p = ctx->d_ss_stage;
     rt_scene_update dev{};
     auto put = [&](const void *src, size_t bytes) -> const void * {
@@ -1389,17 +1202,14 @@ extern "C" int rt_row_map(const rt_ctx *ctx, uint32_t *rows)
 
 extern "C" size_t rt_pixel_bytes(const rt_ctx *ctx) { return ctx ? ctx->pixel_bytes : 0; }
 
-extern "C" void *rt_device_fb(rt_ctx *ctx) { return ctx ? ctx->d_fb : nullptr; }
+extern "C" void *rt_device_fb(rt_ctx *ctx) { return ctx ? ctx->d_fb.p : nullptr; }
 
 extern "C" int rt_download(rt_ctx *ctx, void *host_dst, size_t bytes)
 {
     if (!ctx || !host_dst) return fail(RT_ERR_INVALID, "rt_download: null argument");
     const size_t have = (size_t) ctx->local_rows * ctx->width * ctx->pixel_bytes;
     if (bytes > have) return fail(RT_ERR_INVALID, "rt_download: %zu bytes requested, framebuffer holds %zu", bytes, have);
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());
-    RT_HIP(hipMemcpy(host_dst, ctx->d_fb, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return read_synced(ctx, host_dst, ctx->d_fb, bytes);
 }
 
 extern "C" int rt_assemble(rt_ctx *ctx, const void *gathered, void *full, void *stream)
@@ -1427,7 +1237,7 @@ extern "C" int rt_pack_sparse(rt_ctx *ctx, const void *dev_fb, void *dev_msg, ui
 {
     if (!ctx || !dev_msg) return fail(RT_ERR_INVALID, "rt_pack_sparse: null argument");
     const BgPixel bg = bg_pixel(ctx);
-    hipError_t e = rt_launch_pack_sparse_strict(dev_fb ? dev_fb : ctx->d_fb, dev_msg, ctx->width, ctx->local_rows, bg.w, capacity_tiles,
+    hipError_t e = rt_launch_pack_sparse_strict(dev_fb ? dev_fb : ctx->d_fb.p, dev_msg, ctx->width, ctx->local_rows, bg.w, capacity_tiles,
                                                 ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pack launch failed: %s", hipGetErrorString(e));
     return RT_OK;
@@ -1443,18 +1253,20 @@ extern "C" int rt_assemble_sparse(rt_ctx *ctx, const void *gathered, uint32_t ca
     return RT_OK;
 }
 
+// tiles of the rank with the most rows: the stamps of the incremental assembly are [world][max_tiles]
+static size_t sparse_max_tiles(const rt_ctx *ctx) { return (size_t) ((ctx->width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u); }
+
 extern "C" size_t rt_sparse_stamp_bytes(rt_ctx *ctx)
 {
     if (!ctx) return 0;
-    const size_t max_tiles = (size_t) ((ctx->width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
-    return sizeof(uint32_t) * (size_t) ctx->cfg.world * max_tiles;
+    return sizeof(uint32_t) * (size_t) ctx->cfg.world * sparse_max_tiles(ctx);
 }
 
 extern "C" int rt_assemble_sparse_incremental(rt_ctx *ctx, const void *gathered, uint32_t capacity_tiles, void *full, void *stamps, uint32_t frame_tag,
                                               void *stream)
 {
     if (!ctx || !gathered || !full || !stamps) return fail(RT_ERR_INVALID, "rt_assemble_sparse_incremental: null argument");
-    const uint32_t max_tiles = ((ctx->width + 15u) / 16u) * ((ctx->max_local_rows + 15u) / 16u);
+    const uint32_t max_tiles = (uint32_t) sparse_max_tiles(ctx);
     const BgPixel bg = bg_pixel(ctx);
     hipError_t e = rt_launch_assemble_sparse_strict(gathered, full, ctx->width, ctx->height, ctx->cfg.world, ctx->cfg.band_rows, bg.w, capacity_tiles,
                                                     stamps, max_tiles, frame_tag, ctx->cfg.format == RT_FMT_RGBA8, (hipStream_t) stream);
@@ -1485,9 +1297,7 @@ extern "C" int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels)
     if (!ctx || !pixels) return fail(RT_ERR_INVALID, "rt_get_ssaa_refined: null argument");
     if (!ctx->adaptive) return fail(RT_ERR_INVALID, "rt_get_ssaa_refined: the context was not created with RT_FLAG_SSAA_ADAPTIVE");
     uint32_t n = 0;
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());
-    RT_HIP(hipMemcpy(&n, ctx->d_list + (size_t) ctx->local_rows * ctx->width, sizeof(n), hipMemcpyDeviceToHost));
+    if (int rc = read_synced(ctx, &n, ctx->d_list + (size_t) ctx->local_rows * ctx->width, sizeof(n))) return rc;
     *pixels = n;
     return RT_OK;
 }
@@ -1497,9 +1307,7 @@ extern "C" int rt_get_counters(rt_ctx *ctx, rt_counters *out)
     if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_get_counters: null argument");
     if (!ctx->counted) return fail(RT_ERR_INVALID, "rt_get_counters: the last render was not done with RT_FLAG_COUNT");
     unsigned long long h[8];
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());
-    RT_HIP(hipMemcpy(h, ctx->d_counters, sizeof(h), hipMemcpyDeviceToHost));
+    if (int rc = read_synced(ctx, h, ctx->d_counters, sizeof(h))) return rc;
     out->primary_rays = h[0];
     out->shadow_rays = h[1];
     out->reflect_rays = h[2];
@@ -1517,9 +1325,7 @@ extern "C" int rt_get_counters_detail(rt_ctx *ctx, rt_counters_detail *out)
     if (!ctx->counted) return fail(RT_ERR_INVALID, "rt_get_counters_detail: the last render was not done with RT_FLAG_COUNT");
     if (ctx->cfg.flags & RT_FLAG_SIMPLE) return fail(RT_ERR_INVALID, "rt_get_counters_detail: the simple kernel does not split its counters");
     unsigned long long h[21];
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());
-    RT_HIP(hipMemcpy(h, ctx->d_counters + 32, sizeof(h), hipMemcpyDeviceToHost));
+    if (int rc = read_synced(ctx, h, ctx->d_counters + 32, sizeof(h))) return rc;
     for (int i = 0; i < 4; i++) out->tests_executed[i] = h[i];
     for (int i = 0; i < 3; i++) out->solves[i] = h[4 + i];
     for (int i = 0; i < 5; i++) out->cull_evals[i] = h[7 + i];
@@ -1535,9 +1341,7 @@ extern "C" int rt_get_counters_detail(rt_ctx *ctx, rt_counters_detail *out)
 extern "C" int rt_debug_counters(rt_ctx *ctx, uint64_t out[32])
 {
     if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_counters: null argument");
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());
-    RT_HIP(hipMemcpy(out, ctx->d_counters, sizeof(uint64_t) * 32, hipMemcpyDeviceToHost));
+    if (int rc = read_synced(ctx, out, ctx->d_counters, sizeof(uint64_t) * 32)) return rc;
     if (ctx->d_stamps) { // diagnostic build: sum the per-wave stamp rows into words 8..19
         std::vector<uint64_t> rows(ctx->n_stamp_rows * 16);
         RT_HIP(hipMemcpy(rows.data(), ctx->d_stamps, rows.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
@@ -1554,50 +1358,13 @@ extern "C" int rt_debug_stamp_rows(rt_ctx *ctx, uint64_t *out, size_t max_rows, 
     *n_rows = ctx->d_stamps ? ctx->n_stamp_rows : 0;
     if (!out || !ctx->d_stamps) return RT_OK;
     const size_t n = max_rows < ctx->n_stamp_rows ? max_rows : ctx->n_stamp_rows;
-    RT_HIP(hipSetDevice(ctx->device));
-    RT_HIP(hipDeviceSynchronize());
-    RT_HIP(hipMemcpy(out, ctx->d_stamps, n * 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return RT_OK;
+    return read_synced(ctx, out, ctx->d_stamps, n * 16 * sizeof(uint64_t));
 }
 
 extern "C" int rt_destroy(rt_ctx *ctx)
 {
     if (!ctx) return RT_OK;
-    (void) hipSetDevice(ctx->device);
-    if (ctx->d_obj) (void) hipFree(ctx->d_obj);
-    if (ctx->d_light) (void) hipFree(ctx->d_light);
-    if (ctx->d_fb) (void) hipFree(ctx->d_fb);
-    if (ctx->d_ss) (void) hipFree(ctx->d_ss);
-    if (ctx->d_p) (void) hipFree(ctx->d_p);
-    if (ctx->d_halo) (void) hipFree(ctx->d_halo);
-    if (ctx->d_geo_obj) (void) hipFree(ctx->d_geo_obj);
-    if (ctx->d_geo_nrm) (void) hipFree(ctx->d_geo_nrm);
-    if (ctx->d_geo_xy) (void) hipFree(ctx->d_geo_xy);
-    if (ctx->d_geo_halo) (void) hipFree(ctx->d_geo_halo);
-    if (ctx->d_list) (void) hipFree(ctx->d_list);
-    if (ctx->d_camxk) (void) hipFree(ctx->d_camxk);
-    if (ctx->d_camyk) (void) hipFree(ctx->d_camyk);
-    if (ctx->d_counters) (void) hipFree(ctx->d_counters);
-    if (ctx->d_stamps) (void) hipFree(ctx->d_stamps);
-    if (ctx->d_camx) (void) hipFree(ctx->d_camx);
-    if (ctx->d_camy) (void) hipFree(ctx->d_camy);
-    if (ctx->fa.order_state) (void) hipFree(ctx->fa.order_state);
-    if (ctx->fa.tile_state) (void) hipFree(ctx->fa.tile_state);
-    if (ctx->h_listed) (void) hipHostFree(ctx->h_listed);
-    if (ctx->ev0) (void) hipEventDestroy(ctx->ev0);
-    if (ctx->ev1) (void) hipEventDestroy(ctx->ev1);
-    if (ctx->ev_done) (void) hipEventDestroy(ctx->ev_done);
-    if (ctx->gb_ev0) (void) hipEventDestroy(ctx->gb_ev0);
-    if (ctx->gb_ev1) (void) hipEventDestroy(ctx->gb_ev1);
-    if (ctx->d_pick_xy) (void) hipFree(ctx->d_pick_xy);
-    if (ctx->d_pick_out) (void) hipFree(ctx->d_pick_out);
-    if (ctx->d_rq_rays) (void) hipFree(ctx->d_rq_rays);
-    if (ctx->d_rq_hits) (void) hipFree(ctx->d_rq_hits);
-    if (ctx->rq_ev0) (void) hipEventDestroy(ctx->rq_ev0);
-    if (ctx->rq_ev1) (void) hipEventDestroy(ctx->rq_ev1);
-    if (ctx->d_ss_status) (void) hipFree(ctx->d_ss_status);
-    if (ctx->d_ss_stage) (void) hipFree(ctx->d_ss_stage);
-
+    (void) hipSetDevice(ctx->device); // (the members release what the context holds there)
     delete ctx;
     return RT_OK;
 }

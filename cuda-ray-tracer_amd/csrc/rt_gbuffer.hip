@@ -10,7 +10,7 @@
 // The pass reads the scene blob and the camera-plane tables (both constant after rt_create) and writes the caller's planes: no tile
 // words, launch-order generations, census, counters or frame tag -- it is invisible to rt_render.
 #include <hip/hip_runtime.h>
-
+#include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_shade.hpp"          // RT_SYM and the variant's namespace
 #include "rt_wavefront_math.hpp" // class-table coefficients, us_needs_solve, accept, sphere_in_cone, sphere_normal
 

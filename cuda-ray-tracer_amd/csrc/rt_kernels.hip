@@ -9,7 +9,7 @@
 // helper get_color_and_object (:65-102).  Not a translation of it: see the notes in rt_math.hpp and
 // DESIGN.md ("Kernels").
 #include <hip/hip_runtime.h>
-
+#include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_shade.hpp" // Cnt, trace, blend, render_ray: the per-lane shading, shared with rt_adaptive.hip
 
 namespace RT_SYM(rtk) {

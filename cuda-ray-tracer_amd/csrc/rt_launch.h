@@ -1,0 +1,76 @@
+// rt_launch.h -- every launcher the kernel files export to the host (rt_capi.cpp), declared once.  The launchers have C linkage, which
+// carries no types: this header is what both sides see, so a definition that disagrees with the call does not compile.  Included by
+// rt_capi.cpp and by every .hip file that defines a launcher.
+#ifndef RT_LAUNCH_H
+#define RT_LAUNCH_H
+
+#include <hip/hip_runtime.h>
+
+#include "rt_scene_dev.h"
+#include "rt_set_scene.h"
+
+// name_<variant>: the kernel files that are compiled once per floating-point contraction mode (-DRT_VARIANT=strict|fast) define RT_SYM(name)
+#define RT_CAT2(a, b) a##_##b
+#define RT_CAT(a, b) RT_CAT2(a, b)
+#ifdef RT_VARIANT
+#define RT_SYM(name) RT_CAT(name, RT_VARIANT)
+#endif
+#define RT_PER_VARIANT(ret, name, ...)                \
+    extern "C" ret RT_CAT(name, strict)(__VA_ARGS__); \
+    extern "C" ret RT_CAT(name, fast)(__VA_ARGS__);
+
+// rt_kernels.hip: the simple kernel, and the frame transport (the host calls the _strict ones: they do no arithmetic a contraction changes)
+RT_PER_VARIANT(hipError_t, rt_launch_trace, const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, void *fb, unsigned long long *counters, int rgba8,
+               int count, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_assemble, const void *gathered, void *full, uint32_t width, uint32_t height, uint32_t world, uint32_t band_rows,
+               uint32_t max_local_rows, int rgba8, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_pack_sparse, const void *fb, void *msg, uint32_t width, uint32_t local_rows, const uint32_t *bg, uint32_t cap, int rgba8,
+               hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_assemble_sparse, const void *gathered, void *full, uint32_t width, uint32_t height, uint32_t world, uint32_t band_rows,
+               const uint32_t *bg, uint32_t cap, void *stamps, uint32_t max_tiles, uint32_t tag, int rgba8, hipStream_t stream)
+// rt_wavefront.hip: the product kernel
+RT_PER_VARIANT(size_t, rt_wavefront_lds_bytes, uint32_t stage_bytes, uint32_t n_lights, int has_mirror, uint32_t n_cull_spheres, int lean, uint32_t n_cub)
+RT_PER_VARIANT(hipError_t, rt_launch_wavefront, const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, void *fb, unsigned long long *counters, int count,
+               const double *camx, const double *camy, hipStream_t stream)
+// rt_adaptive.hip: the ray-list kernel of adaptive supersampling and the classifiers (the host calls classify*_strict)
+RT_PER_VARIANT(hipError_t, rt_launch_ray_list, const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, const double *camx, const double *camy,
+               const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, int count,
+               unsigned long long *counters, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_classify, const void *p, const void *halo, uint32_t width, uint32_t height, uint32_t local_rows, uint32_t band_rows,
+               uint32_t world, uint32_t rank, float tau, void *out, int rgba8, uint32_t *list, uint32_t *count, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_classify_geometry, const void *p, const void *halo, const int32_t *obj, const float *nrm, const void *ghalo, uint32_t width,
+               uint32_t height, uint32_t local_rows, uint32_t band_rows, uint32_t world, uint32_t rank, float tau, float min_cos, void *out, int rgba8,
+               uint32_t *list, uint32_t *count, hipStream_t stream)
+// rt_gbuffer.hip: primary-hit G-buffer, picking, and the G pass of an RT_FLAG_SSAA_GEOMETRY frame
+RT_PER_VARIANT(size_t, rt_gbuffer_lds_bytes, const FrameArgs *fa)
+RT_PER_VARIANT(hipError_t, rt_launch_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
+               float *out_normal, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
+               hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_gbuffer_edges, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object,
+               float *out_normal, const uint32_t *halo_xy, uint32_t n_halo, void *halo_rec, hipStream_t stream)
+// rt_rays.hip, rt_shade_rays.hip: caller-supplied rays
+RT_PER_VARIANT(size_t, rt_rays_lds_bytes, const FrameArgs *fa)
+RT_PER_VARIANT(hipError_t, rt_launch_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_occluded_rays, const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
+               uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
+               uint32_t max_grid, hipStream_t stream)
+// built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
+extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
+extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
+
+// the launchers a context calls per variant; rt_create picks one of the two instances (rt_capi.cpp) from RT_FLAG_FAST
+struct Kernels {
+    decltype(&rt_launch_trace_strict) trace;
+    decltype(&rt_launch_wavefront_strict) wavefront;
+    decltype(&rt_launch_ray_list_strict) ray_list;
+    decltype(&rt_launch_gbuffer_strict) gbuffer;
+    decltype(&rt_launch_pick_strict) pick;
+    decltype(&rt_launch_gbuffer_edges_strict) gbuffer_edges;
+    decltype(&rt_launch_trace_rays_strict) trace_rays;
+    decltype(&rt_launch_occluded_rays_strict) occluded_rays;
+    decltype(&rt_launch_shade_rays_strict) shade_rays;
+};
+
+#endif

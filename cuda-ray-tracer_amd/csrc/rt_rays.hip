@@ -9,7 +9,7 @@
 // The kernel reads the scene blob and the caller's rays and writes the caller's records / flags: no camera tables, tile words,
 // launch-order generations, census, counters or frame tag -- it is invisible to rt_render.
 #include <hip/hip_runtime.h>
-
+#include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_rayquery.hpp" // RayQueryArgs, the class tables in LDS, rq_tables / rq_plain, the ray and record layouts
 
 namespace RT_SYM(rtk) {

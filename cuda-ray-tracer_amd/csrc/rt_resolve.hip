@@ -5,7 +5,7 @@
 // same tree over the sub-rows, one multiplication by 1/k^2, then the render kernels' quantisation), so a FAST context resolves
 // exactly as a strict one does.
 #include <hip/hip_runtime.h>
-
+#include "rt_launch.h" // the launcher below, as the host sees it
 #include <cstdint>
 
 namespace {

@@ -1,4 +1,4 @@
-// rt_scene_dev.h -- scene records as they sit in HBM / LDS, shared by the host packer (rt_capi.cpp)
+// rt_scene_dev.h -- scene records as they sit in HBM / LDS, shared by the host packer (rt_scene_image.hpp)
 // and the kernels (rt_kernels.hip).
 //
 // The reference keeps an array of Object (176 B: SurfaceCoefs + reflection_ratio + color,

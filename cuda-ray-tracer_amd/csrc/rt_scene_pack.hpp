@@ -1,4 +1,4 @@
-// rt_scene_pack.hpp -- the derived scene data, one record at a time: what rt_create packs on the host (rt_capi.cpp, create_impl) and
+// rt_scene_pack.hpp -- the derived scene data, one record at a time: what rt_create packs on the host (rt_scene_image.hpp, scene_image) and
 // what rt_set_scene rebuilds on the device (rt_set_scene.hip).  Both call these functions, so the two cannot drift apart.
 //
 // Every function is a pure function of the raw descriptor values (rt_scene_desc semantics: 20 coefficients, reflection, albedo; a

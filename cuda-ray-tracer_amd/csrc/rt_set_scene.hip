@@ -25,7 +25,7 @@
 // contraction pragma (seen: cx * cx + cy * cy + cz * cz became two v_fmac_f64), so a "fast" build of this kernel would not reproduce
 // rt_create's bytes.
 #include <hip/hip_runtime.h>
-
+#include "rt_launch.h" // the launcher below, as the host sees it
 #include <stdint.h>
 
 #include "rt_scene_dev.h"

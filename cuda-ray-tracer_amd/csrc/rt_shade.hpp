@@ -6,15 +6,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rt_launch.h" // RT_SYM
 #include "rt_math.hpp"
 #include "rt_scene_dev.h"
 
 #ifndef RT_VARIANT
 #error "define RT_VARIANT=strict|fast"
 #endif
-#define RT_CAT2(a, b) a##_##b
-#define RT_CAT(a, b) RT_CAT2(a, b)
-#define RT_SYM(name) RT_CAT(name, RT_VARIANT)
 
 namespace RT_SYM(rtk) {
 

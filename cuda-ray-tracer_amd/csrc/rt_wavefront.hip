@@ -56,6 +56,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 
+#include "rt_launch.h" // RT_SYM, and the declarations of the launchers defined at the end of this file
 #include "rt_math.hpp"
 #include "rt_scene_dev.h"
 #include "rt_wavefront_math.hpp"
@@ -63,10 +64,9 @@
 #ifndef RT_VARIANT
 #error "define RT_VARIANT=strict|fast"
 #endif
-#define RT_CAT2(a, b) a##_##b
-#define RT_CAT(a, b) RT_CAT2(a, b)
-#define RT_SYM(name) RT_CAT(name, RT_VARIANT)
 
+// everything below lives in the variant's namespace; the launchers at the end are rt_launch_wavefront_<variant> and
+// rt_wavefront_lds_bytes_<variant>
 namespace RT_SYM(rtw) {
 
 using namespace rtm;

@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture(autouse=True)
 def _lean_always(monkeypatch):
     """rt_create reads MI355RT_LEAN: frames as small as these would otherwise switch to the general instantiation after the first one
-    (few tiles with hits: render_impl in rt_capi.cpp); the adaptive choice itself is covered by test_adaptive_choice_of_the_instantiation."""
+    (few tiles with hits: choose_schedule in rt_capi.cpp); the adaptive choice itself is covered by test_adaptive_choice_of_the_instantiation."""
     monkeypatch.setenv("MI355RT_LEAN", "always")
 
 

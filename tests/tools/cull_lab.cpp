@@ -16,6 +16,7 @@
 #include <cstring>
 #include <vector>
 
+#include "rt_frame_host.hpp"
 #include "rt_wavefront_math.hpp"
 #include "../../oracle/rt_oracle.h"
 #include "cull_lab_records.h"
@@ -53,7 +54,7 @@ struct LabOut {
 
 namespace {
 
-// ---- formation code restated from rt_capi.cpp (create_impl / rt_render), cited line by line there -------------------------------
+// ---- formation code: the frame from the library's own function; the records restated from rt_scene_pack.hpp, cited line by line -----
 bool is_unitsq(const double *c)
 {
     for (int i = 0; i < 10; i++)
@@ -73,7 +74,7 @@ bool has_deg2(const double *c)
     return false;
 }
 
-UsEntry make_us(const double *c, uint32_t orig) // create_impl: bounding sphere, table entry and own-sphere window
+UsEntry make_us(const double *c, uint32_t orig) // pack_object + pack_us: bounding sphere, table entry and own-sphere window
 {
     UsEntry e{};
     e.kx = c[ORC_X]; e.ky = c[ORC_Y]; e.kz = c[ORC_Z]; e.c = c[ORC_C];
@@ -107,7 +108,7 @@ struct LabLight {
     DevLight l;
     LightK k;
 };
-LabLight make_light(const orc_light &src, bool colours_finite) // create_impl: DevLight and LightK of one light
+LabLight make_light(const orc_light &src, bool colours_finite) // pack_light + pack_lightk: DevLight and LightK of one light
 {
     LabLight o;
     memset(&o, 0, sizeof(o));
@@ -137,7 +138,7 @@ LabLight make_light(const orc_light &src, bool colours_finite) // create_impl: D
     return o;
 }
 
-// rt_render: the frame constants behind tile_planes
+// rt_render: the frame constants behind tile_planes, formed by the library's own function (csrc/rt_frame_host.hpp) for the oracle's scene
 void make_frame(FrameArgs &fa, const orc_scene *sc, const double cam[16])
 {
     memset(&fa, 0, sizeof(fa));
@@ -145,25 +146,7 @@ void make_frame(FrameArgs &fa, const orc_scene *sc, const double cam[16])
     fa.height = sc->px_height;
     fa.aspect = (double) sc->px_width / sc->px_height;
     fa.tan_half_fov = std::tan(0.5 * sc->vertical_fov);
-    memcpy(fa.cam, cam, sizeof(double) * 16);
-    for (int r = 0; r < 3; r++) fa.origin[r] = (cam[0 + r] * 0.0 + cam[4 + r] * 0.0) + (cam[8 + r] * 0.0 + cam[12 + r] * 1.0);
-    const double a = cam[0], b = cam[4], c = cam[8], d = cam[1], e = cam[5], f = cam[9], g = cam[2], h = cam[6], i = cam[10];
-    const double co00 = e * i - f * h, co01 = -(d * i - f * g), co02 = d * h - e * g;
-    const double co10 = -(b * i - c * h), co11 = a * i - c * g, co12 = -(a * h - b * g);
-    const double co20 = b * f - c * e, co21 = -(a * f - c * d), co22 = a * e - b * d;
-    const double det = a * co00 + b * co01 + c * co02;
-    const double amax = std::fabs(a) + std::fabs(b) + std::fabs(c) + std::fabs(d) + std::fabs(e) + std::fabs(f) + std::fabs(g) + std::fabs(h) + std::fabs(i);
-    fa.tile_planes_ok = (std::isfinite(det) && std::isfinite(amax) && std::fabs(det) > 1e-9 * amax * amax * amax) ? 1u : 0u;
-    if (fa.tile_planes_ok) {
-        const double inv = 1.0 / det;
-        const double nt[9] = {co00 * inv, co10 * inv, co20 * inv, co01 * inv, co11 * inv, co21 * inv, co02 * inv, co12 * inv, co22 * inv};
-        for (int k = 0; k < 9; k++) fa.tile_nt[k] = nt[k];
-    }
-    fa.cx_a = 2.0 * fa.aspect * fa.tan_half_fov / (double) fa.width;
-    fa.cx_b = (1.0 / (double) fa.width - 1.0) * fa.aspect * fa.tan_half_fov;
-    fa.cy_a = 2.0 * fa.tan_half_fov / (double) fa.height;
-    fa.cy_b = (1.0 / (double) fa.height - 1.0) * fa.tan_half_fov;
-    if (!(fa.cx_a > 0.0) || !(fa.cy_a > 0.0) || !std::isfinite(fa.cx_a) || !std::isfinite(fa.cy_a)) fa.tile_planes_ok = 0;
+    rtf::frame_camera(fa, cam, {});
 }
 
 // ---- formation code restated from the kernels ---------------------------------------------------------------------------------

@@ -6,6 +6,7 @@
 
 #include <stdint.h>
 
+#include "mi355rt.h"
 #include "rt_scene_dev.h"
 
 struct LabDesc { // the arrays of rt_scene_desc
@@ -16,6 +17,15 @@ struct LabDesc { // the arrays of rt_scene_desc
     const double *light_p;
     const float *light_color;
 };
+
+inline rt_scene_desc lab_desc(const LabDesc *sd) // ... as the rt_scene_desc the library's own host code takes
+{
+    rt_scene_desc d{};
+    d.n_objects = sd->n_objects; d.n_lights = sd->n_lights;
+    d.coefs = sd->coefs; d.reflection = sd->reflection; d.albedo = sd->albedo;
+    d.light_is_spherical = sd->light_is_spherical; d.light_p = sd->light_p; d.light_color = sd->light_color;
+    return d;
+}
 
 struct alignas(16) LabHeader {
     uint32_t has_mirror, n_cullable, lights_plain, pad;

@@ -31,12 +31,15 @@ def build():
         os.makedirs(os.path.dirname(out), exist_ok=True)
         # the flags of the library's own host code (cuda-ray-tracer_amd/Makefile, HOSTFLAGS): no FMA contraction
         subprocess.run(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc"),
-                        "-I" + TOOLS, os.path.join(TOOLS, "scene_pack_lab.cpp"), os.path.join(TOOLS, "scene_pack_parent.cpp"), "-o", out], check=True)
+                        "-I" + os.path.join(ROOT, "include"), "-I" + TOOLS, os.path.join(TOOLS, "scene_pack_lab.cpp"), os.path.join(TOOLS, "scene_image_lab.cpp"),
+                        os.path.join(TOOLS, "scene_pack_parent.cpp"), "-o", out], check=True)
         lib = C.CDLL(out)
         lib.lab_pack_bytes.restype = C.c_uint64
         lib.lab_pack_bytes.argtypes = [C.c_uint32, C.c_uint32]
         lib.lab_pack_header.argtypes = lib.lab_pack_parent.argtypes = [C.POINTER(LabDesc), C.c_void_p]
         lib.lab_pack_header.restype = lib.lab_pack_parent.restype = None
+        lib.lab_scene_image.restype = C.c_uint64
+        lib.lab_scene_image.argtypes = [C.POINTER(LabDesc), C.c_uint32, C.c_void_p, C.c_uint64]
         _LIB = lib
     return _LIB
 
@@ -54,6 +57,17 @@ def pack_both(coefs, reflection, albedo, light_is_spherical, light_p, light_colo
     lib.lab_pack_header(C.byref(d), new.ctypes.data)
     lib.lab_pack_parent(C.byref(d), old.ctypes.data)
     return new, old
+
+
+def scene_image(coefs, reflection, albedo, light_is_spherical, light_p, light_color, flags=0):
+    """The scene image a context with these rt_config flags uploads, as rt_debug_scene_blob returns it: [blob][DevLight x n][LightK x n]."""
+    lib = build()
+    keep = [np.ascontiguousarray(coefs, np.float64), np.ascontiguousarray(reflection, np.float32), np.ascontiguousarray(albedo, np.float32),
+            np.ascontiguousarray(light_is_spherical, np.uint8), np.ascontiguousarray(light_p, np.float64), np.ascontiguousarray(light_color, np.float32)]
+    d = LabDesc(keep[1].size, keep[3].size, *[a.ctypes.data for a in keep])
+    out = np.zeros(lib.lab_scene_image(C.byref(d), flags, None, 0), np.uint8)
+    assert lib.lab_scene_image(C.byref(d), flags, out.ctypes.data, out.size) == out.size
+    return out
 
 
 def pack_scene(osc):
