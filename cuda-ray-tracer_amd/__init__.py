@@ -43,7 +43,7 @@ ABI_SYMBOLS = [
     "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined",
-    "rt_render_gbuffer", "rt_pick",
+    "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
@@ -101,6 +101,11 @@ class Hit(C.Structure):
 
 
 HIT_DTYPE = np.dtype([("t", np.float64), ("point", np.float64, 3), ("normal", np.float32, 3), ("object", np.int32)])   # the same record, for numpy
+
+
+# rt_object_extent (include/mi355rt.h): per object, the pixels that show it, their box and their range of t; 40 bytes
+EXTENT_DTYPE = np.dtype([("pixels", np.uint64), ("x_min", np.uint32), ("y_min", np.uint32), ("x_max", np.uint32), ("y_max", np.uint32),
+                         ("t_min", np.float64), ("t_max", np.float64)])
 
 
 class Ray(C.Structure):
@@ -200,6 +205,8 @@ def lib():
         L.rt_get_ssaa_refined.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
+        L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
+        L.rt_object_extents_host.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp]
         L.rt_trace_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, fp]
         L.rt_occluded_rays.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, fp]
         L.rt_trace_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.POINTER(Hit), vp]
@@ -454,6 +461,35 @@ class Renderer:
         _check(lib().rt_pick(self._h, _dptr(cam), q.ctypes.data_as(C.POINTER(C.c_uint32)), q.shape[0], out.ctypes.data_as(C.POINTER(Hit)),
                              C.c_void_p(stream) if stream else None))
         return out
+
+    @staticmethod
+    def _rect(rect):
+        if rect is None:
+            return None, None
+        r = np.ascontiguousarray(rect, dtype=np.uint32).reshape(4)
+        return r, r.ctypes.data_as(C.POINTER(C.c_uint32))
+
+    def object_extents(self, cam=None, rect=None, stream=None):
+        """Per object: how many pixels of rect = (x0, y0, x1, y1) (inclusive, global coordinates, row 0 = bottom; None = the whole
+        frame) in this rank's rows show it, their bounding box and their range of t: a structured numpy array of n_objects EXTENT_DTYPE
+        records (rt_object_extents_host; blocks).  An object that is not seen has pixels 0, x_min = y_min = 0xFFFFFFFF, x_max = y_max
+        = 0, t_min +inf, t_max 0, so the records of several ranks merge by sum / min / max."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        keep, rp = self._rect(rect)
+        out = np.zeros(self._desc.n_objects, dtype=EXTENT_DTYPE)
+        buf = out if len(out) else np.zeros(1, dtype=EXTENT_DTYPE)   # (a scene without objects: the call still wants a pointer)
+        _check(lib().rt_object_extents_host(self._h, _dptr(cam), rp, buf.ctypes.data_as(C.c_void_p), C.c_void_p(stream) if stream else None))
+        return out
+
+    def object_extents_into(self, cam, rect, out_ptr, stream=None, timed=True):
+        """rt_object_extents into the caller's device memory (a raw pointer to n_objects records of 40 bytes, 8-byte aligned): device
+        milliseconds, or None unless timed (then the call only enqueues two kernels and can be captured into a graph)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        keep, rp = self._rect(rect)
+        ms = C.c_float(0.0)
+        _check(lib().rt_object_extents(self._h, _dptr(cam), rp, C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None,
+                                       C.byref(ms) if timed else None))
+        return ms.value if timed else None
 
     @staticmethod
     def rays(origins, dirs):

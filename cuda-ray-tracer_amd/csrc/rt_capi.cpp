@@ -28,7 +28,8 @@
 // the launchers a context calls per floating-point contraction mode (rt_launch.h, struct Kernels); rt_create picks one from RT_FLAG_FAST
 #define RT_KERNELS(V)                                                                                                                              \
     {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
-     RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V)}
+     RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
+     RT_CAT(rt_launch_object_extents, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 
 namespace {
@@ -208,6 +209,7 @@ struct rt_ctx {
     int lean_force = 0;           // MI355RT_LEAN=always / never (experiments)
     bool ord_on = true;           // launch-order feedback in use (off while most tiles have hits)
     Staging pick;  // rt_pick: [cap][2] coordinates in, [cap] rt_hit out; created on first use
+    Staging ext;   // rt_object_extents_host: [cap] rt_object_extent out (nothing goes in); created on first use
     Staging rq;    // the _host ray entry points: [cap] rt_ray in, [cap] rt_hit out (rt_shade_rays_host: its 4 x float32 pixels); created on first use
     // scene updates (rt_set_scene): the kernel's status block, and the staging memory of rt_set_scene_host, created on first use
     DevMem<SetSceneStatus> d_ss_status;
@@ -922,6 +924,60 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
     const hipError_t e = ctx->kern->pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pick kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out_host, ctx->pick.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+// ---- object extents (rt_gbuffer.hip) ----------------------------------------------------------------------
+// What both entry points check before a device is looked for, and the rectangle they trace (the whole frame for NULL)
+static int extents_args(const char *who, rt_ctx *ctx, const double cam[16], const uint32_t *rect, const void *out, bool dev_out, FrameArgs &fa, uint32_t r[4])
+{
+    if (!ctx || !cam || !out) return fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (dev_out && ((uintptr_t) out & 7u)) return fail(RT_ERR_INVALID, "%s: the output must be 8-byte aligned", who); // (the kernels' 64-bit atomics; a host array is only copied into)
+    if (rect && (rect[0] > rect[2] || rect[1] > rect[3])) // (decided without reading the context)
+        return fail(RT_ERR_INVALID, "%s: rect = (%u, %u) .. (%u, %u) is not a rectangle: x0 > x1 or y0 > y1", who, rect[0], rect[1], rect[2], rect[3]);
+    if (rect && (rect[2] >= ctx->width || rect[3] >= ctx->height))
+        return fail(RT_ERR_INVALID, "%s: rect = (%u, %u) .. (%u, %u) is not a rectangle inside the %u x %u image", who, rect[0], rect[1], rect[2], rect[3], ctx->width,
+                    ctx->height);
+    r[0] = rect ? rect[0] : 0u;
+    r[1] = rect ? rect[1] : 0u;
+    r[2] = rect ? rect[2] : ctx->width - 1u;
+    r[3] = rect ? rect[3] : ctx->height - 1u;
+    return gbuffer_args(who, ctx, cam, fa);
+}
+
+// workgroups of one extents launch: four per CU, each striding over the tiles (rt_gbuffer.hip, extents_kernel)
+static uint32_t extents_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
+
+extern "C" int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32_t rect[4], rt_object_extent *dev_out, void *stream_, float *ms)
+{
+    static_assert(sizeof(rt_object_extent) == 40 && alignof(rt_object_extent) == 8, "rt_object_extent layout");
+    hipStream_t stream = (hipStream_t) stream_;
+    FrameArgs fa;
+    uint32_t r[4];
+    if (int rc = extents_args("rt_object_extents", ctx, cam, rect, dev_out, true, fa, r)) return rc;
+    if (fa.n_obj == 0u) return RT_OK;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = ctx->kern->object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents: kernel launch failed: %s", hipGetErrorString(e));
+    return timer_end(ctx, stream, ms);
+}
+
+extern "C" int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const uint32_t rect[4], rt_object_extent *out_host, void *stream_)
+{
+    hipStream_t stream = (hipStream_t) stream_;
+    FrameArgs fa;
+    uint32_t r[4];
+    if (int rc = extents_args("rt_object_extents_host", ctx, cam, rect, out_host, false, fa, r)) return rc;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(RT_ERR_INVALID, "rt_object_extents_host: the stream is capturing, and this call allocates and waits; capture rt_object_extents (device memory) instead");
+    if (fa.n_obj == 0u) return RT_OK;
+    if (int rc = ctx->ext.reserve(fa.n_obj, 8, sizeof(rt_object_extent))) return rc;
+    const hipError_t e = ctx->kern->object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents_host: kernel launch failed: %s", hipGetErrorString(e));
+    RT_HIP(hipMemcpyAsync(out_host, ctx->ext.out, sizeof(rt_object_extent) * (size_t) fa.n_obj, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
 }

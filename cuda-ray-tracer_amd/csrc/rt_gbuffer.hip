@@ -1,5 +1,5 @@
 // rt_gbuffer.hip -- the primary-hit G-buffer (object, depth, normal planes) and pixel picking for gfx950 (include/mi355rt.h,
-// rt_render_gbuffer / rt_pick).
+// rt_render_gbuffer / rt_pick), and the same rays reduced per object (rt_object_extents; section 18; at the end).
 //
 // What is under a pixel: the nearest hit of its primary ray -- phase A of the wavefront kernel (rt_wavefront.hip) without anything
 // behind it.  Compiled twice like rt_adaptive.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).
@@ -310,4 +310,195 @@ extern "C" hipError_t RT_SYM(rt_launch_gbuffer_edges)(const FrameArgs *fa, const
     }
     if (n_halo == 0u) return hipSuccess;
     return RT_SYM(rtk)::launch(fa, scene, camx, camy, (n_halo + 255u) / 256u, nullptr, nullptr, nullptr, halo_xy, n_halo, halo_rec, stream);
+}
+
+// ---- object extents (include/mi355rt.h, "Object extents") ------------------------------------------------------
+// Per object: how many pixels of a rectangle show it, their bounding box and their range of t -- the planes' object and t entries
+// reduced on the device, without the planes.  The rays, the work geometry (16 x 16 tiles, 8 x 8 blocks, clamped lanes) and the
+// per-lane function are gbuffer_kernel's, so a record is the reduction of that kernel's planes bit for bit; the normal is not formed.
+namespace RT_SYM(rtk) {
+
+// One rt_object_extent as the kernels update it: t_min / t_max as the bits of the double (t is in [1e-7, 1e6), so the bits order as
+// unsigned integers and +inf / +0.0 are the identities of min / max).
+struct ExtRecord {
+    unsigned long long pixels;
+    uint32_t x_min, y_min, x_max, y_max;
+    unsigned long long t_min, t_max;
+};
+static_assert(sizeof(ExtRecord) == 40, "rt_object_extent layout");
+#define RT_EXT_INF_BITS 0x7FF0000000000000ull
+
+// what the launcher derives from the rectangle: its columns, this rank's LOCAL rows inside it, and the tiles that meet both
+struct ExtArgs {
+    uint32_t x0, x1, lr0, lr1; // inclusive
+    uint32_t tx0, ty0, ntx;    // first tile column / tile row, tile columns
+    uint32_t n_tiles;          // tiles to trace
+    uint32_t lds_acc;          // 1: one ExtRecord per object in LDS behind the tables, flushed once per workgroup; 0: every wave updates `out`
+};
+
+__global__ __launch_bounds__(256) void extents_init_kernel(ExtRecord *__restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull};
+}
+
+// merge one partial record into r: seven atomics whose result does not depend on their order
+template <int SCOPE>
+__device__ __forceinline__ void ext_merge(ExtRecord *r, unsigned long long n, uint32_t x_min, uint32_t y_min, uint32_t x_max, uint32_t y_max, unsigned long long t_min,
+                                          unsigned long long t_max)
+{
+    __hip_atomic_fetch_add(&r->pixels, n, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_fetch_min(&r->x_min, x_min, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_fetch_min(&r->y_min, y_min, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_fetch_max(&r->x_max, x_max, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_fetch_max(&r->y_max, y_max, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_fetch_min(&r->t_min, t_min, __ATOMIC_RELAXED, SCOPE);
+    __hip_atomic_fetch_max(&r->t_max, t_max, __ATOMIC_RELAXED, SCOPE);
+}
+
+// A few workgroups per CU, each striding over the tiles that meet the rectangle.  Three levels: the wave reduces the lanes of each distinct
+// object (count = popcount of their ballot, the box from the ballot's rows and columns, t by a butterfly), one lane merges that into the
+// workgroup's LDS record of the object, and the workgroup adds the records it touched to `out` once, at its end.  Lanes outside the
+// rectangle (and outside the image) trace their ray for the block's cone and count nothing.
+template <bool HAS_GQ, bool HAS_CUBIC>
+__global__ __launch_bounds__(256) void extents_kernel(const FrameArgs fa, const ExtArgs ea, const unsigned char *__restrict__ scene, const double *__restrict__ camx,
+                                                      const double *__restrict__ camy, ExtRecord *__restrict__ out)
+{
+    extern __shared__ __align__(16) unsigned char smem[];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t tab_bytes = fa.off_mat - fa.off_us;
+    const uint32_t acc_off = tab_bytes + (HAS_CUBIC ? (uint32_t) sizeof(double) * (RT_CUB_REC + 4) * RT_CUB_AT_MAX : 0u); // (a multiple of 16)
+    ExtRecord *acc = reinterpret_cast<ExtRecord *>(smem + acc_off);
+    {
+        const uint4 *src = reinterpret_cast<const uint4 *>(scene + fa.off_us);
+        uint4 *dst = reinterpret_cast<uint4 *>(smem);
+        for (uint32_t i = tid; i < (tab_bytes >> 4); i += 256u) dst[i] = src[i];
+        if (HAS_CUBIC && tid < (RT_CUB_REC + 4) * RT_CUB_AT_MAX) reinterpret_cast<double *>(smem + tab_bytes)[tid] = (&fa.cub_rec[0][0])[tid];
+        if (ea.lds_acc)
+            for (uint32_t i = tid; i < fa.n_obj; i += 256u) acc[i] = ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull};
+    }
+    __syncthreads();
+    GbTables S;
+    S.us = reinterpret_cast<const UsEntry *>(smem);
+    S.gq = reinterpret_cast<const GqEntry *>(smem + (fa.off_gq - fa.off_us));
+    S.lin = reinterpret_cast<const LinEntry *>(smem + (fa.off_lin - fa.off_us));
+    S.cub = reinterpret_cast<const uint32_t *>(smem + (fa.off_cub - fa.off_us));
+    S.prim = reinterpret_cast<const double *>(smem + tab_bytes);
+    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
+    constexpr bool NEED_CROSS = HAS_GQ || HAS_CUBIC;
+
+    for (uint32_t tile = blockIdx.x; tile < ea.n_tiles; tile += gridDim.x) { // workgroup-uniform
+        const uint32_t tile_x = ea.tx0 + tile % ea.ntx, tile_y = ea.ty0 + tile / ea.ntx;
+        const uint32_t bx = tile_x * 16u + (wave & 1u) * 8u, blr = tile_y * 16u + (wave >> 1) * 8u; // the block's first column and local row
+        const uint32_t x = bx + (lane & 7u), lr = blr + (lane >> 3);
+        const bool live = x < fa.width && lr < fa.local_rows;
+        const uint32_t col = x < fa.width ? x : fa.width - 1u;
+        const uint32_t row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
+        const D3 dir = primary_dir_tab(fa, camx[col], camy[row]);
+        Mono m;
+        mono_set_o<NEED_CROSS>(m, o);
+        mono_set_d<NEED_CROSS>(m, dir);
+        mono_set_od<NEED_CROSS>(m);
+        double best_t;
+        int best;
+        nearest_hit<HAS_GQ, HAS_CUBIC>(fa, S, reinterpret_cast<const DevObject *>(scene), m, live, true, lane, best_t, best);
+        const bool counted = live && best >= 0 && x >= ea.x0 && x <= ea.x1 && lr >= ea.lr0 && lr <= ea.lr1;
+        const unsigned long long tb = (unsigned long long) __double_as_longlong(best_t);
+        unsigned long long todo = __ballot(counted);
+        while (todo) { // wave-uniform: one turn per distinct object among the counted lanes
+            const int id = __builtin_amdgcn_readlane(best, __builtin_ctzll(todo));
+            const bool mine = counted && best == id;
+            const unsigned long long mask = __ballot(mine); // bit 8 r + c: row r, column c of the block
+            todo &= ~mask;
+            unsigned long long lo = mine ? tb : RT_EXT_INF_BITS, hi = mine ? tb : 0ull;
+#pragma unroll
+            for (int s = 32; s; s >>= 1) {
+                const unsigned long long l2 = __shfl_xor(lo, s), h2 = __shfl_xor(hi, s);
+                lo = l2 < lo ? l2 : lo;
+                hi = h2 > hi ? h2 : hi;
+            }
+            if (lane == 0u) {
+                uint32_t cols = (uint32_t) mask | (uint32_t) (mask >> 32);
+                cols |= cols >> 16;
+                cols = (cols | (cols >> 8)) & 0xFFu;
+                const uint32_t x_min = bx + (uint32_t) __builtin_ctz(cols), x_max = bx + 31u - (uint32_t) __builtin_clz(cols);
+                const uint32_t y_min = global_row(fa, blr + ((uint32_t) __builtin_ctzll(mask) >> 3)); // (global_row rises with the local row)
+                const uint32_t y_max = global_row(fa, blr + ((63u - (uint32_t) __builtin_clzll(mask)) >> 3));
+                const unsigned long long n = (unsigned long long) __builtin_popcountll(mask);
+                if (ea.lds_acc) ext_merge<__HIP_MEMORY_SCOPE_WORKGROUP>(acc + id, n, x_min, y_min, x_max, y_max, lo, hi);
+                else ext_merge<__HIP_MEMORY_SCOPE_AGENT>(out + id, n, x_min, y_min, x_max, y_max, lo, hi);
+            }
+        }
+    }
+    if (ea.lds_acc) {
+        __syncthreads();
+        for (uint32_t i = tid; i < fa.n_obj; i += 256u) {
+            const ExtRecord a = acc[i];
+            if (a.pixels) ext_merge<__HIP_MEMORY_SCOPE_AGENT>(out + i, a.pixels, a.x_min, a.y_min, a.x_max, a.y_max, a.t_min, a.t_max);
+        }
+    }
+}
+
+} // namespace RT_SYM(rtk)
+
+// Do the LDS accumulators (40 bytes per object) fit behind `table_bytes` of class tables in the 160 KiB a workgroup may take?  Otherwise
+// the waves update the output records themselves.
+extern "C" int RT_SYM(rt_extents_lds_accumulators)(size_t table_bytes, uint32_t n_obj)
+{
+    return table_bytes + sizeof(RT_SYM(rtk)::ExtRecord) * (size_t) n_obj <= 160u * 1024u;
+}
+
+// LDS bytes of one extents_kernel workgroup for this scene
+extern "C" size_t RT_SYM(rt_extents_lds_bytes)(const FrameArgs *fa)
+{
+    const size_t tables = RT_SYM(rt_gbuffer_lds_bytes)(fa);
+    return tables + (RT_SYM(rt_extents_lds_accumulators)(tables, fa->n_obj) ? sizeof(RT_SYM(rtk)::ExtRecord) * (size_t) fa->n_obj : 0u);
+}
+
+// rect = x0, y0, x1, y1 (inclusive, inside the image, GLOBAL rows); out = n_obj records in device memory.  Two nodes on `stream`: the
+// identities, then -- when this rank owns a row of the rectangle -- the kernel, at most max_grid workgroups.
+extern "C" hipError_t RT_SYM(rt_launch_object_extents)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out,
+                                                        uint32_t max_grid, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (fa->n_obj == 0u) return hipSuccess;
+    ExtRecord *rec = reinterpret_cast<ExtRecord *>(out);
+    hipLaunchKernelGGL(extents_init_kernel, dim3((fa->n_obj + 255u) / 256u), dim3(256), 0, stream, rec, fa->n_obj);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    // this rank's local rows inside [y0, y1]: the global row rises with the local one
+    const auto grow = [&](uint32_t lr) { const uint32_t b = lr / fa->band_rows; return (uint64_t) (b * (uint64_t) fa->world + fa->rank) * fa->band_rows + (lr - b * fa->band_rows); };
+    const auto first_at_least = [&](uint64_t y) { // the first local row whose global row is >= y (local_rows if none)
+        uint32_t lo = 0, hi = fa->local_rows;
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (grow(mid) >= y) hi = mid;
+            else lo = mid + 1u;
+        }
+        return lo;
+    };
+    const uint32_t lr_lo = first_at_least(rect[1]), lr_end = first_at_least((uint64_t) rect[3] + 1u);
+    if (lr_lo >= lr_end) return hipSuccess; // no row of the rectangle is this rank's: the identities stand
+    ExtArgs ea;
+    ea.x0 = rect[0];
+    ea.x1 = rect[2];
+    ea.lr0 = lr_lo;
+    ea.lr1 = lr_end - 1u;
+    ea.tx0 = ea.x0 / 16u;
+    ea.ty0 = ea.lr0 / 16u;
+    ea.ntx = ea.x1 / 16u - ea.tx0 + 1u;
+    ea.n_tiles = ea.ntx * (ea.lr1 / 16u - ea.ty0 + 1u);
+    const size_t tables = RT_SYM(rt_gbuffer_lds_bytes)(fa);
+    ea.lds_acc = RT_SYM(rt_extents_lds_accumulators)(tables, fa->n_obj) ? 1u : 0u;
+    const size_t lds = RT_SYM(rt_extents_lds_bytes)(fa);
+    const dim3 g(ea.n_tiles < max_grid ? ea.n_tiles : (max_grid ? max_grid : 1u)), block(256);
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    if (fa->n_cub) {
+        if (fa->n_gq) hipLaunchKernelGGL((extents_kernel<true, true>), g, block, lds, stream, *fa, ea, s, camx, camy, rec);
+        else hipLaunchKernelGGL((extents_kernel<false, true>), g, block, lds, stream, *fa, ea, s, camx, camy, rec);
+    } else {
+        if (fa->n_gq) hipLaunchKernelGGL((extents_kernel<true, false>), g, block, lds, stream, *fa, ea, s, camx, camy, rec);
+        else hipLaunchKernelGGL((extents_kernel<false, false>), g, block, lds, stream, *fa, ea, s, camx, camy, rec);
+    }
+    return hipGetLastError();
 }

@@ -49,6 +49,11 @@ RT_PER_VARIANT(hipError_t, rt_launch_pick, const FrameArgs *fa, const void *scen
                hipStream_t stream)
 RT_PER_VARIANT(hipError_t, rt_launch_gbuffer_edges, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object,
                float *out_normal, const uint32_t *halo_xy, uint32_t n_halo, void *halo_rec, hipStream_t stream)
+// ... and the object extents: the same rays reduced per object instead of stored (rect = x0, y0, x1, y1 inclusive, validated by the caller)
+RT_PER_VARIANT(int, rt_extents_lds_accumulators, size_t table_bytes, uint32_t n_obj)
+RT_PER_VARIANT(size_t, rt_extents_lds_bytes, const FrameArgs *fa)
+RT_PER_VARIANT(hipError_t, rt_launch_object_extents, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out,
+               uint32_t max_grid, hipStream_t stream)
 // rt_rays.hip, rt_shade_rays.hip: caller-supplied rays
 RT_PER_VARIANT(size_t, rt_rays_lds_bytes, const FrameArgs *fa)
 RT_PER_VARIANT(hipError_t, rt_launch_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid, hipStream_t stream)
@@ -71,6 +76,7 @@ struct Kernels {
     decltype(&rt_launch_trace_rays_strict) trace_rays;
     decltype(&rt_launch_occluded_rays_strict) occluded_rays;
     decltype(&rt_launch_shade_rays_strict) shade_rays;
+    decltype(&rt_launch_object_extents_strict) object_extents;
 };
 
 #endif

@@ -185,6 +185,24 @@ extern "C" int mi355rt_update_pick(unsigned int x, unsigned int y, rt_hit *out)
     return rt_pick(g_ctx, g_last_cam, xy, 1, out, nullptr);
 }
 
+// Which objects the frame of the last update() shows, where and how far away: rt_object_extents_host with that call's camera, for the
+// pixels of rect = x0, y0, x1, y1 (inclusive; NULL = the whole frame); n = the number of objects of the loaded scene, one record each.
+// Single-context back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices, before the first update(), for another n
+// and for supersampling contexts.
+extern "C" int mi355rt_update_extents(const unsigned rect[4], rt_object_extent *out, unsigned n)
+{
+    if (!g_ctx || !g_have_cam || !out) {
+        rt_set_last_error(g_multi ? "mi355rt_update_extents: not available with several devices (MI355RT_DEVICES)"
+                                  : (!out ? "mi355rt_update_extents: null argument" : "mi355rt_update_extents: no update() call yet"));
+        return RT_ERR_INVALID;
+    }
+    if (n != g_n_objects) {
+        rt_set_last_error("mi355rt_update_extents: n must be the number of objects init_update() loaded");
+        return RT_ERR_INVALID;
+    }
+    return rt_object_extents_host(g_ctx, g_last_cam, rect, out, nullptr);
+}
+
 // The closest hit of n caller-supplied rays against the scene init_update() loaded (rt_trace_rays_host; include/mi355rt.h, "Ray
 // queries").  Valid after init_update(): unlike picking it needs no earlier update() call, a ray query uses no camera.  Single-context
 // back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices and before init_update().

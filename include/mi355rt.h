@@ -371,6 +371,50 @@ int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev_object, do
 int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * Object extents: which objects a camera sees, where on the screen, how far away (csrc/rt_gbuffer.hip)
+ *
+ * Definition, in the G-buffer's terms: obj(x, y) and t(x, y) are the `object` and `t` entries of the G-buffer definition for this
+ * context and `cam`; P is the set of pixels that lie in `rect` (x0, y0, x1, y1 inclusive, GLOBAL coordinates, row 0 = bottom; NULL = the
+ * whole W x H frame) and in a row this rank owns.  Record i describes { (x, y) in P : obj(x, y) == i }: `pixels` is its size, the four
+ * bounds are the minima and maxima of x and y over it, t_min / t_max the minimum and maximum of t(x, y) over it.  An object that owns
+ * no pixel of P gets the identities of those reductions -- pixels = 0, x_min = y_min = 0xFFFFFFFF, x_max = y_max = 0, t_min = +inf,
+ * t_max = +0.0 --, so the records of several ranks merge by sum / min / max without a special case.  Misses get no record: the caller
+ * has |P| minus the sum of `pixels`.
+ *
+ * Accuracy is the G-buffer's: in every context kind rt_render_gbuffer accepts, the records are bit for bit the reduction of the planes
+ * rt_render_gbuffer writes for the same context and camera (degree 3 and RT_FLAG_FAST included: the same per-ray function on the same
+ * 16 x 16 tiles and 8 x 8 blocks); hence they equal the reference's nearest-hit loop for surfaces of degree <= 2 in strict contexts.
+ * The result does not depend on the order of execution: every step is an integer sum, minimum or maximum (t is in [1e-7, 1e6), so the
+ * bits of the double order as an unsigned integer).
+ *
+ * Like the G-buffer pass it reads the scene and the camera-plane tables and nothing else -- no tile words, census, counters (with
+ * RT_FLAG_COUNT it books nothing) or frame tag --, needs no ordering against rt_render, and does need the caller's ordering against
+ * rt_set_scene on another stream ("Scene updates").  Only the tiles that meet `rect` are traced.
+ *
+ * Out of scope: the multi-GPU layer (rt_*_multi) has no such entry point -- a rank-level caller merges the ranks' records itself;
+ * supersampling contexts are refused as by rt_render_gbuffer; and only the primary hit counts: an object seen through a mirror is
+ * not seen.
+ * ------------------------------------------------------------------------------------------------- */
+typedef struct rt_object_extent {
+    uint64_t pixels;                      /* pixels whose primary hit is this object */
+    uint32_t x_min, y_min, x_max, y_max;  /* inclusive, GLOBAL pixel coordinates, row 0 = bottom */
+    double   t_min, t_max;                /* smallest / largest best_t over those pixels */
+} rt_object_extent;                       /* 40 bytes, 8-byte aligned */
+
+/* Enqueue on `stream`: n_objects records into device memory (8-byte aligned).  ms as in rt_render_gbuffer: NULL = enqueue only, and the
+ * call can be captured into a graph, to which it adds two kernel nodes (one that writes the identities, then the reduction; a rank
+ * that owns no row of `rect` adds the first only and so still writes the identities); else synchronise and report the device time.  A
+ * scene without objects returns RT_OK and enqueues nothing.  RT_ERR_INVALID for a NULL context / camera / output, an output that is
+ * not 8-byte aligned, a `rect` with x0 > x1, y0 > y1, x1 >= W or y1 >= H, and supersampling contexts; RT_ERR_SCENE for a scene whose
+ * class tables exceed the LDS of a workgroup, as rt_render_gbuffer. */
+int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32_t rect[4] /* x0,y0,x1,y1 inclusive, or NULL */,
+                      rt_object_extent *dev_out /* [n_objects] */, void *stream, float *ms);
+/* The same into host memory (any alignment: the records are copied there); blocks.  The staging buffer is the context's own (allocated on the first call, freed by rt_destroy); a
+ * capturing stream is refused (RT_ERR_INVALID): the call allocates and waits. */
+int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const uint32_t rect[4],
+                           rt_object_extent *out_host, void *stream);   /* blocks */
+
+/* ---------------------------------------------------------------------------------------------------
  * Ray queries: closest hit, occlusion and colour for rays the caller supplies (csrc/rt_rays.hip, csrc/rt_shade_rays.hip; DESIGN.md
  * sections 15 and 16)
  *
@@ -484,7 +528,7 @@ int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_
  * only (one kernel, nothing else: `(rt_set_scene, rt_render) x K` can be captured into one graph, and a replay reads the device arrays
  * again, so rewriting them between replays animates the scene); another stream first waits for the event recorded behind the previous
  * call; the event is not recorded while capturing, and after a captured call a call on another stream is refused (RT_ERR_INVALID).
- * The arrays must stay unchanged until the kernel has run.  The passes that READ the scene -- rt_render_gbuffer, rt_pick, rt_trace_rays,
+ * The arrays must stay unchanged until the kernel has run.  The passes that READ the scene -- rt_render_gbuffer, rt_pick, rt_object_extents, rt_trace_rays,
  * rt_occluded_rays, rt_shade_rays and their _host forms -- need no ordering against rt_render, but they DO need ordering against
  * rt_set_scene when issued on another stream, and that ordering is the caller's to establish (on one stream it is automatic).
  * Frame-to-frame state (launch order, census, tile words) survives an update: it affects speed only, never the image, exactly as under
