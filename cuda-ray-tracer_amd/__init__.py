@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
+    "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
     "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
 ]
@@ -114,6 +115,16 @@ class Ray(C.Structure):
 
 
 RAY_DTYPE = np.dtype([("o", np.float64, 3), ("d", np.float64, 3)])   # the same record, for numpy
+
+
+class PathEnd(C.Structure):
+    """rt_path_end (include/mi355rt.h): how the path of one ray along its mirror bounces ended; 16 bytes."""
+    _fields_ = [("segments", C.c_uint32), ("end", C.c_uint32), ("ratio", C.c_float), ("object", C.c_int32)]
+
+
+PATH_END_DTYPE = np.dtype([("segments", np.uint32), ("end", np.uint32), ("ratio", np.float32), ("object", np.int32)])   # the same record, for numpy
+RT_PATH_MISS, RT_PATH_SURFACE, RT_PATH_ESCAPED, RT_PATH_CAP = 0, 1, 2, 3
+RT_PATH_MAX_SEGMENTS = 64
 
 
 class SceneUpdate(C.Structure):
@@ -212,6 +223,10 @@ def lib():
         L.rt_trace_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_shade_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, fp]
         L.rt_shade_rays_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, fp, vp]
+        L.rt_trace_paths.argtypes = [vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, fp]
+        L.rt_trace_paths_host.argtypes = [vp, C.POINTER(Ray), C.c_uint32, C.c_uint32, C.POINTER(Hit), C.POINTER(Hit), C.POINTER(PathEnd), vp]
+        L.rt_primary_rays.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
+        L.rt_pick_paths.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(Hit), C.POINTER(PathEnd), vp]
         L.rt_set_scene.argtypes = [vp, C.POINTER(SceneUpdate), vp]
         L.rt_set_scene_host.argtypes = [vp, C.POINTER(SceneUpdate), vp]
         L.rt_set_scene_status.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -555,6 +570,62 @@ class Renderer:
         _check(lib().rt_shade_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, int(n), C.c_void_p(rgba_ptr) if rgba_ptr else None,
                                    C.c_void_p(hit_ptr) if hit_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
+
+    def _max_segments(self, max_segments):
+        return min(self._desc.max_reflections + 1, RT_PATH_MAX_SEGMENTS) if max_segments is None else int(max_segments)
+
+    def paths(self, origins, dirs, max_segments=None, stream=None):
+        """The hits along every ray's mirror bounces (rt_trace_paths_host; blocks): (segments, last, ends) -- HIT_DTYPE records [M, n]
+        of the segments (a segment the path did not reach is a miss record), HIT_DTYPE records [n] of the last hits, PATH_END_DTYPE
+        records [n].  M = max_segments, by default max_reflections + 1 (every segment a path can have), at most 64; it limits what is
+        stored, not how far a path is followed.  Works in every context kind."""
+        rays = self.rays(origins, dirs)
+        m, n = self._max_segments(max_segments), len(rays)
+        seg, last, ends = np.zeros((m, n), dtype=HIT_DTYPE), np.zeros(n, dtype=HIT_DTYPE), np.zeros(n, dtype=PATH_END_DTYPE)
+        _check(lib().rt_trace_paths_host(self._h, rays.ctypes.data_as(C.POINTER(Ray)), n, m, seg.ctypes.data_as(C.POINTER(Hit)) if m else None,
+                                         last.ctypes.data_as(C.POINTER(Hit)), ends.ctypes.data_as(C.POINTER(PathEnd)), C.c_void_p(stream) if stream else None))
+        return seg, last, ends
+
+    def paths_into(self, ray_ptr, n, max_segments, segments_ptr, last_ptr, ends_ptr, stream=None, timed=True):
+        """rt_trace_paths on the caller's device memory (raw pointers to n rt_ray / max_segments x n rt_hit, None iff max_segments is 0 /
+        optionally n rt_hit / n rt_path_end, 16-byte aligned): device milliseconds, or None unless timed (then the call only enqueues
+        one kernel)."""
+        ms = C.c_float(0.0)
+        _check(lib().rt_trace_paths(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, int(n), int(max_segments), C.c_void_p(segments_ptr) if segments_ptr else None,
+                                    C.c_void_p(last_ptr) if last_ptr else None, C.c_void_p(ends_ptr) if ends_ptr else None, C.c_void_p(stream) if stream else None,
+                                    C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def primary_rays(self, cam=None, rect=None, stream=None, timed=True):
+        """The context's own primary rays of rect = (x0, y0, x1, y1) (inclusive, global coordinates, row 0 = bottom; None = the whole
+        frame) as explicit rays (rt_primary_rays): a torch float64 device tensor [rows, columns, 6] of (origin, direction) -- bit for
+        bit the rays the frame kernels trace -- and the device milliseconds (None unless timed)."""
+        import torch
+        x0, y0, x1, y1 = (0, 0, self.width - 1, self.height - 1) if rect is None else (int(v) for v in rect)
+        out = torch.empty((max(y1 - y0 + 1, 0), max(x1 - x0 + 1, 0), 6), dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
+        ms = self.primary_rays_into(cam, rect, out.data_ptr() if out.numel() else None, stream=stream, timed=timed)
+        return out, ms
+
+    def primary_rays_into(self, cam, rect, ray_ptr, stream=None, timed=True):
+        """rt_primary_rays into the caller's device memory (a raw pointer to one rt_ray per pixel of rect, 16-byte aligned)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        keep, rp = self._rect(rect)
+        ms = C.c_float(0.0)
+        _check(lib().rt_primary_rays(self._h, _dptr(cam), rp, C.c_void_p(ray_ptr) if ray_ptr else None, C.c_void_p(stream) if stream else None,
+                                     C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def pick_paths(self, xy, cam=None, max_segments=None, stream=None):
+        """Pick through mirrors (rt_pick_paths; blocks): the paths of the primary rays of the pixels xy = [(x, y), ...] as (segments
+        [M, n] HIT_DTYPE, ends [n] PATH_END_DTYPE).  Plane 0 is pick()'s record; ends["object"] is what the pixel finally shows where
+        ends["end"] == RT_PATH_SURFACE."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        q = np.ascontiguousarray(xy, dtype=np.uint32).reshape(-1, 2)
+        m, n = self._max_segments(max_segments), q.shape[0]
+        seg, ends = np.zeros((m, n), dtype=HIT_DTYPE), np.zeros(n, dtype=PATH_END_DTYPE)
+        _check(lib().rt_pick_paths(self._h, _dptr(cam), q.ctypes.data_as(C.POINTER(C.c_uint32)), n, m, seg.ctypes.data_as(C.POINTER(Hit)) if m else None,
+                                   ends.ctypes.data_as(C.POINTER(PathEnd)), C.c_void_p(stream) if stream else None))
+        return seg, ends
 
     def set_scene(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None):
         """Replace the scene's raw descriptor arrays (numpy, rt_scene_desc layout; None = keep what the context holds) without a new

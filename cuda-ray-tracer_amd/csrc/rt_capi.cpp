@@ -29,7 +29,7 @@
 #define RT_KERNELS(V)                                                                                                                              \
     {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
      RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
-     RT_CAT(rt_launch_object_extents, V)}
+     RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 
 namespace {
@@ -97,6 +97,21 @@ struct Staging {
         RT_HIP(in.alloc(in_each * (size_t) want));
         RT_HIP(out.alloc(out_each * (size_t) want));
         cap = want;
+        return RT_OK;
+    }
+};
+
+// one device buffer that only grows: the staging memory of the path entry points that take host arrays, laid out per call
+struct Scratch {
+    DevMem<unsigned char> p;
+    size_t cap = 0;
+    int reserve(size_t bytes)
+    {
+        if (bytes <= cap) return RT_OK; // (every earlier call has synchronised: nothing uses the old buffer)
+        p.reset();
+        cap = 0;
+        RT_HIP(p.alloc(bytes));
+        cap = bytes;
         return RT_OK;
     }
 };
@@ -211,6 +226,7 @@ struct rt_ctx {
     Staging pick;  // rt_pick: [cap][2] coordinates in, [cap] rt_hit out; created on first use
     Staging ext;   // rt_object_extents_host: [cap] rt_object_extent out (nothing goes in); created on first use
     Staging rq;    // the _host ray entry points: [cap] rt_ray in, [cap] rt_hit out (rt_shade_rays_host: its 4 x float32 pixels); created on first use
+    Scratch pth;   // rt_trace_paths_host / rt_pick_paths: [rays][max_segments planes][last][ends][coordinates]; created on first use
     // scene updates (rt_set_scene): the kernel's status block, and the staging memory of rt_set_scene_host, created on first use
     DevMem<SetSceneStatus> d_ss_status;
     DevMem<unsigned char> d_ss_stage;
@@ -908,14 +924,21 @@ extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev
     return timer_end(ctx, stream, ms);
 }
 
+// n pixels by GLOBAL coordinates: all of them are checked before anything is enqueued
+static int pixels_inside(const char *who, const rt_ctx *ctx, const uint32_t *xy, uint32_t n)
+{
+    for (uint32_t i = 0; i < n; i++)
+        if (xy[2 * (size_t) i] >= ctx->width || xy[2 * (size_t) i + 1] >= ctx->height)
+            return fail(RT_ERR_INVALID, "%s: pixel %u = (%u, %u) lies outside the %u x %u image", who, i, xy[2 * (size_t) i], xy[2 * (size_t) i + 1], ctx->width, ctx->height);
+    return RT_OK;
+}
+
 extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, rt_hit *out_host, void *stream_)
 {
     static_assert(sizeof(rt_hit) == 48, "rt_hit layout");
     if (!ctx || !cam || !xy || !out_host) return fail(RT_ERR_INVALID, "rt_pick: null argument");
     if (n == 0) return fail(RT_ERR_INVALID, "rt_pick: n is 0");
-    for (uint32_t i = 0; i < n; i++)
-        if (xy[2 * (size_t) i] >= ctx->width || xy[2 * (size_t) i + 1] >= ctx->height)
-            return fail(RT_ERR_INVALID, "rt_pick: pixel %u = (%u, %u) lies outside the %u x %u image", i, xy[2 * (size_t) i], xy[2 * (size_t) i + 1], ctx->width, ctx->height);
+    if (int rc = pixels_inside("rt_pick", ctx, xy, n)) return rc;
     hipStream_t stream = (hipStream_t) stream_;
     FrameArgs fa;
     if (int rc = gbuffer_args("rt_pick", ctx, cam, fa)) return rc;
@@ -929,11 +952,9 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
 }
 
 // ---- object extents (rt_gbuffer.hip) ----------------------------------------------------------------------
-// What both entry points check before a device is looked for, and the rectangle they trace (the whole frame for NULL)
-static int extents_args(const char *who, rt_ctx *ctx, const double cam[16], const uint32_t *rect, const void *out, bool dev_out, FrameArgs &fa, uint32_t r[4])
+// A caller's rectangle of GLOBAL pixels (x0, y0, x1, y1 inclusive; NULL = the whole frame) as r[4], or why it is none
+static int rect_args(const char *who, const rt_ctx *ctx, const uint32_t *rect, uint32_t r[4])
 {
-    if (!ctx || !cam || !out) return fail(RT_ERR_INVALID, "%s: null argument", who);
-    if (dev_out && ((uintptr_t) out & 7u)) return fail(RT_ERR_INVALID, "%s: the output must be 8-byte aligned", who); // (the kernels' 64-bit atomics; a host array is only copied into)
     if (rect && (rect[0] > rect[2] || rect[1] > rect[3])) // (decided without reading the context)
         return fail(RT_ERR_INVALID, "%s: rect = (%u, %u) .. (%u, %u) is not a rectangle: x0 > x1 or y0 > y1", who, rect[0], rect[1], rect[2], rect[3]);
     if (rect && (rect[2] >= ctx->width || rect[3] >= ctx->height))
@@ -943,6 +964,15 @@ static int extents_args(const char *who, rt_ctx *ctx, const double cam[16], cons
     r[1] = rect ? rect[1] : 0u;
     r[2] = rect ? rect[2] : ctx->width - 1u;
     r[3] = rect ? rect[3] : ctx->height - 1u;
+    return RT_OK;
+}
+
+// What both entry points check before a device is looked for, and the rectangle they trace (the whole frame for NULL)
+static int extents_args(const char *who, rt_ctx *ctx, const double cam[16], const uint32_t *rect, const void *out, bool dev_out, FrameArgs &fa, uint32_t r[4])
+{
+    if (!ctx || !cam || !out) return fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (dev_out && ((uintptr_t) out & 7u)) return fail(RT_ERR_INVALID, "%s: the output must be 8-byte aligned", who); // (the kernels' 64-bit atomics; a host array is only copied into)
+    if (int rc = rect_args(who, ctx, rect, r)) return rc;
     return gbuffer_args(who, ctx, cam, fa);
 }
 
@@ -1089,6 +1119,119 @@ extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, f
     RT_HIP(hipMemcpyAsync(rgba_out, d_rgba, 4 * sizeof(float) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
+}
+
+// ---- paths and the context's own primary rays (rt_paths.hip) ------------------------------------------------------
+// Like the ray queries the path kernel reads the scene blob and nothing of the frame.
+static hipError_t paths_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, uint32_t max_segments, void *dev_segments, void *dev_last, void *dev_ends, hipStream_t stream)
+{
+    return ctx->kern->trace_paths(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), stream);
+}
+
+extern "C" int rt_trace_paths(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, uint32_t max_segments, rt_hit *dev_segments, rt_hit *dev_last, rt_path_end *dev_ends,
+                              void *stream_, float *ms)
+{
+    static_assert(sizeof(rt_path_end) == 16, "rt_path_end layout");
+    if (!ctx || !dev_rays || !dev_ends) return fail(RT_ERR_INVALID, "rt_trace_paths: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_trace_paths: n is 0");
+    if (max_segments > RT_PATH_MAX_SEGMENTS) return fail(RT_ERR_INVALID, "rt_trace_paths: max_segments %u exceeds %u", max_segments, RT_PATH_MAX_SEGMENTS);
+    if (!dev_segments != (max_segments == 0u)) return fail(RT_ERR_INVALID, "rt_trace_paths: segments must be null if and only if max_segments is 0");
+    if (((uintptr_t) dev_rays | (uintptr_t) dev_segments | (uintptr_t) dev_last | (uintptr_t) dev_ends) & 15u)
+        return fail(RT_ERR_INVALID, "rt_trace_paths: rays, segments, last and ends must be 16-byte aligned");
+    const struct { const void *p; size_t bytes; } range[4] = {{dev_rays, sizeof(rt_ray) * (size_t) n}, {dev_segments, sizeof(rt_hit) * (size_t) n * max_segments},
+                                                              {dev_last, sizeof(rt_hit) * (size_t) n}, {dev_ends, sizeof(rt_path_end) * (size_t) n}};
+    for (int a = 0; a < 4; a++)
+        for (int b = a + 1; b < 4; b++)
+            if (range[a].p && range[b].p && ranges_overlap(range[a].p, range[a].bytes, range[b].p, range[b].bytes))
+                return fail(RT_ERR_INVALID, "rt_trace_paths: two of the rays, segments, last and ends ranges overlap");
+    hipStream_t stream = (hipStream_t) stream_;
+    if (int rc = rays_ready("rt_trace_paths", ctx)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = paths_launch(ctx, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_trace_paths: kernel launch failed: %s", hipGetErrorString(e));
+    return timer_end(ctx, stream, ms);
+}
+
+// the layout of ctx->pth for n rays and max_segments planes: every part a multiple of 16 bytes but the coordinates, which come last
+struct PathStage {
+    size_t rays, segments, last, ends, xy, bytes;
+    PathStage(uint32_t n, uint32_t max_segments)
+    {
+        rays = 0;
+        segments = rays + sizeof(rt_ray) * (size_t) n;
+        last = segments + sizeof(rt_hit) * (size_t) n * max_segments;
+        ends = last + sizeof(rt_hit) * (size_t) n;
+        xy = ends + sizeof(rt_path_end) * (size_t) n;
+        bytes = xy + sizeof(uint32_t) * 2 * (size_t) n;
+    }
+};
+
+// the staged path kernel behind both blocking forms, and the copies back (last_out may be NULL)
+static int paths_staged(const char *who, rt_ctx *ctx, const PathStage &st, uint32_t n, uint32_t max_segments, rt_hit *segments_out, rt_hit *last_out, rt_path_end *ends_out,
+                        hipStream_t stream)
+{
+    unsigned char *d = ctx->pth.p;
+    const hipError_t e = paths_launch(ctx, d + st.rays, n, max_segments, max_segments ? d + st.segments : nullptr, last_out ? d + st.last : nullptr, d + st.ends, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    if (max_segments) RT_HIP(hipMemcpyAsync(segments_out, d + st.segments, st.last - st.segments, hipMemcpyDeviceToHost, stream));
+    if (last_out) RT_HIP(hipMemcpyAsync(last_out, d + st.last, st.ends - st.last, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipMemcpyAsync(ends_out, d + st.ends, st.xy - st.ends, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+extern "C" int rt_trace_paths_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, uint32_t max_segments, rt_hit *segments_out, rt_hit *last_out, rt_path_end *ends_out,
+                                   void *stream_)
+{
+    if (!ctx || !rays || !ends_out) return fail(RT_ERR_INVALID, "rt_trace_paths_host: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_trace_paths_host: n is 0");
+    if (max_segments > RT_PATH_MAX_SEGMENTS) return fail(RT_ERR_INVALID, "rt_trace_paths_host: max_segments %u exceeds %u", max_segments, RT_PATH_MAX_SEGMENTS);
+    if (!segments_out != (max_segments == 0u)) return fail(RT_ERR_INVALID, "rt_trace_paths_host: segments must be null if and only if max_segments is 0");
+    hipStream_t stream = (hipStream_t) stream_;
+    if (int rc = rays_ready("rt_trace_paths_host", ctx)) return rc;
+    const PathStage st(n, max_segments);
+    if (int rc = ctx->pth.reserve(st.bytes)) return rc;
+    RT_HIP(hipMemcpyAsync(ctx->pth.p + st.rays, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
+    return paths_staged("rt_trace_paths_host", ctx, st, n, max_segments, segments_out, last_out, ends_out, stream);
+}
+
+// workgroups of one primary-ray launch: the kernel only streams, a few workgroups per CU carry it
+static uint32_t primary_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 8u; }
+
+extern "C" int rt_primary_rays(rt_ctx *ctx, const double cam[16], const uint32_t rect[4], rt_ray *dev_rays, void *stream_, float *ms)
+{
+    if (!ctx || !cam || !dev_rays) return fail(RT_ERR_INVALID, "rt_primary_rays: null argument");
+    if ((uintptr_t) dev_rays & 15u) return fail(RT_ERR_INVALID, "rt_primary_rays: the rays must be 16-byte aligned");
+    hipStream_t stream = (hipStream_t) stream_;
+    FrameArgs fa;
+    uint32_t r[4];
+    if (int rc = rect_args("rt_primary_rays", ctx, rect, r)) return rc;
+    if (int rc = gbuffer_args("rt_primary_rays", ctx, cam, fa)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = ctx->kern->primary_rays(&fa, ctx->d_camx, ctx->d_camy, r, nullptr, 0u, dev_rays, primary_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_primary_rays: kernel launch failed: %s", hipGetErrorString(e));
+    return timer_end(ctx, stream, ms);
+}
+
+extern "C" int rt_pick_paths(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, uint32_t max_segments, rt_hit *segments_host, rt_path_end *ends_host,
+                             void *stream_)
+{
+    if (!ctx || !cam || !xy || !ends_host) return fail(RT_ERR_INVALID, "rt_pick_paths: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_pick_paths: n is 0");
+    if (max_segments > RT_PATH_MAX_SEGMENTS) return fail(RT_ERR_INVALID, "rt_pick_paths: max_segments %u exceeds %u", max_segments, RT_PATH_MAX_SEGMENTS);
+    if (!segments_host != (max_segments == 0u)) return fail(RT_ERR_INVALID, "rt_pick_paths: segments must be null if and only if max_segments is 0");
+    if (int rc = pixels_inside("rt_pick_paths", ctx, xy, n)) return rc;
+    hipStream_t stream = (hipStream_t) stream_;
+    FrameArgs fa;
+    if (int rc = gbuffer_args("rt_pick_paths", ctx, cam, fa)) return rc;
+    if (int rc = rays_ready("rt_pick_paths", ctx)) return rc;
+    const PathStage st(n, max_segments);
+    if (int rc = ctx->pth.reserve(st.bytes)) return rc;
+    unsigned char *d = ctx->pth.p;
+    RT_HIP(hipMemcpyAsync(d + st.xy, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
+    const hipError_t e = ctx->kern->primary_rays(&fa, ctx->d_camx, ctx->d_camy, nullptr, reinterpret_cast<const uint32_t *>(d + st.xy), n, d + st.rays, primary_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_pick_paths: kernel launch failed: %s", hipGetErrorString(e));
+    return paths_staged("rt_pick_paths", ctx, st, n, max_segments, segments_host, nullptr, ends_host, stream);
 }
 
 // ---- scene updates (rt_set_scene.hip) -----------------------------------------------------------------------

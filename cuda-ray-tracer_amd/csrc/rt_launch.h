@@ -61,6 +61,11 @@ RT_PER_VARIANT(hipError_t, rt_launch_occluded_rays, const FrameArgs *fa, const v
                uint32_t max_grid, hipStream_t stream)
 RT_PER_VARIANT(hipError_t, rt_launch_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
                uint32_t max_grid, hipStream_t stream)
+// rt_paths.hip: the hits along a ray's mirror bounces; the context's own primary rays as explicit rays (rect = x0, y0, x1, y1 inclusive, or a pixel list)
+RT_PER_VARIANT(hipError_t, rt_launch_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments, void *last,
+               void *ends, uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_primary_rays, const FrameArgs *fa, const double *camx, const double *camy, const uint32_t *rect, const uint32_t *xy, uint32_t n_list,
+               void *out, uint32_t max_grid, hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -77,6 +82,8 @@ struct Kernels {
     decltype(&rt_launch_occluded_rays_strict) occluded_rays;
     decltype(&rt_launch_shade_rays_strict) shade_rays;
     decltype(&rt_launch_object_extents_strict) object_extents;
+    decltype(&rt_launch_trace_paths_strict) trace_paths;
+    decltype(&rt_launch_primary_rays_strict) primary_rays;
 };
 
 #endif

@@ -185,6 +185,20 @@ extern "C" int mi355rt_update_pick(unsigned int x, unsigned int y, rt_hit *out)
     return rt_pick(g_ctx, g_last_cam, xy, 1, out, nullptr);
 }
 
+// Pick through mirrors: the path of pixel (x, y)'s primary ray along its mirror bounces (rt_pick_paths with the camera of the last
+// update()): `segments` receives max_segments rt_hit records (NULL iff max_segments == 0; segments the path did not reach are miss
+// records), *end what the pixel finally shows.  Refused where mi355rt_update_pick is.
+extern "C" int mi355rt_update_pick_path(unsigned int x, unsigned int y, rt_hit *segments, unsigned int max_segments, rt_path_end *end)
+{
+    if (!g_ctx || !g_have_cam || !end) {
+        rt_set_last_error(g_multi ? "mi355rt_update_pick_path: not available with several devices (MI355RT_DEVICES)"
+                                  : (!end ? "mi355rt_update_pick_path: null argument" : "mi355rt_update_pick_path: no update() call yet"));
+        return RT_ERR_INVALID;
+    }
+    const uint32_t xy[2] = {x, y};
+    return rt_pick_paths(g_ctx, g_last_cam, xy, 1, max_segments, segments, end, nullptr);
+}
+
 // Which objects the frame of the last update() shows, where and how far away: rt_object_extents_host with that call's camera, for the
 // pixels of rect = x0, y0, x1, y1 (inclusive; NULL = the whole frame); n = the number of objects of the loaded scene, one record each.
 // Single-context back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices, before the first update(), for another n

@@ -144,7 +144,7 @@ typedef struct rt_scene_desc {
  * rt_get_ssaa_refined and rt_render_sparse work as in every adaptive context.  RT_FLAG_COUNT does not book the rays of that pass (as
  * rt_render_gbuffer books none): primary_rays = width * local_rows + halo rays + k^2 * refined, with the new refined count.
  * Known limits: two sheets of ONE object at different depths whose normals agree are not told apart (there is no depth term), and a
- * mirror shows only itself.  rt_render_gbuffer and rt_pick keep refusing every supersampling context. */
+ * mirror shows only itself (edges inside a reflection are not followed; rt_trace_paths reports what a mirror shows).  rt_render_gbuffer and rt_pick keep refusing every supersampling context. */
 #define RT_FLAG_SSAA_GEOMETRY 4096u
 
 /* rt_config.format -- framebuffer pixel format */
@@ -338,7 +338,8 @@ int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
  *     normal  4 x float32  (float) n.x, (float) n.y, (float) n.z, 0.0f with n = normal_vector(object, o + best_t * d)
  *                          (include/surface_impl.h:157-172: the normalised gradient, never flipped towards the eye), every component
  *                          rounded once from FP64, to nearest even                         miss: four +0.0f
- * Only the primary ray counts: a mirror shows itself, not what it reflects.  Each plane is [local_rows][W] in the context's own row
+ * Only the primary ray counts: a mirror shows itself, not what it reflects (rt_pick_paths and rt_trace_paths, "Ray queries", follow the
+ * reflections).  Each plane is [local_rows][W] in the context's own row
  * layout (rt_local_rows, rt_row_map), so bands and ranks work as for the framebuffer; the planes do not depend on cfg.format.
  * Strict contexts compute exactly these values for surfaces of degree <= 2 (degree 3: as the render kernels, within their guard's
  * 1e-8 of t under the device's cbrt / acos / cos); RT_FLAG_FAST contexts run the FMA-contracted build of the same kernels.
@@ -393,7 +394,7 @@ int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, r
  *
  * Out of scope: the multi-GPU layer (rt_*_multi) has no such entry point -- a rank-level caller merges the ranks' records itself;
  * supersampling contexts are refused as by rt_render_gbuffer; and only the primary hit counts: an object seen through a mirror is
- * not seen.
+ * not seen (a caller that wants it reduces the `dev_last` records of rt_trace_paths on the rays of rt_primary_rays itself).
  * ------------------------------------------------------------------------------------------------- */
 typedef struct rt_object_extent {
     uint64_t pixels;                      /* pixels whose primary hit is this object */
@@ -499,6 +500,83 @@ int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rg
 /* rt_shade_rays for rays and pixels in HOST memory; blocks.  Staging buffers as rt_trace_rays_host. */
 int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_out, void *stream); /* host memory, blocks */
 
+/* Paths: the hits along a ray's mirror bounces (csrc/rt_paths.hip).
+ *
+ * A path is the geometry of the reference's render_pixel (src/update-cpu.cpp:82-119) with ray_origin := o and dir := d, as rt_shade_rays
+ * defines it, minus everything that concerns colour.  R is the scene's max_reflections.
+ *     (o_0, d_0) = (o, d);  ratio = 1.0f;  k = 0
+ *     loop:
+ *       h_k = closest hit of (o_k, d_k)            -- exactly rt_trace_rays' definition (t >= EPS, t < MAX_T, nearest, lowest index on a tie)
+ *       miss:  end = (k == 0) ? RT_PATH_MISS : RT_PATH_ESCAPED;  segments = k;  stop
+ *       sp = o_k + t * d_k  (FP64);   sn = normal_vector(object, sp)  (FP64, never flipped)
+ *       if !((double) reflection_ratio[object] > EPS):   end = RT_PATH_SURFACE;  segments = k + 1;  stop      -- a NaN ratio is no mirror
+ *       ratio = ratio * reflection_ratio[object]          (float32, one rounding)
+ *       if k == R:                                        end = RT_PATH_CAP;      segments = k + 1;  stop
+ *       d_{k+1} = reflect_ray(d_k, sn)   (include/light_impl.h:46-49, the direction as it is, never normalised)
+ *       o_{k+1} = sp + SHADOW_BIAS * sn;   k = k + 1
+ * The order of the ratio product and the cap test is the reference's (lines 101-107): a path that ends at the cap has the last mirror's
+ * ratio in `ratio`.
+ *
+ * Outputs.  dev_segments is segment-major: record k * n + i is hit k of ray i as an rt_hit, its t, point and float normal those of
+ * segment k, t in units of |d_k|; plane 0 is what rt_trace_rays writes for the same rays.  Every one of the max_segments planes is
+ * written: a segment the path did not reach is the miss record (object -1, t +inf, zeros), so the caller never reads memory the call did
+ * not define.  max_segments is a storage limit only: the path is followed to its end whatever it is, so dev_ends and dev_last do not
+ * depend on it.  dev_last is the hit of segment `segments - 1`, the miss record when segments == 0; with `end` it answers "what does this
+ * ray finally show": an object (RT_PATH_SURFACE) or the background (RT_PATH_MISS, RT_PATH_ESCAPED, RT_PATH_CAP).  The direction of an
+ * escaped ray is not reported.  A mirror-aware form of rt_object_extents is a reduction of dev_last and is left to the caller.
+ *
+ * Accuracy is rt_shade_rays' (the same arithmetic without the lights): strict contexts are exact for surfaces of degree <= 2, for every
+ * ray, non-finite components and components beyond 1e100 included.  Whether the class tables are proven is decided for every segment's
+ * ray, not only the caller's: a derived ray can leave the proven range (a hit point beyond 1e100, a NaN normal where a gradient vanishes),
+ * and such lanes go through the dense expansion.  Degree 3 behaves as the render kernels do.  RT_FLAG_FAST contexts run the
+ * FMA-contracted build, whose results are their own arithmetic.
+ * No frame state: paths work in every context kind, supersampling included, need no ordering against rt_render (against rt_set_scene on
+ * another stream the ordering is the caller's, "Scene updates"), are one kernel with ms == NULL (capturable into a graph), and
+ * RT_FLAG_COUNT books none of their rays.  The multi-GPU layer (rt_*_multi) has no such entry point. */
+#define RT_PATH_MISS 0u     /* the ray itself hits nothing; segments = 0 */
+#define RT_PATH_SURFACE 1u  /* the last hit is no mirror: that is what the ray finally shows */
+#define RT_PATH_ESCAPED 2u  /* a bounce left the scene: the reference blends the background */
+#define RT_PATH_CAP 3u      /* max_reflections bounces taken, the last hit is still a mirror: the reference blends the background */
+#define RT_PATH_MAX_SEGMENTS 64u
+typedef struct rt_path_end {
+    uint32_t segments;  /* hits along the path, 0 .. max_reflections + 1 */
+    uint32_t end;       /* RT_PATH_* */
+    float    ratio;     /* cur_ratio as the reference's last UPDATE_COLOR used it; 1.0f when no mirror was met */
+    int32_t  object;    /* object of the last hit, -1 when segments == 0 */
+} rt_path_end;          /* 16 bytes, 16-byte aligned in device memory */
+
+/* n rays -> max_segments planes of n rt_hit, optionally n rt_hit of the last hits, n rt_path_end; all in device memory, on `stream`; ms
+ * as in rt_trace_rays.  RT_ERR_INVALID for a NULL context, dev_rays or dev_ends and for n == 0 (all before a device is looked for),
+ * max_segments > RT_PATH_MAX_SEGMENTS, dev_segments == NULL with max_segments != 0 and the reverse, any pointer that is not 16-byte
+ * aligned, and any overlap between the input range and an output range or between two output ranges.  Scenes beyond the LDS limit are
+ * refused as by rt_trace_rays. */
+int rt_trace_paths(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, uint32_t max_segments,
+                   rt_hit *dev_segments /* [max_segments][n], or NULL iff max_segments == 0 */,
+                   rt_hit *dev_last /* [n] or NULL */, rt_path_end *dev_ends /* [n] */, void *stream, float *ms);
+/* rt_trace_paths for rays and records in HOST memory; blocks.  The staging buffer is the context's own (it grows as rt_pick's do,
+ * rt_destroy frees it); calls on one context must not overlap in time. */
+int rt_trace_paths_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, uint32_t max_segments,
+                        rt_hit *segments_out, rt_hit *last_out /* may be NULL */, rt_path_end *ends_out, void *stream); /* blocks */
+
+/* The context's own primary rays as explicit rays.  For every pixel (x, y) of `rect` (GLOBAL coordinates, whatever rows this rank owns,
+ * as rt_pick) one rt_ray: o = the frame's ray origin (cam * (0,0,0,1)), d = the primary direction of the pixel, both bit for bit what the
+ * render, G-buffer and pick kernels use (the same function on the context's camera-plane tables), hence the reference's
+ * src/update-cpu.cpp:82-89.  The kernel reads the camera-plane tables and writes the rays, nothing else; with ms == NULL it is one
+ * kernel and can be captured, so whole-frame colours, hits, occlusion and paths can be formed and traced in one graph without the host.
+ * On a strict context without supersampling, with rays = rt_primary_rays(cam): rt_shade_rays(rays) is the RGBA32F frame of
+ * rt_render(cam); for surfaces of degree <= 2 rt_trace_rays(rays) is rt_pick of those pixels (degree 3: the two form the cubic's data at
+ * the origin differently, one on the host and one per lane, so only the ray queries' degree-3 accuracy is promised).
+ * RT_ERR_INVALID for a NULL context / camera / output, an output that is not 16-byte aligned, a `rect` as rt_object_extents refuses it,
+ * and supersampling contexts (refused as by rt_render_gbuffer: their tables describe another pixel grid). */
+int rt_primary_rays(rt_ctx *ctx, const double cam[16], const uint32_t rect[4] /* x0,y0,x1,y1 inclusive, GLOBAL, or NULL = W x H */,
+                    rt_ray *dev_rays /* [(y1-y0+1)][(x1-x0+1)], row y0 first, row 0 = bottom */, void *stream, float *ms);
+/* Pick through mirrors: the primary rays of n pixels (GLOBAL coordinates xy[2*i], xy[2*i+1]; the list form of rt_primary_rays' kernel),
+ * then rt_trace_paths, on the context's staging buffer; blocks and writes host memory.  Refusals, staging growth and the rule "calls
+ * on one context must not overlap in time" are rt_pick's, plus rt_trace_paths' for max_segments.  For surfaces of degree <= 2 plane 0 is
+ * rt_pick's record bit for bit; ends[i].object is what pixel i finally shows when ends[i].end == RT_PATH_SURFACE. */
+int rt_pick_paths(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, uint32_t max_segments,
+                  rt_hit *segments_host /* [max_segments][n] or NULL iff 0 */, rt_path_end *ends_host, void *stream); /* blocks */
+
 /* ---------------------------------------------------------------------------------------------------
  * Scene updates: move objects and lights of a live context (csrc/rt_set_scene.hip)
  *
@@ -529,7 +607,7 @@ int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_
  * again, so rewriting them between replays animates the scene); another stream first waits for the event recorded behind the previous
  * call; the event is not recorded while capturing, and after a captured call a call on another stream is refused (RT_ERR_INVALID).
  * The arrays must stay unchanged until the kernel has run.  The passes that READ the scene -- rt_render_gbuffer, rt_pick, rt_object_extents, rt_trace_rays,
- * rt_occluded_rays, rt_shade_rays and their _host forms -- need no ordering against rt_render, but they DO need ordering against
+ * rt_occluded_rays, rt_shade_rays, rt_trace_paths, rt_primary_rays, rt_pick_paths and their _host forms -- need no ordering against rt_render, but they DO need ordering against
  * rt_set_scene when issued on another stream, and that ordering is the caller's to establish (on one stream it is automatic).
  * Frame-to-frame state (launch order, census, tile words) survives an update: it affects speed only, never the image, exactly as under
  * a moving camera.  Works in every context kind.  The multi-GPU layer (rt_*_multi) has no scene-update entry point.
