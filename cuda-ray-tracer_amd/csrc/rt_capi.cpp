@@ -29,7 +29,7 @@
 #define RT_KERNELS(V)                                                                                                                              \
     {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
      RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
-     RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V)}
+     RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 
 namespace {
@@ -218,6 +218,7 @@ struct rt_ctx {
     MappedWords h_listed;         // host-mapped words the kernel writes (FrameArgs::ord_host)
     uint32_t ord_split = 0;       // FrameArgs::ord_split of non-sparse frames
     std::vector<double> cub_coefs; // the 20 coefficients of the first RT_CUB_AT_MAX degree-3 objects (FrameArgs::cub_at is formed from them every frame)
+    bool streamed = false;        // rt_render is the streamed frame kernel (rt_stream.hip): RT_FLAG_STREAM, or a scene whose tables the context's own kernel cannot hold in LDS
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -432,6 +433,11 @@ static int create_checks(rt_ctx *ctx, const rt_scene_desc *sd, const rt_config *
     if (ctx->adaptive && k == 1u) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_ADAPTIVE needs RT_FLAG_SSAA2 or RT_FLAG_SSAA4");
     ctx->geometry = (cfg.flags & RT_FLAG_SSAA_GEOMETRY) != 0;
     if (ctx->geometry && !ctx->adaptive) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_GEOMETRY needs RT_FLAG_SSAA_ADAPTIVE");
+    if ((cfg.flags & RT_FLAG_STREAM) && (cfg.flags & RT_FLAG_SIMPLE)) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM and RT_FLAG_SIMPLE exclude each other");
+    if ((cfg.flags & RT_FLAG_STREAM) && ctx->adaptive)
+        return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM is not available with RT_FLAG_SSAA_ADAPTIVE (the refine pass has no streamed kernel)");
+    if ((cfg.flags & RT_FLAG_STREAM) && (cfg.flags & RT_FLAG_COUNT))
+        return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM is not available with RT_FLAG_COUNT (the streamed kernel books no counters)");
     if (sd->width == 0 || sd->height == 0) return fail(RT_ERR_INVALID, "rt_create: empty image %ux%u", sd->width, sd->height);
     if (k > 1u && ((uint64_t) k * sd->width > 65536u || (uint64_t) k * sd->height > 65536u))
         return fail(RT_ERR_INVALID, "rt_create: %ux%u supersampled %ux%u exceeds 65536 samples per axis", sd->width, sd->height, k, k);
@@ -501,13 +507,20 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
     im = rtp::scene_image(*sd, ctx->cfg.flags, fa);
     ctx->cub_coefs = im.cub_coefs;
     ctx->lean_ok = im.lean_ok && !std::getenv("MI355RT_NOLEAN"); // (experiments)
-    if (!(ctx->cfg.flags & RT_FLAG_SIMPLE)) {
-        const size_t lds = rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub);
-        if (lds > 160u * 1024u) return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", lds);
-    }
+    // Which kernel is rt_render?  The streamed one (rt_stream.hip) where the caller asks for it, and where the context's own kernel cannot
+    // hold the scene in a workgroup's LDS: the class tables and per-tile state of the wavefront kernel, the object records of the simple one.
+    const size_t lds = (ctx->cfg.flags & RT_FLAG_SIMPLE) ? (size_t) sd->n_objects * sizeof(DevObject)
+                                                         : rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub);
+    if (ctx->adaptive && !(ctx->cfg.flags & RT_FLAG_SIMPLE) && lds > 160u * 1024u) // (the refine pass has no streamed kernel: refused as ever)
+        return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", lds);
+    ctx->streamed = (ctx->cfg.flags & RT_FLAG_STREAM) || lds > 160u * 1024u;
+    if (ctx->streamed) ctx->lean_ok = false;
     if (ctx->adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)",
                     (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)));
+    if (ctx->streamed && (ctx->cfg.flags & RT_FLAG_COUNT)) // (RT_FLAG_STREAM itself was refused in create_checks: this is streaming forced by the scene's size, RT_FLAG_SIMPLE contexts included)
+        return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB), so it takes the streamed kernel, and the streamed kernel books no counters "
+                                  "(RT_FLAG_COUNT)", lds);
     if (ctx->geometry && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
     return RT_OK;
@@ -589,7 +602,8 @@ static int create_order_state(rt_ctx *ctx)
 {
     FrameArgs &fa = ctx->fa;
     const uint32_t flags = ctx->cfg.flags;
-    if (!(flags & (RT_FLAG_SIMPLE | RT_FLAG_STATIC_ORDER)) && fa.n_tiles > 0 && fa.n_tiles <= RT_ORD_MAX_TILES) {
+    const bool stateless = (flags & RT_FLAG_SIMPLE) || ctx->streamed; // one kernel per frame that reads nothing an earlier frame left
+    if (!stateless && !(flags & RT_FLAG_STATIC_ORDER) && fa.n_tiles > 0 && fa.n_tiles <= RT_ORD_MAX_TILES) {
         // launch-order feedback: three generations, all empty (first frame = index order)
         fa.ord_stride = (RT_ORD_HDR + 17u * fa.n_tiles + 15u) & ~15u;
         // ... and behind them one word per tile, the last frame in which one of a split tile's two workgroups entered the tile (FrameArgs::ord_frame)
@@ -610,7 +624,7 @@ static int create_order_state(rt_ctx *ctx)
             (void) hipGetLastError();
         }
     }
-    if (!(flags & RT_FLAG_SIMPLE) && fa.all_cullable && fa.n_tiles > 0) {
+    if (!stateless && fa.all_cullable && fa.n_tiles > 0) {
         // one word per tile for the scan workgroups (rt_wavefront.hip, scan_tiles); all zero = "no frame has classified it"
         if (int rc = device_table(ctx->d_tiles, nullptr, sizeof(uint32_t) * fa.n_tiles, "tile state")) return rc;
         fa.tile_state = ctx->d_tiles;
@@ -843,7 +857,8 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     if (fa.order_state)
         if (int rc = rotate_launch_order(ctx, fa, stream)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
+    const hipError_t e = ctx->streamed ? ctx->kern->stream(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, stream)
+                         : (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
                                                            : ctx->kern->wavefront(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
     const int out8 = ctx->cfg.format == RT_FMT_RGBA8;
@@ -891,6 +906,7 @@ extern "C" int rt_render_sparse(rt_ctx *ctx, const double cam[16], void *dev_msg
 {
     if (!ctx || !cam || !dev_msg) return fail(RT_ERR_INVALID, "rt_render_sparse: null argument");
     if (ctx->cfg.flags & RT_FLAG_SIMPLE) return fail(RT_ERR_INVALID, "rt_render_sparse: not available with RT_FLAG_SIMPLE");
+    if (ctx->streamed) return fail(RT_ERR_INVALID, "rt_render_sparse: not available on a streamed context (rt_get_streamed); rt_render and rt_pack_sparse give the same message");
     return render_impl(ctx, cam, dev_msg, stream, ms, true, capacity_tiles);
 }
 
@@ -1501,9 +1517,17 @@ extern "C" int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels)
     return RT_OK;
 }
 
+extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)
+{
+    if (!ctx || !streamed) return fail(RT_ERR_INVALID, "rt_get_streamed: null argument");
+    *streamed = ctx->streamed ? 1u : 0u;
+    return RT_OK;
+}
+
 extern "C" int rt_get_counters(rt_ctx *ctx, rt_counters *out)
 {
     if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_get_counters: null argument");
+    if (ctx->streamed) return fail(RT_ERR_INVALID, "rt_get_counters: the streamed kernel books no counters (rt_get_streamed)");
     if (!ctx->counted) return fail(RT_ERR_INVALID, "rt_get_counters: the last render was not done with RT_FLAG_COUNT");
     unsigned long long h[8];
     if (int rc = read_synced(ctx, h, ctx->d_counters, sizeof(h))) return rc;
@@ -1521,6 +1545,7 @@ extern "C" int rt_get_counters(rt_ctx *ctx, rt_counters *out)
 extern "C" int rt_get_counters_detail(rt_ctx *ctx, rt_counters_detail *out)
 {
     if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_get_counters_detail: null argument");
+    if (ctx->streamed) return fail(RT_ERR_INVALID, "rt_get_counters_detail: the streamed kernel books no counters (rt_get_streamed)");
     if (!ctx->counted) return fail(RT_ERR_INVALID, "rt_get_counters_detail: the last render was not done with RT_FLAG_COUNT");
     if (ctx->cfg.flags & RT_FLAG_SIMPLE) return fail(RT_ERR_INVALID, "rt_get_counters_detail: the simple kernel does not split its counters");
     unsigned long long h[21];

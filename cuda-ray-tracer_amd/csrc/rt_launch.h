@@ -66,6 +66,9 @@ RT_PER_VARIANT(hipError_t, rt_launch_trace_paths, const FrameArgs *fa, const voi
                void *ends, uint32_t max_grid, hipStream_t stream)
 RT_PER_VARIANT(hipError_t, rt_launch_primary_rays, const FrameArgs *fa, const double *camx, const double *camy, const uint32_t *rect, const uint32_t *xy, uint32_t n_list,
                void *out, uint32_t max_grid, hipStream_t stream)
+// rt_stream.hip: the streamed frame kernel (scenes of any size)
+RT_PER_VARIANT(hipError_t, rt_launch_stream, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
+               hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -84,6 +87,7 @@ struct Kernels {
     decltype(&rt_launch_object_extents_strict) object_extents;
     decltype(&rt_launch_trace_paths_strict) trace_paths;
     decltype(&rt_launch_primary_rays_strict) primary_rays;
+    decltype(&rt_launch_stream_strict) stream;
 };
 
 #endif

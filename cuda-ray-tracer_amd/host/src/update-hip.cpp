@@ -40,6 +40,8 @@
 //   MI355RT_SSAA_GEOMETRY=<min_cos>  with MI355RT_SSAA_ADAPTIVE: also supersample the pixels next to one whose primary ray hits another
 //                             object (RT_FLAG_SSAA_GEOMETRY, rt_set_ssaa_geometry); empty: object boundaries only; a number: also where the
 //                             normals of one object make a cosine below it
+//   MI355RT_STREAM=1          render with the streamed frame kernel whatever the scene's size (RT_FLAG_STREAM; same frame).  A scene too large
+//                             for a workgroup's LDS takes that kernel without being asked; not together with MI355RT_SSAA_ADAPTIVE
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -288,6 +290,12 @@ void init_update(unsigned int texture, const Scene &scene)
         else if (!std::strcmp(f, "4")) ssaa = RT_FLAG_SSAA4;
         else if (*f) die_text("MI355RT_SSAA", "expected 2 or 4");
     }
+    // MI355RT_STREAM=1: the streamed frame kernel whatever the scene's size (scenes too large for LDS take it without being asked)
+    uint32_t streamed = 0;
+    if (const char *f = std::getenv("MI355RT_STREAM")) {
+        if (!std::strcmp(f, "1")) streamed = RT_FLAG_STREAM;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM", "expected 0 or 1");
+    }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;
     if (const char *f = std::getenv("MI355RT_SSAA_ADAPTIVE")) {
@@ -343,7 +351,7 @@ void init_update(unsigned int texture, const Scene &scene)
         load_multi();
         if (std::getenv("MI355RT_MULTI_SPARSE") && std::getenv("MI355RT_MULTI_BANDWISE"))
             die_text("init_update", "MI355RT_MULTI_SPARSE and MI355RT_MULTI_BANDWISE exclude each other (tiles travel as sparse messages, or rows band by band): set one");
-        const uint32_t flags = RT_FLAG_STRICT | ssaa | (std::getenv("MI355RT_MULTI_SELF") ? RT_MULTI_SELF_EXCHANGE : 0u) |
+        const uint32_t flags = RT_FLAG_STRICT | ssaa | streamed | (std::getenv("MI355RT_MULTI_SELF") ? RT_MULTI_SELF_EXCHANGE : 0u) |
                                (std::getenv("MI355RT_MULTI_BANDWISE") ? RT_MULTI_BANDWISE : 0u) | // (rows band by band into their place in the frame: no reassembly pass)
                                (std::getenv("MI355RT_MULTI_SPARSE") ? RT_MULTI_SPARSE : 0u);     // (only tiles with content travel)
         if (g_mapi.create(&g_multi, &sd, devs.data(), (uint32_t) devs.size(), env_u32("MI355RT_BAND_ROWS", 16), env_u32("MI355RT_PARTS", 2), flags, g_format) != RT_OK)
@@ -355,7 +363,7 @@ void init_update(unsigned int texture, const Scene &scene)
     rt_config cfg{};
     cfg.device = devs.empty() ? -1 : devs[0];
     cfg.world = 1;
-    cfg.flags = RT_FLAG_STRICT | ssaa;
+    cfg.flags = RT_FLAG_STRICT | ssaa | streamed;
     cfg.format = g_format;
     if (rt_create(&g_ctx, &sd, &cfg) != RT_OK) die("init_update");
     if (adaptive && rt_set_ssaa_threshold(g_ctx, tau) != RT_OK) die("init_update (MI355RT_SSAA_ADAPTIVE)");

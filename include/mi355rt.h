@@ -147,6 +147,31 @@ typedef struct rt_scene_desc {
  * mirror shows only itself (edges inside a reflection are not followed; rt_trace_paths reports what a mirror shows).  rt_render_gbuffer and rt_pick keep refusing every supersampling context. */
 #define RT_FLAG_SSAA_GEOMETRY 4096u
 
+/* Streamed frames: rt_render for scenes of any size.  The render kernels above keep the scene in a workgroup's LDS
+ * (the wavefront kernel its class tables, the simple kernel the object records), which bounds a scene at roughly 1 700 spheres; the
+ * streamed kernel (rt_stream.hip) leaves the tables in global memory and passes them through a wave-private LDS slice 64 entries at a
+ * time.  A context is streamed -- rt_get_streamed says so -- when it was created with RT_FLAG_STREAM, or without RT_FLAG_SIMPLE for a
+ * scene whose wavefront kernel would need more than 160 KiB of LDS, or with RT_FLAG_SIMPLE for more than 160 KiB of object records.
+ * Definition: the frame of rt_render, by the arithmetic of rt_shade_rays on the rays of rt_primary_rays -- pixel (x, y) is the colour
+ * rt_shade_rays gives the ray rt_primary_rays forms for (x, y), quantised for RGBA8 as the render kernels do.
+ * Accuracy: in strict contexts bit-identical to the other render kernels (and the CPU reference) for surfaces of degree <= 2, in both
+ * formats, and bit-identical to rt_shade_rays(rt_primary_rays) for every degree; degree-3 frames meet the bar of the other kernels'
+ * degree-3 frames (1e-5 relative per channel, at most max(3, 0.2 % of the pixels) beyond it against the CPU reference).  RT_FLAG_FAST is
+ * its own arithmetic (FMA contraction), held to 1e-5 relative like every RT_FLAG_FAST frame.  RT_FLAG_NOCULL switches the one piece of
+ * work removal off (primary rays skip the spheres outside their 8 x 8 block's cone); same results.
+ * A streamed context holds no frame-to-frame state: rt_render is one kernel (plus the resolve under RT_FLAG_SSAA2 / RT_FLAG_SSAA4),
+ * captured and replayed freely.  Formats, ranks and bands, rt_pack_sparse and the assemble calls, rt_set_scene and the multi-GPU layer
+ * work as on any context.
+ * Refused: RT_FLAG_STREAM with RT_FLAG_SIMPLE, RT_FLAG_SSAA_ADAPTIVE or RT_FLAG_COUNT (RT_ERR_INVALID, before rt_create looks for a
+ * device); RT_FLAG_COUNT for a scene that must be streamed, with or without RT_FLAG_SIMPLE (RT_ERR_SCENE: the streamed kernel books no
+ * counters); rt_get_counters and
+ * rt_get_counters_detail (RT_ERR_INVALID); rt_render_sparse (RT_ERR_INVALID, as with RT_FLAG_SIMPLE: rt_render + rt_pack_sparse give
+ * the same message).
+ * Out of scope: adaptive supersampling, the G-buffer, picking, object extents, the ray queries and the path queries still stage the
+ * tables in LDS and keep refusing scenes beyond 160 KiB with their own messages; shadow and bounce rays of a streamed frame test
+ * every object. */
+#define RT_FLAG_STREAM 8192u
+
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
                                  produces (src/update-cpu.cpp:128-131) plus an alpha lane for 16-byte stores */
@@ -325,6 +350,8 @@ int rt_set_ssaa_threshold(rt_ctx *ctx, float tau);
 int rt_set_ssaa_geometry(rt_ctx *ctx, float min_cos);
 /* The number of refined pixels of this context's last frame (waits for that frame). */
 int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
+/* Streamed frames (RT_FLAG_STREAM above): *streamed = 1 where rt_render is the streamed kernel, else 0. */
+int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
