@@ -41,7 +41,7 @@ ABI_SYMBOLS = [
     "rt_abi_version", "rt_last_error", "rt_set_last_error", "rt_scene_load_file", "rt_scene_new", "rt_scene_add_object",
     "rt_scene_add_light", "rt_surface_make", "rt_scene_set_size", "rt_scene_set_max_reflections",
     "rt_scene_get_desc", "rt_scene_free", "rt_camera_matrix", "rt_create", "rt_render", "rt_local_rows", "rt_max_local_rows",
-    "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
+    "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_assemble_planes", "rt_merge_object_extents", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
@@ -52,7 +52,9 @@ ABI_SYMBOLS = [
 ]
 # ... and the ones libmi355rt_multi.so exports
 MULTI_ABI_SYMBOLS = ["rt_create_multi", "rt_render_multi", "rt_multi_wait", "rt_multi_fb", "rt_multi_stream", "rt_multi_download", "rt_multi_info",
-                     "rt_multi_last_transfer", "rt_multi_set_ssaa_threshold", "rt_multi_set_ssaa_geometry", "rt_multi_destroy"]
+                     "rt_multi_last_transfer", "rt_multi_set_ssaa_threshold", "rt_multi_set_ssaa_geometry", "rt_multi_destroy",
+                     "rt_set_scene_multi", "rt_multi_set_scene_status", "rt_multi_query_ctx", "rt_render_gbuffer_multi", "rt_object_extents_multi",
+                     "rt_object_extents_multi_host"]
 RT_MULTI_SELF_EXCHANGE = 0x10000
 RT_MULTI_BANDWISE = 0x20000
 RT_MULTI_SPARSE = 0x40000
@@ -233,6 +235,8 @@ def lib():
         L.rt_set_scene_host.argtypes = [vp, C.POINTER(SceneUpdate), vp]
         L.rt_set_scene_status.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.rt_debug_scene_blob.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.rt_assemble_planes.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp]
+        L.rt_merge_object_extents.argtypes = [vp, vp, C.c_uint32, vp, vp]
         _lib = L
     return _lib
 
@@ -278,6 +282,13 @@ def multi_lib():
         M.rt_multi_destroy.argtypes = [vp]
         M.rt_multi_set_ssaa_threshold.argtypes = [vp, C.c_float]
         M.rt_multi_set_ssaa_geometry.argtypes = [vp, C.c_float]
+        M.rt_set_scene_multi.argtypes = [vp, C.POINTER(SceneUpdate)]
+        M.rt_multi_set_scene_status.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        M.rt_multi_query_ctx.argtypes = [vp]
+        M.rt_multi_query_ctx.restype = vp
+        M.rt_render_gbuffer_multi.argtypes = [vp, C.POINTER(C.c_double), vp, vp, vp, C.POINTER(C.c_float)]
+        M.rt_object_extents_multi.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), vp, C.POINTER(C.c_float)]
+        M.rt_object_extents_multi_host.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32), vp]
         _mlib = M
     return _mlib
 
@@ -670,10 +681,24 @@ class Renderer:
         _check(lib().rt_debug_scene_blob(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
         return out
 
+    @classmethod
+    def _borrowed_view(cls, handle, desc, flags, fmt):
+        """A Renderer over a context somebody else owns (MultiRenderer's query context): it never destroys it."""
+        self = cls.__new__(cls)
+        self._h, self._borrowed, self._desc = C.c_void_p(handle), True, desc
+        self.width, self.height, self.fmt, self.flags = desc.width, desc.height, fmt, int(flags)
+        n = C.c_uint32()
+        _check(lib().rt_local_rows(self._h, C.byref(n)))
+        self.local_rows = n.value
+        _check(lib().rt_max_local_rows(self._h, C.byref(n)))
+        self.max_local_rows = n.value
+        self.pixel_bytes = lib().rt_pixel_bytes(self._h)
+        return self
+
     def cleanup_update(self):
-        if self._h:
+        if self._h and not getattr(self, "_borrowed", False):
             lib().rt_destroy(self._h)
-            self._h = None
+        self._h = None
 
     close = cleanup_update
 
@@ -703,6 +728,17 @@ class Renderer:
 
     def assemble(self, gathered_ptr, full_ptr, stream=None):
         _check(lib().rt_assemble(self._h, C.c_void_p(gathered_ptr), C.c_void_p(full_ptr), C.c_void_p(stream) if stream else None))
+
+    def assemble_planes(self, gathered_ptr, slot_stride_bytes, full_ptr, elem_bytes, stream=None):
+        """rt_assemble_planes: assemble() for gathered planes of 4-, 8- or 16-byte elements (the G-buffer's), rank q's slot at
+        gathered_ptr + q * slot_stride_bytes."""
+        _check(lib().rt_assemble_planes(self._h, C.c_void_p(gathered_ptr) if gathered_ptr else None, int(slot_stride_bytes), C.c_void_p(full_ptr) if full_ptr else None,
+                                        int(elem_bytes), C.c_void_p(stream) if stream else None))
+
+    def merge_object_extents(self, parts_ptr, n_parts, out_ptr, stream=None):
+        """rt_merge_object_extents: [n_parts][n_objects] records in device memory into n_objects records (sum / min / max)."""
+        _check(lib().rt_merge_object_extents(self._h, C.c_void_p(parts_ptr) if parts_ptr else None, int(n_parts), C.c_void_p(out_ptr) if out_ptr else None,
+                                             C.c_void_p(stream) if stream else None))
 
     # sparse transport of a frame (tiles with content only): see include/mi355rt.h
     @staticmethod
@@ -778,6 +814,7 @@ class MultiRenderer:
         self._h = None
         d = scene.desc() if isinstance(scene, Scene) else scene
         self._desc = d
+        self._devices, self._flags, self._query = [int(v) for v in devices], int(flags) & 0xFFFF, None
         devs = (C.c_int * len(devices))(*[int(v) for v in devices])
         h = C.c_void_p()
         _check(multi_lib().rt_create_multi(C.byref(h), C.byref(d), devs, len(devices), int(band_rows), int(parts), int(flags), int(fmt)))
@@ -812,6 +849,95 @@ class MultiRenderer:
     def wait(self):
         _check(multi_lib().rt_multi_wait(self._h))
 
+    @property
+    def stream(self):
+        """rt_multi_stream: the root's stream frames, planes and extents are complete on, and the one the queries run on."""
+        return multi_lib().rt_multi_stream(self._h)
+
+    def set_scene(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None):
+        """Renderer.set_scene on every context (rt_set_scene_multi): enqueues only, in every context's frame order; whether the update
+        was applied is on the devices (set_scene_status)."""
+        given = dict(coefs=coefs, reflection=reflection, albedo=albedo, light_p=light_p, light_color=light_color)
+        keep = {n: np.ascontiguousarray(given[n], dtype=dt) for n, dt in SCENE_UPDATE_FIELDS if given[n] is not None}
+        no, nl = self._desc.n_objects, self._desc.n_lights
+        want = dict(coefs=no * RT_NCOEF, reflection=no, albedo=3 * no, light_p=3 * nl, light_color=3 * nl)
+        for n, a in keep.items():
+            if a.size != want[n]:
+                raise ValueError(f"set_scene: {n} has {a.size} values, the scene takes {want[n]}")
+        u = SceneUpdate(**{n: (a.ctypes.data if a.size else None) for n, a in keep.items()})
+        _check(multi_lib().rt_set_scene_multi(self._h, C.byref(u)))
+
+    def set_scene_status(self):
+        """Updates applied / rejected and the reason / index of the last rejection, the same on every context (waits for all of them)."""
+        a, r, why, idx = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        _check(multi_lib().rt_multi_set_scene_status(self._h, C.byref(a), C.byref(r), C.byref(why), C.byref(idx)))
+        return dict(applied=int(a.value), rejected=int(r.value), reason=int(why.value), index=int(idx.value))
+
+    def gbuffer(self, cam=None, object=True, t=True, normal=True, timed=True):
+        """The primary-hit G-buffer of the whole frame on devices[0] (rt_render_gbuffer_multi): torch device tensors (object int32
+        [H, W], t float64 [H, W], normal float32 [H, W, 4]; None for a plane not asked for) and the device milliseconds (None unless
+        timed; then complete on `stream`, not on the host)."""
+        import torch
+        dev = torch.device("cuda", self._devices[0])
+        h, w = self.height, self.width
+        po = torch.empty((h, w), dtype=torch.int32, device=dev) if object else None
+        pt = torch.empty((h, w), dtype=torch.float64, device=dev) if t else None
+        pn = torch.empty((h, w, 4), dtype=torch.float32, device=dev) if normal else None
+        torch.cuda.synchronize(dev)   # (the allocations are torch's; the planes are written on the object's own stream)
+        ms = self.gbuffer_into(cam, po.data_ptr() if object else None, pt.data_ptr() if t else None, pn.data_ptr() if normal else None, timed=timed)
+        return po, pt, pn, ms
+
+    def gbuffer_into(self, cam, object_ptr, t_ptr, normal_ptr, timed=True):
+        """rt_render_gbuffer_multi into the caller's device memory on devices[0] (raw pointers, None = plane not written)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        ms = C.c_float(0.0)
+        _check(multi_lib().rt_render_gbuffer_multi(self._h, _dptr(cam), C.c_void_p(object_ptr) if object_ptr else None, C.c_void_p(t_ptr) if t_ptr else None,
+                                                   C.c_void_p(normal_ptr) if normal_ptr else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def object_extents(self, cam=None, rect=None):
+        """Renderer.object_extents of the whole frame: the contexts' records merged on the root (rt_object_extents_multi_host; blocks)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        keep, rp = Renderer._rect(rect)
+        out = np.zeros(self._desc.n_objects, dtype=EXTENT_DTYPE)
+        buf = out if len(out) else np.zeros(1, dtype=EXTENT_DTYPE)
+        _check(multi_lib().rt_object_extents_multi_host(self._h, _dptr(cam), rp, buf.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def object_extents_into(self, cam, rect, out_ptr, timed=True):
+        """rt_object_extents_multi into the caller's device memory on devices[0] (n_objects records of 40 bytes, 8-byte aligned)."""
+        cam = np.ascontiguousarray(IDENTITY if cam is None else cam, dtype=np.float64).reshape(16)
+        keep, rp = Renderer._rect(rect)
+        ms = C.c_float(0.0)
+        _check(multi_lib().rt_object_extents_multi(self._h, _dptr(cam), rp, C.c_void_p(out_ptr) if out_ptr else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    @property
+    def query(self):
+        """A Renderer view of rt_multi_query_ctx's context, for the queries that depend neither on rows nor on frame state.  Borrowed:
+        it lives as long as this object and never destroys the context.  Use it on `stream` (the methods below do)."""
+        if self._query is None:
+            self._query = Renderer._borrowed_view(multi_lib().rt_multi_query_ctx(self._h), self._desc, self._flags, self.fmt)
+        return self._query
+
+    def pick(self, xy, cam=None):
+        return self.query.pick(xy, cam=cam, stream=self.stream)
+
+    def pick_paths(self, xy, cam=None, max_segments=None):
+        return self.query.pick_paths(xy, cam=cam, max_segments=max_segments, stream=self.stream)
+
+    def trace(self, origins, dirs):
+        return self.query.trace(origins, dirs, stream=self.stream)
+
+    def occluded(self, origins, dirs, t_max=None, timed=True):
+        return self.query.occluded(origins, dirs, t_max=t_max, stream=self.stream, timed=timed)
+
+    def shade(self, origins, dirs):
+        return self.query.shade(origins, dirs, stream=self.stream)
+
+    def paths(self, origins, dirs, max_segments=None):
+        return self.query.paths(origins, dirs, max_segments=max_segments, stream=self.stream)
+
     def download(self):
         dt = np.uint8 if self.fmt == RT_FMT_RGBA8 else np.float32
         out = np.empty((self.height, self.width, 4), dtype=dt)
@@ -820,6 +946,8 @@ class MultiRenderer:
 
     def cleanup_update(self):
         if self._h:
+            if self._query is not None:   # (the view dies with the object it borrows from)
+                self._query.cleanup_update()
             multi_lib().rt_multi_destroy(self._h)
             self._h = None
 

@@ -1436,6 +1436,43 @@ extern "C" int rt_assemble(rt_ctx *ctx, const void *gathered, void *full, void *
     return RT_OK;
 }
 
+// ---- planes and records of several ranks (rt_planes.hip) ----------------------------------------------------
+// rt_assemble for planes that are not frames: elements of 4, 8 or 16 bytes (the G-buffer's object, t and normal planes), rank q's slot at
+// gathered + q * slot_stride_bytes.  Everything is decided from the arguments and the context's geometry before a device is looked for.
+extern "C" int rt_assemble_planes(rt_ctx *ctx, const void *gathered, size_t slot_stride_bytes, void *full, uint32_t elem_bytes, void *stream)
+{
+    if (!ctx || !gathered || !full) return fail(RT_ERR_INVALID, "rt_assemble_planes: null argument");
+    if (elem_bytes != 4u && elem_bytes != 8u && elem_bytes != 16u) return fail(RT_ERR_INVALID, "rt_assemble_planes: elem_bytes is %u (4, 8 or 16)", elem_bytes);
+    if (ctx->ssaa > 1u || ctx->adaptive)
+        return fail(RT_ERR_INVALID, "rt_assemble_planes: not available for contexts created with RT_FLAG_SSAA2 / RT_FLAG_SSAA4 / RT_FLAG_SSAA_ADAPTIVE");
+    const size_t slot = (size_t) ctx->max_local_rows * ctx->width * elem_bytes, full_bytes = (size_t) ctx->height * ctx->width * elem_bytes;
+    if (slot_stride_bytes < slot || slot_stride_bytes % elem_bytes)
+        return fail(RT_ERR_INVALID, "rt_assemble_planes: a slot stride of %zu bytes (at least one slot of %zu bytes, and a multiple of elem_bytes = %u)", slot_stride_bytes, slot,
+                    elem_bytes);
+    if (((uintptr_t) gathered | (uintptr_t) full) & (elem_bytes - 1u)) return fail(RT_ERR_INVALID, "rt_assemble_planes: gathered and full must be aligned to elem_bytes = %u", elem_bytes);
+    if (ranges_overlap(gathered, slot_stride_bytes * (ctx->cfg.world - 1u) + slot, full, full_bytes)) return fail(RT_ERR_INVALID, "rt_assemble_planes: full overlaps gathered");
+    if (int rc = use_device(ctx)) return rc;
+    const hipError_t e = rt_launch_assemble_planes(gathered, slot_stride_bytes / elem_bytes, full, ctx->width, ctx->height, ctx->cfg.world, ctx->cfg.band_rows, elem_bytes,
+                                                   (hipStream_t) stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_assemble_planes: kernel launch failed: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
+// The records of n_parts ranks (or of anything else that reduces the same way) into one: sum / min / max, the identities included.
+extern "C" int rt_merge_object_extents(rt_ctx *ctx, const rt_object_extent *dev_parts, uint32_t n_parts, rt_object_extent *dev_out, void *stream)
+{
+    if (!ctx || !dev_parts || !dev_out) return fail(RT_ERR_INVALID, "rt_merge_object_extents: null argument");
+    if (n_parts == 0u) return fail(RT_ERR_INVALID, "rt_merge_object_extents: n_parts is 0");
+    if (((uintptr_t) dev_parts | (uintptr_t) dev_out) & 7u) return fail(RT_ERR_INVALID, "rt_merge_object_extents: the records must be 8-byte aligned");
+    const size_t out_bytes = sizeof(rt_object_extent) * (size_t) ctx->fa.n_obj;
+    if (out_bytes && ranges_overlap(dev_parts, out_bytes * n_parts, dev_out, out_bytes)) return fail(RT_ERR_INVALID, "rt_merge_object_extents: the output overlaps the parts");
+    if (ctx->fa.n_obj == 0u) return RT_OK;
+    if (int rc = use_device(ctx)) return rc;
+    const hipError_t e = rt_launch_merge_extents(dev_parts, n_parts, ctx->fa.n_obj, dev_out, (hipStream_t) stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_merge_object_extents: kernel launch failed: %s", hipGetErrorString(e));
+    return RT_OK;
+}
+
 extern "C" size_t rt_sparse_bytes(uint32_t capacity_tiles)
 {
     return ((size_t) ((4u + capacity_tiles + 3u) & ~3u) + (size_t) capacity_tiles * 256u) * sizeof(uint32_t);

@@ -90,4 +90,10 @@ struct Kernels {
     decltype(&rt_launch_stream_strict) stream;
 };
 
+// rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements
+// (slot_stride in elements) and the merge of [n_parts][n_obj] object-extent records
+extern "C" hipError_t rt_launch_assemble_planes(const void *gathered, size_t slot_stride, void *full, uint32_t width, uint32_t height, uint32_t world, uint32_t band_rows,
+                                                uint32_t elem_bytes, hipStream_t stream);
+extern "C" hipError_t rt_launch_merge_extents(const void *parts, uint32_t n_parts, uint32_t n_obj, void *out, hipStream_t stream);
+
 #endif

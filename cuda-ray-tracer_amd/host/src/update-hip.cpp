@@ -54,6 +54,10 @@ struct MultiApi {
     int (*destroy)(rt_multi *) = nullptr;
     int (*set_threshold)(rt_multi *, float) = nullptr;
     int (*set_geometry)(rt_multi *, float) = nullptr;
+    rt_ctx *(*query_ctx)(rt_multi *) = nullptr;
+    void *(*stream)(rt_multi *) = nullptr;
+    int (*set_scene)(rt_multi *, const rt_scene_update *) = nullptr;
+    int (*scene_status)(rt_multi *, uint64_t *, uint64_t *, uint32_t *, uint32_t *) = nullptr;
 } g_mapi;
 unsigned int g_texture = 0;
 unsigned int g_width = 0, g_height = 0;
@@ -123,7 +127,13 @@ void load_multi()
     g_mapi.destroy = (decltype(g_mapi.destroy)) dlsym(g_multi_lib, "rt_multi_destroy");
     g_mapi.set_threshold = (decltype(g_mapi.set_threshold)) dlsym(g_multi_lib, "rt_multi_set_ssaa_threshold");
     g_mapi.set_geometry = (decltype(g_mapi.set_geometry)) dlsym(g_multi_lib, "rt_multi_set_ssaa_geometry");
-    if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold || !g_mapi.set_geometry) die_text("libmi355rt_multi.so", "missing entry points");
+    g_mapi.query_ctx = (decltype(g_mapi.query_ctx)) dlsym(g_multi_lib, "rt_multi_query_ctx");
+    g_mapi.stream = (decltype(g_mapi.stream)) dlsym(g_multi_lib, "rt_multi_stream");
+    g_mapi.set_scene = (decltype(g_mapi.set_scene)) dlsym(g_multi_lib, "rt_set_scene_multi");
+    g_mapi.scene_status = (decltype(g_mapi.scene_status)) dlsym(g_multi_lib, "rt_multi_set_scene_status");
+    if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold || !g_mapi.set_geometry || !g_mapi.query_ctx || !g_mapi.stream ||
+        !g_mapi.set_scene || !g_mapi.scene_status)
+        die_text("libmi355rt_multi.so", "missing entry points");
 }
 
 // the Scene's objects and lights as the ABI's flat arrays
@@ -160,6 +170,14 @@ struct FlatScene {
 size_t g_n_objects = 0, g_n_lights = 0; // of the scene init_update() loaded: what mi355rt_update_scene may replace
 std::vector<uint8_t> g_light_kind;
 
+// The context the queries run on and its stream: the single context on the default stream, or with several devices the multi-GPU
+// object's query context on its root stream (behind mi355rt_update_scene's update of the root).  NULL before init_update().
+rt_ctx *query_ctx(void **stream)
+{
+    *stream = g_multi ? g_mapi.stream(g_multi) : nullptr;
+    return g_multi ? g_mapi.query_ctx(g_multi) : g_ctx;
+}
+
 } // namespace
 
 // Exported so a host can install / query without new headers.
@@ -175,7 +193,9 @@ extern "C" int mi355rt_update_download(void *host_dst, size_t bytes)
 }
 extern "C" unsigned int mi355rt_update_format(void) { return g_format; }
 // What lies under pixel (x, y) (row 0 = bottom) of the frame the last update() drew: rt_pick with that call's camera.  Single-context
-// back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices, before the first update(), and for supersampling contexts.
+// back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices (tests/test_gbuffer_gpu.py pins that answer; there
+// mi355rt_update_pick_path with max_segments = 1 returns the same record, and a caller of the C ABI has rt_multi_query_ctx), before the
+// first update(), and for supersampling contexts.
 extern "C" int mi355rt_update_pick(unsigned int x, unsigned int y, rt_hit *out)
 {
     if (!g_ctx || !g_have_cam || !out) {
@@ -189,22 +209,24 @@ extern "C" int mi355rt_update_pick(unsigned int x, unsigned int y, rt_hit *out)
 
 // Pick through mirrors: the path of pixel (x, y)'s primary ray along its mirror bounces (rt_pick_paths with the camera of the last
 // update()): `segments` receives max_segments rt_hit records (NULL iff max_segments == 0; segments the path did not reach are miss
-// records), *end what the pixel finally shows.  Refused where mi355rt_update_pick is.
+// records), *end what the pixel finally shows.  One device or several (the multi-GPU object's query context); RT_ERR_INVALID before the
+// first update() and for supersampling contexts.
 extern "C" int mi355rt_update_pick_path(unsigned int x, unsigned int y, rt_hit *segments, unsigned int max_segments, rt_path_end *end)
 {
-    if (!g_ctx || !g_have_cam || !end) {
-        rt_set_last_error(g_multi ? "mi355rt_update_pick_path: not available with several devices (MI355RT_DEVICES)"
-                                  : (!end ? "mi355rt_update_pick_path: null argument" : "mi355rt_update_pick_path: no update() call yet"));
+    void *stream = nullptr;
+    rt_ctx *ctx = query_ctx(&stream);
+    if (!ctx || !g_have_cam || !end) {
+        rt_set_last_error(!end ? "mi355rt_update_pick_path: null argument" : "mi355rt_update_pick_path: no update() call yet");
         return RT_ERR_INVALID;
     }
     const uint32_t xy[2] = {x, y};
-    return rt_pick_paths(g_ctx, g_last_cam, xy, 1, max_segments, segments, end, nullptr);
+    return rt_pick_paths(ctx, g_last_cam, xy, 1, max_segments, segments, end, stream);
 }
 
 // Which objects the frame of the last update() shows, where and how far away: rt_object_extents_host with that call's camera, for the
 // pixels of rect = x0, y0, x1, y1 (inclusive; NULL = the whole frame); n = the number of objects of the loaded scene, one record each.
-// Single-context back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices, before the first update(), for another n
-// and for supersampling contexts.
+// Single-context back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices (a caller of the C ABI has
+// rt_object_extents_multi), before the first update(), for another n and for supersampling contexts.
 extern "C" int mi355rt_update_extents(const unsigned rect[4], rt_object_extent *out, unsigned n)
 {
     if (!g_ctx || !g_have_cam || !out) {
@@ -220,37 +242,42 @@ extern "C" int mi355rt_update_extents(const unsigned rect[4], rt_object_extent *
 }
 
 // The closest hit of n caller-supplied rays against the scene init_update() loaded (rt_trace_rays_host; include/mi355rt.h, "Ray
-// queries").  Valid after init_update(): unlike picking it needs no earlier update() call, a ray query uses no camera.  Single-context
-// back end only: RT_ERR_INVALID with MI355RT_DEVICES naming several devices and before init_update().
+// queries").  Valid after init_update(): unlike picking it needs no earlier update() call, a ray query uses no camera.  One device or
+// several (the multi-GPU object's query context); RT_ERR_INVALID before init_update().
 extern "C" int mi355rt_update_trace(const rt_ray *rays, unsigned int n, rt_hit *out)
 {
-    if (!g_ctx) {
-        rt_set_last_error(g_multi ? "mi355rt_update_trace: not available with several devices (MI355RT_DEVICES)" : "mi355rt_update_trace: no init_update() call yet");
+    void *stream = nullptr;
+    rt_ctx *ctx = query_ctx(&stream);
+    if (!ctx) {
+        rt_set_last_error("mi355rt_update_trace: no init_update() call yet");
         return RT_ERR_INVALID;
     }
-    return rt_trace_rays_host(g_ctx, rays, n, out, nullptr);
+    return rt_trace_rays_host(ctx, rays, n, out, stream);
 }
 
 // The reference's colour of n caller-supplied rays (rt_shade_rays_host; include/mi355rt.h, "Ray queries"): n x 4 float32, (r, g, b, 1).
 // Valid after init_update() like mi355rt_update_trace, and refused where that is.
 extern "C" int mi355rt_update_shade(const rt_ray *rays, unsigned int n, float *rgba_out)
 {
-    if (!g_ctx) {
-        rt_set_last_error(g_multi ? "mi355rt_update_shade: not available with several devices (MI355RT_DEVICES)" : "mi355rt_update_shade: no init_update() call yet");
+    void *stream = nullptr;
+    rt_ctx *ctx = query_ctx(&stream);
+    if (!ctx) {
+        rt_set_last_error("mi355rt_update_shade: no init_update() call yet");
         return RT_ERR_INVALID;
     }
-    return rt_shade_rays_host(g_ctx, rays, n, rgba_out, nullptr);
+    return rt_shade_rays_host(ctx, rays, n, rgba_out, stream);
 }
 
 // Move the objects and lights of the scene init_update() loaded: the same number of objects and lights, every light of its kind, the new
 // coefficients, materials, light vectors and colours (rt_set_scene_host; include/mi355rt.h, "Scene updates").  Valid after init_update();
 // the next update() draws the new scene.  RT_ERR_SCENE when the update would change the scene's layout (nothing is written then),
-// RT_ERR_INVALID for other counts or kinds, before init_update() and with MI355RT_DEVICES naming several devices: the multi-GPU layer
-// has no scene-update entry point.  Image size, background, field of view and max_reflections of `scene` are not looked at.
+// RT_ERR_INVALID for other counts or kinds and before init_update().  With several devices (MI355RT_DEVICES) every context is updated
+// (rt_set_scene_multi) and the call waits for all of them (rt_multi_set_scene_status).  Image size, background, field of view and
+// max_reflections of `scene` are not looked at.
 extern "C" int mi355rt_update_scene(const Scene &scene)
 {
-    if (!g_ctx) {
-        rt_set_last_error(g_multi ? "mi355rt_update_scene: not available with several devices (MI355RT_DEVICES)" : "mi355rt_update_scene: no init_update() call yet");
+    if (!g_ctx && !g_multi) {
+        rt_set_last_error("mi355rt_update_scene: no init_update() call yet");
         return RT_ERR_INVALID;
     }
     const FlatScene flat(scene);
@@ -269,7 +296,19 @@ extern "C" int mi355rt_update_scene(const Scene &scene)
         u.light_p = flat.light_p.data();
         u.light_color = flat.light_c.data();
     }
-    return rt_set_scene_host(g_ctx, &u, nullptr);
+    if (!g_multi) return rt_set_scene_host(g_ctx, &u, nullptr);
+    uint64_t before = 0, after = 0;
+    uint32_t reason = 0, index = 0;
+    if (int rc = g_mapi.scene_status(g_multi, nullptr, &before, nullptr, nullptr)) return rc;
+    if (int rc = g_mapi.set_scene(g_multi, &u)) return rc;
+    if (int rc = g_mapi.scene_status(g_multi, nullptr, &after, &reason, &index)) return rc;
+    if (after != before) {
+        char text[160];
+        std::snprintf(text, sizeof(text), "mi355rt_update_scene: update rejected by every context, nothing was written: reason %u at index %u: see RT_SCENE_REJECT_*", reason, index);
+        rt_set_last_error(text);
+        return RT_ERR_SCENE;
+    }
+    return RT_OK;
 }
 
 void init_update(unsigned int texture, const Scene &scene)

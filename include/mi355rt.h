@@ -300,6 +300,14 @@ int rt_download(rt_ctx *ctx, void *host_dst, size_t bytes);
  * [world][max_local_rows][width] pixels in rank order, `full` receives [height][width] pixels in row order.
  * Both are device pointers; enqueued on `stream`. */
 int rt_assemble(rt_ctx *ctx, const void *gathered, void *full, void *stream);
+/* rt_assemble for planes that are not frames (the G-buffer's object, t and normal planes; what a torch.distributed host calls after its
+ * own gather): gathered + q * slot_stride_bytes = rank q's [max_local_rows][width] elements of elem_bytes (4, 8 or 16) each; full
+ * receives [height][width] elements in row order.  Row ownership is the context's (band_rows, world), i.e. exactly the mapping of
+ * rt_assemble.  Device pointers, enqueued on `stream`: one kernel (csrc/rt_planes.hip), elements moved as they are.  RT_ERR_INVALID,
+ * before a device is looked for: NULL arguments, another elem_bytes, a stride smaller than one slot or not a multiple of elem_bytes,
+ * pointers not aligned to elem_bytes, `full` overlapping `gathered`, and supersampling contexts (their row map is the output frame's,
+ * as for rt_render_gbuffer, which refuses them too). */
+int rt_assemble_planes(rt_ctx *ctx, const void *gathered, size_t slot_stride_bytes, void *full, uint32_t elem_bytes, void *stream);
 
 /* Sparse transport of a frame (what `rt_assemble` does, with fewer bytes over the links): most 16x16 tiles of a
  * typical frame are pure background, so a rank may send only the others.  rt_pack_sparse turns this rank's rows
@@ -374,8 +382,8 @@ int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed);
  * of a normal component that is itself an exact zero, and only for a hit point with a negative-zero coordinate.)
  *
  * Limits: primary hit only; contexts created with RT_FLAG_SSAA2, RT_FLAG_SSAA4 or RT_FLAG_SSAA_ADAPTIVE are refused (their frame
- * arguments describe another pixel grid; supporting them is a follow-up); the multi-GPU layer (rt_*_multi) has no G-buffer entry
- * point -- a rank-level caller gathers the planes itself with rt_row_map.
+ * arguments describe another pixel grid; supporting them is a follow-up); the multi-GPU layer's entry point is
+ * rt_render_gbuffer_multi ("Several GPUs"); a rank-level caller gathers the planes itself with rt_row_map and rt_assemble_planes.
  *
  * The pass reads the context's scene (constant between rt_set_scene calls) and camera-plane tables (constant after rt_create) and
  * nothing else: no tile words, launch-order generations, census, counters or frame tag.  Interleaving it with rt_render, on the same or another stream, changes no image and no
@@ -419,8 +427,8 @@ int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_t n, r
  * RT_FLAG_COUNT it books nothing) or frame tag --, needs no ordering against rt_render, and does need the caller's ordering against
  * rt_set_scene on another stream ("Scene updates").  Only the tiles that meet `rect` are traced.
  *
- * Out of scope: the multi-GPU layer (rt_*_multi) has no such entry point -- a rank-level caller merges the ranks' records itself;
- * supersampling contexts are refused as by rt_render_gbuffer; and only the primary hit counts: an object seen through a mirror is
+ * The multi-GPU layer's entry point is rt_object_extents_multi ("Several GPUs"); a rank-level caller merges the ranks' records with
+ * rt_merge_object_extents.  Out of scope: supersampling contexts are refused as by rt_render_gbuffer; and only the primary hit counts: an object seen through a mirror is
  * not seen (a caller that wants it reduces the `dev_last` records of rt_trace_paths on the rays of rt_primary_rays itself).
  * ------------------------------------------------------------------------------------------------- */
 typedef struct rt_object_extent {
@@ -441,6 +449,12 @@ int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32_t rect[4] 
  * capturing stream is refused (RT_ERR_INVALID): the call allocates and waits. */
 int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const uint32_t rect[4],
                            rt_object_extent *out_host, void *stream);   /* blocks */
+/* The records of several ranks into one: dev_parts = [n_parts][n_objects] records (n_objects = the context's); dev_out[i] = pixels summed,
+ * x_min / y_min / t_min the minimum, x_max / y_max / t_max the maximum over the parts.  t is compared as the unsigned integer of its
+ * bits, as the reduction kernel does.  All-identity in gives identity out, bit for bit.  Device pointers, one kernel on `stream`
+ * (csrc/rt_planes.hip); a scene without objects returns RT_OK and enqueues nothing.  RT_ERR_INVALID, before a device is looked for:
+ * NULL arguments, n_parts == 0, records not 8-byte aligned, an output that overlaps the parts. */
+int rt_merge_object_extents(rt_ctx *ctx, const rt_object_extent *dev_parts, uint32_t n_parts, rt_object_extent *dev_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * Ray queries: closest hit, occlusion and colour for rays the caller supplies (csrc/rt_rays.hip, csrc/rt_shade_rays.hip; DESIGN.md
@@ -481,7 +495,7 @@ int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const uint32_t rec
  * Ray queries carry no frame state, so they work in EVERY context: plain, RT_FLAG_SSAA2 / RT_FLAG_SSAA4, adaptive, any rank or world,
  * any format.  They read the scene blob and nothing else -- no camera tables, tile words, launch-order generations, census, counters
  * or frame tag -- and need no ordering against rt_render (against rt_set_scene they do: "Scene updates").  Scenes whose class
- * tables exceed the LDS limit are refused as rt_render_gbuffer refuses them.  Limits: the multi-GPU layer (rt_*_multi) has no ray-query entry point.
+ * tables exceed the LDS limit are refused as rt_render_gbuffer refuses them.  With several GPUs they are called on rt_multi_query_ctx's context ("Several GPUs").
  *
  * Colour (rt_shade_rays; csrc/rt_shade_rays.hip).  The reference's render_pixel (src/update-cpu.cpp:82-119) with
  * ray_origin := o and dir := d, d used exactly as given, never normalised.  The first segment is get_color_and_object
@@ -559,7 +573,7 @@ int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_
  * FMA-contracted build, whose results are their own arithmetic.
  * No frame state: paths work in every context kind, supersampling included, need no ordering against rt_render (against rt_set_scene on
  * another stream the ordering is the caller's, "Scene updates"), are one kernel with ms == NULL (capturable into a graph), and
- * RT_FLAG_COUNT books none of their rays.  The multi-GPU layer (rt_*_multi) has no such entry point. */
+ * RT_FLAG_COUNT books none of their rays.  With several GPUs: rt_multi_query_ctx's context. */
 #define RT_PATH_MISS 0u     /* the ray itself hits nothing; segments = 0 */
 #define RT_PATH_SURFACE 1u  /* the last hit is no mirror: that is what the ray finally shows */
 #define RT_PATH_ESCAPED 2u  /* a bounce left the scene: the reference blends the background */
@@ -637,7 +651,7 @@ int rt_pick_paths(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_
  * rt_occluded_rays, rt_shade_rays, rt_trace_paths, rt_primary_rays, rt_pick_paths and their _host forms -- need no ordering against rt_render, but they DO need ordering against
  * rt_set_scene when issued on another stream, and that ordering is the caller's to establish (on one stream it is automatic).
  * Frame-to-frame state (launch order, census, tile words) survives an update: it affects speed only, never the image, exactly as under
- * a moving camera.  Works in every context kind.  The multi-GPU layer (rt_*_multi) has no scene-update entry point.
+ * a moving camera.  Works in every context kind.  The multi-GPU layer's entry point is rt_set_scene_multi ("Several GPUs").
  * ------------------------------------------------------------------------------------------------- */
 typedef struct rt_scene_update {
     const double *coefs;       /* [n_objects][RT_NCOEF]  or NULL */
@@ -718,6 +732,39 @@ int rt_multi_last_transfer(const rt_multi *m, uint64_t *bytes_sent, uint64_t *by
 int rt_multi_set_ssaa_threshold(rt_multi *m, float tau);
 /* rt_set_ssaa_geometry on every context of the object (RT_FLAG_SSAA_GEOMETRY objects only). */
 int rt_multi_set_ssaa_geometry(rt_multi *m, float min_cos);
+/* Scene updates, queries, G-buffer and extents with several GPUs (csrc/rt_multi.cpp; DESIGN.md section 21 has the stream and event
+ * order of each call).  All of them refuse an object on which an earlier call failed with part of it enqueued, as rt_render_multi
+ * does, and leave the calling thread on the device it came with.
+ *
+ * rt_set_scene_multi: rt_set_scene on every context.  The arrays are in HOST memory, with the meaning of rt_set_scene_host (NULL =
+ * keep, not all five).  The call copies them into a pinned block the object owns and, on every device's RENDER stream, enqueues the
+ * upload into that device's copy and rt_set_scene for each of its contexts; it does not wait for them -- only, before it overwrites
+ * the pinned block and the device copies, for the previous call's uploads and kernels.  The update is therefore ordered with every
+ * context's frames exactly as on a single context: frames enqueued before it show the old scene, frames after it the new one.  Whether
+ * it was applied is on the devices: rt_multi_set_scene_status waits for every context's last call and returns context 0's numbers
+ * (every context gives the same verdict: the layout rule depends on the scene alone; RT_ERR_DEVICE if they ever differ).  A call that
+ * fails after the first context has been enqueued leaves the contexts with different scenes and the object failed. */
+int rt_set_scene_multi(rt_multi *m, const rt_scene_update *host);
+int rt_multi_set_scene_status(rt_multi *m, uint64_t *applied, uint64_t *rejected, uint32_t *reason, uint32_t *index);
+/* The root's context 0, borrowed until rt_multi_destroy, for the queries that depend neither on row ownership nor on frame state:
+ * rt_pick, rt_pick_paths, rt_primary_rays, rt_trace_rays, rt_occluded_rays, rt_shade_rays, rt_trace_paths and their _host forms, all on
+ * rt_multi_stream(m), where they are ordered behind rt_set_scene_multi on the root.  Nothing else may be called on it: frames, scene
+ * updates, the G-buffer, extents, thresholds and its destruction are the object's business.  NULL for a NULL object. */
+rt_ctx *rt_multi_query_ctx(rt_multi *m);
+/* rt_render_gbuffer over all contexts: full [height][width] planes in device memory on devices[0]; any of the three pointers may be
+ * NULL, not all three.  Each context runs rt_render_gbuffer for its rows on its render stream, the rows travel to the root as the dense
+ * frame's rows do under the object's transport (RT_MULTI_BANDWISE and RT_MULTI_SPARSE objects use the plain dense choreography here), and
+ * rt_assemble_planes rebuilds each requested plane on rt_multi_stream(m).  Enqueue-only unless ms is given: then the device time on the
+ * root from the first G-buffer kernel to the last reassembly.  Row y of every plane is bit for bit the row rt_render_gbuffer writes on a
+ * context of that rank, world and band size; in strict contexts and for surfaces of degree <= 2 the planes therefore equal a single
+ * context's.  The contexts' own refusals pass through unchanged (supersampling, scenes beyond the LDS limit). */
+int rt_render_gbuffer_multi(rt_multi *m, const double cam[16], int32_t *root_object, double *root_t, float *root_normal, float *ms);
+/* rt_object_extents over all contexts: each writes its records, the world x n_objects records travel to the root by device copies and
+ * rt_merge_object_extents merges them on rt_multi_stream(m) into root_dev_out (device memory on devices[0], 8-byte aligned).  ms as
+ * above.  The result is the merge of the rank-level records, always, and equals a single context's records in strict contexts for
+ * surfaces of degree <= 2.  The _host form writes host memory and blocks. */
+int rt_object_extents_multi(rt_multi *m, const double cam[16], const uint32_t rect[4], rt_object_extent *root_dev_out, float *ms);
+int rt_object_extents_multi_host(rt_multi *m, const double cam[16], const uint32_t rect[4], rt_object_extent *out_host);
 int rt_multi_destroy(rt_multi *m);
 
 #ifdef __cplusplus
