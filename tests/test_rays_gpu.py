@@ -299,7 +299,7 @@ def test_every_context_kind_answers_alike(pkg, oracle):
         assert (ref["object"] >= 0).any()
         kinds = [dict(flags=pkg.RT_FLAG_SSAA4), dict(flags=pkg.RT_FLAG_SSAA2 | pkg.RT_FLAG_SSAA_ADAPTIVE | pkg.RT_FLAG_SSAA_GEOMETRY),
                  dict(rank=1, world=3, band_rows=5), dict(fmt=pkg.RT_FMT_RGBA8), dict(flags=pkg.RT_FLAG_SIMPLE), dict(flags=pkg.RT_FLAG_NOCULL),
-                 dict(flags=pkg.RT_FLAG_NOLEAN)]
+                 dict(flags=pkg.RT_FLAG_NOLEAN), dict(flags=pkg.RT_FLAG_STREAM)]
         for kw in kinds:
             r = pkg.Renderer(sc, device=0, **kw)
             assert_records(trace_dev(r, rays), ref, kw)
