@@ -29,8 +29,12 @@
 #define RT_KERNELS(V)                                                                                                                              \
     {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
      RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
-     RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V)}
+     RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
+     RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
+     RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
+// the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
+#define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
 
 namespace {
 
@@ -218,6 +222,7 @@ struct rt_ctx {
     MappedWords h_listed;         // host-mapped words the kernel writes (FrameArgs::ord_host)
     uint32_t ord_split = 0;       // FrameArgs::ord_split of non-sparse frames
     std::vector<double> cub_coefs; // the 20 coefficients of the first RT_CUB_AT_MAX degree-3 objects (FrameArgs::cub_at is formed from them every frame)
+    bool stream_queries = false;  // the queries are the streamed kernels (rt_stream_queries.hip): RT_FLAG_STREAM_QUERIES on a streamed context or on a scene whose tables the staged query kernels cannot hold in LDS
     bool streamed = false;        // rt_render is the streamed frame kernel (rt_stream.hip): RT_FLAG_STREAM, or a scene whose tables the context's own kernel cannot hold in LDS
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
@@ -515,6 +520,8 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
         return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", lds);
     ctx->streamed = (ctx->cfg.flags & RT_FLAG_STREAM) || lds > 160u * 1024u;
     if (ctx->streamed) ctx->lean_ok = false;
+    // ... and which kernels are the queries?  One decision per context: rt_set_scene cannot change the layout.
+    ctx->stream_queries = (ctx->cfg.flags & RT_FLAG_STREAM_QUERIES) && (ctx->streamed || rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u);
     if (ctx->adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)",
                     (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)));
@@ -922,7 +929,7 @@ static int gbuffer_args(const char *who, rt_ctx *ctx, const double cam[16], Fram
     fa.ord_host = nullptr;
     fa.tile_state = nullptr;
     rtf::frame_origin(fa, cam, ctx->cub_coefs);
-    if (rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
+    if (!ctx->stream_queries && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "%s: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", who, rt_gbuffer_lds_bytes_strict(&fa));
     return use_device(ctx);
 }
@@ -935,7 +942,7 @@ extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev
     FrameArgs fa;
     if (int rc = gbuffer_args("rt_render_gbuffer", ctx, cam, fa)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->kern->gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "G-buffer kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -960,7 +967,7 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
     if (int rc = gbuffer_args("rt_pick", ctx, cam, fa)) return rc;
     if (int rc = ctx->pick.reserve(n, sizeof(uint32_t) * 2, sizeof(rt_hit))) return rc;
     RT_HIP(hipMemcpyAsync(ctx->pick.in, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = ctx->kern->pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pick kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out_host, ctx->pick.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1004,7 +1011,7 @@ extern "C" int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32
     if (int rc = extents_args("rt_object_extents", ctx, cam, rect, dev_out, true, fa, r)) return rc;
     if (fa.n_obj == 0u) return RT_OK;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->kern->object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents: kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1021,7 +1028,7 @@ extern "C" int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const u
         return fail(RT_ERR_INVALID, "rt_object_extents_host: the stream is capturing, and this call allocates and waits; capture rt_object_extents (device memory) instead");
     if (fa.n_obj == 0u) return RT_OK;
     if (int rc = ctx->ext.reserve(fa.n_obj, 8, sizeof(rt_object_extent))) return rc;
-    const hipError_t e = ctx->kern->object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents_host: kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out_host, ctx->ext.out, sizeof(rt_object_extent) * (size_t) fa.n_obj, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1039,7 +1046,7 @@ static bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 
 static int rays_ready(const char *who, rt_ctx *ctx)
 {
-    if (rt_rays_lds_bytes_strict(&ctx->fa) > 160u * 1024u)
+    if (!ctx->stream_queries && rt_rays_lds_bytes_strict(&ctx->fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "%s: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", who, rt_rays_lds_bytes_strict(&ctx->fa));
     return use_device(ctx);
 }
@@ -1058,7 +1065,7 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt
     hipStream_t stream = (hipStream_t) stream_;
     if (int rc = rays_ready("rt_trace_rays", ctx)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->kern->trace_rays(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, trace_rays)(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1075,7 +1082,7 @@ extern "C" int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const doubl
     hipStream_t stream = (hipStream_t) stream_;
     if (int rc = rays_ready("rt_occluded_rays", ctx)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->kern->occluded_rays(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, occluded_rays)(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1089,7 +1096,7 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
     if (int rc = rays_ready("rt_trace_rays_host", ctx)) return rc;
     if (int rc = ctx->rq.reserve(n, sizeof(rt_ray), sizeof(rt_hit))) return rc;
     RT_HIP(hipMemcpyAsync(ctx->rq.in, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = ctx->kern->trace_rays(&ctx->fa, ctx->d_obj, ctx->rq.in, n, ctx->rq.out, rays_max_grid(ctx), stream);
+    const hipError_t e = RT_QUERY_KERNEL(ctx, trace_rays)(&ctx->fa, ctx->d_obj, ctx->rq.in, n, ctx->rq.out, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out, ctx->rq.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1100,7 +1107,7 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
 // Like the ray queries it reads the scene (blob and lights) and nothing of the frame; always 4 x float32 per ray, whatever cfg.format.
 static hipError_t shade_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, float *dev_rgba, void *dev_hits, hipStream_t stream)
 {
-    return ctx->kern->shade_rays(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
+    return RT_QUERY_KERNEL(ctx, shade_rays)(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
 }
 
 extern "C" int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits, void *stream_, float *ms)
@@ -1141,7 +1148,7 @@ extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, f
 // Like the ray queries the path kernel reads the scene blob and nothing of the frame.
 static hipError_t paths_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, uint32_t max_segments, void *dev_segments, void *dev_last, void *dev_ends, hipStream_t stream)
 {
-    return ctx->kern->trace_paths(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), stream);
+    return RT_QUERY_KERNEL(ctx, trace_paths)(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), stream);
 }
 
 extern "C" int rt_trace_paths(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, uint32_t max_segments, rt_hit *dev_segments, rt_hit *dev_last, rt_path_end *dev_ends,
@@ -1551,6 +1558,13 @@ extern "C" int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels)
     uint32_t n = 0;
     if (int rc = read_synced(ctx, &n, ctx->d_list + (size_t) ctx->local_rows * ctx->width, sizeof(n))) return rc;
     *pixels = n;
+    return RT_OK;
+}
+
+extern "C" int rt_get_streamed_queries(const rt_ctx *ctx, uint32_t *streamed)
+{
+    if (!ctx || !streamed) return fail(RT_ERR_INVALID, "rt_get_streamed_queries: null argument");
+    *streamed = ctx->stream_queries ? 1u : 0u;
     return RT_OK;
 }
 

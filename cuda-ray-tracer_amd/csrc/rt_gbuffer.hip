@@ -13,6 +13,7 @@
 #include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_shade.hpp"          // RT_SYM and the variant's namespace
 #include "rt_wavefront_math.hpp" // class-table coefficients, us_needs_solve, accept, sphere_in_cone, sphere_normal
+#include "rt_extents.hpp"        // the extent record, its merge and the rectangle's tiles: shared with rt_stream_queries.hip
 
 namespace RT_SYM(rtk) {
 
@@ -318,42 +319,10 @@ extern "C" hipError_t RT_SYM(rt_launch_gbuffer_edges)(const FrameArgs *fa, const
 // per-lane function are gbuffer_kernel's, so a record is the reduction of that kernel's planes bit for bit; the normal is not formed.
 namespace RT_SYM(rtk) {
 
-// One rt_object_extent as the kernels update it: t_min / t_max as the bits of the double (t is in [1e-7, 1e6), so the bits order as
-// unsigned integers and +inf / +0.0 are the identities of min / max).
-struct ExtRecord {
-    unsigned long long pixels;
-    uint32_t x_min, y_min, x_max, y_max;
-    unsigned long long t_min, t_max;
-};
-static_assert(sizeof(ExtRecord) == 40, "rt_object_extent layout");
-#define RT_EXT_INF_BITS 0x7FF0000000000000ull
-
-// what the launcher derives from the rectangle: its columns, this rank's LOCAL rows inside it, and the tiles that meet both
-struct ExtArgs {
-    uint32_t x0, x1, lr0, lr1; // inclusive
-    uint32_t tx0, ty0, ntx;    // first tile column / tile row, tile columns
-    uint32_t n_tiles;          // tiles to trace
-    uint32_t lds_acc;          // 1: one ExtRecord per object in LDS behind the tables, flushed once per workgroup; 0: every wave updates `out`
-};
-
 __global__ __launch_bounds__(256) void extents_init_kernel(ExtRecord *__restrict__ out, uint32_t n)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i < n) out[i] = ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull};
-}
-
-// merge one partial record into r: seven atomics whose result does not depend on their order
-template <int SCOPE>
-__device__ __forceinline__ void ext_merge(ExtRecord *r, unsigned long long n, uint32_t x_min, uint32_t y_min, uint32_t x_max, uint32_t y_max, unsigned long long t_min,
-                                          unsigned long long t_max)
-{
-    __hip_atomic_fetch_add(&r->pixels, n, __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_min(&r->x_min, x_min, __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_min(&r->y_min, y_min, __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_max(&r->x_max, x_max, __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_max(&r->y_max, y_max, __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_min(&r->t_min, t_min, __ATOMIC_RELAXED, SCOPE);
-    __hip_atomic_fetch_max(&r->t_max, t_max, __ATOMIC_RELAXED, SCOPE);
 }
 
 // A few workgroups per CU, each striding over the tiles that meet the rectangle.  Three levels: the wave reduces the lanes of each distinct
@@ -405,7 +374,7 @@ __global__ __launch_bounds__(256) void extents_kernel(const FrameArgs fa, const 
         const bool counted = live && best >= 0 && x >= ea.x0 && x <= ea.x1 && lr >= ea.lr0 && lr <= ea.lr1;
         const unsigned long long tb = (unsigned long long) __double_as_longlong(best_t);
         unsigned long long todo = __ballot(counted);
-        while (todo) { // wave-uniform: one turn per distinct object among the counted lanes
+        while (todo) { // wave-uniform: one turn per distinct object among the counted lanes (rt_extents.hpp: ext_reduce_wave, with the LDS records in front)
             const int id = __builtin_amdgcn_readlane(best, __builtin_ctzll(todo));
             const bool mine = counted && best == id;
             const unsigned long long mask = __ballot(mine); // bit 8 r + c: row r, column c of the block
@@ -466,28 +435,8 @@ extern "C" hipError_t RT_SYM(rt_launch_object_extents)(const FrameArgs *fa, cons
     hipLaunchKernelGGL(extents_init_kernel, dim3((fa->n_obj + 255u) / 256u), dim3(256), 0, stream, rec, fa->n_obj);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // this rank's local rows inside [y0, y1]: the global row rises with the local one
-    const auto grow = [&](uint32_t lr) { const uint32_t b = lr / fa->band_rows; return (uint64_t) (b * (uint64_t) fa->world + fa->rank) * fa->band_rows + (lr - b * fa->band_rows); };
-    const auto first_at_least = [&](uint64_t y) { // the first local row whose global row is >= y (local_rows if none)
-        uint32_t lo = 0, hi = fa->local_rows;
-        while (lo < hi) {
-            const uint32_t mid = lo + (hi - lo) / 2u;
-            if (grow(mid) >= y) hi = mid;
-            else lo = mid + 1u;
-        }
-        return lo;
-    };
-    const uint32_t lr_lo = first_at_least(rect[1]), lr_end = first_at_least((uint64_t) rect[3] + 1u);
-    if (lr_lo >= lr_end) return hipSuccess; // no row of the rectangle is this rank's: the identities stand
     ExtArgs ea;
-    ea.x0 = rect[0];
-    ea.x1 = rect[2];
-    ea.lr0 = lr_lo;
-    ea.lr1 = lr_end - 1u;
-    ea.tx0 = ea.x0 / 16u;
-    ea.ty0 = ea.lr0 / 16u;
-    ea.ntx = ea.x1 / 16u - ea.tx0 + 1u;
-    ea.n_tiles = ea.ntx * (ea.lr1 / 16u - ea.ty0 + 1u);
+    if (!ext_args(fa, rect, ea)) return hipSuccess; // no row of the rectangle is this rank's: the identities stand
     const size_t tables = RT_SYM(rt_gbuffer_lds_bytes)(fa);
     ea.lds_acc = RT_SYM(rt_extents_lds_accumulators)(tables, fa->n_obj) ? 1u : 0u;
     const size_t lds = RT_SYM(rt_extents_lds_bytes)(fa);

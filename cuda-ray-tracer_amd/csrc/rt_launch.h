@@ -69,6 +69,21 @@ RT_PER_VARIANT(hipError_t, rt_launch_primary_rays, const FrameArgs *fa, const do
 // rt_stream.hip: the streamed frame kernel (scenes of any size)
 RT_PER_VARIANT(hipError_t, rt_launch_stream, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
                hipStream_t stream)
+// rt_stream_queries.hip: the streamed twins of the query launchers above (RT_FLAG_STREAM_QUERIES), each with its twin's signature
+RT_PER_VARIANT(hipError_t, rt_launch_stream_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
+               float *out_normal, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n,
+               void *out, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_object_extents, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect,
+               void *out, uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
+               hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_occluded_rays, const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
+               uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba,
+               void *hits, uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
+               void *last, void *ends, uint32_t max_grid, hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -88,6 +103,14 @@ struct Kernels {
     decltype(&rt_launch_trace_paths_strict) trace_paths;
     decltype(&rt_launch_primary_rays_strict) primary_rays;
     decltype(&rt_launch_stream_strict) stream;
+    // the query launchers of a context whose queries are streamed (rt_get_streamed_queries): the types are the staged twins'
+    decltype(&rt_launch_gbuffer_strict) stream_gbuffer;
+    decltype(&rt_launch_pick_strict) stream_pick;
+    decltype(&rt_launch_object_extents_strict) stream_object_extents;
+    decltype(&rt_launch_trace_rays_strict) stream_trace_rays;
+    decltype(&rt_launch_occluded_rays_strict) stream_occluded_rays;
+    decltype(&rt_launch_shade_rays_strict) stream_shade_rays;
+    decltype(&rt_launch_trace_paths_strict) stream_trace_paths;
 };
 
 // rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements

@@ -16,20 +16,6 @@
 
 namespace RT_SYM(rtk) {
 
-struct PathArgs {
-    RayQueryArgs qa;
-    uint32_t max_refl, max_segments;
-};
-
-// One rt_path_end (include/mi355rt.h) as one 16-byte word
-struct alignas(16) PathEnd {
-    uint32_t segments, end;
-    float ratio;
-    int32_t object;
-};
-static_assert(sizeof(PathEnd) == 16, "rt_path_end layout");
-enum : uint32_t { PATH_MISS = 0u, PATH_SURFACE = 1u, PATH_ESCAPED = 2u, PATH_CAP = 3u }; // RT_PATH_*
-
 // 256-thread workgroups, one ray per lane, the grid-stride loop of ray_query_kernel; the class tables go to LDS once per workgroup.
 // Per ray one bounce loop for the whole wave: iteration k traces segment k of every lane that is still bouncing, and every lane with a
 // ray -- done or not -- stores its record of plane k while k < max_segments (a lane that is done stores the miss record), so the wave's

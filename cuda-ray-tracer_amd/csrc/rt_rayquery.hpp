@@ -178,6 +178,27 @@ static inline RayQueryArgs rq_args(const FrameArgs *fa, uint32_t n)
     return qa;
 }
 
+// the argument words of the colour kernels (rt_shade_rays.hip, rt_stream_queries.hip) and of the path kernels (rt_paths.hip, rt_stream_queries.hip)
+struct ShadeRaysArgs {
+    RayQueryArgs qa;
+    uint32_t n_lights, max_refl;
+    float bg[3];
+};
+
+struct PathArgs {
+    RayQueryArgs qa;
+    uint32_t max_refl, max_segments;
+};
+
+// One rt_path_end (include/mi355rt.h) as one 16-byte word
+struct alignas(16) PathEnd {
+    uint32_t segments, end;
+    float ratio;
+    int32_t object;
+};
+static_assert(sizeof(PathEnd) == 16, "rt_path_end layout");
+enum : uint32_t { PATH_MISS = 0u, PATH_SURFACE = 1u, PATH_ESCAPED = 2u, PATH_CAP = 3u }; // RT_PATH_*
+
 // the hit record of a ray (o, d) whose nearest hit is object `best` at best_t with normal nv at point p; a miss for best < 0
 __device__ __forceinline__ void rq_store_record(RqRecord *__restrict__ dst_rec, int best, double best_t, const D3 &p, const D3 &nv)
 {

@@ -15,12 +15,6 @@
 
 namespace RT_SYM(rtk) {
 
-struct ShadeRaysArgs {
-    RayQueryArgs qa;
-    uint32_t n_lights, max_refl;
-    float bg[3];
-};
-
 // One object loop for the ray (o, d) of every lane in `use`: through the tables where rq_tables_proven says so, the plain path for
 // the other lanes.  OCCLUSION: best = 1 once something blocks before t_max.
 template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>

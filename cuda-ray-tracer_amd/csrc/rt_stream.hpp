@@ -3,8 +3,8 @@
 // The chunks are the chunks rq_tables iterates over and a chunk's body is rq_tables' body, so a query returns what rq_tables returns
 // for the same ray -- whatever the scene's size.  One ray per lane; the caller owns the whole wave (all 64 lanes call, `use` says which
 // of them have a ray).  Nothing here is workgroup-wide: no barrier, no shared state between waves, so the waves of a workgroup may run
-// any number of queries each.  Written for the streamed frame kernel (rt_stream.hip); the other entry points can take the same loops
-// when they learn large scenes.
+// any number of queries each.  Used by the streamed frame kernel (rt_stream.hip) and by the streamed query kernels
+// (rt_stream_queries.hip).
 // Included by files that are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
 #ifndef RT_STREAM_HPP
 #define RT_STREAM_HPP
@@ -91,9 +91,12 @@ __device__ __forceinline__ void sq_stage_indices(const uint32_t *__restrict__ ta
 // rq_tables with the tables streamed.  scene: the blob (DevObject records first, the tables from qa.off_us on); slice: SQ_SLICE_BYTES of
 // LDS that belong to this wave.  All control flow around the staging is wave-uniform; `use` stays a predicate.  cone.on (primary rays
 // of a block, wave-uniform): the lane that loaded a sphere tests it against the block's cone, and the wave sweeps only the survivors.
-template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+// HOST_CUB (rays from the frame's origin: the G-buffer family, rt_gbuffer.hip: nearest_hit): the first RT_CUB_AT_MAX degree-3 objects
+// take their data at the origin from the host's records in `frame` (cub_rec, cub_abs), indexed by the wave-uniform table position --
+// kernel arguments, read by scalar loads, nothing in LDS.
+template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION, bool HOST_CUB = false>
 __device__ __forceinline__ void sq_tables(const RayQueryArgs &qa, const unsigned char *__restrict__ scene, unsigned char *slice, uint32_t lane, const Mono &m, bool use,
-                                          const SqCone &cone, double t_max, double &best_t, int &best)
+                                          const SqCone &cone, double t_max, double &best_t, int &best, const FrameArgs *frame = nullptr)
 {
 #define SQ_ALL_DECIDED() (OCCLUSION && __ballot(use && best == 0) == 0ull)
     const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
@@ -178,8 +181,16 @@ __device__ __forceinline__ void sq_tables(const RayQueryArgs &qa, const unsigned
                 const uint32_t k = (uint32_t) __builtin_amdgcn_readfirstlane((int) s_cub[j]);
                 if (use && !(OCCLUSION && best != 0)) {
                     // the guarded Taylor test with the surface's data at the lane's own origin, as the ray queries form it
-                    const CubicAt ca = cubic_at(gobj[k].c, m.o);
-                    const CubicAbs ab = cubic_abs(gobj[k].c);
+                    CubicAt ca;
+                    CubicAbs ab;
+                    if (HOST_CUB && base + j < RT_CUB_AT_MAX) { // (wave-uniform)
+                        const double *r = frame->cub_rec[base + j], *a = frame->cub_abs[base + j];
+                        ca = CubicAt{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9]};
+                        ab = CubicAbs{a[0], a[1], a[2], a[3]};
+                    } else {
+                        ca = cubic_at(gobj[k].c, m.o);
+                        ab = cubic_abs(gobj[k].c);
+                    }
                     bool refused;
                     const double t = intersect_cubic_taylor<false>(gobj[k].c, ca, cubic_mag_origin(ab, m.o), m.o, m.d, OCCLUSION ? t_max : MAX_T, OCCLUSION, refused);
                     rq_take<OCCLUSION>(t, (int) k, t_max, best_t, best);

@@ -1,0 +1,474 @@
+// rt_stream_queries.hip -- the streamed query kernels: the G-buffer, picking, object extents, the ray queries, their colour and their
+// paths for scenes of any size (include/mi355rt.h, RT_FLAG_STREAM_QUERIES).
+//
+// Every kernel here is the twin of a kernel that copies all class tables into one workgroup's LDS (rt_gbuffer.hip, rt_rays.hip,
+// rt_shade_rays.hip, rt_paths.hip) and differs from it in one thing: the object loops read the tables from the scene blob in global
+// memory through a wave-private LDS slice, 64 entries at a time (rt_stream.hpp), as the streamed frame kernel does (rt_stream.hip).  The
+// chunks are the staged loops' chunks and a chunk's body is theirs, so in a strict context a streamed kernel returns what its twin
+// returns, bit for bit.  Rays, work geometry, loads, stores and launch bounds are the twin's.
+// Compiled twice like rt_stream.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).
+// There is no workgroup barrier anywhere in this file, and no lane leaves before its wave's last ballot, readlane or staged chunk: a
+// lane without work stays with `use = false`.  Every kernel takes 4 * SQ_SLICE_BYTES = 24 KiB of LDS whatever the tables hold.
+#include <hip/hip_runtime.h>
+#include "rt_launch.h"   // the launchers below, as the host sees them
+#include "rt_stream.hpp" // the streamed object loops; RayQueryArgs, the plain path, the ray and record layouts (rt_rayquery.hpp)
+#include "rt_extents.hpp" // the extent record, its merge and the wave reduction
+
+namespace RT_SYM(rtk) {
+
+// one caller-supplied ray per lane: three 16-byte loads (lanes without a ray keep zeroes)
+__device__ __forceinline__ void sqk_load_ray(const RqRay *__restrict__ rays, uint64_t i, bool live, D3 &o, D3 &d)
+{
+    o = D3{0.0, 0.0, 0.0};
+    d = D3{0.0, 0.0, 0.0};
+    if (live) {
+        const double2 *w = reinterpret_cast<const double2 *>(rays + i);
+        const double2 w0 = w[0], w1 = w[1], w2 = w[2];
+        o = D3{w0.x, w0.y, w1.x};
+        d = D3{w1.y, w2.x, w2.y};
+    }
+}
+
+// ---- closest hit and occlusion (rt_rays.hip: ray_query_kernel) ---------------------------------------------------------------------------
+template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+__global__ __launch_bounds__(256) void ray_query_stream_kernel(const RayQueryArgs qa, const unsigned char *__restrict__ scene, const RqRay *__restrict__ rays,
+                                                               const double *__restrict__ t_max, RqRecord *__restrict__ out_rec, int32_t *__restrict__ out_blocked)
+{
+    __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    unsigned char *slice = smem + wave * SQ_SLICE_BYTES; // this wave's, never another's
+    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
+
+    const uint64_t stride = (uint64_t) gridDim.x * 256u;
+    for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (workgroup-uniform trip count)
+        const uint64_t i = first + tid;
+        const bool live = i < qa.n;
+        D3 o, d;
+        sqk_load_ray(rays, i, live, o, d);
+        double tm = MAX_T;
+        if (OCCLUSION && t_max && live) tm = t_max[i];
+        double best_t = INFINITY;
+        int best = OCCLUSION ? 0 : -1;
+        sq_query<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, slice, lane, o, d, live, false, tm, best_t, best);
+        if (OCCLUSION) {
+            if (live) out_blocked[i] = best;
+        } else if (live) {
+            D3 p{0.0, 0.0, 0.0}, nv{0.0, 0.0, 0.0};
+            if (best >= 0) {
+                p = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
+                nv = normal_vector(gobj[best].c, p); // in full for every class, as ray_query_kernel
+            }
+            rq_store_record(out_rec + i, best, best_t, p, nv);
+        }
+    }
+}
+
+// ---- colour (rt_shade_rays.hip: shade_rays_kernel; the bounce loop is stream_frame_kernel's on caller rays, without a cone) --------------
+template <bool HAS_GQ, bool HAS_CUBIC>
+__global__ __launch_bounds__(256) void shade_rays_stream_kernel(const ShadeRaysArgs sa, const unsigned char *__restrict__ scene, const DevLight *__restrict__ lights,
+                                                                const RqRay *__restrict__ rays, float4 *__restrict__ out_rgba, RqRecord *__restrict__ out_rec)
+{
+    __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
+    const RayQueryArgs &qa = sa.qa;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
+    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
+    const F3 bg{sa.bg[0], sa.bg[1], sa.bg[2]};
+
+    const uint64_t stride = (uint64_t) gridDim.x * 256u;
+    for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (workgroup-uniform trip count)
+        const uint64_t i = first + tid;
+        const bool live = i < qa.n;
+        D3 o, d;
+        sqk_load_ray(rays, i, live, o, d);
+        F3 res = bg; // a first-segment miss is the background colour
+        float cur_ratio = 1.0f;
+        bool bouncing = live;
+        for (uint32_t k = 0; __ballot(bouncing) != 0ull; k++) {
+            // get_color_and_object, src/update-cpu.cpp:45-80: the nearest hit ...
+            double best_t = INFINITY;
+            int best = -1;
+            sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best);
+            const bool hit = bouncing && best >= 0;
+            const DevObject *bo = &gobj[hit ? best : 0]; // per-lane index: gathers from global memory, per hit
+            D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0};
+            if (hit) {
+                sp = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
+                sn = normal_vector(bo->c, sp); // all twenty coefficients; FP64, never flipped
+            }
+            if (k == 0u && out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
+            // ... every light in index order (wave-uniform: scalar loads), shadow_ray from sp + SHADOW_BIAS * sn; a ray the kernel formed, so
+            // sq_query decides anew whether the tables are proven for it
+            const D3 so{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
+            F3 acc{0.0f, 0.0f, 0.0f};
+            if (__ballot(hit) != 0ull) {
+                const F3 albedo{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
+                for (uint32_t l = 0; l < sa.n_lights; l++) {
+                    const DevLight *lt = &lights[l];
+                    const bool spherical = lt->spherical != 0;
+                    double max_t;
+                    const D3 sd = shadow_dir(lt->p, spherical, sp, max_t);
+                    double unused_t = INFINITY;
+                    int blocked = 0;
+                    sq_query<HAS_GQ, HAS_CUBIC, true>(qa, scene, slice, lane, so, sd, hit, false, max_t, unused_t, blocked);
+                    if (hit && blocked == 0) {
+                        const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
+                        acc.x += c.x;
+                        acc.y += c.y;
+                        acc.z += c.z;
+                    }
+                }
+            }
+            if (bouncing) {
+                if (!hit) {
+                    if (k != 0u) RT_SYM(rtk)::blend(res, cur_ratio, bg); // a bounce that leaves the scene picks up the background
+                    bouncing = false;
+                } else {
+                    // glm::min(vec3(1.0f), acc)
+                    const F3 oc{(acc.x < 1.0f) ? acc.x : 1.0f, (acc.y < 1.0f) ? acc.y : 1.0f, (acc.z < 1.0f) ? acc.z : 1.0f};
+                    if (k == 0u) res = oc;
+                    else RT_SYM(rtk)::blend(res, cur_ratio, oc);
+                    // the reflection loop, src/update-cpu.cpp:96-117
+                    const float refl = bo->refl;
+                    if (!((double) refl > EPS)) {
+                        bouncing = false;
+                    } else {
+                        cur_ratio *= refl;
+                        if (k == sa.max_refl) {
+                            RT_SYM(rtk)::blend(res, cur_ratio, bg);
+                            bouncing = false;
+                        } else {
+                            d = reflect_ray(d, sn); // of the direction as it is
+                            o = so;
+                        }
+                    }
+                }
+            }
+        }
+        if (live) out_rgba[i] = float4{res.x, res.y, res.z, 1.0f}; // one 16-byte store
+    }
+}
+
+// ---- paths (rt_paths.hip: path_query_kernel) -------------------------------------------------------------------------------------------------
+template <bool HAS_GQ, bool HAS_CUBIC>
+__global__ __launch_bounds__(256) void path_query_stream_kernel(const PathArgs pa, const unsigned char *__restrict__ scene, const RqRay *__restrict__ rays,
+                                                                RqRecord *__restrict__ out_seg, RqRecord *__restrict__ out_last, PathEnd *__restrict__ out_end)
+{
+    __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
+    const RayQueryArgs &qa = pa.qa;
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
+    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
+
+    const uint64_t stride = (uint64_t) gridDim.x * 256u;
+    for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (workgroup-uniform trip count)
+        const uint64_t i = first + tid;
+        const bool live = i < qa.n;
+        D3 o, d;
+        sqk_load_ray(rays, i, live, o, d);
+        float cur_ratio = 1.0f;
+        uint32_t segments = 0u, end = PATH_MISS;
+        int last = -1; // the last hit: what out_last receives
+        double last_t = INFINITY;
+        D3 last_p{0.0, 0.0, 0.0}, last_n{0.0, 0.0, 0.0};
+        bool bouncing = live;
+        uint32_t k = 0;
+        for (; __ballot(bouncing) != 0ull; k++) {
+            // the nearest hit of segment k; from the first bounce on the ray is one the kernel formed, so sq_query decides for every segment
+            double best_t = INFINITY;
+            int best = -1;
+            sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best);
+            const bool hit = bouncing && best >= 0;
+            const DevObject *bo = &gobj[hit ? best : 0]; // per-lane index: gathers from global memory, per hit
+            D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0};
+            if (hit) {
+                sp = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
+                sn = normal_vector(bo->c, sp);
+            }
+            if (k < pa.max_segments && live) rq_store_record(out_seg + ((uint64_t) k * qa.n + i), hit ? best : -1, best_t, sp, sn);
+            if (bouncing) {
+                if (!hit) {
+                    end = (k == 0u) ? PATH_MISS : PATH_ESCAPED;
+                    bouncing = false;
+                } else {
+                    segments = k + 1u;
+                    last = best;
+                    last_t = best_t;
+                    last_p = sp;
+                    last_n = sn;
+                    // the reflection loop, src/update-cpu.cpp:96-117
+                    const float refl = bo->refl;
+                    if (!((double) refl > EPS)) {
+                        end = PATH_SURFACE;
+                        bouncing = false;
+                    } else {
+                        cur_ratio *= refl;
+                        if (k == pa.max_refl) {
+                            end = PATH_CAP;
+                            bouncing = false;
+                        } else {
+                            d = reflect_ray(d, sn); // of the direction as it is
+                            o = D3{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
+                        }
+                    }
+                }
+            }
+        }
+        if (live) {
+            const D3 zero{0.0, 0.0, 0.0};
+            for (; k < pa.max_segments; k++) rq_store_record(out_seg + ((uint64_t) k * qa.n + i), -1, INFINITY, zero, zero); // planes no lane of the wave reached
+            if (out_last) rq_store_record(out_last + i, last, last_t, last_p, last_n);
+            out_end[i] = PathEnd{segments, end, cur_ratio, last}; // one 16-byte store
+        }
+    }
+}
+
+// ---- pixels: the G-buffer, picking, object extents (rt_gbuffer.hip) --------------------------------------------------------------------------
+// nearest_hit with the tables streamed.  The G-buffer family has no plain path, and this one has none either: sq_tables directly, not
+// sq_query.  The cone is nearest_hit's: the block's where the context culls and the wave is a block; for unrelated pixels (picking) a
+// cone that culls nothing, through the same loop -- planes and picks share the kernel, so a picked pixel is the planes' entry in the
+// FMA-contracted build too.  The first RT_CUB_AT_MAX degree-3 objects take the host's records at the frame's origin.
+template <bool HAS_GQ, bool HAS_CUBIC>
+__device__ __forceinline__ void sqk_nearest_hit(const FrameArgs &fa, const RayQueryArgs &qa, const unsigned char *__restrict__ scene, unsigned char *slice, uint32_t lane,
+                                                const Mono &m, bool live, bool block, double &best_t, int &best)
+{
+    best = -1;
+    best_t = INFINITY;
+    SqCone cone{fa.cull != 0u, D3{0.0, 0.0, 1.0}, block ? 1.0 : -1.0}; // (sphere_in_cone: no cone wider than a half-space culls anything)
+    if (cone.on && block) cone = sq_block_cone(m.d);                     // launch-uniform
+    sq_tables<HAS_GQ, HAS_CUBIC, false, true>(qa, scene, slice, lane, m, live, cone, MAX_T, best_t, best, &fa);
+}
+
+template <bool NEED_CROSS>
+__device__ __forceinline__ Mono sqk_mono(const D3 &o, const D3 &dir)
+{
+    Mono m;
+    mono_set_o<NEED_CROSS>(m, o);
+    mono_set_d<NEED_CROSS>(m, dir);
+    mono_set_od<NEED_CROSS>(m);
+    return m;
+}
+
+// gbuffer_kernel's two launch modes, work geometry and stores: planes (xy == NULL; one workgroup per 16 x 16 tile, one wave per 8 x 8
+// block, lanes outside the image trace a clamped pixel's ray and store nothing) and picking (one lane per query, no cone).
+template <bool HAS_GQ, bool HAS_CUBIC>
+__global__ __launch_bounds__(256) void gbuffer_stream_kernel(const FrameArgs fa, const RayQueryArgs qa, const unsigned char *__restrict__ scene,
+                                                             const double *__restrict__ camx, const double *__restrict__ camy, int32_t *__restrict__ out_object,
+                                                             double *__restrict__ out_t, float4 *__restrict__ out_normal, const uint32_t *__restrict__ xy,
+                                                             uint32_t n_query, RqRecord *__restrict__ out_rec)
+{
+    __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
+    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
+
+    const bool pick = xy != nullptr; // launch-uniform
+    uint32_t col, row, lr = 0, x = 0; // camera-table indices: pixel column, GLOBAL image row
+    bool live;
+    if (pick) {
+        const uint32_t q = blockIdx.x * 256u + tid;
+        live = q < n_query;
+        col = live ? xy[2u * q] : 0u; // (validated by the host: col < width, row < height)
+        row = live ? xy[2u * q + 1u] : 0u;
+    } else {
+        const uint32_t tile_x = blockIdx.x % fa.tiles_x, tile_y = blockIdx.x / fa.tiles_x;
+        x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
+        lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
+        live = x < fa.width && lr < fa.local_rows;
+        col = x < fa.width ? x : fa.width - 1u;
+        row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
+    }
+    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
+    const D3 dir = primary_dir_tab(fa, camx[col], camy[row]);
+    const Mono m = sqk_mono<HAS_GQ || HAS_CUBIC>(o, dir);
+    double best_t;
+    int best;
+    sqk_nearest_hit<HAS_GQ, HAS_CUBIC>(fa, qa, scene, slice, lane, m, live, !pick, best_t, best);
+    // (behind the last wave-wide operation) primary_hit's record: object = -1, t = +inf, point = normal = 0 on a miss
+    RqRecord r{INFINITY, {0.0, 0.0, 0.0}, {0.0f, 0.0f, 0.0f}, -1};
+    if (live && best >= 0) {
+        r.object = best;
+        r.t = best_t;
+        const D3 p{o.x + best_t * dir.x, o.y + best_t * dir.y, o.z + best_t * dir.z};
+        r.p[0] = p.x; r.p[1] = p.y; r.p[2] = p.z;
+        const DevObject *bo = &gobj[best]; // per-lane index: a gather from global memory, per hit
+        D3 n;
+        if (bo->cls & RT_CLS_UNITSQ) { // the pixel family's own normal: three coefficients instead of twenty (sphere_normal)
+            UsEntry e{};
+            e.kx = bo->c[K_X];
+            e.ky = bo->c[K_Y];
+            e.kz = bo->c[K_Z];
+            n = sphere_normal(e, p);
+        } else {
+            n = normal_vector(bo->c, p);
+        }
+        r.n[0] = (float) n.x; r.n[1] = (float) n.y; r.n[2] = (float) n.z;
+    }
+    if (live && pick) {
+        out_rec[blockIdx.x * 256u + tid] = r;
+    } else if (live) {
+        const size_t at = (size_t) lr * fa.width + x;
+        if (out_object) out_object[at] = r.object;
+        if (out_t) out_t[at] = r.t;
+        if (out_normal) out_normal[at] = make_float4(r.n[0], r.n[1], r.n[2], 0.0f);
+    }
+}
+
+__global__ __launch_bounds__(256) void extents_init_stream_kernel(ExtRecord *__restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull};
+}
+
+// extents_kernel without accumulators in LDS: the wave reduces the lanes of each distinct object and lane 0 merges into `out` itself.
+template <bool HAS_GQ, bool HAS_CUBIC>
+__global__ __launch_bounds__(256) void extents_stream_kernel(const FrameArgs fa, const RayQueryArgs qa, const ExtArgs ea, const unsigned char *__restrict__ scene,
+                                                             const double *__restrict__ camx, const double *__restrict__ camy, ExtRecord *__restrict__ out)
+{
+    __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
+    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
+
+    for (uint32_t tile = blockIdx.x; tile < ea.n_tiles; tile += gridDim.x) { // workgroup-uniform
+        const uint32_t tile_x = ea.tx0 + tile % ea.ntx, tile_y = ea.ty0 + tile / ea.ntx;
+        const uint32_t bx = tile_x * 16u + (wave & 1u) * 8u, blr = tile_y * 16u + (wave >> 1) * 8u; // the block's first column and local row
+        const uint32_t x = bx + (lane & 7u), lr = blr + (lane >> 3);
+        const bool live = x < fa.width && lr < fa.local_rows;
+        const uint32_t col = x < fa.width ? x : fa.width - 1u;
+        const uint32_t row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
+        const D3 dir = primary_dir_tab(fa, camx[col], camy[row]);
+        const Mono m = sqk_mono<HAS_GQ || HAS_CUBIC>(o, dir);
+        double best_t;
+        int best;
+        sqk_nearest_hit<HAS_GQ, HAS_CUBIC>(fa, qa, scene, slice, lane, m, live, true, best_t, best);
+        const bool counted = live && best >= 0 && x >= ea.x0 && x <= ea.x1 && lr >= ea.lr0 && lr <= ea.lr1;
+        ext_reduce_wave(fa, bx, blr, lane, counted, best, best_t, out);
+    }
+}
+
+// ---- launchers -------------------------------------------------------------------------------------------------------------------------------
+static inline dim3 sqk_ray_grid(uint32_t n, uint32_t max_grid)
+{
+    const uint32_t need = (uint32_t) (((uint64_t) n + 255u) / 256u);
+    return dim3(need < max_grid ? need : (max_grid ? max_grid : 1u));
+}
+
+// launch kernel<HAS_GQ, HAS_CUBIC, extra...> for the scene's classes
+#define SQK_LAUNCH(fa, kernel, extra, g, stream, ...)                                                                     \
+    do {                                                                                                                  \
+        if ((fa)->n_cub) {                                                                                                \
+            if ((fa)->n_gq) hipLaunchKernelGGL((kernel<true, true extra>), g, dim3(256), 0, stream, __VA_ARGS__);        \
+            else hipLaunchKernelGGL((kernel<false, true extra>), g, dim3(256), 0, stream, __VA_ARGS__);                  \
+        } else {                                                                                                          \
+            if ((fa)->n_gq) hipLaunchKernelGGL((kernel<true, false extra>), g, dim3(256), 0, stream, __VA_ARGS__);       \
+            else hipLaunchKernelGGL((kernel<false, false extra>), g, dim3(256), 0, stream, __VA_ARGS__);                 \
+        }                                                                                                                 \
+    } while (0)
+#define SQK_COMMA ,
+
+static hipError_t sqk_launch_pixels(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, uint32_t grid, int32_t *out_object, double *out_t,
+                                    float *out_normal, const uint32_t *xy, uint32_t n, void *rec, hipStream_t stream)
+{
+    const RayQueryArgs qa = rq_args(fa, 0u);
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    float4 *nrm = reinterpret_cast<float4 *>(out_normal);
+    RqRecord *r = reinterpret_cast<RqRecord *>(rec);
+    SQK_LAUNCH(fa, gbuffer_stream_kernel, , dim3(grid), stream, *fa, qa, s, camx, camy, out_object, out_t, nrm, xy, n, r);
+    return hipGetLastError();
+}
+
+} // namespace RT_SYM(rtk)
+
+// The signatures are the staged launchers' (rt_gbuffer.hip, rt_rays.hip, rt_shade_rays.hip, rt_paths.hip), so an entry point picks one
+// or the other by the context's one decision; a launch is the same number of graph nodes as its twin's.
+extern "C" hipError_t RT_SYM(rt_launch_stream_gbuffer)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
+                                                        float *out_normal, hipStream_t stream)
+{
+    if (fa->n_tiles == 0u) return hipSuccess;
+    return RT_SYM(rtk)::sqk_launch_pixels(fa, scene, camx, camy, fa->n_tiles, out_object, out_t, out_normal, nullptr, 0u, nullptr, stream);
+}
+
+extern "C" hipError_t RT_SYM(rt_launch_stream_pick)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
+                                                     hipStream_t stream)
+{
+    if (n == 0u) return hipSuccess;
+    return RT_SYM(rtk)::sqk_launch_pixels(fa, scene, camx, camy, (n + 255u) / 256u, nullptr, nullptr, nullptr, xy, n, out, stream);
+}
+
+// Two nodes on `stream`, as rt_launch_object_extents: the identities, then -- when this rank owns a row of the rectangle -- the kernel.
+extern "C" hipError_t RT_SYM(rt_launch_stream_object_extents)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out,
+                                                               uint32_t max_grid, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (fa->n_obj == 0u) return hipSuccess;
+    ExtRecord *rec = reinterpret_cast<ExtRecord *>(out);
+    hipLaunchKernelGGL(extents_init_stream_kernel, dim3((fa->n_obj + 255u) / 256u), dim3(256), 0, stream, rec, fa->n_obj);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    ExtArgs ea;
+    if (!ext_args(fa, rect, ea)) return hipSuccess; // no row of the rectangle is this rank's: the identities stand
+    const RayQueryArgs qa = rq_args(fa, 0u);
+    const dim3 g(ea.n_tiles < max_grid ? ea.n_tiles : (max_grid ? max_grid : 1u));
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    SQK_LAUNCH(fa, extents_stream_kernel, , g, stream, *fa, qa, ea, s, camx, camy, rec);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_SYM(rt_launch_stream_trace_rays)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
+                                                           hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (n == 0u) return hipSuccess;
+    const RayQueryArgs qa = rq_args(fa, n);
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
+    SQK_LAUNCH(fa, ray_query_stream_kernel, SQK_COMMA false, sqk_ray_grid(n, max_grid), stream, qa, s, r, (const double *) nullptr, reinterpret_cast<RqRecord *>(out),
+               (int32_t *) nullptr);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_SYM(rt_launch_stream_occluded_rays)(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
+                                                              uint32_t max_grid, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (n == 0u) return hipSuccess;
+    const RayQueryArgs qa = rq_args(fa, n);
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
+    SQK_LAUNCH(fa, ray_query_stream_kernel, SQK_COMMA true, sqk_ray_grid(n, max_grid), stream, qa, s, r, t_max, (RqRecord *) nullptr, out);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_SYM(rt_launch_stream_shade_rays)(const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
+                                                           uint32_t max_grid, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (n == 0u) return hipSuccess;
+    ShadeRaysArgs sa;
+    sa.qa = rq_args(fa, n);
+    sa.n_lights = fa->n_lights;
+    sa.max_refl = fa->max_refl;
+    sa.bg[0] = fa->bg[0]; sa.bg[1] = fa->bg[1]; sa.bg[2] = fa->bg[2];
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    const DevLight *lt = reinterpret_cast<const DevLight *>(lights);
+    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
+    SQK_LAUNCH(fa, shade_rays_stream_kernel, , sqk_ray_grid(n, max_grid), stream, sa, s, lt, r, reinterpret_cast<float4 *>(rgba), reinterpret_cast<RqRecord *>(hits));
+    return hipGetLastError();
+}
+
+extern "C" hipError_t RT_SYM(rt_launch_stream_trace_paths)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
+                                                            void *last, void *ends, uint32_t max_grid, hipStream_t stream)
+{
+    using namespace RT_SYM(rtk);
+    if (n == 0u) return hipSuccess;
+    PathArgs pa;
+    pa.qa = rq_args(fa, n);
+    pa.max_refl = fa->max_refl;
+    pa.max_segments = max_segments;
+    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
+    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
+    SQK_LAUNCH(fa, path_query_stream_kernel, , sqk_ray_grid(n, max_grid), stream, pa, s, r, reinterpret_cast<RqRecord *>(segments), reinterpret_cast<RqRecord *>(last),
+               reinterpret_cast<PathEnd *>(ends));
+    return hipGetLastError();
+}

@@ -42,6 +42,8 @@
 //                             normals of one object make a cosine below it
 //   MI355RT_STREAM=1          render with the streamed frame kernel whatever the scene's size (RT_FLAG_STREAM; same frame).  A scene too large
 //                             for a workgroup's LDS takes that kernel without being asked; not together with MI355RT_SSAA_ADAPTIVE
+//   MI355RT_STREAM_QUERIES=1  picking, extents and the ray-query hooks take their streamed kernels where the scene is too large for a
+//                             workgroup's LDS (RT_FLAG_STREAM_QUERIES; same answers) instead of refusing it
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -334,6 +336,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM")) {
         if (!std::strcmp(f, "1")) streamed = RT_FLAG_STREAM;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_QUERIES=1: the queries of a scene too large for LDS take their streamed kernels instead of refusing
+    if (const char *f = std::getenv("MI355RT_STREAM_QUERIES")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_QUERIES;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_QUERIES", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

@@ -167,10 +167,32 @@ typedef struct rt_scene_desc {
  * counters); rt_get_counters and
  * rt_get_counters_detail (RT_ERR_INVALID); rt_render_sparse (RT_ERR_INVALID, as with RT_FLAG_SIMPLE: rt_render + rt_pack_sparse give
  * the same message).
- * Out of scope: adaptive supersampling, the G-buffer, picking, object extents, the ray queries and the path queries still stage the
- * tables in LDS and keep refusing scenes beyond 160 KiB with their own messages; shadow and bounce rays of a streamed frame test
- * every object. */
+ * Out of scope: adaptive supersampling still stages the scene in LDS and keeps its rt_create refusals; the G-buffer, picking, object
+ * extents, the ray queries and the path queries stage the tables in LDS and refuse scenes beyond 160 KiB with their own messages unless
+ * the context was created with RT_FLAG_STREAM_QUERIES (below); shadow and bounce rays of a streamed frame test every object. */
 #define RT_FLAG_STREAM 8192u
+
+/* Streamed queries: the queries for scenes of any size.  rt_render_gbuffer, rt_pick, rt_object_extents[_host],
+ * rt_trace_rays[_host], rt_occluded_rays, rt_shade_rays[_host], rt_trace_paths[_host] and rt_pick_paths -- and through them
+ * rt_render_gbuffer_multi, rt_object_extents_multi[_host] and rt_multi_query_ctx's context -- copy all class tables into one
+ * workgroup's LDS and answer RT_ERR_SCENE from 2 561 spheres on.  Their streamed twins (rt_stream_queries.hip) read the tables as the
+ * streamed frame kernel does, 64 entries at a time through a wave-private LDS slice.  The rule is one decision per context, made in
+ * rt_create and never revisited (rt_set_scene cannot change the layout); rt_get_streamed_queries reports it:
+ *     streamed queries = RT_FLAG_STREAM_QUERIES && (rt_get_streamed || the G-buffer's tables exceed 160 KiB of LDS)
+ * False: every entry point is what it is without the flag, refusals and messages included -- the flag alone costs a small scene
+ * nothing.  True: every entry point above launches its streamed kernel and none refuses for size.  RT_FLAG_STREAM | RT_FLAG_STREAM_QUERIES
+ * forces the streamed query kernels on a scene of any size.
+ * Accuracy: in strict contexts every streamed entry point returns bit for bit what the staged one returns wherever both run, for every
+ * degree (the same chunks, the same chunk bodies, an acceptance rule that does not depend on the order within a tie); within one
+ * context, RT_FLAG_FAST included, rt_pick is the planes' entry, rt_object_extents the reduction of the planes, and plane 0 of
+ * rt_pick_paths is rt_pick for degree <= 2 -- the promises of the staged family.  RT_FLAG_FAST is its own arithmetic.
+ * The flag combines with every other RT_FLAG_* and has no refusal of its own; through rt_create_multi it reaches every context.
+ * Unchanged: adaptive supersampling and RT_FLAG_SSAA_GEOMETRY keep their rt_create refusals for large scenes, the G-buffer family
+ * keeps refusing supersampling contexts, and RT_FLAG_COUNT books none of these rays.  Argument checks, alignment and overlap
+ * refusals, `ms` and capturability are those of the staged calls, with the same number of graph nodes per call.
+ * (16384 = 0x4000 is also the value of RT_ABI_DIAGNOSTIC; that define lives in the version word rt_abi_version returns, not in
+ * rt_config.flags: the two never meet.) */
+#define RT_FLAG_STREAM_QUERIES 16384u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -360,6 +382,9 @@ int rt_set_ssaa_geometry(rt_ctx *ctx, float min_cos);
 int rt_get_ssaa_refined(rt_ctx *ctx, uint64_t *pixels);
 /* Streamed frames (RT_FLAG_STREAM above): *streamed = 1 where rt_render is the streamed kernel, else 0. */
 int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed);
+/* Streamed queries (RT_FLAG_STREAM_QUERIES above): *streamed = 1 where the query entry points launch their streamed kernels, else 0.
+ * RT_ERR_INVALID for a NULL argument, before a device is looked for. */
+int rt_get_streamed_queries(const rt_ctx *ctx, uint32_t *streamed);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
@@ -442,7 +467,7 @@ typedef struct rt_object_extent {
  * that owns no row of `rect` adds the first only and so still writes the identities); else synchronise and report the device time.  A
  * scene without objects returns RT_OK and enqueues nothing.  RT_ERR_INVALID for a NULL context / camera / output, an output that is
  * not 8-byte aligned, a `rect` with x0 > x1, y0 > y1, x1 >= W or y1 >= H, and supersampling contexts; RT_ERR_SCENE for a scene whose
- * class tables exceed the LDS of a workgroup, as rt_render_gbuffer. */
+ * class tables exceed the LDS of a workgroup, as rt_render_gbuffer (not with RT_FLAG_STREAM_QUERIES). */
 int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32_t rect[4] /* x0,y0,x1,y1 inclusive, or NULL */,
                       rt_object_extent *dev_out /* [n_objects] */, void *stream, float *ms);
 /* The same into host memory (any alignment: the records are copied there); blocks.  The staging buffer is the context's own (allocated on the first call, freed by rt_destroy); a
@@ -495,7 +520,7 @@ int rt_merge_object_extents(rt_ctx *ctx, const rt_object_extent *dev_parts, uint
  * Ray queries carry no frame state, so they work in EVERY context: plain, RT_FLAG_SSAA2 / RT_FLAG_SSAA4, adaptive, any rank or world,
  * any format.  They read the scene blob and nothing else -- no camera tables, tile words, launch-order generations, census, counters
  * or frame tag -- and need no ordering against rt_render (against rt_set_scene they do: "Scene updates").  Scenes whose class
- * tables exceed the LDS limit are refused as rt_render_gbuffer refuses them.  With several GPUs they are called on rt_multi_query_ctx's context ("Several GPUs").
+ * tables exceed the LDS limit are refused as rt_render_gbuffer refuses them (not with RT_FLAG_STREAM_QUERIES).  With several GPUs they are called on rt_multi_query_ctx's context ("Several GPUs").
  *
  * Colour (rt_shade_rays; csrc/rt_shade_rays.hip).  The reference's render_pixel (src/update-cpu.cpp:82-119) with
  * ray_origin := o and dir := d, d used exactly as given, never normalised.  The first segment is get_color_and_object
@@ -536,7 +561,7 @@ int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, rt_hit *out,
 /* n rays -> n pixels of 4 x float32 (r, g, b, 1.0f), optionally n rt_hit of the rays themselves (dev_hits may be NULL); all in device
  * memory, on `stream`; ms as in rt_trace_rays.  RT_ERR_INVALID for a NULL context, dev_rays or dev_rgba and for n == 0 (both before a
  * device is looked for), rays, rgba or hits that are not 16-byte aligned, and any overlap between input and output ranges or between
- * the two outputs.  Scenes beyond the LDS limit are refused as by rt_trace_rays. */
+ * the two outputs.  Scenes beyond the LDS limit are refused as by rt_trace_rays (not with RT_FLAG_STREAM_QUERIES). */
 int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits /* may be NULL */, void *stream, float *ms);
 /* rt_shade_rays for rays and pixels in HOST memory; blocks.  Staging buffers as rt_trace_rays_host. */
 int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, float *rgba_out, void *stream); /* host memory, blocks */
@@ -590,7 +615,7 @@ typedef struct rt_path_end {
  * as in rt_trace_rays.  RT_ERR_INVALID for a NULL context, dev_rays or dev_ends and for n == 0 (all before a device is looked for),
  * max_segments > RT_PATH_MAX_SEGMENTS, dev_segments == NULL with max_segments != 0 and the reverse, any pointer that is not 16-byte
  * aligned, and any overlap between the input range and an output range or between two output ranges.  Scenes beyond the LDS limit are
- * refused as by rt_trace_rays. */
+ * refused as by rt_trace_rays (not with RT_FLAG_STREAM_QUERIES). */
 int rt_trace_paths(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, uint32_t max_segments,
                    rt_hit *dev_segments /* [max_segments][n], or NULL iff max_segments == 0 */,
                    rt_hit *dev_last /* [n] or NULL */, rt_path_end *dev_ends /* [n] */, void *stream, float *ms);
@@ -757,7 +782,8 @@ rt_ctx *rt_multi_query_ctx(rt_multi *m);
  * rt_assemble_planes rebuilds each requested plane on rt_multi_stream(m).  Enqueue-only unless ms is given: then the device time on the
  * root from the first G-buffer kernel to the last reassembly.  Row y of every plane is bit for bit the row rt_render_gbuffer writes on a
  * context of that rank, world and band size; in strict contexts and for surfaces of degree <= 2 the planes therefore equal a single
- * context's.  The contexts' own refusals pass through unchanged (supersampling, scenes beyond the LDS limit). */
+ * context's.  The contexts' own refusals pass through unchanged (supersampling, scenes beyond the LDS limit -- none of
+ * the latter where RT_FLAG_STREAM_QUERIES was among rt_create_multi's flags: it reaches every context). */
 int rt_render_gbuffer_multi(rt_multi *m, const double cam[16], int32_t *root_object, double *root_t, float *root_normal, float *ms);
 /* rt_object_extents over all contexts: each writes its records, the world x n_objects records travel to the root by device copies and
  * rt_merge_object_extents merges them on rt_multi_stream(m) into root_dev_out (device memory on devices[0], 8-byte aligned).  ms as
