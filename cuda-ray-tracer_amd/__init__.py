@@ -33,6 +33,7 @@ RT_FLAG_SSAA_ADAPTIVE = 2048                # ... only where the plain frame sho
 RT_FLAG_SSAA_GEOMETRY = 4096                # ... and where the primary hit changes object or its normal turns (with RT_FLAG_SSAA_ADAPTIVE)
 RT_FLAG_STREAM = 8192                       # render with the streamed frame kernel whatever the scene's size (scenes too large for LDS take it anyway)
 RT_FLAG_STREAM_QUERIES = 16384              # the query entry points take their streamed kernels where the context is streamed or the tables exceed LDS: no size refusal
+RT_FLAG_STREAM_ADAPTIVE = 32768             # adaptive supersampling takes its streamed passes where the staged ones refuse the scene (or with RT_FLAG_STREAM): no size refusal
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -44,7 +45,7 @@ ABI_SYMBOLS = [
     "rt_scene_get_desc", "rt_scene_free", "rt_camera_matrix", "rt_create", "rt_render", "rt_local_rows", "rt_max_local_rows",
     "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_assemble_planes", "rt_merge_object_extents", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
-    "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries",
+    "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries", "rt_get_streamed_adaptive",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
@@ -220,6 +221,7 @@ def lib():
         L.rt_get_ssaa_refined.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_get_streamed.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_get_streamed_queries.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.rt_get_streamed_adaptive.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
@@ -459,6 +461,14 @@ class Renderer:
         RT_FLAG_STREAM_QUERIES on a streamed context or on a scene whose class tables do not fit a workgroup's LDS."""
         n = C.c_uint32()
         _check(lib().rt_get_streamed_queries(self._h, C.byref(n)))
+        return bool(n.value)
+
+    @property
+    def streamed_adaptive(self):
+        """True where the halo, G and refine passes of an adaptive frame are the streamed kernels: RT_FLAG_STREAM_ADAPTIVE on an adaptive
+        context that is created with RT_FLAG_STREAM or whose scene the staged passes cannot hold in a workgroup's LDS."""
+        n = C.c_uint32()
+        _check(lib().rt_get_streamed_adaptive(self._h, C.byref(n)))
         return bool(n.value)
 
     @property

@@ -31,7 +31,8 @@
      RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
      RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
      RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
-     RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V)}
+     RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
+     RT_CAT(rt_launch_stream_ray_list, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 // the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
 #define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
@@ -223,6 +224,7 @@ struct rt_ctx {
     uint32_t ord_split = 0;       // FrameArgs::ord_split of non-sparse frames
     std::vector<double> cub_coefs; // the 20 coefficients of the first RT_CUB_AT_MAX degree-3 objects (FrameArgs::cub_at is formed from them every frame)
     bool stream_queries = false;  // the queries are the streamed kernels (rt_stream_queries.hip): RT_FLAG_STREAM_QUERIES on a streamed context or on a scene whose tables the staged query kernels cannot hold in LDS
+    bool stream_adaptive = false; // the halo, G and refine passes of an adaptive frame are the streamed kernels (rt_stream_adaptive.hip, rt_stream_queries.hip): RT_FLAG_STREAM_ADAPTIVE on a scene or context the staged passes refuse
     bool streamed = false;        // rt_render is the streamed frame kernel (rt_stream.hip): RT_FLAG_STREAM, or a scene whose tables the context's own kernel cannot hold in LDS
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
@@ -439,7 +441,8 @@ static int create_checks(rt_ctx *ctx, const rt_scene_desc *sd, const rt_config *
     ctx->geometry = (cfg.flags & RT_FLAG_SSAA_GEOMETRY) != 0;
     if (ctx->geometry && !ctx->adaptive) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_SSAA_GEOMETRY needs RT_FLAG_SSAA_ADAPTIVE");
     if ((cfg.flags & RT_FLAG_STREAM) && (cfg.flags & RT_FLAG_SIMPLE)) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM and RT_FLAG_SIMPLE exclude each other");
-    if ((cfg.flags & RT_FLAG_STREAM) && ctx->adaptive)
+    if ((cfg.flags & RT_FLAG_STREAM_ADAPTIVE) && !ctx->adaptive) return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM_ADAPTIVE needs RT_FLAG_SSAA_ADAPTIVE");
+    if ((cfg.flags & RT_FLAG_STREAM) && ctx->adaptive && !(cfg.flags & RT_FLAG_STREAM_ADAPTIVE))
         return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM is not available with RT_FLAG_SSAA_ADAPTIVE (the refine pass has no streamed kernel)");
     if ((cfg.flags & RT_FLAG_STREAM) && (cfg.flags & RT_FLAG_COUNT))
         return fail(RT_ERR_INVALID, "rt_create: RT_FLAG_STREAM is not available with RT_FLAG_COUNT (the streamed kernel books no counters)");
@@ -516,19 +519,27 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
     // hold the scene in a workgroup's LDS: the class tables and per-tile state of the wavefront kernel, the object records of the simple one.
     const size_t lds = (ctx->cfg.flags & RT_FLAG_SIMPLE) ? (size_t) sd->n_objects * sizeof(DevObject)
                                                          : rt_wavefront_lds_bytes_strict(fa.stage_bytes, sd->n_lights, (int) fa.has_mirror, fa.cull ? fa.n_us : 0u, 0, fa.n_cub);
-    if (ctx->adaptive && !(ctx->cfg.flags & RT_FLAG_SIMPLE) && lds > 160u * 1024u) // (the refine pass has no streamed kernel: refused as ever)
+    // Which kernels are the halo, G and refine passes of an adaptive frame?  The streamed ones where the caller allows them
+    // (RT_FLAG_STREAM_ADAPTIVE) and the staged ones cannot take the context: one decision, before the refusals it lifts.
+    const size_t ray_lds = (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry));
+    ctx->stream_adaptive = ctx->adaptive && (ctx->cfg.flags & RT_FLAG_STREAM_ADAPTIVE) &&
+                           ((ctx->cfg.flags & RT_FLAG_STREAM) || (!(ctx->cfg.flags & RT_FLAG_SIMPLE) && lds > 160u * 1024u) || ray_lds > 160u * 1024u ||
+                            (ctx->geometry && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u));
+    if (ctx->stream_adaptive && (ctx->cfg.flags & RT_FLAG_COUNT))
+        return fail(RT_ERR_SCENE, "rt_create: the adaptive passes of this context are the streamed ones (RT_FLAG_STREAM_ADAPTIVE), and the streamed passes book no counters "
+                                  "(RT_FLAG_COUNT)");
+    if (ctx->adaptive && !ctx->stream_adaptive && !(ctx->cfg.flags & RT_FLAG_SIMPLE) && lds > 160u * 1024u) // (without RT_FLAG_STREAM_ADAPTIVE: refused as ever)
         return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB)", lds);
     ctx->streamed = (ctx->cfg.flags & RT_FLAG_STREAM) || lds > 160u * 1024u;
     if (ctx->streamed) ctx->lean_ok = false;
     // ... and which kernels are the queries?  One decision per context: rt_set_scene cannot change the layout.
     ctx->stream_queries = (ctx->cfg.flags & RT_FLAG_STREAM_QUERIES) && (ctx->streamed || rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u);
-    if (ctx->adaptive && (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)) > 160u * 1024u)
-        return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)",
-                    (size_t) sd->n_objects * (sizeof(DevObject) + sizeof(UsEntry)));
+    if (ctx->adaptive && !ctx->stream_adaptive && ray_lds > 160u * 1024u)
+        return fail(RT_ERR_SCENE, "rt_create: adaptive supersampling stages %zu bytes of LDS per workgroup (limit 160 KiB)", ray_lds);
     if (ctx->streamed && (ctx->cfg.flags & RT_FLAG_COUNT)) // (RT_FLAG_STREAM itself was refused in create_checks: this is streaming forced by the scene's size, RT_FLAG_SIMPLE contexts included)
         return fail(RT_ERR_SCENE, "rt_create: scene needs %zu bytes of LDS per workgroup (limit 160 KiB), so it takes the streamed kernel, and the streamed kernel books no counters "
                                   "(RT_FLAG_COUNT)", lds);
-    if (ctx->geometry && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
+    if (ctx->geometry && !ctx->stream_adaptive && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
     return RT_OK;
 }
@@ -557,6 +568,9 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
     return device_table(ctx->d_camy, cy.data(), sizeof(double) * cy.size(), "camy");
 }
 
+// workgroups of ray_list_stream_kernel a CU holds: the occupancy build/spills.txt reports for its instantiations (waves per SIMD; a workgroup is one wave per SIMD)
+constexpr uint32_t SA_WG_PER_CU = 2;
+
 // 5. RT_FLAG_SSAA_ADAPTIVE / RT_FLAG_SSAA_GEOMETRY: the refine list, the halo rows, the sample grid's tables, the primary-hit planes
 static int create_adaptive(rt_ctx *ctx)
 {
@@ -573,7 +587,10 @@ static int create_adaptive(rt_ctx *ctx)
     // the ray-list kernel keeps one workgroup per CU resident (it needs all 512 registers of a lane); twice that many keeps every CU
     // busy while the last workgroups drain
     const uint64_t ppw = 64u / (k * k), want = (px + ppw * 4u - 1u) / (ppw * 4u), hwant = ((uint64_t) ctx->halo_slots * width + 255u) / 256u;
-    const uint32_t cap = ctx->wg_slots / 3u ? ctx->wg_slots / 3u : 1u;
+    // (the streamed twin keeps SA_WG_PER_CU workgroups per CU resident -- its registers, build/spills.txt -- and its waves share nothing, so the
+    // grid is exactly the resident set: wg_slots = 6 per CU)
+    const uint32_t slots = ctx->stream_adaptive ? ctx->wg_slots * SA_WG_PER_CU / 6u : ctx->wg_slots / 3u;
+    const uint32_t cap = slots ? slots : 1u;
     ctx->ray_grid = (uint32_t) std::min<uint64_t>(want, cap);
     ctx->halo_grid = (uint32_t) std::min<uint64_t>(hwant, cap);
     RT_TRY("hipMalloc(refine list)", ctx->d_list.alloc(sizeof(uint32_t) * (px + 1u)));
@@ -873,7 +890,11 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         // halo rows -> clear the list -> classify (unrefined pixels written out) -> the k^2 sample rays of the listed pixels; the next
         // frame's plain pass overwrites what these read, and the ordering event below is recorded behind the last of them
         const size_t px = (size_t) ctx->local_rows * ctx->width;
-        if (ctx->halo_slots)
+        // (a context whose adaptive passes are streamed -- rt_ctx::stream_adaptive, decided once in rt_create -- launches each pass's streamed twin)
+        if (ctx->halo_slots && ctx->stream_adaptive)
+            RT_HIP(ctx->kern->stream_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid,
+                                              ctx->d_halo, 0, stream));
+        else if (ctx->halo_slots)
             RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo,
                                        0, count, ctx->d_counters, stream));
         RT_HIP(hipMemsetAsync(ctx->d_list + px, 0, sizeof(uint32_t), stream));
@@ -881,7 +902,12 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             // the primary-hit object (and, for a finite min_cos, normal) of this rank's rows and of the halo rows: gbuffer_kernel itself, which
             // reads no frame state and books no rays; then the classifier with the geometric term
             float *nrm = ctx->min_cos == -INFINITY ? nullptr : ctx->d_geo_nrm.p;
-            RT_HIP(ctx->kern->gbuffer_edges(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nrm, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
+            if (ctx->stream_adaptive) { // gbuffer_stream_kernel in its two modes, as rt_render_gbuffer / rt_pick launch it: two nodes with several ranks
+                RT_HIP(ctx->kern->stream_gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, stream));
+                RT_HIP(ctx->kern->stream_pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
+            } else {
+                RT_HIP(ctx->kern->gbuffer_edges(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nrm, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
+            }
             RT_HIP(rt_launch_classify_geometry_strict(fb, ctx->d_halo, ctx->d_geo_obj, nrm, ctx->d_geo_halo, ctx->width, ctx->height, ctx->local_rows,
                                                       ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau, ctx->min_cos, dest, out8, ctx->d_list,
                                                       ctx->d_list + px, stream));
@@ -889,8 +915,12 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
                                              dest, out8, ctx->d_list, ctx->d_list + px, stream));
         }
-        RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
-                                   ctx->d_counters, stream));
+        if (ctx->stream_adaptive)
+            RT_HIP(ctx->kern->stream_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8,
+                                              stream));
+        else
+            RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
+                                       ctx->d_counters, stream));
     }
     if (ss) // the next frame's render overwrites the internal frame this reads, so the ordering event below is recorded behind it
         RT_HIP(rt_launch_resolve(ctx->d_ss, dest, ctx->width, ctx->local_rows, ctx->ssaa, out8, ctx->resolve_nt, stream));
@@ -1565,6 +1595,13 @@ extern "C" int rt_get_streamed_queries(const rt_ctx *ctx, uint32_t *streamed)
 {
     if (!ctx || !streamed) return fail(RT_ERR_INVALID, "rt_get_streamed_queries: null argument");
     *streamed = ctx->stream_queries ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_get_streamed_adaptive(const rt_ctx *ctx, uint32_t *streamed)
+{
+    if (!ctx || !streamed) return fail(RT_ERR_INVALID, "rt_get_streamed_adaptive: null argument");
+    *streamed = ctx->stream_adaptive ? 1u : 0u;
     return RT_OK;
 }
 

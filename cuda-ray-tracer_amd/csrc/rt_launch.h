@@ -84,6 +84,9 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_shade_rays, const FrameArgs *fa, con
                void *hits, uint32_t max_grid, hipStream_t stream)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
                void *last, void *ends, uint32_t max_grid, hipStream_t stream)
+// rt_stream_adaptive.hip: the streamed twin of rt_launch_ray_list (RT_FLAG_STREAM_ADAPTIVE): its arguments without the counters, scene = the blob
+RT_PER_VARIANT(hipError_t, rt_launch_stream_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
+               const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -111,6 +114,8 @@ struct Kernels {
     decltype(&rt_launch_occluded_rays_strict) stream_occluded_rays;
     decltype(&rt_launch_shade_rays_strict) stream_shade_rays;
     decltype(&rt_launch_trace_paths_strict) stream_trace_paths;
+    // the halo and refine passes of a context whose adaptive passes are streamed (rt_get_streamed_adaptive)
+    decltype(&rt_launch_stream_ray_list_strict) stream_ray_list;
 };
 
 // rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements

@@ -44,6 +44,8 @@
 //                             for a workgroup's LDS takes that kernel without being asked; not together with MI355RT_SSAA_ADAPTIVE
 //   MI355RT_STREAM_QUERIES=1  picking, extents and the ray-query hooks take their streamed kernels where the scene is too large for a
 //                             workgroup's LDS (RT_FLAG_STREAM_QUERIES; same answers) instead of refusing it
+//   MI355RT_STREAM_ADAPTIVE=1 adaptive supersampling (MI355RT_SSAA_ADAPTIVE) takes its streamed passes where the scene is too large for
+//                             a workgroup's LDS (RT_FLAG_STREAM_ADAPTIVE; same frame) instead of refusing it; needs MI355RT_SSAA_ADAPTIVE
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -341,6 +343,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_QUERIES")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_QUERIES;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_QUERIES", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_ADAPTIVE=1: adaptive supersampling of a scene too large for LDS takes its streamed passes instead of refusing
+    if (const char *f = std::getenv("MI355RT_STREAM_ADAPTIVE")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_ADAPTIVE;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_ADAPTIVE", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

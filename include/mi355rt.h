@@ -162,12 +162,13 @@ typedef struct rt_scene_desc {
  * A streamed context holds no frame-to-frame state: rt_render is one kernel (plus the resolve under RT_FLAG_SSAA2 / RT_FLAG_SSAA4),
  * captured and replayed freely.  Formats, ranks and bands, rt_pack_sparse and the assemble calls, rt_set_scene and the multi-GPU layer
  * work as on any context.
- * Refused: RT_FLAG_STREAM with RT_FLAG_SIMPLE, RT_FLAG_SSAA_ADAPTIVE or RT_FLAG_COUNT (RT_ERR_INVALID, before rt_create looks for a
+ * Refused: RT_FLAG_STREAM with RT_FLAG_SIMPLE, RT_FLAG_SSAA_ADAPTIVE (unless with RT_FLAG_STREAM_ADAPTIVE, below) or RT_FLAG_COUNT (RT_ERR_INVALID, before rt_create looks for a
  * device); RT_FLAG_COUNT for a scene that must be streamed, with or without RT_FLAG_SIMPLE (RT_ERR_SCENE: the streamed kernel books no
  * counters); rt_get_counters and
  * rt_get_counters_detail (RT_ERR_INVALID); rt_render_sparse (RT_ERR_INVALID, as with RT_FLAG_SIMPLE: rt_render + rt_pack_sparse give
  * the same message).
- * Out of scope: adaptive supersampling still stages the scene in LDS and keeps its rt_create refusals; the G-buffer, picking, object
+ * Out of scope: adaptive supersampling stages the scene in LDS and keeps its rt_create refusals unless the context was created with
+ * RT_FLAG_STREAM_ADAPTIVE (below); the G-buffer, picking, object
  * extents, the ray queries and the path queries stage the tables in LDS and refuse scenes beyond 160 KiB with their own messages unless
  * the context was created with RT_FLAG_STREAM_QUERIES (below); shadow and bounce rays of a streamed frame test every object. */
 #define RT_FLAG_STREAM 8192u
@@ -187,12 +188,50 @@ typedef struct rt_scene_desc {
  * context, RT_FLAG_FAST included, rt_pick is the planes' entry, rt_object_extents the reduction of the planes, and plane 0 of
  * rt_pick_paths is rt_pick for degree <= 2 -- the promises of the staged family.  RT_FLAG_FAST is its own arithmetic.
  * The flag combines with every other RT_FLAG_* and has no refusal of its own; through rt_create_multi it reaches every context.
- * Unchanged: adaptive supersampling and RT_FLAG_SSAA_GEOMETRY keep their rt_create refusals for large scenes, the G-buffer family
+ * Unchanged: adaptive supersampling and RT_FLAG_SSAA_GEOMETRY keep their rt_create refusals for large scenes (RT_FLAG_STREAM_ADAPTIVE,
+ * below, lifts them), the G-buffer family
  * keeps refusing supersampling contexts, and RT_FLAG_COUNT books none of these rays.  Argument checks, alignment and overlap
  * refusals, `ms` and capturability are those of the staged calls, with the same number of graph nodes per call.
  * (16384 = 0x4000 is also the value of RT_ABI_DIAGNOSTIC; that define lives in the version word rt_abi_version returns, not in
  * rt_config.flags: the two never meet.) */
 #define RT_FLAG_STREAM_QUERIES 16384u
+
+/* Streamed adaptive supersampling: RT_FLAG_SSAA_ADAPTIVE, with or without RT_FLAG_SSAA_GEOMETRY, for scenes of
+ * any size.  The refine and halo passes of an adaptive frame copy every object record and a culling entry into one workgroup's LDS
+ * (288 bytes per object: RT_ERR_SCENE from 569 objects on), the G pass of RT_FLAG_SSAA_GEOMETRY all class tables (from 2 561 spheres
+ * on), and without RT_FLAG_SIMPLE the plain pass must fit the wavefront kernel (from 1 685 spheres on).  Their streamed twins
+ * (rt_stream_adaptive.hip; the G-buffer kernel of rt_stream_queries.hip) read the tables 64 entries at a time through a wave-private LDS
+ * slice.  The rule is one decision per context, made in rt_create and never revisited (rt_set_scene cannot change the layout);
+ * rt_get_streamed_adaptive reports it:
+ *     streamed adaptive = RT_FLAG_SSAA_ADAPTIVE && RT_FLAG_STREAM_ADAPTIVE &&
+ *                         (RT_FLAG_STREAM || (!RT_FLAG_SIMPLE && the wavefront kernel's LDS exceeds 160 KiB)
+ *                          || n_objects * 288 bytes exceed 160 KiB || (RT_FLAG_SSAA_GEOMETRY && the G-buffer's tables exceed 160 KiB))
+ * False: the context is, call for call and message for message, what it is without the flag -- the three size refusals keep their
+ * order and texts, and the flag alone costs a small scene nothing.  True: none of the three refuses, nor does the refusal of
+ * RT_FLAG_STREAM with RT_FLAG_SSAA_ADAPTIVE.  RT_FLAG_STREAM | RT_FLAG_SSAA_ADAPTIVE | RT_FLAG_STREAM_ADAPTIVE forces the streamed
+ * passes on a scene of any size.
+ * Definition: the frame of RT_FLAG_SSAA_ADAPTIVE / RT_FLAG_SSAA_GEOMETRY unchanged -- the same refine(x, y), tau, geo and
+ * 8-neighbourhood; output = the resolve of S where refined, else P.  P is what rt_render of a k = 1 context with otherwise equal flags
+ * stores: the plain pass keeps the rule of rt_get_streamed (at 569 ... 1 684 spheres it is still the wavefront kernel).  S(X, Y) is
+ * the colour of sample (X, Y) of the k-times finer grid by the arithmetic of the streamed frame kernel, i.e. of rt_shade_rays, resolved
+ * with the fixed pairwise tree, times 1/k^2, quantised for RGBA8 as everywhere.  obj / N of RT_FLAG_SSAA_GEOMETRY are bit for bit what
+ * rt_render_gbuffer / rt_pick report on a streamed-queries context (the same kernel computes them).
+ * Accuracy: in strict contexts, for surfaces of degree <= 2, the frame and rt_get_ssaa_refined are bit-identical to the CPU reference's
+ * composition and to the context without the flag wherever that one is accepted; for every degree tau < 0 gives bit for bit the frame of
+ * a RT_FLAG_STREAM | RT_FLAG_SSAAk context.  RT_FLAG_FAST is its own arithmetic, held to 1e-5 relative like every RT_FLAG_FAST frame.
+ * Unchanged: rt_set_ssaa_threshold, rt_set_ssaa_geometry, rt_get_ssaa_refined, both formats, ranks and bands (every rank's rows equal
+ * the single context's), rt_pack_sparse, rt_set_scene, the multi-GPU layer (through rt_create_multi the flag reaches every context);
+ * rt_render_sparse is refused where rt_get_streamed says 1 and is render + pack otherwise.  Nothing is read back and a frame is
+ * capturable with ms == NULL.  Graph nodes per frame behind the plain pass: the halo kernel (world > 1), the list's memset, with
+ * RT_FLAG_SSAA_GEOMETRY the G pass -- one node, two with world > 1 (planes, then the halo records; the staged pass is one or two as
+ * well) --, the classifier, the refine kernel, and the pack of a sparse call.
+ * Refused: RT_FLAG_STREAM_ADAPTIVE without RT_FLAG_SSAA_ADAPTIVE (RT_ERR_INVALID, before rt_create looks for a device); RT_FLAG_COUNT
+ * on a context whose decision is true (RT_ERR_SCENE: the streamed passes book no counters); RT_FLAG_STREAM | RT_FLAG_COUNT stays
+ * RT_ERR_INVALID.
+ * Known limits: sample rays and halo rays are not cone-culled (their waves are not 8 x 8 blocks), and shadow and bounce rays test
+ * every object, as in every streamed kernel.  Out of scope: counters in streamed passes; the flag as a default; the G-buffer and picking
+ * on supersampling contexts; degree-3 scene updates. */
+#define RT_FLAG_STREAM_ADAPTIVE 32768u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -385,6 +424,9 @@ int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed);
 /* Streamed queries (RT_FLAG_STREAM_QUERIES above): *streamed = 1 where the query entry points launch their streamed kernels, else 0.
  * RT_ERR_INVALID for a NULL argument, before a device is looked for. */
 int rt_get_streamed_queries(const rt_ctx *ctx, uint32_t *streamed);
+/* Streamed adaptive supersampling (RT_FLAG_STREAM_ADAPTIVE above): *streamed = 1 where the halo, G and refine passes of rt_render are
+ * the streamed kernels, else 0.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
+int rt_get_streamed_adaptive(const rt_ctx *ctx, uint32_t *streamed);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
