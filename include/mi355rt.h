@@ -60,8 +60,15 @@ typedef struct rt_scene_desc {
 /* rt_config.flags */
 #define RT_FLAG_STRICT 0u     /* default: FP64 geometry / FP32 colour with NO FMA contraction -- the arithmetic
                                  of src/update-cpu.cpp on x86-64; this is the parity mode */
-#define RT_FLAG_FAST 1u       /* same algorithm with FMA contraction allowed (results differ by <=1 ulp per
-                                 operation; pixels on solver discontinuities may flip) */
+#define RT_FLAG_FAST 1u       /* same algorithm with FMA contraction allowed.  For surfaces of degree <= 2 the result of
+                                 every ray whose decisions are not near-ties is the exact one up to rounding: `object` and
+                                 the blocked flag are those of exact arithmetic, t is within the first-order running-error
+                                 bound B of the exact root, point is o + t d to 2u per term, the normal is the exact normal
+                                 at point to half a float32 ulp, and a frame's pixel is the strict frame's to 1e-5 relative.
+                                 A near-tie is a decision (|t2| or |t1| against EPS, the discriminant's sign, a root against
+                                 EPS, MAX_T or t_max, two objects' roots against each other) closer to its threshold than
+                                 2^20 times its bound; only such rays may differ ("The FAST build against exact
+                                 arithmetic"; tests/test_fast_truth_gpu.py).  Degree 3: within the bars of the degree-3 tests */
 #define RT_FLAG_COUNT 2u      /* also count rays / intersection tests on the device (slower; for accounting) */
 #define RT_FLAG_SIMPLE 4u     /* use the simple one-thread-per-pixel kernel (rt_kernels.hip) instead of the
                                  workgroup wavefront kernel (rt_wavefront.hip); same results, kept for A/B runs */
