@@ -34,6 +34,7 @@ RT_FLAG_SSAA_GEOMETRY = 4096                # ... and where the primary hit chan
 RT_FLAG_STREAM = 8192                       # render with the streamed frame kernel whatever the scene's size (scenes too large for LDS take it anyway)
 RT_FLAG_STREAM_QUERIES = 16384              # the query entry points take their streamed kernels where the context is streamed or the tables exceed LDS: no size refusal
 RT_FLAG_STREAM_ADAPTIVE = 32768             # adaptive supersampling takes its streamed passes where the staged ones refuse the scene (or with RT_FLAG_STREAM): no size refusal
+RT_FLAG_STREAM_CULL = 524288                # a streamed context keeps its unit spheres in a spatial order and culls them by 64-entry chunk (same frame)
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -46,6 +47,7 @@ ABI_SYMBOLS = [
     "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_assemble_planes", "rt_merge_object_extents", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries", "rt_get_streamed_adaptive",
+    "rt_get_stream_cull", "rt_debug_stream_bounds", "rt_debug_stream_cull",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
@@ -222,6 +224,9 @@ def lib():
         L.rt_get_streamed.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_get_streamed_queries.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_get_streamed_adaptive.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.rt_get_stream_cull.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.rt_debug_stream_bounds.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.rt_debug_stream_cull.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
@@ -470,6 +475,30 @@ class Renderer:
         n = C.c_uint32()
         _check(lib().rt_get_streamed_adaptive(self._h, C.byref(n)))
         return bool(n.value)
+
+    @property
+    def stream_cull(self):
+        """True where update() culls whole chunks of the unit-sphere table: RT_FLAG_STREAM_CULL on a streamed context whose culling is on."""
+        n = C.c_uint32()
+        _check(lib().rt_get_stream_cull(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def stream_bounds(self):
+        """Diagnostics: the chunk-bound table as the device holds it, as bytes (64 per chunk; rt_debug_stream_bounds; waits).  Empty
+        where stream_cull is False."""
+        n = C.c_size_t()
+        _check(lib().rt_debug_stream_bounds(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            _check(lib().rt_debug_stream_bounds(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
+        return out
+
+    def stream_cull_stats(self):
+        """The culling kernel's eight work words since the context was created (rt_debug_stream_cull; waits).  They exist only where
+        stream_cull is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
+        w = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_stream_cull(self._h, w))
+        return [int(v) for v in w]
 
     @property
     def samples(self):

@@ -32,7 +32,7 @@
      RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
      RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
      RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
-     RT_CAT(rt_launch_stream_ray_list, V)}
+     RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 // the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
 #define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
@@ -226,6 +226,11 @@ struct rt_ctx {
     bool stream_queries = false;  // the queries are the streamed kernels (rt_stream_queries.hip): RT_FLAG_STREAM_QUERIES on a streamed context or on a scene whose tables the staged query kernels cannot hold in LDS
     bool stream_adaptive = false; // the halo, G and refine passes of an adaptive frame are the streamed kernels (rt_stream_adaptive.hip, rt_stream_queries.hip): RT_FLAG_STREAM_ADAPTIVE on a scene or context the staged passes refuse
     bool streamed = false;        // rt_render is the streamed frame kernel (rt_stream.hip): RT_FLAG_STREAM, or a scene whose tables the context's own kernel cannot hold in LDS
+    // RT_FLAG_STREAM_CULL (rt_stream_cull.hip): the decision, the bounds of the 64-entry chunks of the (ordered) unit-sphere table, the work words
+    bool stream_cull = false;     // RT_FLAG_STREAM_CULL && streamed && fa.cull: rt_render is the culling streamed kernel
+    uint32_t n_chunks = 0;
+    DevMem<UsEntry> d_bounds;
+    DevMem<unsigned long long> d_cull_stats; // only with MI355RT_STREAM_CULL_STATS=1 in the environment at rt_create
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -541,6 +546,13 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
                                   "(RT_FLAG_COUNT)", lds);
     if (ctx->geometry && !ctx->stream_adaptive && rt_gbuffer_lds_bytes_strict(&fa) > 160u * 1024u)
         return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
+    // Does rt_render cull whole chunks of the unit-sphere table (rt_stream_cull.hip)?  One decision, as above.  True: the table takes the
+    // context's spatial order and every chunk gets its bound (rt_scene_image.hpp); false: nothing of the context differs from one without the flag.
+    ctx->stream_cull = (ctx->cfg.flags & RT_FLAG_STREAM_CULL) && ctx->streamed && fa.cull;
+    if (ctx->stream_cull) {
+        im.bounds = rtp::stream_cull_image(im, fa);
+        ctx->n_chunks = (uint32_t) im.bounds.size();
+    }
     return RT_OK;
 }
 
@@ -558,6 +570,12 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
     RT_TRY("hipMalloc(framebuffer)", ctx->d_fb.alloc((size_t) (ctx->local_rows ? ctx->local_rows : 1) * ctx->width * ctx->pixel_bytes));
     if (int rc = device_table(ctx->d_counters, nullptr, sizeof(unsigned long long) * 64, "counters")) return rc;
     if (int rc = device_table(ctx->d_ss_status, nullptr, sizeof(SetSceneStatus), "scene-update status")) return rc;
+    if (ctx->stream_cull) {
+        if (int rc = device_table(ctx->d_bounds, im.bounds.data(), sizeof(UsEntry) * im.bounds.size(), "chunk bounds")) return rc;
+        const char *e = std::getenv("MI355RT_STREAM_CULL_STATS");
+        if (e && !std::strcmp(e, "1"))
+            if (int rc = device_table(ctx->d_cull_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull work words")) return rc;
+    }
     RT_TRY("hipEventCreate", ctx->ev0.create());
     RT_TRY("hipEventCreate", ctx->ev1.create());
     RT_TRY("hipEventCreate", ctx->ev_done.create(hipEventDisableTiming));
@@ -881,7 +899,8 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     if (fa.order_state)
         if (int rc = rotate_launch_order(ctx, fa, stream)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->streamed ? ctx->kern->stream(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, stream)
+    const hipError_t e = ctx->stream_cull ? ctx->kern->stream_cull(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_stats, stream)
+                         : ctx->streamed ? ctx->kern->stream(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, stream)
                          : (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
                                                            : ctx->kern->wavefront(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "kernel launch failed: %s", hipGetErrorString(e));
@@ -1353,6 +1372,8 @@ static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update
     a.off_lin = fa.off_lin;
     a.off_mat = fa.off_mat;
     a.has_mirror = fa.has_mirror;
+    a.n_chunks = ctx->stream_cull ? ctx->n_chunks : 0u; // (the chunk bounds follow the rebuilt entries; the order chosen at rt_create stays)
+    a.bounds = ctx->stream_cull ? ctx->d_bounds.p : nullptr;
     const hipError_t e = rt_launch_set_scene(&a, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
     return order_end(ctx, stream, capturing);
@@ -1603,6 +1624,32 @@ extern "C" int rt_get_streamed_adaptive(const rt_ctx *ctx, uint32_t *streamed)
     if (!ctx || !streamed) return fail(RT_ERR_INVALID, "rt_get_streamed_adaptive: null argument");
     *streamed = ctx->stream_adaptive ? 1u : 0u;
     return RT_OK;
+}
+
+extern "C" int rt_get_stream_cull(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull: null argument");
+    *on = ctx->stream_cull ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_stream_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes)
+{
+    if (!ctx || !bytes) return fail(RT_ERR_INVALID, "rt_debug_stream_bounds: null argument");
+    const size_t need = ctx->stream_cull ? sizeof(UsEntry) * (size_t) ctx->n_chunks : 0u;
+    *bytes = need;
+    if (!out || !need) return RT_OK;
+    if (cap < need) return fail(RT_ERR_INVALID, "rt_debug_stream_bounds: %zu bytes offered, the bounds take %zu", cap, need);
+    return read_behind_last_call("rt_debug_stream_bounds", ctx, out, ctx->d_bounds, need);
+}
+
+extern "C" int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull: null argument");
+    if (!ctx->d_cull_stats)
+        return fail(RT_ERR_INVALID, "rt_debug_stream_cull: the context keeps no work words (they exist where rt_get_stream_cull says 1 and MI355RT_STREAM_CULL_STATS=1 was set at rt_create)");
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "work words");
+    return read_behind_last_call("rt_debug_stream_cull", ctx, out, ctx->d_cull_stats, sizeof(uint64_t) * 8);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

@@ -87,6 +87,10 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_paths, const FrameArgs *fa, co
 // rt_stream_adaptive.hip: the streamed twin of rt_launch_ray_list (RT_FLAG_STREAM_ADAPTIVE): its arguments without the counters, scene = the blob
 RT_PER_VARIANT(hipError_t, rt_launch_stream_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
                const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, hipStream_t stream)
+// rt_stream_cull.hip: the streamed frame kernel with whole chunks of the unit-sphere table culled (RT_FLAG_STREAM_CULL): rt_launch_stream's arguments, the
+// chunk bounds ([n_chunks] UsEntry, n_chunks = ceil(n_us / 64)) and the work words (8, or NULL)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
+               const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -116,6 +120,8 @@ struct Kernels {
     decltype(&rt_launch_trace_paths_strict) stream_trace_paths;
     // the halo and refine passes of a context whose adaptive passes are streamed (rt_get_streamed_adaptive)
     decltype(&rt_launch_stream_ray_list_strict) stream_ray_list;
+    // rt_render of a context whose RT_FLAG_STREAM_CULL decision is true (rt_get_stream_cull)
+    decltype(&rt_launch_stream_cull_strict) stream_cull;
 };
 
 // rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements

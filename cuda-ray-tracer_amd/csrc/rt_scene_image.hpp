@@ -8,6 +8,7 @@
 #ifndef RT_SCENE_IMAGE_HPP
 #define RT_SCENE_IMAGE_HPP
 
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -22,6 +23,7 @@ struct SceneImage {
     std::vector<LightK> lightk;      // the same lights as the lean path reads them
     std::vector<double> cub_coefs;   // the 20 coefficients of the first RT_CUB_AT_MAX degree-3 objects (FrameArgs::cub_rec is formed from them every frame)
     uint32_t n_cullable = 0;         // objects with a bounding radius
+    std::vector<UsEntry> bounds;     // RT_FLAG_STREAM_CULL contexts: the bound of every 64-entry chunk of the ordered unit-sphere table (stream_cull_image)
     bool lean_ok = false;            // the scene and the flags qualify for the wave-per-block instantiation (FrameArgs::lean)
 };
 
@@ -105,6 +107,62 @@ inline SceneImage scene_image(const rt_scene_desc &sd, uint32_t flags, FrameArgs
     for (uint32_t i = 0; i < sd.n_lights && i < 64u; i++)
         if (sd.light_is_spherical[i]) fa.pt_mask[i >> 5] |= 1u << (i & 31u);
     return im;
+}
+
+// RT_FLAG_STREAM_CULL, for a context whose decision is true: put the blob's unit-sphere table into the context's
+// spatial order and form the chunk bounds (one UsEntry per 64 entries of the ordered table, pack_chunk_bound).  Nothing else in the blob
+// moves; an entry keeps its bytes, `orig` included.
+//
+// The order (slot_orig == nullptr, rt_create): the spheres with a bounding radius first, by the Morton key of their centres, ties by
+// object index; the others behind them in index order.  Key: per axis q = (uint64) ((c - lo) / (hi - lo) * 2097151.0) (21 bits; 0 where
+// hi == lo), lo / hi = the box of the bounded spheres' centres; bit 3 b + 2 of the key is bit b of q_x, 3 b + 1 that of q_y, 3 b that of
+// q_z.  No result depends on it: it only decides which spheres share a chunk.
+// slot_orig != nullptr (the tests, for a context that has seen rt_set_scene): slot s takes the entry of object slot_orig[s] -- the order
+// is the context's, chosen at rt_create, and stays.
+inline std::vector<UsEntry> stream_cull_image(SceneImage &im, const FrameArgs &fa, unsigned char fill = 0, const uint32_t *slot_orig = nullptr)
+{
+    const uint32_t n = fa.n_us;
+    UsEntry *t_us = reinterpret_cast<UsEntry *>(im.blob.data() + fa.off_us);
+    const std::vector<UsEntry> old(t_us, t_us + n);
+    std::vector<uint32_t> order(n); // slot -> index into `old`
+    if (slot_orig) {
+        std::vector<uint32_t> where(fa.n_obj, 0u);
+        for (uint32_t j = 0; j < n; j++) where[old[j].orig] = j;
+        for (uint32_t s = 0; s < n; s++) order[s] = where[slot_orig[s]];
+    } else {
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+        for (const UsEntry &e : old) {
+            if (!(e.r < INFINITY)) continue;
+            const double c[3] = {-0.5 * e.kx, -0.5 * e.ky, -0.5 * e.kz};
+            for (int k = 0; k < 3; k++) {
+                lo[k] = c[k] < lo[k] ? c[k] : lo[k];
+                hi[k] = c[k] > hi[k] ? c[k] : hi[k];
+            }
+        }
+        std::vector<uint64_t> key(n, ~(uint64_t) 0); // (unbounded: behind every bounded sphere)
+        for (uint32_t j = 0; j < n; j++) {
+            const UsEntry &e = old[j];
+            if (!(e.r < INFINITY)) continue;
+            const double c[3] = {-0.5 * e.kx, -0.5 * e.ky, -0.5 * e.kz};
+            uint64_t m = 0;
+            for (int k = 0; k < 3; k++) {
+                const double span = hi[k] - lo[k];
+                double f = (span > 0.0 && finite64(span)) ? (c[k] - lo[k]) / span * 2097151.0 : 0.0;
+                f = f > 0.0 ? (f < 2097151.0 ? f : 2097151.0) : 0.0;
+                const uint64_t q = (uint64_t) f;
+                for (int b = 0; b < 21; b++) m |= ((q >> b) & 1u) << (3 * b + (2 - k));
+            }
+            key[j] = m;
+        }
+        for (uint32_t j = 0; j < n; j++) order[j] = j;
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] != key[b] ? key[a] < key[b] : old[a].orig < old[b].orig; });
+    }
+    for (uint32_t s = 0; s < n; s++) t_us[s] = old[order[s]];
+    const uint32_t n_chunks = (n + 63u) / 64u;
+    std::vector<UsEntry> bounds(n_chunks);
+    if (n_chunks) std::memset(bounds.data(), fill, sizeof(UsEntry) * n_chunks);
+    for (uint32_t c = 0; c < n_chunks; c++) pack_chunk_bound(bounds[c], t_us + 64u * c, (n - 64u * c < 64u) ? n - 64u * c : 64u, c);
+    return bounds;
 }
 
 } // namespace rtp

@@ -112,6 +112,80 @@ RT_PACK_FN void pack_us(UsEntry &e, const DevObject &o, uint32_t orig)
     }
 }
 
+// The bound of one 64-entry chunk of the unit-sphere table (RT_FLAG_STREAM_CULL): a sphere entry that the culling
+// predicates of rt_wavefront_math.hpp (sphere_in_cone, sphere_relevant) are asked about INSTEAD of the chunk's members, so that a
+// "skip" for the bound skips the whole chunk.  members: the chunk's n entries (1 .. 64) as pack_us wrote them; chunk: its index.
+//
+//   centre C   the middle of the box of the members' centres (a member's centre is -k / 2, exactly)
+//   inv_r      the largest of the members' inv_r
+//   r          max_i (|c_i - C| + r_i) + pad, pad = 2e-6 D + 1e-12 inv_r D (2 |C|_1 + D) + 1e-14 (|C|_1 + D + r_max), D = max_i |c_i - C|,
+//              the sum then rounded outwards by a factor 1 + 1e-12
+//   kx .. kz   -2 C;  c = |C|^2 - r^2 (a genuine sphere);  orig = chunk;  no own-sphere window
+//
+// Why a verdict about the bound covers every member.  Both predicates skip a sphere (centre c, radius r, 1 / r = q) when a distance of
+// its centre from the rays' cone / axis / segment exceeds  lim(c, r, q) = r + [R] + 1e-6 (|c - p|_1 + r + ...) + 1e-12 (|c|^2 + s + 1) q,
+// p and s being the same for every sphere of the call.  For a member i, with d_i = |c_i - C| <= D:
+//   * its distance is at least the bound's distance minus d_i (triangle inequality; the "entirely behind" half of the directional test
+//     moves by at most d_i |sdir| < d_i len_u);
+//   * lim(c_i, r_i, q_i) - lim(C, r, inv_r) <= (r_i - r) + 1e-6 (|c_i - C|_1 + r_i - r) + 1e-12 (|c_i|^2 - |C|^2) inv_r, since inv_r >= q_i;
+//     |c_i - C|_1 <= sqrt(3) d_i and |c_i|^2 - |C|^2 <= d_i (2 |C| + d_i), so the difference is at most (r_i - r) + (pad - 1e-14 (...)).
+// Hence r >= d_i + r_i + pad makes "bound skipped" imply "member i skipped by its own predicate in exact arithmetic", whose margins
+// (1e-6 relative) dwarf the rounding of either evaluation; the 1e-14 term covers the rounding of c_i - C itself when the centres are
+// far from the origin, the factor that of the sums here.  A chunk with a member without a bounding radius (r = +inf) gets r = +inf,
+// inv_r = 0 and a zero centre: every predicate answers "test it".  So does one whose r overflows.
+// Only + - * / sqrt fabs and comparisons; writes every byte; called by rt_create on the host and by rt_set_scene on the device.
+RT_PACK_FN void pack_chunk_bound(UsEntry &out, const UsEntry *members, uint32_t n, uint32_t chunk)
+{
+    RT_PACK_STRICT
+    out.orig = chunk;
+    out.pad = 0u;
+    out.own_lo = INFINITY;
+    out.own_hi = 0.0f;
+    bool bounded = n > 0u;
+    double lx = INFINITY, ly = INFINITY, lz = INFINITY, hx = -INFINITY, hy = -INFINITY, hz = -INFINITY, q = 0.0, rmax = 0.0;
+    for (uint32_t i = 0; i < n; i++) {
+        const UsEntry &e = members[i];
+        if (!(e.r < INFINITY)) {
+            bounded = false;
+            continue;
+        }
+        const double cx = -0.5 * e.kx, cy = -0.5 * e.ky, cz = -0.5 * e.kz;
+        lx = cx < lx ? cx : lx; ly = cy < ly ? cy : ly; lz = cz < lz ? cz : lz;
+        hx = cx > hx ? cx : hx; hy = cy > hy ? cy : hy; hz = cz > hz ? cz : hz;
+        q = e.inv_r > q ? e.inv_r : q;
+        rmax = e.r > rmax ? e.r : rmax;
+    }
+    double Cx = 0.0, Cy = 0.0, Cz = 0.0, r = INFINITY;
+    if (bounded) {
+        Cx = 0.5 * lx + 0.5 * hx; // (halves first: no overflow)
+        Cy = 0.5 * ly + 0.5 * hy;
+        Cz = 0.5 * lz + 0.5 * hz;
+        double reach = 0.0, D = 0.0;
+        for (uint32_t i = 0; i < n; i++) {
+            const UsEntry &e = members[i];
+            const double wx = -0.5 * e.kx - Cx, wy = -0.5 * e.ky - Cy, wz = -0.5 * e.kz - Cz;
+            const double d = sqrt(wx * wx + wy * wy + wz * wz);
+            D = d > D ? d : D;
+            reach = d + e.r > reach ? d + e.r : reach;
+        }
+        const double C1 = fabs(Cx) + fabs(Cy) + fabs(Cz);
+        const double pad = 2e-6 * D + 1e-12 * q * D * (2.0 * C1 + D) + 1e-14 * (C1 + D + rmax);
+        r = (reach + pad) * (1.0 + 1e-12);
+        if (!(r < INFINITY)) bounded = false; // (overflow, or a NaN: never culled)
+    }
+    if (!bounded) {
+        Cx = Cy = Cz = 0.0;
+        r = INFINITY;
+        q = 0.0;
+    }
+    out.kx = -2.0 * Cx;
+    out.ky = -2.0 * Cy;
+    out.kz = -2.0 * Cz;
+    out.r = r;
+    out.inv_r = q;
+    out.c = bounded ? ((Cx * Cx + Cy * Cy) + Cz * Cz) - r * r : 0.0;
+}
+
 RT_PACK_FN void pack_gq(GqEntry &e, const DevObject &o, uint32_t orig)
 {
     e.x2 = o.c[K_X2]; e.y2 = o.c[K_Y2]; e.z2 = o.c[K_Z2];

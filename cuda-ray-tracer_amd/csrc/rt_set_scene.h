@@ -35,6 +35,8 @@ struct SetSceneArgs {
     uint32_t n_us, n_gq, n_lin;
     uint32_t off_us, off_gq, off_lin, off_mat;
     uint32_t has_mirror;       // FrameArgs::has_mirror of the context: must not change
+    uint32_t n_chunks;         // RT_FLAG_STREAM_CULL contexts (rt_get_stream_cull): the 64-entry chunks of the unit-sphere table, and their bounds;
+    UsEntry *bounds;           // 0 / NULL elsewhere
 };
 
 #endif

@@ -12,7 +12,8 @@
 //   phase 2  derive + validate, lights: DevLight and LightK of every light; LightK::flags must be the ones the context holds.
 //   phase 3  commit, all or nothing: nothing offended -> DevObject and MatEntry of every object, barrier, the table entries (slot by
 //            slot, from the new DevObject of the slot's `orig`, exactly as rt_create forms them from its object array), DevLight and
-//            LightK, then status.applied += 1.  Otherwise status.rejected += 1 with the reason and the index of the first offender.
+//            LightK, then (contexts with chunk bounds, RT_FLAG_STREAM_CULL) barrier and the bound of every 64-entry chunk of the
+//            unit-sphere table from its rebuilt entries, then status.applied += 1.  Otherwise status.rejected += 1 with the reason and the index of the first offender.
 //
 // A record is 224 bytes and rt_create accepts about 2 500 objects (160 KiB of class tables), so the derived records of phase 1 cannot
 // wait in LDS for the verdict (560 KB); phase 3 derives them again from the same inputs -- a few dozen FP64 operations per object --
@@ -158,6 +159,15 @@ __global__ void __launch_bounds__(SS_THREADS) set_scene_kernel(SetSceneArgs a)
             lin[s] = e;
         }
         // (degree 3: the table is the objects' indices, which stay; their coefficients were held equal above)
+        if (a.n_chunks) { // (launch-uniform) RT_FLAG_STREAM_CULL: the chunk bounds from the rebuilt entries, as rt_create forms them (rt_scene_image.hpp)
+            __syncthreads();
+            for (uint32_t c = tid; c < a.n_chunks; c += SS_THREADS) {
+                const uint32_t first = 64u * c, n = a.n_us - first < 64u ? a.n_us - first : 64u;
+                UsEntry b;
+                rtp::pack_chunk_bound(b, us + first, n, c);
+                a.bounds[c] = b;
+            }
+        }
     }
     if (tid == 0) {
         SetSceneStatus *st = a.status;

@@ -46,6 +46,8 @@
 //                             workgroup's LDS (RT_FLAG_STREAM_QUERIES; same answers) instead of refusing it
 //   MI355RT_STREAM_ADAPTIVE=1 adaptive supersampling (MI355RT_SSAA_ADAPTIVE) takes its streamed passes where the scene is too large for
 //                             a workgroup's LDS (RT_FLAG_STREAM_ADAPTIVE; same frame) instead of refusing it; needs MI355RT_SSAA_ADAPTIVE
+//   MI355RT_STREAM_CULL=1     a streamed context keeps its unit spheres in a spatial order and culls them by 64-entry chunk
+//                             (RT_FLAG_STREAM_CULL; same frame); nothing changes where the context is not streamed
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -348,6 +350,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_ADAPTIVE")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_ADAPTIVE;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_ADAPTIVE", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_CULL=1: a streamed context culls whole chunks of its unit-sphere table
+    if (const char *f = std::getenv("MI355RT_STREAM_CULL")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

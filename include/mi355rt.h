@@ -177,7 +177,8 @@ typedef struct rt_scene_desc {
  * Out of scope: adaptive supersampling stages the scene in LDS and keeps its rt_create refusals unless the context was created with
  * RT_FLAG_STREAM_ADAPTIVE (below); the G-buffer, picking, object
  * extents, the ray queries and the path queries stage the tables in LDS and refuse scenes beyond 160 KiB with their own messages unless
- * the context was created with RT_FLAG_STREAM_QUERIES (below); shadow and bounce rays of a streamed frame test every object. */
+ * the context was created with RT_FLAG_STREAM_QUERIES (below); shadow and bounce rays of a streamed frame test every object
+ * (RT_FLAG_STREAM_CULL, below, culls the shadow rays' unit spheres by chunk). */
 #define RT_FLAG_STREAM 8192u
 
 /* Streamed queries: the queries for scenes of any size.  rt_render_gbuffer, rt_pick, rt_object_extents[_host],
@@ -239,6 +240,35 @@ typedef struct rt_scene_desc {
  * every object, as in every streamed kernel.  Out of scope: counters in streamed passes; the flag as a default; the G-buffer and picking
  * on supersampling contexts; degree-3 scene updates. */
 #define RT_FLAG_STREAM_ADAPTIVE 32768u
+
+/* Culled streamed frames: the streamed frame kernel stages every 64-entry chunk of the unit-sphere table for
+ * every query, so a frame costs O(hits x lights x spheres).  With this flag the table is kept in a spatial order, every chunk has a
+ * bounding sphere, and a query stages only the chunks whose bound the culling predicates of the wavefront kernel cannot rule out
+ * (csrc/rt_stream_cull.hip).  (Bits 0x10000 .. 0x40000 are rt_create_multi's RT_MULTI_*.)  One decision per context, made in rt_create
+ * and never revisited (rt_set_scene cannot change the layout); rt_get_stream_cull reports it:
+ *     stream cull = RT_FLAG_STREAM_CULL && rt_get_streamed && culling is on (no RT_FLAG_NOCULL, at least 4 unit spheres with a radius)
+ * False: the context is, call for call and byte for byte, what it is without the flag.  True: rt_create puts the unit-sphere table of
+ * the scene blob into a deterministic order -- spheres with a bounding radius first, by a Morton key of their centres (21 bits per axis
+ * over the box of those centres, ties by object index), the others behind them in index order; `orig` carries the object index as ever
+ * and nothing else in the blob moves -- and keeps one bound per chunk in an allocation of its own (rt_debug_stream_bounds).  The order
+ * is part of the layout and stays: after rt_set_scene the device holds, byte for byte, what rt_create packs for the new scene UNDER THE
+ * CONTEXT'S ORDER, and the bounds of the rebuilt chunks (the update kernel forms them with rt_create's own function).
+ * Culled: the primary rays of an 8 x 8 block stage only the chunks whose bound reaches into the block's cone; the shadow rays of a
+ * wave's hits towards one light stage only the chunks whose bound can block a ray from the ball around those hits, and sweep only the
+ * entries of a staged chunk that can.  Not culled: a segment with a non-finite hit point; a directional light with |d|^2 <= 1e-7;
+ * rays with components beyond 1e100 (they take the dense path over all objects); general quadrics, planes and degree-3 objects, which
+ * are streamed in full; the nearest-hit queries of bounce rays (segments >= 1).
+ * Results are unchanged by definition: the frame is RT_FLAG_STREAM's frame.  Strict contexts: bit for bit, both formats, every degree.
+ * RT_FLAG_FAST: the same arithmetic per tested object; only the set of tested objects shrinks, and a dropped object's answer could not
+ * have been accepted.  The nearest-hit rule does not depend on the table's order (nearest, lowest object index on a tie), so every
+ * other reader of the blob -- the query kernels, staged or streamed, and the adaptive passes -- returns what it returns without the flag.
+ * No refusal of its own; combines with every flag; through rt_create_multi it reaches every context.
+ * Known limits: the bounds are spheres around Morton runs of 64 entries, not a hierarchy: a scene whose spheres all overlap gains
+ * nothing and pays one decision per chunk, and so does a scene of a single chunk (measured: 20spheres with its 19 lights takes 1.67 x
+ * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Out of scope: culling bounce rays and caller-supplied rays; bounds for the other classes;
+ * a second level over the chunk bounds; culling in the streamed query and adaptive kernels (they only read the reordered table);
+ * counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
+#define RT_FLAG_STREAM_CULL 524288u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -434,6 +464,9 @@ int rt_get_streamed_queries(const rt_ctx *ctx, uint32_t *streamed);
 /* Streamed adaptive supersampling (RT_FLAG_STREAM_ADAPTIVE above): *streamed = 1 where the halo, G and refine passes of rt_render are
  * the streamed kernels, else 0.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
 int rt_get_streamed_adaptive(const rt_ctx *ctx, uint32_t *streamed);
+/* Culled streamed frames (RT_FLAG_STREAM_CULL above): *on = 1 where rt_render culls whole chunks of the unit-sphere table, else 0.
+ * RT_ERR_INVALID for a NULL argument (before a device is looked for). */
+int rt_get_stream_cull(const rt_ctx *ctx, uint32_t *on);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
@@ -698,7 +731,9 @@ int rt_pick_paths(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_
  * rt_create uploads the scene once; rt_set_scene rewrites it in stream order, without a new context: one kernel of one workgroup reads
  * raw descriptor arrays from DEVICE memory -- the layout and meaning of the rt_scene_desc arrays of the same names -- and rebuilds the
  * scene blob and both light tables with the very functions rt_create packs them with (csrc/rt_scene_pack.hpp), so the device holds,
- * byte for byte, what a fresh rt_create of the new scene with the same rt_config would have uploaded (rt_debug_scene_blob shows it).
+ * byte for byte, what a fresh rt_create of the new scene with the same rt_config would have uploaded (rt_debug_scene_blob shows it) --
+ * in a context whose RT_FLAG_STREAM_CULL decision is true: what rt_create packs for the new scene under the context's order of the
+ * unit-sphere table, which was chosen at rt_create and stays, and the bounds of its chunks (rt_debug_stream_bounds).
  * Any of the five pointers may be NULL = "keep what the context holds" (the kernel takes those raw values from its own records), not all
  * five.  n_objects, n_lights and every light's kind are fixed, and so are the background, field of view and max_reflections.
  *
@@ -756,6 +791,18 @@ int rt_set_scene_status(rt_ctx *ctx, uint64_t *applied, uint64_t *rejected, uint
 /* Diagnostics: the scene as the device holds it -- the blob, then DevLight[n_lights], then LightK[n_lights] (csrc/rt_scene_dev.h).
  * *bytes receives the size; out may be NULL (size only), else cap must be at least that.  Waits as rt_set_scene_status does. */
 int rt_debug_scene_blob(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
+/* Diagnostics of RT_FLAG_STREAM_CULL: the chunk-bound table as the device holds it, one 64-byte UsEntry (csrc/rt_scene_dev.h) per
+ * 64-entry chunk of the blob's unit-sphere table.  Calling conventions of rt_debug_scene_blob; 0 bytes where rt_get_stream_cull says 0. */
+int rt_debug_stream_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
+/* ... and the kernel's work words, cumulative since rt_create; waits for the context's last call as rt_set_scene_status does.
+ *   [0] primary chunk decisions (one per wave and chunk bound asked)      [1] primary chunks staged
+ *   [2] shadow chunk decisions, one per (wave, segment, light, chunk) where culling applied      [3] shadow chunks staged
+ *   [4] shadow entries decided (the entries of the staged chunks)         [5] shadow entries swept
+ *   [6] shadow queries (wave, segment, light) that ran unculled           [7] 0
+ * A wave whose rays are all decided stops asking (the occlusion early-out), so [2] counts every chunk only in scenes of at most 64
+ * chunks.  The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true;
+ * otherwise the kernel counts nothing and the call answers RT_ERR_INVALID. */
+int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8]);
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
