@@ -47,7 +47,7 @@ ABI_SYMBOLS = [
     "rt_row_map", "rt_pixel_bytes", "rt_device_fb", "rt_download", "rt_assemble", "rt_assemble_planes", "rt_merge_object_extents", "rt_sparse_bytes", "rt_sparse_msg_bytes", "rt_render_sparse", "rt_pack_sparse", "rt_assemble_sparse", "rt_sparse_stamp_bytes",
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries", "rt_get_streamed_adaptive",
-    "rt_get_stream_cull", "rt_debug_stream_bounds", "rt_debug_stream_cull",
+    "rt_get_stream_cull", "rt_debug_stream_bounds", "rt_debug_stream_cull", "rt_get_stream_cull_adaptive", "rt_debug_stream_cull_adaptive",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
@@ -227,6 +227,8 @@ def lib():
         L.rt_get_stream_cull.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_debug_stream_bounds.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_debug_stream_cull.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_get_stream_cull_adaptive.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.rt_debug_stream_cull_adaptive.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
@@ -498,6 +500,22 @@ class Renderer:
         stream_cull is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
         w = (C.c_uint64 * 8)()
         _check(lib().rt_debug_stream_cull(self._h, w))
+        return [int(v) for v in w]
+
+    @property
+    def stream_cull_adaptive(self):
+        """True where the halo and refine passes of an adaptive frame cull whole chunks of the unit-sphere table as well: stream_cull and
+        streamed_adaptive on a scene of at least two chunks (rt_get_stream_cull_adaptive)."""
+        n = C.c_uint32()
+        _check(lib().rt_get_stream_cull_adaptive(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def stream_cull_adaptive_stats(self):
+        """The eight work words of the culling halo and refine kernels since the context was created (rt_debug_stream_cull_adaptive;
+        waits).  They exist only where stream_cull_adaptive is True, MI355RT_STREAM_CULL_STATS=1 was in the environment when the context
+        was created, and the scene does not hold both general quadrics and degree-3 objects."""
+        w = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_stream_cull_adaptive(self._h, w))
         return [int(v) for v in w]
 
     @property

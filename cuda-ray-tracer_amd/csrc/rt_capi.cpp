@@ -32,7 +32,7 @@
      RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
      RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
      RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
-     RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V)}
+     RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V), RT_CAT(rt_launch_stream_cull_ray_list, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 // the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
 #define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
@@ -231,6 +231,9 @@ struct rt_ctx {
     uint32_t n_chunks = 0;
     DevMem<UsEntry> d_bounds;
     DevMem<unsigned long long> d_cull_stats; // only with MI355RT_STREAM_CULL_STATS=1 in the environment at rt_create
+    // ... and the same chunks culled in the halo and refine passes (rt_stream_cull_adaptive.hip), with work words of their own
+    bool stream_cull_adaptive = false; // stream_cull && stream_adaptive && n_chunks >= 2
+    DevMem<unsigned long long> d_cull_adaptive_stats; // as d_cull_stats; not for scenes with both general quadrics and degree-3 objects (that counting kernel is not built)
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -553,6 +556,9 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
         im.bounds = rtp::stream_cull_image(im, fa);
         ctx->n_chunks = (uint32_t) im.bounds.size();
     }
+    // ... and do the halo and refine passes cull them too (rt_stream_cull_adaptive.hip)?  Both decisions above, and a second chunk: with one,
+    // the chunk level can remove nothing and is paid per query.
+    ctx->stream_cull_adaptive = ctx->stream_cull && ctx->stream_adaptive && ctx->n_chunks >= 2u;
     return RT_OK;
 }
 
@@ -575,6 +581,8 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
         const char *e = std::getenv("MI355RT_STREAM_CULL_STATS");
         if (e && !std::strcmp(e, "1"))
             if (int rc = device_table(ctx->d_cull_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull work words")) return rc;
+        if (e && !std::strcmp(e, "1") && ctx->stream_cull_adaptive && !(fa.n_gq && fa.n_cub))
+            if (int rc = device_table(ctx->d_cull_adaptive_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-adaptive work words")) return rc;
     }
     RT_TRY("hipEventCreate", ctx->ev0.create());
     RT_TRY("hipEventCreate", ctx->ev1.create());
@@ -910,7 +918,10 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         // frame's plain pass overwrites what these read, and the ordering event below is recorded behind the last of them
         const size_t px = (size_t) ctx->local_rows * ctx->width;
         // (a context whose adaptive passes are streamed -- rt_ctx::stream_adaptive, decided once in rt_create -- launches each pass's streamed twin)
-        if (ctx->halo_slots && ctx->stream_adaptive)
+        if (ctx->halo_slots && ctx->stream_cull_adaptive)
+            RT_HIP(ctx->kern->stream_cull_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid,
+                                                   ctx->d_halo, 0, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_adaptive_stats, stream));
+        else if (ctx->halo_slots && ctx->stream_adaptive)
             RT_HIP(ctx->kern->stream_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid,
                                               ctx->d_halo, 0, stream));
         else if (ctx->halo_slots)
@@ -934,7 +945,10 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
                                              dest, out8, ctx->d_list, ctx->d_list + px, stream));
         }
-        if (ctx->stream_adaptive)
+        if (ctx->stream_cull_adaptive)
+            RT_HIP(ctx->kern->stream_cull_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest,
+                                                   out8, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_adaptive_stats, stream));
+        else if (ctx->stream_adaptive)
             RT_HIP(ctx->kern->stream_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8,
                                               stream));
         else
@@ -1650,6 +1664,22 @@ extern "C" int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8])
         return fail(RT_ERR_INVALID, "rt_debug_stream_cull: the context keeps no work words (they exist where rt_get_stream_cull says 1 and MI355RT_STREAM_CULL_STATS=1 was set at rt_create)");
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "work words");
     return read_behind_last_call("rt_debug_stream_cull", ctx, out, ctx->d_cull_stats, sizeof(uint64_t) * 8);
+}
+
+extern "C" int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_adaptive: null argument");
+    *on = ctx->stream_cull_adaptive ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_adaptive: null argument");
+    if (!ctx->d_cull_adaptive_stats)
+        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_adaptive: the context keeps no work words (they exist where rt_get_stream_cull_adaptive says 1, MI355RT_STREAM_CULL_STATS=1 was "
+                                    "set at rt_create and the scene does not hold both general quadrics and degree-3 objects)");
+    return read_behind_last_call("rt_debug_stream_cull_adaptive", ctx, out, ctx->d_cull_adaptive_stats, sizeof(uint64_t) * 8);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

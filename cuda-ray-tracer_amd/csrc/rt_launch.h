@@ -91,6 +91,11 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_ray_list, const FrameArgs *fa, const
 // chunk bounds ([n_chunks] UsEntry, n_chunks = ceil(n_us / 64)) and the work words (8, or NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
                const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+// rt_stream_cull_adaptive.hip: rt_launch_stream_ray_list with the same chunks culled (rt_get_stream_cull_adaptive): its arguments, the chunk bounds and
+// work words of its own (8, or NULL)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
+               const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, const void *bounds,
+               uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -122,6 +127,8 @@ struct Kernels {
     decltype(&rt_launch_stream_ray_list_strict) stream_ray_list;
     // rt_render of a context whose RT_FLAG_STREAM_CULL decision is true (rt_get_stream_cull)
     decltype(&rt_launch_stream_cull_strict) stream_cull;
+    // the halo and refine passes of a context whose streamed adaptive passes cull as well (rt_get_stream_cull_adaptive)
+    decltype(&rt_launch_stream_cull_ray_list_strict) stream_cull_ray_list;
 };
 
 // rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements

@@ -236,8 +236,8 @@ typedef struct rt_scene_desc {
  * Refused: RT_FLAG_STREAM_ADAPTIVE without RT_FLAG_SSAA_ADAPTIVE (RT_ERR_INVALID, before rt_create looks for a device); RT_FLAG_COUNT
  * on a context whose decision is true (RT_ERR_SCENE: the streamed passes book no counters); RT_FLAG_STREAM | RT_FLAG_COUNT stays
  * RT_ERR_INVALID.
- * Known limits: sample rays and halo rays are not cone-culled (their waves are not 8 x 8 blocks), and shadow and bounce rays test
- * every object, as in every streamed kernel.  Out of scope: counters in streamed passes; the flag as a default; the G-buffer and picking
+ * Known limits: without RT_FLAG_STREAM_CULL sample rays and halo rays are not cone-culled (their waves are not 8 x 8 blocks), and shadow
+ * and bounce rays test every object; with it, see "Culled streamed adaptive passes" below.  Out of scope: counters in streamed passes; the flag as a default; the G-buffer and picking
  * on supersampling contexts; degree-3 scene updates. */
 #define RT_FLAG_STREAM_ADAPTIVE 32768u
 
@@ -262,11 +262,30 @@ typedef struct rt_scene_desc {
  * RT_FLAG_FAST: the same arithmetic per tested object; only the set of tested objects shrinks, and a dropped object's answer could not
  * have been accepted.  The nearest-hit rule does not depend on the table's order (nearest, lowest object index on a tie), so every
  * other reader of the blob -- the query kernels, staged or streamed, and the adaptive passes -- returns what it returns without the flag.
+ * Culled streamed adaptive passes (csrc/rt_stream_cull_adaptive.hip): no flag of its own -- RT_FLAG_STREAM_CULL |
+ * RT_FLAG_STREAM_ADAPTIVE says what the caller wants.  One more decision per context, made in rt_create and never revisited;
+ * rt_get_stream_cull_adaptive reports it:
+ *     stream cull adaptive = rt_get_stream_cull && rt_get_streamed_adaptive && at least 2 chunks (65 unit spheres)
+ * False: the halo and refine passes are RT_FLAG_STREAM_ADAPTIVE's, launch for launch.  True: both are the culling twin of that kernel.
+ * The sample rays (and halo centre rays) of a wave all leave the frame's origin: the wave forms a cone from its lanes' own directions
+ * -- the axis is the direction of the used lane nearest their mean, the opening the minimum over all used lanes -- and stages only the
+ * chunks whose bound reaches into it; the shadow rays of every segment are culled as in the frame kernel, from the ball around the
+ * wave's hit points.  Not culled: what the frame kernel does not cull (above), and a wave with a ray beyond 1e100.  Results are
+ * unchanged by definition: strict and RT_FLAG_FAST frames and rt_get_ssaa_refined are bit for bit those of the same context without
+ * RT_FLAG_STREAM_CULL, every degree, both formats, every rank.  Graph nodes per frame, capturability, ms, rt_render_sparse's rules and
+ * rt_set_scene are those of RT_FLAG_STREAM_ADAPTIVE (the update kernel already rebuilds the bounds).  The two-chunk floor: with a single
+ * chunk the chunk level can remove nothing and is paid per query.
+ * Known limits of the culled adaptive passes (measured; 1080p, k = 4, tau = 1/32): a k = 4 wave holds four
+ * pixels of the refine list, usually from blocks that are not neighbours, so its cone is wide: at 10 000 spheres it still stages 45 of
+ * 157 chunks per wave, the frame takes 0.29 x the unculled passes' time (0.62 x at 1 685 spheres) and, at 4.7 % refined, is still slower
+ * than the culled full RT_FLAG_SSAA4 frame (16.0 against 6.7 ms).  At 65 spheres (two chunks) nothing is gained: 1.003 x in one run,
+ * beyond the 0.2 us spread of the unculled series, 0.999 x in another.
  * No refusal of its own; combines with every flag; through rt_create_multi it reaches every context.
  * Known limits: the bounds are spheres around Morton runs of 64 entries, not a hierarchy: a scene whose spheres all overlap gains
  * nothing and pays one decision per chunk, and so does a scene of a single chunk (measured: 20spheres with its 19 lights takes 1.67 x
  * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Out of scope: culling bounce rays and caller-supplied rays; bounds for the other classes;
- * a second level over the chunk bounds; culling in the streamed query and adaptive kernels (they only read the reordered table);
+ * a second level over the chunk bounds; culling in the streamed query kernels (they only read the reordered table); reordering the
+ * refine list for tighter wave cones;
  * counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
 #define RT_FLAG_STREAM_CULL 524288u
 
@@ -467,6 +486,10 @@ int rt_get_streamed_adaptive(const rt_ctx *ctx, uint32_t *streamed);
 /* Culled streamed frames (RT_FLAG_STREAM_CULL above): *on = 1 where rt_render culls whole chunks of the unit-sphere table, else 0.
  * RT_ERR_INVALID for a NULL argument (before a device is looked for). */
 int rt_get_stream_cull(const rt_ctx *ctx, uint32_t *on);
+/* Culled streamed adaptive passes (RT_FLAG_STREAM_CULL above): *on = 1 where the halo and refine passes of rt_render cull whole chunks
+ * of the unit-sphere table (rt_get_stream_cull && rt_get_streamed_adaptive && at least two chunks), else 0.  RT_ERR_INVALID for a NULL
+ * argument (before a device is looked for). */
+int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
@@ -803,6 +826,17 @@ int rt_debug_stream_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
  * chunks.  The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true;
  * otherwise the kernel counts nothing and the call answers RT_ERR_INVALID. */
 int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8]);
+/* ... and the work words of the culling halo and refine kernels (rt_get_stream_cull_adaptive), eight words of their own, cumulative
+ * since rt_create; rt_debug_stream_cull's words stay the plain pass's alone.  Waits as rt_set_scene_status does.
+ *   [0] primary chunk decisions (one per wave, pass of its item loop and chunk bound asked)      [1] primary chunks staged
+ *   [2] shadow chunk decisions      [3] shadow chunks staged      [4] shadow entries decided      [5] shadow entries swept
+ *   [6] shadow queries (wave, segment, light) that ran unculled
+ *   [7] segment-0 queries that ran without a cone (a ray beyond 1e100 in the wave, or no lane in use: a wholly off-image halo wave)
+ * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create, the decision is true and the scene does not
+ * hold both general quadrics and degree-3 objects (the counting kernel for that pair does not fit two waves per SIMD and is not built);
+ * otherwise the kernel counts nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is
+ * looked for. */
+int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8]);
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
