@@ -35,6 +35,7 @@ RT_FLAG_STREAM = 8192                       # render with the streamed frame ker
 RT_FLAG_STREAM_QUERIES = 16384              # the query entry points take their streamed kernels where the context is streamed or the tables exceed LDS: no size refusal
 RT_FLAG_STREAM_ADAPTIVE = 32768             # adaptive supersampling takes its streamed passes where the staged ones refuse the scene (or with RT_FLAG_STREAM): no size refusal
 RT_FLAG_STREAM_CULL = 524288                # a streamed context keeps its unit spheres in a spatial order and culls them by 64-entry chunk (same frame)
+RT_FLAG_STREAM_CULL_BOUNCE = 1048576        # ... and culls the chunks of its bounce rays per ray (with RT_FLAG_STREAM_CULL, mirrors and at least two chunks; same frame)
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -48,6 +49,7 @@ ABI_SYMBOLS = [
     "rt_assemble_sparse_incremental",
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries", "rt_get_streamed_adaptive",
     "rt_get_stream_cull", "rt_debug_stream_bounds", "rt_debug_stream_cull", "rt_get_stream_cull_adaptive", "rt_debug_stream_cull_adaptive",
+    "rt_get_stream_cull_bounce", "rt_debug_stream_cull_bounce",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
@@ -229,6 +231,8 @@ def lib():
         L.rt_debug_stream_cull.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_get_stream_cull_adaptive.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_debug_stream_cull_adaptive.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.rt_get_stream_cull_bounce.argtypes = [vp, C.POINTER(C.c_uint32)]
+        L.rt_debug_stream_cull_bounce.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
@@ -516,6 +520,21 @@ class Renderer:
         was created, and the scene does not hold both general quadrics and degree-3 objects."""
         w = (C.c_uint64 * 8)()
         _check(lib().rt_debug_stream_cull_adaptive(self._h, w))
+        return [int(v) for v in w]
+
+    @property
+    def stream_cull_bounce(self):
+        """True where update() culls the unit-sphere chunks of its bounce rays per ray as well: RT_FLAG_STREAM_CULL_BOUNCE on a context whose
+        stream_cull is True, with a mirror in the scene, max_reflections >= 1 and at least two chunks (rt_get_stream_cull_bounce)."""
+        n = C.c_uint32()
+        _check(lib().rt_get_stream_cull_bounce(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def stream_cull_bounce_stats(self):
+        """The eight work words of the bounce queries since the context was created (rt_debug_stream_cull_bounce; waits).  They exist only
+        where stream_cull_bounce is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
+        w = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_stream_cull_bounce(self._h, w))
         return [int(v) for v in w]
 
     @property
@@ -978,6 +997,12 @@ class MultiRenderer:
         ms = C.c_float(0.0)
         _check(multi_lib().rt_object_extents_multi(self._h, _dptr(cam), rp, C.c_void_p(out_ptr) if out_ptr else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
+
+    @property
+    def stream_cull_bounce(self):
+        """Renderer.stream_cull_bounce of the contexts: they share scene, flags and max_reflections, hence the decision (read from
+        rt_multi_query_ctx's context)."""
+        return self.query.stream_cull_bounce
 
     @property
     def query(self):

@@ -32,7 +32,8 @@
      RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
      RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
      RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
-     RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V), RT_CAT(rt_launch_stream_cull_ray_list, V)}
+     RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V), RT_CAT(rt_launch_stream_cull_bounce, V), \
+     RT_CAT(rt_launch_stream_cull_ray_list, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 // the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
 #define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
@@ -234,6 +235,9 @@ struct rt_ctx {
     // ... and the same chunks culled in the halo and refine passes (rt_stream_cull_adaptive.hip), with work words of their own
     bool stream_cull_adaptive = false; // stream_cull && stream_adaptive && n_chunks >= 2
     DevMem<unsigned long long> d_cull_adaptive_stats; // as d_cull_stats; not for scenes with both general quadrics and degree-3 objects (that counting kernel is not built)
+    // ... and the bounce rays of rt_render culled per ray (rt_stream_cull_bounce.hip), with work words of their own
+    bool stream_cull_bounce = false; // RT_FLAG_STREAM_CULL_BOUNCE && stream_cull && fa.has_mirror && max_reflections >= 1 && n_chunks >= 2
+    DevMem<unsigned long long> d_cull_bounce_stats; // as d_cull_stats
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -559,6 +563,10 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
     // ... and do the halo and refine passes cull them too (rt_stream_cull_adaptive.hip)?  Both decisions above, and a second chunk: with one,
     // the chunk level can remove nothing and is paid per query.
     ctx->stream_cull_adaptive = ctx->stream_cull && ctx->stream_adaptive && ctx->n_chunks >= 2u;
+    // ... and does rt_render cull its bounce rays per ray (rt_stream_cull_bounce.hip)?  The decision above, a scene and a context in which a ray
+    // can bounce at all, and a second chunk.  False: launch for launch the context without the flag.  rt_set_scene keeps has_mirror and the chunk
+    // layout, so this holds for the context's life.
+    ctx->stream_cull_bounce = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_BOUNCE) && ctx->stream_cull && fa.has_mirror && fa.max_refl >= 1u && ctx->n_chunks >= 2u;
     return RT_OK;
 }
 
@@ -581,6 +589,8 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
         const char *e = std::getenv("MI355RT_STREAM_CULL_STATS");
         if (e && !std::strcmp(e, "1"))
             if (int rc = device_table(ctx->d_cull_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull work words")) return rc;
+        if (e && !std::strcmp(e, "1") && ctx->stream_cull_bounce)
+            if (int rc = device_table(ctx->d_cull_bounce_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-bounce work words")) return rc;
         if (e && !std::strcmp(e, "1") && ctx->stream_cull_adaptive && !(fa.n_gq && fa.n_cub))
             if (int rc = device_table(ctx->d_cull_adaptive_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-adaptive work words")) return rc;
     }
@@ -907,7 +917,9 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     if (fa.order_state)
         if (int rc = rotate_launch_order(ctx, fa, stream)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->stream_cull ? ctx->kern->stream_cull(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_stats, stream)
+    const hipError_t e = ctx->stream_cull_bounce ? ctx->kern->stream_cull_bounce(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_stats,
+                                                                                 ctx->d_cull_bounce_stats, stream)
+                         : ctx->stream_cull ? ctx->kern->stream_cull(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_stats, stream)
                          : ctx->streamed ? ctx->kern->stream(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, stream)
                          : (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
                                                            : ctx->kern->wavefront(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
@@ -1680,6 +1692,22 @@ extern "C" int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8])
         return fail(RT_ERR_INVALID, "rt_debug_stream_cull_adaptive: the context keeps no work words (they exist where rt_get_stream_cull_adaptive says 1, MI355RT_STREAM_CULL_STATS=1 was "
                                     "set at rt_create and the scene does not hold both general quadrics and degree-3 objects)");
     return read_behind_last_call("rt_debug_stream_cull_adaptive", ctx, out, ctx->d_cull_adaptive_stats, sizeof(uint64_t) * 8);
+}
+
+extern "C" int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_bounce: null argument");
+    *on = ctx->stream_cull_bounce ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_bounce: null argument");
+    if (!ctx->d_cull_bounce_stats)
+        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_bounce: the context keeps no work words (they exist where rt_get_stream_cull_bounce says 1 and MI355RT_STREAM_CULL_STATS=1 "
+                                    "was set at rt_create)");
+    return read_behind_last_call("rt_debug_stream_cull_bounce", ctx, out, ctx->d_cull_bounce_stats, sizeof(uint64_t) * 8);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

@@ -91,6 +91,10 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_ray_list, const FrameArgs *fa, const
 // chunk bounds ([n_chunks] UsEntry, n_chunks = ceil(n_us / 64)) and the work words (8, or NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
                const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+// rt_stream_cull_bounce.hip: rt_launch_stream_cull with the bounce rays culled per ray as well (RT_FLAG_STREAM_CULL_BOUNCE): its arguments and the bounce
+// work words (8, NULL exactly where stats is NULL)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_bounce, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
+               const void *bounds, uint32_t n_chunks, unsigned long long *stats, unsigned long long *bounce_stats, hipStream_t stream)
 // rt_stream_cull_adaptive.hip: rt_launch_stream_ray_list with the same chunks culled (rt_get_stream_cull_adaptive): its arguments, the chunk bounds and
 // work words of its own (8, or NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
@@ -127,6 +131,8 @@ struct Kernels {
     decltype(&rt_launch_stream_ray_list_strict) stream_ray_list;
     // rt_render of a context whose RT_FLAG_STREAM_CULL decision is true (rt_get_stream_cull)
     decltype(&rt_launch_stream_cull_strict) stream_cull;
+    // rt_render of a context whose RT_FLAG_STREAM_CULL_BOUNCE decision is true (rt_get_stream_cull_bounce)
+    decltype(&rt_launch_stream_cull_bounce_strict) stream_cull_bounce;
     // the halo and refine passes of a context whose streamed adaptive passes cull as well (rt_get_stream_cull_adaptive)
     decltype(&rt_launch_stream_cull_ray_list_strict) stream_cull_ray_list;
 };

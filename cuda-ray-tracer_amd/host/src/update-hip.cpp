@@ -48,6 +48,8 @@
 //                             a workgroup's LDS (RT_FLAG_STREAM_ADAPTIVE; same frame) instead of refusing it; needs MI355RT_SSAA_ADAPTIVE
 //   MI355RT_STREAM_CULL=1     a streamed context keeps its unit spheres in a spatial order and culls them by 64-entry chunk
 //                             (RT_FLAG_STREAM_CULL; same frame); nothing changes where the context is not streamed
+//   MI355RT_STREAM_CULL_BOUNCE=1  ... and culls the chunks of its bounce rays per ray (RT_FLAG_STREAM_CULL_BOUNCE; same frame); nothing
+//                             changes without MI355RT_STREAM_CULL, without mirrors or below 65 unit spheres
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -355,6 +357,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_CULL")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_CULL_BOUNCE=1: ... and the chunks of its bounce rays, per ray
+    if (const char *f = std::getenv("MI355RT_STREAM_CULL_BOUNCE")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_BOUNCE;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_BOUNCE", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

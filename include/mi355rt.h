@@ -257,7 +257,7 @@ typedef struct rt_scene_desc {
  * wave's hits towards one light stage only the chunks whose bound can block a ray from the ball around those hits, and sweep only the
  * entries of a staged chunk that can.  Not culled: a segment with a non-finite hit point; a directional light with |d|^2 <= 1e-7;
  * rays with components beyond 1e100 (they take the dense path over all objects); general quadrics, planes and degree-3 objects, which
- * are streamed in full; the nearest-hit queries of bounce rays (segments >= 1).
+ * are streamed in full; the nearest-hit queries of bounce rays (segments >= 1) unless RT_FLAG_STREAM_CULL_BOUNCE says otherwise.
  * Results are unchanged by definition: the frame is RT_FLAG_STREAM's frame.  Strict contexts: bit for bit, both formats, every degree.
  * RT_FLAG_FAST: the same arithmetic per tested object; only the set of tested objects shrinks, and a dropped object's answer could not
  * have been accepted.  The nearest-hit rule does not depend on the table's order (nearest, lowest object index on a tie), so every
@@ -283,11 +283,43 @@ typedef struct rt_scene_desc {
  * No refusal of its own; combines with every flag; through rt_create_multi it reaches every context.
  * Known limits: the bounds are spheres around Morton runs of 64 entries, not a hierarchy: a scene whose spheres all overlap gains
  * nothing and pays one decision per chunk, and so does a scene of a single chunk (measured: 20spheres with its 19 lights takes 1.67 x
- * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Out of scope: culling bounce rays and caller-supplied rays; bounds for the other classes;
+ * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Bounce rays: RT_FLAG_STREAM_CULL_BOUNCE below.  Out of scope: culling caller-supplied rays; bounds for the other classes;
  * a second level over the chunk bounds; culling in the streamed query kernels (they only read the reordered table); reordering the
  * refine list for tighter wave cones;
  * counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
 #define RT_FLAG_STREAM_CULL 524288u
+
+/* Culled bounce rays (csrc/rt_stream_cull_bounce.hip): in a culled streamed frame the nearest-hit query of a bounce
+ * ray (segments >= 1) still sweeps the whole unit-sphere table, so a frame with mirrors is back at O(hits x spheres).  With this flag
+ * every lane asks about its OWN ray and each chunk bound (csrc/rt_ray_bound.hpp: sphere_relevant for the half-line from the ray's origin
+ * along its direction, the ball shrunk to radius 0), the wave stages a chunk only if some lane in use reaches its bound, and sweeps it for
+ * those lanes alone.  One decision per context, made in rt_create and never revisited (rt_set_scene keeps both the mirrors' presence and
+ * the chunk layout); rt_get_stream_cull_bounce reports it:
+ *     stream cull bounce = RT_FLAG_STREAM_CULL_BOUNCE && rt_get_stream_cull && some object has a reflection ratio > 1e-7
+ *                          && max_reflections >= 1 && at least 2 chunks (65 unit spheres)
+ * False: the context is, launch for launch and byte for byte, the context without the flag; the flag without RT_FLAG_STREAM_CULL is simply
+ * false.  There is no refusal of its own, and the flag combines with every other.  True: rt_render launches
+ * stream_cull_bounce_frame_kernel, the culled frame kernel with that one query exchanged; primary and shadow rays are culled as before.
+ * Not culled for: a ray with |d|^2 <= 1e-7 or not finite (the reference's linear branch is not geometry); a ray with a component
+ * beyond 1e100 (it takes the dense path over all objects); a chunk whose bound is +inf; the other classes' tables.
+ * Results are unchanged by definition: the frame is RT_FLAG_STREAM's frame.  Strict contexts: bit for bit, every degree, both formats.
+ * RT_FLAG_FAST: bit for bit the unflagged FAST frame (the same arithmetic per tested object).  Graph nodes per frame, ms, capturability,
+ * RT_FLAG_SSAA2/4, ranks, rt_pack_sparse and rt_set_scene are those of RT_FLAG_STREAM_CULL.  The halo and refine passes of adaptive
+ * frames and the query kernels are not touched.  Through rt_create_multi the flag reaches every context.  All four instantiations of
+ * both builds fit two waves per SIMD without a spill (the strict one for general quadrics plus degree 3 at exactly 256 VGPRs), so no
+ * scene is excluded.
+ * Known limits: the chunk level works on the union over a wave's 64 lanes, and the bounce rays of a block are not coherent -- a chunk is
+ * staged as soon as ONE lane reaches its bound; chunks are not pruned against the nearest hit found so far (no best_t test, no near-to-far
+ * order), so a ray pays for every chunk along its whole half-line; there is no per-entry level inside a staged chunk; every lane pays one
+ * verdict per chunk and query, which a scene of few chunks does not earn back.  Measured (DESIGN.md section 27,
+ * profiles/stream_cull_bounce.txt; MI355X, 1920 x 1080, strict RGBA32F, the mirrored sphere field with two bounces, against
+ * RT_FLAG_STREAM | RT_FLAG_STREAM_CULL): 10 000 spheres 10 660 -> 4 467 us (0.42 x), 1 685 spheres 812 -> 680 us (0.84 x), 65 spheres
+ * 409.5 -> 406.8 us; with spheres 20 pixels across 0.71 x, 0.88 x and 1.002 x (1.1 us more, beyond the 0.8 us spread).  At 10 000
+ * spheres a lane reaches 12 % of the bounds ([3] / [2]) while the wave stages 24 % of them ([1] / [0]); at 65 spheres both are one half.
+ * Out of scope: pruning by best_t and an ordered traversal; a per-entry level; the bounce rays of the adaptive and query kernels;
+ * caller-supplied rays; bounds for the other classes; a hierarchy over the bounds; the flag as a default or as part of
+ * RT_FLAG_STREAM_CULL. */
+#define RT_FLAG_STREAM_CULL_BOUNCE 1048576u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -490,6 +522,9 @@ int rt_get_stream_cull(const rt_ctx *ctx, uint32_t *on);
  * of the unit-sphere table (rt_get_stream_cull && rt_get_streamed_adaptive && at least two chunks), else 0.  RT_ERR_INVALID for a NULL
  * argument (before a device is looked for). */
 int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on);
+/* Culled bounce rays (RT_FLAG_STREAM_CULL_BOUNCE above): *on = 1 where rt_render culls the unit-sphere chunks of its bounce rays per ray,
+ * else 0.  RT_ERR_INVALID for a NULL argument (before a device is looked for). */
+int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
@@ -837,6 +872,15 @@ int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8]);
  * otherwise the kernel counts nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is
  * looked for. */
 int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8]);
+/* ... and the work words of the bounce queries of rt_render (rt_get_stream_cull_bounce), eight words of their own, cumulative since
+ * rt_create; rt_debug_stream_cull's words keep counting the primary and shadow work of the same kernel exactly as before.  Waits as
+ * rt_set_scene_status does.
+ *   [0] bounce chunk decisions: one per (wave, segment >= 1 with a lane in use, chunk bound asked)      [1] bounce chunks staged
+ *   [2] (lane, chunk) pairs asked by lanes that can be culled for      [3] of [2], the pairs that reach
+ *   [4] bounce queries in which no lane in use could be culled for      [5] - [7] 0
+ * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true; otherwise the
+ * kernel counts nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
+int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8]);
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
