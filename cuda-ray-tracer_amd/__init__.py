@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
     "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob",
-    "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_destroy",
+    "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_debug_wave_box", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
 MULTI_ABI_SYMBOLS = ["rt_create_multi", "rt_render_multi", "rt_multi_wait", "rt_multi_fb", "rt_multi_stream", "rt_multi_download", "rt_multi_info",
@@ -219,6 +219,7 @@ def lib():
         L.rt_get_counters_detail.argtypes = [vp, C.POINTER(CountersDetail)]
         L.rt_debug_counters.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_debug_stamp_rows.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.rt_debug_wave_box.argtypes = [vp, dp, C.POINTER(C.c_uint64), C.c_uint32, fp]
         L.rt_destroy.argtypes = [vp]
         L.rt_set_ssaa_threshold.argtypes = [vp, C.c_float]
         L.rt_set_ssaa_geometry.argtypes = [vp, C.c_float]
@@ -870,6 +871,17 @@ class Renderer:
         out = np.zeros((n.value, 16), dtype=np.uint64)
         if n.value:
             _check(lib().rt_debug_stamp_rows(self._h, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return out
+
+    def wave_box(self, pts, use_masks):
+        """Diagnostics (rt_debug_wave_box): the kernel's box helper alone.  pts = [n, 64, 3] float64, use_masks = [n] uint64 -> [n, 6] float32
+        (lox, hix, loy, hiy, loz, hiz)."""
+        pts = np.ascontiguousarray(pts, dtype=np.float64)
+        use_masks = np.ascontiguousarray(use_masks, dtype=np.uint64)
+        assert pts.ndim == 3 and pts.shape[1:] == (64, 3) and use_masks.shape == (pts.shape[0],)
+        out = np.zeros((pts.shape[0], 6), dtype=np.float32)
+        _check(lib().rt_debug_wave_box(self._h, pts.ctypes.data_as(C.POINTER(C.c_double)), use_masks.ctypes.data_as(C.POINTER(C.c_uint64)), pts.shape[0],
+                                       out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
     def counters(self):

@@ -1778,6 +1778,38 @@ extern "C" int rt_debug_stamp_rows(rt_ctx *ctx, uint64_t *out, size_t max_rows, 
     return read_synced(ctx, out, ctx->d_stamps, n * 16 * sizeof(uint64_t));
 }
 
+// The box helper of the render kernel (rt_wave_box.hpp) alone: one wave per entry.  Staged in buffers of the call's own, on the stream of
+// the context's last call, and waited for there, like read_behind_last_call.
+extern "C" int rt_debug_wave_box(rt_ctx *ctx, const double *pts, const uint64_t *use_masks, uint32_t n_waves, float *out)
+{
+    if (!ctx || !pts || !use_masks || !out) return fail(RT_ERR_INVALID, "rt_debug_wave_box: null argument");
+    if (n_waves == 0) return fail(RT_ERR_INVALID, "rt_debug_wave_box: n_waves is 0");
+    if (n_waves > 65536u) return fail(RT_ERR_INVALID, "rt_debug_wave_box: n_waves %u exceeds 65536", n_waves);
+    if (int rc = use_device(ctx)) return rc;
+    hipStream_t stream = ctx->last_stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream) RT_HIP(hipStreamIsCapturing(stream, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(RT_ERR_INVALID, "rt_debug_wave_box: the context's stream is capturing; end the capture first");
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "lane masks");
+    const size_t pts_bytes = sizeof(double) * 192u * (size_t) n_waves, mask_bytes = sizeof(uint64_t) * (size_t) n_waves, out_bytes = sizeof(float) * 6u * (size_t) n_waves;
+    DevMem<double> d_pts;
+    DevMem<unsigned long long> d_masks;
+    DevMem<float> d_out;
+    RT_HIP(d_pts.alloc(pts_bytes));
+    RT_HIP(d_masks.alloc(mask_bytes));
+    RT_HIP(d_out.alloc(out_bytes));
+    RT_HIP(hipMemcpyAsync(d_pts, pts, pts_bytes, hipMemcpyHostToDevice, stream));
+    RT_HIP(hipMemcpyAsync(d_masks, use_masks, mask_bytes, hipMemcpyHostToDevice, stream));
+    const hipError_t e = rt_launch_wave_box(d_pts, d_masks, n_waves, d_out, stream);
+    if (e != hipSuccess) {
+        (void) hipStreamSynchronize(stream); // (the copies read the caller's arrays and write buffers this call frees)
+        return fail(RT_ERR_DEVICE, "rt_debug_wave_box: kernel launch failed: %s", hipGetErrorString(e));
+    }
+    RT_HIP(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+    RT_HIP(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
 extern "C" int rt_destroy(rt_ctx *ctx)
 {
     if (!ctx) return RT_OK;

@@ -142,5 +142,8 @@ struct Kernels {
 extern "C" hipError_t rt_launch_assemble_planes(const void *gathered, size_t slot_stride, void *full, uint32_t width, uint32_t height, uint32_t world, uint32_t band_rows,
                                                 uint32_t elem_bytes, hipStream_t stream);
 extern "C" hipError_t rt_launch_merge_extents(const void *parts, uint32_t n_parts, uint32_t n_obj, void *out, hipStream_t stream);
+// rt_wave_box.hip, built once: the box helper of rt_wavefront.hip (rt_wave_box.hpp) alone, one wave per entry (rt_debug_wave_box); pts = [n_waves][64][3],
+// use_masks = [n_waves], out = [n_waves][6]
+extern "C" hipError_t rt_launch_wave_box(const double *pts, const unsigned long long *use_masks, uint32_t n_waves, float *out, hipStream_t stream);
 
 #endif

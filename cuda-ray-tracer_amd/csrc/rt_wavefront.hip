@@ -59,6 +59,7 @@
 #include "rt_launch.h" // RT_SYM, and the declarations of the launchers defined at the end of this file
 #include "rt_math.hpp"
 #include "rt_scene_dev.h"
+#include "rt_wave_box.hpp"
 #include "rt_wavefront_math.hpp"
 
 #ifndef RT_VARIANT
@@ -265,54 +266,13 @@ __device__ __noinline__ double cubic_test(const double *c, uint32_t rec, uint32_
     return cubic_test_body<true>(c, rec, abs, ox, oy, oz, dx, dy, dz, max_t, decide, refused);
 }
 
-// Cross-lane helpers.  Reductions run on DPP row operations (VALU latency) instead of ds_bpermute round trips
-// through the LDS crossbar; the result is taken from lane 63 with v_readlane and is wave-uniform.
+// Cross-lane helpers.  The one wave reduction of this file, the FP32 bounding box of a wave's hit points, is rt_wave_box.hpp's: six
+// fused DPP min / max chains (VALU latency) instead of ds_bpermute round trips through the LDS crossbar, wave-uniform results.
 __device__ __forceinline__ double readlane_d(double v, int l)
 {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
 }
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_d(double v)
-{
-    // lanes without a valid source (or masked rows) keep their own value: op(v, v) == v for min / max
-    const int lo = __builtin_amdgcn_update_dpp(__double2loint(v), __double2loint(v), CTRL, ROW_MASK, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(v), __double2hiint(v), CTRL, ROW_MASK, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-#define RT_WAVE_REDUCE(OP)                                                     \
-    {                                                                          \
-        double t;                                                              \
-        t = dpp_d<0xB1, 0xf>(v); v = OP; /* quad_perm [1,0,3,2] */           \
-        t = dpp_d<0x4E, 0xf>(v); v = OP; /* quad_perm [2,3,0,1] */           \
-        t = dpp_d<0x124, 0xf>(v); v = OP; /* row_ror:4 */                    \
-        t = dpp_d<0x128, 0xf>(v); v = OP; /* row_ror:8: every lane has its row of 16 */ \
-        t = dpp_d<0x142, 0xa>(v); v = OP; /* row_bcast:15 into rows 1, 3 */  \
-        t = dpp_d<0x143, 0xc>(v); v = OP; /* row_bcast:31 into rows 2, 3 */  \
-        return readlane_d(v, 63);                                              \
-    }
-// 32-bit flavour: one DPP-modified v_min_f32 / v_max_f32 per step
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_f(float v)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-#define RT_WAVE_REDUCE_F(OP)                                                     \
-    {                                                                            \
-        v = OP(v, dpp_f<0xB1, 0xf>(v));                                          \
-        v = OP(v, dpp_f<0x4E, 0xf>(v));                                          \
-        v = OP(v, dpp_f<0x124, 0xf>(v));                                         \
-        v = OP(v, dpp_f<0x128, 0xf>(v));                                         \
-        v = OP(v, dpp_f<0x142, 0xa>(v));                                         \
-        v = OP(v, dpp_f<0x143, 0xc>(v));                                         \
-        return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63)); \
-    }
-__device__ __forceinline__ float wave_min_f(float v) RT_WAVE_REDUCE_F(fminf)
-__device__ __forceinline__ float wave_max_f(float v) RT_WAVE_REDUCE_F(fmaxf)
-#undef RT_WAVE_REDUCE_F
-__device__ __forceinline__ double wave_min(double v) RT_WAVE_REDUCE((t < v ? t : v))
-__device__ __forceinline__ double wave_max(double v) RT_WAVE_REDUCE((t > v ? t : v))
-#undef RT_WAVE_REDUCE
 
 __device__ __forceinline__ unsigned long long primary_cone_mask(const UsEntry *us, uint32_t base, uint32_t end, const D3 &org,
                                                                 const D3 &axis, double cos_t, uint32_t lane)
@@ -1041,10 +1001,9 @@ __device__ __forceinline__ void lean_block(const FrameArgs &fa, const SceneLds &
 
                 // ---- the block's bounding box / ball and its culling records (phase A' of the other path), private to this wave ----
                 {
-                    const float inf = __builtin_inff();
-                    const float lox = wave_min_f(hit ? __double2float_rd(sp.x) : inf), hix = wave_max_f(hit ? __double2float_ru(sp.x) : -inf);
-                    const float loy = wave_min_f(hit ? __double2float_rd(sp.y) : inf), hiy = wave_max_f(hit ? __double2float_ru(sp.y) : -inf);
-                    const float loz = wave_min_f(hit ? __double2float_rd(sp.z) : inf), hiz = wave_max_f(hit ? __double2float_ru(sp.z) : -inf);
+                    float lo[3], hi[3];
+                    wave_box_f32(hit, sp.x, sp.y, sp.z, lo, hi);
+                    const float lox = lo[0], hix = hi[0], loy = lo[1], hiy = hi[1], loz = lo[2], hiz = hi[2];
                     const double dx = (double) hix - (double) lox, dy = (double) hiy - (double) loy, dz = (double) hiz - (double) loz;
                     Ball b;
                     b.cx = 0.5 * ((double) lox + (double) hix);
@@ -1713,10 +1672,11 @@ __global__ __launch_bounds__(256, (wf_occupancy<COUNT, HAS_GQ, HAS_CUBIC, HAS_MI
                 if (fa.n_us != 0u) { // (launch-uniform: box, ball and records only serve the culling of spheres)
                 // Bounding box of the chunk's hit points, reduced in FP32 with outward rounding (a box that is one float ulp larger
                 // costs nothing -- it only feeds the conservative culling -- and a 32-bit DPP min / max step is one instruction
-                // where the FP64 one is five); centre and radius of its ball in FP64.
-                const float lox = wave_min_f(__double2float_rd(px)), hix = wave_max_f(__double2float_ru(px));
-                const float loy = wave_min_f(__double2float_rd(py)), hiy = wave_max_f(__double2float_ru(py));
-                const float loz = wave_min_f(__double2float_rd(pz)), hiz = wave_max_f(__double2float_ru(pz));
+                // where the FP64 one is five); centre and radius of its ball in FP64.  (Every lane counts: the lanes past the chunk's
+                // last hit hold a copy of its first one.)
+                float lo[3], hi[3];
+                wave_box_f32(true, px, py, pz, lo, hi);
+                const float lox = lo[0], hix = hi[0], loy = lo[1], hiy = hi[1], loz = lo[2], hiz = hi[2];
                 const double dx = (double) hix - (double) lox, dy = (double) hiy - (double) loy, dz = (double) hiz - (double) loz;
                 Ball b;
                 b.cx = 0.5 * ((double) lox + (double) hix);

@@ -497,6 +497,14 @@ int rt_debug_counters(rt_ctx *ctx, uint64_t out[32]);
 /* Diagnostics (`make STAMPS=1` + MI355RT_DEBUG_COUNTERS=1 only): the last frame's per-wave rows of 16 words -- 0-11 cycles per phase,
  * 12 / 13 a 100 MHz clock at the wave's start / end; row = workgroup * 4 + wave.  out = NULL: only the row count. */
 int rt_debug_stamp_rows(rt_ctx *ctx, uint64_t *out, size_t max_rows, size_t *n_rows);
+/* Diagnostics: the render kernel's box helper run alone, one wave of 64 lanes per entry (csrc/rt_wave_box.hpp: the FP32 bounding box of a
+ * block's or a chunk's hit points, which feeds the conservative culling of shadow tests).  All four arrays are host memory: pts =
+ * [n_waves][64][3] doubles, lane l's point; use_masks = [n_waves], bit l set: lane l's point counts; out = [n_waves][6] floats: lox, hix, loy,
+ * hiy, loz, hiz -- per axis the minimum over the counted lanes of the largest float <= the coordinate and the maximum of the smallest float
+ * >= it, taken as fminf / fmaxf take them (a NaN coordinate drops out); (+inf, -inf) where no lane counts.  The context only names the device
+ * and the stream (that of its last call); nothing of it is read or changed.  The call copies in, runs one small kernel, copies out and
+ * waits.  RT_ERR_INVALID for a NULL argument, for n_waves == 0 or > 65536, and while the context's stream is capturing. */
+int rt_debug_wave_box(rt_ctx *ctx, const double *pts, const uint64_t *use_masks, uint32_t n_waves, float *out);
 
 /* RT_FLAG_SSAA_ADAPTIVE contexts only (RT_ERR_INVALID otherwise; a NaN tau is refused too).  The threshold applies from the next
  * rt_render on; it is a kernel argument, so a frame captured into a graph keeps the tau it was captured with. */

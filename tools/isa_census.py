@@ -3,7 +3,9 @@
 build, -save-temps): the whole kernel, and the part between the two s_memtime reads that bracket a block's light loop (shadow tests +
 shading).  Scalar-unit audit of DESIGN.md: how many scalar instructions stand next to the vector ones, and of what kind.  Static counts
 (every instruction once, whatever its trip count); the dynamic totals per frame are in profiles/r03_pmc_summary.txt.
-usage: python tools/isa_census.py > profiles/r03_isa_census.txt"""
+A third section counts the fixed prefix of a block with hits: the stretch between the end of the nearest-hit loop (the last loop back-edge in
+front of the first s_memtime) and that s_memtime -- normal, own-sphere window, the block's box (rt_wave_box.hpp), ball and culling records.
+usage: python tools/isa_census.py [another revision's rt_wavefront.hip] > profiles/r04_isa_census.txt"""
 import collections
 import os
 import re
@@ -14,9 +16,11 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc")
 tmp = tempfile.mkdtemp(prefix="isa_census_")
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-mllvm",
-                "-amdgpu-kernarg-preload-count=12", "-DRT_VARIANT=strict", "-ffp-contract=off", "-save-temps", "-c", os.path.join(CSRC, "rt_wavefront.hip"), "-o", "wf.o"],
+run = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-mllvm",
+                "-amdgpu-kernarg-preload-count=12", "-DRT_VARIANT=strict", "-ffp-contract=off", "-save-temps", "-Rpass-analysis=kernel-resource-usage", "-c",
+                sys.argv[1] if len(sys.argv) > 1 else os.path.join(CSRC, "rt_wavefront.hip"), "-o", "wf.o"],
                cwd=tmp, check=True, capture_output=True)
+remarks = run.stderr.decode().splitlines()
 asm = open(os.path.join(tmp, [f for f in os.listdir(tmp) if f.endswith("gfx950.s")][0])).read().splitlines()
 start = next(i for i, l in enumerate(asm) if re.match(r"_ZN10rtw_strict21wavefront_tile_kernelILb0ELb0ELb0ELb0ELb1E.*:", l))
 end = next(i for i in range(start, len(asm)) if asm[i].startswith(".Lfunc_end"))
@@ -66,3 +70,17 @@ census(body, "lean instantiation, whole kernel (wavefront_tile_kernel<false, fal
 mt = [i for i, l in enumerate(body) if "s_memtime" in l]
 if len(mt) >= 2:
     census(body[mt[0]:mt[-1]], "  ... of which between the s_memtime reads around a block's lights (point-light pass, ordered pass, their shadow tests and solves)")
+
+# ---- the fixed prefix of a block with hits: from the last loop back-edge before the first s_memtime to that s_memtime ----
+labels = {m.group(1): i for i, l in enumerate(body) for m in [re.match(r"(\.LBB\d+_\d+):", l)] if m}
+back = [i for i in range(mt[0]) for m in [re.match(r"\s+s_c?branch\w*\s+(\.LBB\d+_\d+)", body[i])] if m and labels.get(m.group(1), len(body)) < i]
+prefix = body[back[-1] + 1:mt[0]]
+print()
+census(prefix, "  fixed prefix of a block with hits (end of the nearest-hit loop .. first s_memtime: normal, own-sphere window, box, ball, records)")
+ops = collections.Counter(m.group(1) for l in prefix for m in [re.match(r"\s+([a-z_0-9]+)\b", l)] if m and not l.lstrip().startswith((".", ";")))
+dpp_minmax = sum(v for k, v in ops.items() if re.fullmatch(r"v_(min|max)_f32_dpp", k))
+print(f"    v_min_f32_dpp / v_max_f32_dpp {dpp_minmax}, v_mov_b32_dpp {ops['v_mov_b32_dpp']}, s_nop {ops['s_nop']}, v_readlane_b32 {ops['v_readlane_b32']}, "
+      f"v_cvt_f32_f64 {ops['v_cvt_f32_f64']}, s_setreg_imm32_b32 {ops['s_setreg_imm32_b32']}, VALU in all {sum(v for k, v in ops.items() if k.startswith('v_'))}")
+i0 = next(i for i, l in enumerate(remarks) if "Function Name: _ZN10rtw_strict21wavefront_tile_kernelILb0ELb0ELb0ELb0ELb1E" in l)
+print("  resources: " + ", ".join(re.sub(r".*remark: [^ ]+ +", "", l).replace(" [-Rpass-analysis=kernel-resource-usage]", "").strip() for l in remarks[i0 + 1:i0 + 10]
+                                 if re.search(r" VGPRs:|Occupancy|ScratchSize|VGPRs Spill", l)))
