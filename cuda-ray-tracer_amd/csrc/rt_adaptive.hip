@@ -166,23 +166,7 @@ __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevOb
     return res;
 }
 
-// the RGBA8 store of the render kernels, (unsigned char)(int)(v * 255.0f + 0.5f), with both operations rounded separately in
-// every build (the strict kernels' and rt_resolve.hip's value)
-__device__ __forceinline__ uchar4 quantise(float x, float y, float z)
-{
-    uchar4 px;
-    px.x = (unsigned char) (int) __fadd_rn(__fmul_rn(x, 255.0f), 0.5f);
-    px.y = (unsigned char) (int) __fadd_rn(__fmul_rn(y, 255.0f), 0.5f);
-    px.z = (unsigned char) (int) __fadd_rn(__fmul_rn(z, 255.0f), 0.5f);
-    px.w = 255;
-    return px;
-}
-
-// pairwise float32 sum over the lanes `m` apart (the resolve's tree, one level)
-__device__ __forceinline__ F3 xor_add(const F3 &v, int m)
-{
-    return F3{__fadd_rn(v.x, __shfl_xor(v.x, m)), __fadd_rn(v.y, __shfl_xor(v.y, m)), __fadd_rn(v.z, __shfl_xor(v.z, m))};
-}
+// (quantise, the RGBA8 store, and xor_add, one level of the resolve's tree: rt_shade.hpp, shared with the streamed ray-list kernels)
 
 // One lane = one sample ray; a wave = 64 / K^2 pixels (K = 4: 4 pixels of 16 lanes; K = 2: 16 pixels of 4 lanes).  Lane bits: i =
 // sub-column (K = 4: bits 0-1, K = 2: bit 0), j = sub-row (the next bits).  Workgroups of four waves stage the scene into LDS once

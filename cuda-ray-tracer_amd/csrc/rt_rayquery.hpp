@@ -7,6 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "rt_shade.hpp"          // RT_SYM and the variant's namespace
 #include "rt_wavefront_math.hpp" // class-table coefficients, us_needs_solve, needs_solve, accept
 
@@ -176,6 +178,20 @@ static inline RayQueryArgs rq_args(const FrameArgs *fa, uint32_t n)
     qa.tab_bytes = fa->off_mat - fa->off_us;
     qa.n = n;
     return qa;
+}
+
+// The launch ladder over the classes the scene of `fa` holds: calls launch(gq, cub) once, with std::true_type / std::false_type for
+// <HAS_GQ, HAS_CUBIC> -- inside, decltype(gq)::value is the template argument of the kernel to launch.
+template <typename Launch>
+static inline void rq_for_classes(const FrameArgs *fa, Launch &&launch)
+{
+    if (fa->n_cub) {
+        if (fa->n_gq) launch(std::true_type{}, std::true_type{});
+        else launch(std::false_type{}, std::true_type{});
+    } else {
+        if (fa->n_gq) launch(std::true_type{}, std::false_type{});
+        else launch(std::false_type{}, std::false_type{});
+    }
 }
 
 // the argument words of the colour kernels (rt_shade_rays.hip, rt_stream_queries.hip) and of the path kernels (rt_paths.hip, rt_stream_queries.hip)

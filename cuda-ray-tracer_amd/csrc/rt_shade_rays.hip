@@ -1,7 +1,8 @@
 // rt_shade_rays.hip -- the reference's colour for caller-supplied rays (include/mi355rt.h, rt_shade_rays).
 //
 // render_pixel (src/update-cpu.cpp:82-119) with ray_origin := o and dir := d of a ray the caller hands in, the direction used exactly as
-// given: nearest hit, every light's shadow test and surface_color, the clamp, then the reflection loop with its blends.  Compiled
+// given: nearest hit, every light's shadow test and surface_color, the clamp, then the reflection loop with its blends -- the shading
+// loop this kernel shares with the streamed kernels (rt_stream_shade.hpp: shade_loop), under the policy ShadeRaysStaged below.  Compiled
 // twice like rt_rays.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).  The object loops are the ray
 // queries' (rt_rayquery.hpp): the class tables where they are proven for the ray in hand -- decided anew for every shadow ray and every
 // bounce, whose origins and directions the kernel forms itself -- and the dense expansion elsewhere.  None of the render kernels' work
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_rayquery.hpp" // RayQueryArgs, the class tables in LDS, rq_tables / rq_plain, the ray and record layouts
+#include "rt_stream_shade.hpp" // the shading loop
 
 namespace RT_SYM(rtk) {
 
@@ -31,6 +33,35 @@ __device__ __forceinline__ void shade_query(const RayQueryArgs &qa, const RqTabl
     if (__ballot(use && !proven) != 0ull) rq_plain<OCCLUSION>(qa, gobj, o, d, use && !proven, t_max, best_t, best);
 }
 
+// The shading policy of a workgroup that holds all class tables in LDS: every query is shade_query; segment 0 stores the rt_hit of the
+// lane's ray, as rt_trace_rays writes it (out_rec == NULL: nothing).
+struct ShadeRaysStaged {
+    using Segment = ShadeNoSegment;
+    const RayQueryArgs qa; // (by value, as in ScShade: rt_stream_cull.hpp)
+    const RqTables S;
+    const DevObject *gobj;
+    RqRecord *out_rec;
+    uint64_t i;
+    bool live;
+
+    template <bool HAS_GQ, bool HAS_CUBIC>
+    __device__ __forceinline__ void nearest(uint32_t, uint32_t, const D3 &o, const D3 &d, bool use, double &best_t, int &best) const
+    {
+        shade_query<HAS_GQ, HAS_CUBIC, false>(qa, S, gobj, o, d, use, MAX_T, best_t, best);
+    }
+    __device__ __forceinline__ Segment segment(bool, const D3 &) const { return Segment{}; }
+    template <bool HAS_GQ, bool HAS_CUBIC>
+    __device__ __forceinline__ void occluded(const Segment &, uint32_t, const DevLight &, const D3 &so, const D3 &sd, bool use, double max_t, int &blocked) const
+    {
+        double unused_t = INFINITY;
+        shade_query<HAS_GQ, HAS_CUBIC, true>(qa, S, gobj, so, sd, use, max_t, unused_t, blocked);
+    }
+    __device__ __forceinline__ void first_hit(int best, double best_t, const D3 &sp, const D3 &sn) const
+    {
+        if (out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
+    }
+};
+
 // 256-thread workgroups, one ray per lane, the grid-stride loop of ray_query_kernel; the class tables go to LDS once per workgroup.
 // Per ray one bounce loop for the whole wave: iteration k traces the k-th segment of every lane that is still bouncing (all such
 // lanes have bounced exactly k times, so the reference's `cur_reflections` is the wave-uniform k).  out_rec != NULL: the rt_hit of
@@ -44,7 +75,6 @@ __global__ __launch_bounds__(256) void shade_rays_kernel(const ShadeRaysArgs sa,
     const uint32_t tid = threadIdx.x;
     const RqTables S = rq_stage_tables(qa, scene, smem);
     const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-    const F3 bg{sa.bg[0], sa.bg[1], sa.bg[2]};
 
     const uint64_t stride = (uint64_t) gridDim.x * 256u;
     for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (wave-uniform trip count)
@@ -57,70 +87,8 @@ __global__ __launch_bounds__(256) void shade_rays_kernel(const ShadeRaysArgs sa,
             o = D3{w0.x, w0.y, w1.x};
             d = D3{w1.y, w2.x, w2.y};
         }
-        F3 res = bg; // a first-segment miss is the background colour
-        float cur_ratio = 1.0f;
-        bool bouncing = live;
-        for (uint32_t k = 0; __ballot(bouncing) != 0ull; k++) {
-            // get_color_and_object, src/update-cpu.cpp:45-80: the nearest hit ...
-            double best_t = INFINITY;
-            int best = -1;
-            shade_query<HAS_GQ, HAS_CUBIC, false>(qa, S, gobj, o, d, bouncing, MAX_T, best_t, best);
-            const bool hit = bouncing && best >= 0;
-            const DevObject *bo = &gobj[hit ? best : 0]; // per-lane index: gathers from global memory, per hit
-            D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0};
-            if (hit) {
-                sp = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
-                sn = normal_vector(bo->c, sp); // all twenty coefficients, as rt_rays.hip; FP64, never flipped
-            }
-            if (k == 0u && out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
-            // ... every light in index order (wave-uniform: scalar loads), shadow_ray from sp + SHADOW_BIAS * sn.  The shadow ray is a ray
-            // the kernel formed: sp can lie beyond the tables' proven range and sn can be NaN, so shade_query decides again.
-            const D3 so{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
-            F3 acc{0.0f, 0.0f, 0.0f};
-            if (__ballot(hit) != 0ull) {
-                const F3 albedo{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
-                for (uint32_t l = 0; l < sa.n_lights; l++) {
-                    const DevLight *lt = &lights[l];
-                    const bool spherical = lt->spherical != 0;
-                    double max_t;
-                    const D3 sd = shadow_dir(lt->p, spherical, sp, max_t);
-                    double unused_t = INFINITY;
-                    int blocked = 0;
-                    shade_query<HAS_GQ, HAS_CUBIC, true>(qa, S, gobj, so, sd, hit, max_t, unused_t, blocked);
-                    if (hit && blocked == 0) {
-                        const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
-                        acc.x += c.x;
-                        acc.y += c.y;
-                        acc.z += c.z;
-                    }
-                }
-            }
-            if (bouncing) {
-                if (!hit) {
-                    if (k != 0u) RT_SYM(rtk)::blend(res, cur_ratio, bg); // a bounce that leaves the scene picks up the background
-                    bouncing = false;
-                } else {
-                    // glm::min(vec3(1.0f), acc)
-                    const F3 oc{(acc.x < 1.0f) ? acc.x : 1.0f, (acc.y < 1.0f) ? acc.y : 1.0f, (acc.z < 1.0f) ? acc.z : 1.0f};
-                    if (k == 0u) res = oc;
-                    else RT_SYM(rtk)::blend(res, cur_ratio, oc);
-                    // the reflection loop, src/update-cpu.cpp:96-117
-                    const float refl = bo->refl;
-                    if (!((double) refl > EPS)) {
-                        bouncing = false;
-                    } else {
-                        cur_ratio *= refl;
-                        if (k == sa.max_refl) {
-                            RT_SYM(rtk)::blend(res, cur_ratio, bg);
-                            bouncing = false;
-                        } else {
-                            d = reflect_ray(d, sn); // of the direction as it is
-                            o = so;
-                        }
-                    }
-                }
-            }
-        }
+        ShadeRaysStaged pol{qa, S, gobj, out_rec, i, live};
+        const F3 res = shade_loop<HAS_GQ, HAS_CUBIC>(sa, scene, lights, tid & 63u, pol, o, d, live);
         if (live) out_rgba[i] = float4{res.x, res.y, res.z, 1.0f}; // one 16-byte store
     }
 }
@@ -147,12 +115,6 @@ extern "C" hipError_t RT_SYM(rt_launch_shade_rays)(const FrameArgs *fa, const vo
     const RqRay *r = reinterpret_cast<const RqRay *>(rays);
     float4 *px = reinterpret_cast<float4 *>(rgba);
     RqRecord *rec = reinterpret_cast<RqRecord *>(hits);
-    if (fa->n_cub) {
-        if (fa->n_gq) hipLaunchKernelGGL((shade_rays_kernel<true, true>), g, block, lds, stream, sa, s, lt, r, px, rec);
-        else hipLaunchKernelGGL((shade_rays_kernel<false, true>), g, block, lds, stream, sa, s, lt, r, px, rec);
-    } else {
-        if (fa->n_gq) hipLaunchKernelGGL((shade_rays_kernel<true, false>), g, block, lds, stream, sa, s, lt, r, px, rec);
-        else hipLaunchKernelGGL((shade_rays_kernel<false, false>), g, block, lds, stream, sa, s, lt, r, px, rec);
-    }
+    rq_for_classes(fa, [&](auto gq, auto cub) { hipLaunchKernelGGL((shade_rays_kernel<decltype(gq)::value, decltype(cub)::value>), g, block, lds, stream, sa, s, lt, r, px, rec); });
     return hipGetLastError();
 }

@@ -1,24 +1,22 @@
 // rt_stream.hip -- the streamed frame kernel: rt_render for scenes of any size (include/mi355rt.h, "Streamed frames").
 //
 // The frame of rt_render by the arithmetic of rt_shade_rays on the rays of rt_primary_rays: one ray per pixel from the frame's origin
-// along primary_dir_tab, then shade_rays_kernel's body -- nearest hit, normal_vector in full, every light in index order with its
-// occlusion query from sp + SHADOW_BIAS * sn, surface_color, the clamp, the reflection loop with its blends.  No facing-away skip and
-// no own-sphere rule.  What differs is where the object loops read the class tables: not from a copy of all of them in LDS, which
-// bounds the scene's size, but from the scene blob in global memory through a wave-private LDS slice, 64 entries at a time
-// (rt_stream.hpp).  The only work removal is the cone culling of primary rays, one lane per sphere as in rt_gbuffer.hip.
+// along primary_dir_tab, then the shading loop every kernel of this family runs (rt_stream_shade.hpp: shade_loop).  What differs from
+// shade_rays_kernel is where the object loops read the class tables: not from a copy of all of them in LDS, which bounds the scene's
+// size, but from the scene blob in global memory through a wave-private LDS slice, 64 entries at a time (rt_stream.hpp).  The only work
+// removal is the cone culling of primary rays, one lane per sphere as in rt_gbuffer.hip (the policy SqShade with its cone on).
 // Compiled twice like rt_shade_rays.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).
 // There is no workgroup barrier anywhere in this file: the four waves of a workgroup run different numbers of bounces and chunks.
 // The kernel reads the scene blob, the lights and the camera-plane tables and writes the frame: no tile words, launch-order
 // generations, census, counters or frame tag -- a frame depends on nothing an earlier frame left.
 #include <hip/hip_runtime.h>
 #include "rt_launch.h" // the launcher below, as the host sees it
-#include "rt_stream.hpp" // the streamed object loops; RayQueryArgs and the plain path (rt_rayquery.hpp)
+#include "rt_stream_shell.hpp" // a lane's pixel and the frame store; the shading loop and SqShade (rt_stream_shade.hpp) over rt_stream.hpp
 
 namespace RT_SYM(rtk) {
 
-// One 256-thread workgroup per 16 x 16 tile of this rank's rows, one wave per 8 x 8 block, lanes are pixels (gbuffer_kernel's shape).
-// Lanes outside the image trace a clamped pixel's whole path, so that the block's corner lanes always span its cone, and store
-// nothing.  Per wave one bounce loop: iteration k traces the k-th segment of every lane that is still bouncing.
+// The frames' launch shape (rt_stream_shell.hpp: sf_pixel).  Per wave one bounce loop: iteration k traces the k-th segment of every
+// lane that is still bouncing.
 template <bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void stream_frame_kernel(const FrameArgs fa, const RayQueryArgs qa, const unsigned char *__restrict__ scene,
                                                            const DevLight *__restrict__ lights, const double *__restrict__ camx, const double *__restrict__ camy,
@@ -27,93 +25,11 @@ __global__ __launch_bounds__(256) void stream_frame_kernel(const FrameArgs fa, c
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     unsigned char *slice = smem + wave * SQ_SLICE_BYTES; // this wave's, never another's
-    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-    const F3 bg{fa.bg[0], fa.bg[1], fa.bg[2]};
-
-    const uint32_t tile_x = blockIdx.x % fa.tiles_x, tile_y = blockIdx.x / fa.tiles_x;
-    const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
-    const bool inside = x < fa.width && lr < fa.local_rows;
-    const uint32_t col = x < fa.width ? x : fa.width - 1u;
-    const uint32_t row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
-
-    D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
-    D3 d = primary_dir_tab(fa, camx[col], camy[row]);
-    F3 res = bg; // a first-segment miss is the background colour
-    float cur_ratio = 1.0f;
-    bool bouncing = true;
-    for (uint32_t k = 0; __ballot(bouncing) != 0ull; k++) {
-        // get_color_and_object, src/update-cpu.cpp:45-80: the nearest hit ...
-        double best_t = INFINITY;
-        int best = -1;
-        sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, k == 0u && fa.cull != 0u, MAX_T, best_t, best);
-        const bool hit = bouncing && best >= 0;
-        const DevObject *bo = &gobj[hit ? best : 0]; // per-lane index: gathers from global memory, per hit
-        D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0};
-        if (hit) {
-            sp = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
-            sn = normal_vector(bo->c, sp); // all twenty coefficients; FP64, never flipped
-        }
-        // ... every light in index order (wave-uniform: scalar loads), shadow_ray from sp + SHADOW_BIAS * sn; a ray the kernel formed, so
-        // sq_query decides anew whether the tables are proven for it
-        const D3 so{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
-        F3 acc{0.0f, 0.0f, 0.0f};
-        if (__ballot(hit) != 0ull) {
-            const F3 albedo{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
-            for (uint32_t l = 0; l < fa.n_lights; l++) {
-                const DevLight *lt = &lights[l];
-                const bool spherical = lt->spherical != 0;
-                double max_t;
-                const D3 sd = shadow_dir(lt->p, spherical, sp, max_t);
-                double unused_t = INFINITY;
-                int blocked = 0;
-                sq_query<HAS_GQ, HAS_CUBIC, true>(qa, scene, slice, lane, so, sd, hit, false, max_t, unused_t, blocked);
-                if (hit && blocked == 0) {
-                    const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
-                    acc.x += c.x;
-                    acc.y += c.y;
-                    acc.z += c.z;
-                }
-            }
-        }
-        if (bouncing) {
-            if (!hit) {
-                if (k != 0u) RT_SYM(rtk)::blend(res, cur_ratio, bg); // a bounce that leaves the scene picks up the background
-                bouncing = false;
-            } else {
-                // glm::min(vec3(1.0f), acc)
-                const F3 oc{(acc.x < 1.0f) ? acc.x : 1.0f, (acc.y < 1.0f) ? acc.y : 1.0f, (acc.z < 1.0f) ? acc.z : 1.0f};
-                if (k == 0u) res = oc;
-                else RT_SYM(rtk)::blend(res, cur_ratio, oc);
-                // the reflection loop, src/update-cpu.cpp:96-117
-                const float refl = bo->refl;
-                if (!((double) refl > EPS)) {
-                    bouncing = false;
-                } else {
-                    cur_ratio *= refl;
-                    if (k == fa.max_refl) {
-                        RT_SYM(rtk)::blend(res, cur_ratio, bg);
-                        bouncing = false;
-                    } else {
-                        d = reflect_ray(d, sn); // of the direction as it is
-                        o = so;
-                    }
-                }
-            }
-        }
-    }
-    if (!inside) return; // (behind the last wave-wide operation)
-    const size_t pix = (size_t) lr * fa.width + x;
-    if (fa.rgba8) { // launch-uniform; the wire format of the render kernels: iround(c * 255), alpha 255
-        uchar4 px;
-        px.x = (unsigned char) (int) (res.x * 255.0f + 0.5f);
-        px.y = (unsigned char) (int) (res.y * 255.0f + 0.5f);
-        px.z = (unsigned char) (int) (res.z * 255.0f + 0.5f);
-        px.w = 255;
-        reinterpret_cast<uchar4 *>(fb)[pix] = px;
-    } else {
-        reinterpret_cast<float4 *>(fb)[pix] = make_float4(res.x, res.y, res.z, 1.0f);
-    }
+    const SfPixel p = sf_pixel(fa, wave, lane);
+    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
+    SqShade pol{qa, scene, slice, fa.cull != 0u};
+    const F3 res = shade_loop<HAS_GQ, HAS_CUBIC>(fa, scene, lights, lane, pol, o, primary_dir_tab(fa, camx[p.col], camy[p.row]), true);
+    sf_store(fa, fb, p, res);
 }
 
 } // namespace RT_SYM(rtk)
@@ -129,12 +45,8 @@ extern "C" hipError_t RT_SYM(rt_launch_stream)(const FrameArgs *fa, const void *
     const dim3 g(fa->n_tiles), block(256);
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     const DevLight *lt = reinterpret_cast<const DevLight *>(lights);
-    if (fa->n_cub) {
-        if (fa->n_gq) hipLaunchKernelGGL((stream_frame_kernel<true, true>), g, block, 0, stream, *fa, qa, s, lt, camx, camy, fb);
-        else hipLaunchKernelGGL((stream_frame_kernel<false, true>), g, block, 0, stream, *fa, qa, s, lt, camx, camy, fb);
-    } else {
-        if (fa->n_gq) hipLaunchKernelGGL((stream_frame_kernel<true, false>), g, block, 0, stream, *fa, qa, s, lt, camx, camy, fb);
-        else hipLaunchKernelGGL((stream_frame_kernel<false, false>), g, block, 0, stream, *fa, qa, s, lt, camx, camy, fb);
-    }
+    rq_for_classes(fa, [&](auto gq, auto cub) {
+        hipLaunchKernelGGL((stream_frame_kernel<decltype(gq)::value, decltype(cub)::value>), g, block, 0, stream, *fa, qa, s, lt, camx, camy, fb);
+    });
     return hipGetLastError();
 }

@@ -1,9 +1,9 @@
 // rt_stream_cull.hip -- the streamed frame kernel with whole chunks of the unit-sphere table culled: rt_render of a context whose
 // RT_FLAG_STREAM_CULL decision is true (include/mi355rt.h, "Culled streamed frames").
 //
-// stream_frame_kernel's launch shape and body (rt_stream.hip): one ray per pixel, nearest hit, every light in index order with its
-// occlusion query, the reflection loop.  What differs is which 64-entry chunks of the unit-sphere table a query stages
-// (rt_stream_cull.hpp): the primary rays of a block only those whose bound reaches into the block's cone, the shadow rays of a segment
+// stream_frame_kernel's launch shape (rt_stream_shell.hpp) and its shading loop (rt_stream_shade.hpp: shade_loop), under another policy
+// (rt_stream_cull.hpp: ScShade).  What differs is which 64-entry chunks of the unit-sphere table a query stages: the primary rays of
+// a block only those whose bound reaches into the block's cone, the shadow rays of a segment
 // towards one light only those whose bound is relevant for the ball around the wave's hit points -- and of a staged chunk's entries
 // only the relevant ones are swept.  Not culled: a segment with a non-finite hit point, a directional light with |d|^2 <= EPS (the
 // reference's linear branch is not geometry), the other class tables, and the nearest-hit queries of bounce rays (segments >= 1).
@@ -13,7 +13,8 @@
 // wave-uniform test and added with one vector atomic per word at the wave's end.
 #include <hip/hip_runtime.h>
 #include "rt_launch.h" // the launcher below, as the host sees it
-#include "rt_stream_cull.hpp" // the culled unit-sphere loops over rt_stream.hpp
+#include "rt_stream_cull.hpp"  // the culled unit-sphere loops over rt_stream.hpp, and their shading policy
+#include "rt_stream_shell.hpp" // a lane's pixel and the frame store
 
 namespace RT_SYM(rtk) {
 
@@ -27,109 +28,13 @@ __global__ __launch_bounds__(256) void stream_cull_frame_kernel(const FrameArgs 
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     unsigned char *slice = smem + wave * SQ_SLICE_BYTES; // this wave's, never another's
-    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-    const F3 bg{fa.bg[0], fa.bg[1], fa.bg[2]};
     ScStats st{ca.stats != nullptr, {0u, 0u, 0u, 0u, 0u, 0u, 0u}};
-
-    const uint32_t tile_x = blockIdx.x % fa.tiles_x, tile_y = blockIdx.x / fa.tiles_x;
-    const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
-    const bool inside = x < fa.width && lr < fa.local_rows;
-    const uint32_t col = x < fa.width ? x : fa.width - 1u;
-    const uint32_t row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
-
-    D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
-    D3 d = primary_dir_tab(fa, camx[col], camy[row]);
-    F3 res = bg; // a first-segment miss is the background colour
-    float cur_ratio = 1.0f;
-    bool bouncing = true;
-    for (uint32_t k = 0; __ballot(bouncing) != 0ull; k++) {
-        // get_color_and_object, src/update-cpu.cpp:45-80: the nearest hit ...
-        double best_t = INFINITY;
-        int best = -1;
-        if (k == 0u) sc_query_primary<HAS_GQ, HAS_CUBIC>(qa, ca, scene, slice, lane, o, d, bouncing, best_t, best, st); // (fa.cull != 0: the context's decision)
-        else sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best); // bounce rays: a full sweep
-        const bool hit = bouncing && best >= 0;
-        const DevObject *bo = &gobj[hit ? best : 0]; // per-lane index: gathers from global memory, per hit
-        D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0};
-        if (hit) {
-            sp = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
-            sn = normal_vector(bo->c, sp); // all twenty coefficients; FP64, never flipped
-        }
-        // ... every light in index order (wave-uniform: scalar loads), shadow_ray from sp + SHADOW_BIAS * sn; a ray the kernel formed, so
-        // sq_query decides anew whether the tables are proven for it
-        const D3 so{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
-        F3 acc{0.0f, 0.0f, 0.0f};
-        if (__ballot(hit) != 0ull) {
-            const F3 albedo{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
-            Ball ball;
-            const bool cull_seg = sc_hit_ball(hit, sp, ball); // once per segment; false: a non-finite hit point, test everything
-            for (uint32_t l = 0; l < fa.n_lights; l++) {
-                const DevLight *lt = &lights[l];
-                const bool spherical = lt->spherical != 0;
-                double max_t;
-                const D3 sd = shadow_dir(lt->p, spherical, sp, max_t);
-                double unused_t = INFINITY;
-                int blocked = 0;
-                if (cull_seg && (spherical || fabs(lt->u2) > EPS)) { // (wave-uniform)
-                    if (spherical) sc_query_shadow<HAS_GQ, HAS_CUBIC, true>(qa, ca, scene, slice, lane, so, sd, hit, ball, *lt, max_t, blocked, st);
-                    else sc_query_shadow<HAS_GQ, HAS_CUBIC, false>(qa, ca, scene, slice, lane, so, sd, hit, ball, *lt, max_t, blocked, st);
-                } else {
-                    sq_query<HAS_GQ, HAS_CUBIC, true>(qa, scene, slice, lane, so, sd, hit, false, max_t, unused_t, blocked);
-                    if (st.on) st.w[6] += 1u;
-                }
-                if (hit && blocked == 0) {
-                    const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
-                    acc.x += c.x;
-                    acc.y += c.y;
-                    acc.z += c.z;
-                }
-            }
-        }
-        if (bouncing) {
-            if (!hit) {
-                if (k != 0u) RT_SYM(rtk)::blend(res, cur_ratio, bg); // a bounce that leaves the scene picks up the background
-                bouncing = false;
-            } else {
-                // glm::min(vec3(1.0f), acc)
-                const F3 oc{(acc.x < 1.0f) ? acc.x : 1.0f, (acc.y < 1.0f) ? acc.y : 1.0f, (acc.z < 1.0f) ? acc.z : 1.0f};
-                if (k == 0u) res = oc;
-                else RT_SYM(rtk)::blend(res, cur_ratio, oc);
-                // the reflection loop, src/update-cpu.cpp:96-117
-                const float refl = bo->refl;
-                if (!((double) refl > EPS)) {
-                    bouncing = false;
-                } else {
-                    cur_ratio *= refl;
-                    if (k == fa.max_refl) {
-                        RT_SYM(rtk)::blend(res, cur_ratio, bg);
-                        bouncing = false;
-                    } else {
-                        d = reflect_ray(d, sn); // of the direction as it is
-                        o = so;
-                    }
-                }
-            }
-        }
-    }
-    if (st.on && lane < 7u) { // one vector atomic per word and wave
-        uint32_t mine = 0u;
-#pragma unroll
-        for (uint32_t i = 0; i < 7u; i++) mine = lane == i ? st.w[i] : mine;
-        if (mine) atomicAdd(ca.stats + lane, (unsigned long long) mine);
-    }
-    if (!inside) return; // (behind the last wave-wide operation)
-    const size_t pix = (size_t) lr * fa.width + x;
-    if (fa.rgba8) { // launch-uniform; the wire format of the render kernels: iround(c * 255), alpha 255
-        uchar4 px;
-        px.x = (unsigned char) (int) (res.x * 255.0f + 0.5f);
-        px.y = (unsigned char) (int) (res.y * 255.0f + 0.5f);
-        px.z = (unsigned char) (int) (res.z * 255.0f + 0.5f);
-        px.w = 255;
-        reinterpret_cast<uchar4 *>(fb)[pix] = px;
-    } else {
-        reinterpret_cast<float4 *>(fb)[pix] = make_float4(res.x, res.y, res.z, 1.0f);
-    }
+    const SfPixel p = sf_pixel(fa, wave, lane);
+    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
+    ScShade pol{qa, ca, scene, slice, st};
+    const F3 res = shade_loop<HAS_GQ, HAS_CUBIC>(fa, scene, lights, lane, pol, o, primary_dir_tab(fa, camx[p.col], camy[p.row]), true);
+    if (st.on) sc_flush(st.w, ca.stats, lane);
+    sf_store(fa, fb, p, res);
 }
 
 } // namespace RT_SYM(rtk)
@@ -147,12 +52,8 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_cull)(const FrameArgs *fa, const v
     const dim3 g(fa->n_tiles), block(256);
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     const DevLight *lt = reinterpret_cast<const DevLight *>(lights);
-    if (fa->n_cub) {
-        if (fa->n_gq) hipLaunchKernelGGL((stream_cull_frame_kernel<true, true>), g, block, 0, stream, *fa, qa, ca, s, lt, camx, camy, fb);
-        else hipLaunchKernelGGL((stream_cull_frame_kernel<false, true>), g, block, 0, stream, *fa, qa, ca, s, lt, camx, camy, fb);
-    } else {
-        if (fa->n_gq) hipLaunchKernelGGL((stream_cull_frame_kernel<true, false>), g, block, 0, stream, *fa, qa, ca, s, lt, camx, camy, fb);
-        else hipLaunchKernelGGL((stream_cull_frame_kernel<false, false>), g, block, 0, stream, *fa, qa, ca, s, lt, camx, camy, fb);
-    }
+    rq_for_classes(fa, [&](auto gq, auto cub) {
+        hipLaunchKernelGGL((stream_cull_frame_kernel<decltype(gq)::value, decltype(cub)::value>), g, block, 0, stream, *fa, qa, ca, s, lt, camx, camy, fb);
+    });
     return hipGetLastError();
 }

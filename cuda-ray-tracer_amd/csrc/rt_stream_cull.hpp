@@ -13,7 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "rt_stream.hpp"
+#include "rt_stream_shade.hpp" // the shading loop whose policy ends this file; sq_query and the staging idiom (rt_stream.hpp)
 
 namespace RT_SYM(rtk) {
 
@@ -30,6 +30,16 @@ struct ScStats {
     bool on;
     uint32_t w[7];
 };
+
+// a wave's work words w[0 .. N) added to dst[0 .. N) at the wave's end: one vector atomic per word, lane i adds word i (`mine`: what a
+// lane beyond N adds to its own word, if anything)
+template <uint32_t N>
+__device__ __forceinline__ void sc_flush(const uint32_t (&w)[N], unsigned long long *dst, uint32_t lane, uint32_t mine = 0u)
+{
+#pragma unroll
+    for (uint32_t i = 0; i < N; i++) mine = lane == i ? w[i] : mine;
+    if (mine) atomicAdd(dst + lane, (unsigned long long) mine);
+}
 
 __device__ __forceinline__ double sc_wave_min(double v)
 {
@@ -203,6 +213,49 @@ __device__ __forceinline__ void sc_query_shadow(const RayQueryArgs &qa, const St
     }
     if (plain != 0ull) rq_plain<true>(qa, reinterpret_cast<const DevObject *>(scene), o, d, use && !proven, t_max, unused_t, best);
 }
+
+// The shading policy (rt_stream_shade.hpp) of a wave whose lanes are the pixels of one 8 x 8 block: segment 0 culled by the block's cone,
+// the shadow rays of a segment by the ball around the wave's hit points, bounce rays (the nearest hit of segments >= 1) swept in full.
+struct ScSegment {
+    Ball ball;
+    bool cull; // false: a non-finite hit point, test everything in this segment
+};
+struct ScShade {
+    using Segment = ScSegment;
+    const RayQueryArgs qa; // (qa and ca by value: held by reference, the bounce sweeps of stream_cull_frame_kernel came out 4.7 % slower on a
+    const StreamCullArgs ca; // mirrored field -- profiles/stream_shared_loop.txt)
+    const unsigned char *scene;
+    unsigned char *slice; // SQ_SLICE_BYTES of LDS that belong to this wave
+    ScStats &st;
+
+    template <bool HAS_GQ, bool HAS_CUBIC>
+    __device__ __forceinline__ void nearest(uint32_t k, uint32_t lane, const D3 &o, const D3 &d, bool use, double &best_t, int &best) const
+    {
+        if (k == 0u) sc_query_primary<HAS_GQ, HAS_CUBIC>(qa, ca, scene, slice, lane, o, d, use, best_t, best, st); // (fa.cull != 0: the context's decision)
+        else sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, use, false, MAX_T, best_t, best); // bounce rays: a full sweep
+    }
+    __device__ __forceinline__ Segment segment(bool hit, const D3 &sp) const
+    {
+        Segment seg;
+        seg.cull = sc_hit_ball(hit, sp, seg.ball);
+        return seg;
+    }
+    // Not culled for: a directional light with |d|^2 <= EPS (the reference's linear branch is not geometry).
+    template <bool HAS_GQ, bool HAS_CUBIC>
+    __device__ __forceinline__ void occluded(const Segment &seg, uint32_t lane, const DevLight &lt, const D3 &so, const D3 &sd, bool use, double max_t, int &blocked) const
+    {
+        const bool spherical = lt.spherical != 0;
+        if (seg.cull && (spherical || fabs(lt.u2) > EPS)) { // (wave-uniform)
+            if (spherical) sc_query_shadow<HAS_GQ, HAS_CUBIC, true>(qa, ca, scene, slice, lane, so, sd, use, seg.ball, lt, max_t, blocked, st);
+            else sc_query_shadow<HAS_GQ, HAS_CUBIC, false>(qa, ca, scene, slice, lane, so, sd, use, seg.ball, lt, max_t, blocked, st);
+        } else {
+            double unused_t = INFINITY;
+            sq_query<HAS_GQ, HAS_CUBIC, true>(qa, scene, slice, lane, so, sd, use, false, max_t, unused_t, blocked);
+            if (st.on) st.w[6] += 1u;
+        }
+    }
+    __device__ __forceinline__ void first_hit(int, double, const D3 &, const D3 &) const {}
+};
 
 } // namespace RT_SYM(rtk)
 

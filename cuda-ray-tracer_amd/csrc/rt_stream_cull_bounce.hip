@@ -1,13 +1,15 @@
 // rt_stream_cull_bounce.hip -- the culled streamed frame kernel with the bounce rays culled as well: rt_render of a context whose
 // RT_FLAG_STREAM_CULL_BOUNCE decision is true (include/mi355rt.h, "Culled bounce rays").
 //
-// stream_cull_frame_kernel's launch shape and body (rt_stream_cull.hip), copied rather than shared so that the twin's machine code stays
-// what it was.  One line differs: the nearest-hit query of a segment k >= 1 is sc_query_bounce (rt_stream_cull_bounce.hpp) instead of
-// sq_query's full sweep -- every lane asks rtm::ray_reaches about its own ray and each chunk bound, the wave stages a chunk only if some
-// lane in use reaches it, and sweeps it for those lanes alone.  The primary and the shadow rays are culled as in the twin, and the twin's
-// work words (rt_debug_stream_cull) count them exactly as the twin does; the bounce queries have five words of their own
-// (rt_debug_stream_cull_bounce).  The frame is stream_frame_kernel's: the same arithmetic per tested object, and no dropped object's root
-// could have been accepted.
+// stream_cull_frame_kernel's launch shape (rt_stream_shell.hpp) and shading loop (rt_stream_cull.hip).  One line differs: the nearest-hit
+// query of a segment k >= 1 is sc_query_bounce (rt_stream_cull_bounce.hpp) instead of sq_query's full sweep -- every lane asks
+// rtm::ray_reaches about its own ray and each chunk bound, the wave stages a chunk only if some lane in use reaches it, and sweeps it for
+// those lanes alone.  The primary and the shadow rays are culled as in the twin, and the twin's work words (rt_debug_stream_cull) count
+// them exactly as the twin does; the bounce queries have five words of their own (rt_debug_stream_cull_bounce).  The frame is
+// stream_frame_kernel's: the same arithmetic per tested object, and no dropped object's root could have been accepted.
+// This kernel alone does not go through the shared loop (rt_stream_shade.hpp: shade_loop) but holds its text, ScShade's hooks written
+// in place: through the shared loop the strict <true, true> instantiation needs 258 registers and loses its second wave per SIMD
+// (profiles/stream_shared_loop.txt), whatever shape the policy takes.  A change to shade_loop has to be made here as well.
 // All four instantiations of both builds meet the build rule (no VGPR spill, no private segment, two waves per SIMD): none keeps sq_query.
 // Compiled twice like rt_stream_cull.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).
 // There is no workgroup barrier anywhere in this file.  The work words are kept per wave in scalars behind a wave-uniform test and added
@@ -15,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "rt_launch.h" // the launcher below, as the host sees it
 #include "rt_stream_cull_bounce.hpp" // sc_query_bounce over rt_stream_cull.hpp's culled unit-sphere loops
+#include "rt_stream_shell.hpp"       // a lane's pixel and the frame store
 
 namespace RT_SYM(rtk) {
 
@@ -29,20 +32,14 @@ __global__ __launch_bounds__(256) void stream_cull_bounce_frame_kernel(const Fra
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     unsigned char *slice = smem + wave * SQ_SLICE_BYTES; // this wave's, never another's
-    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-    const F3 bg{fa.bg[0], fa.bg[1], fa.bg[2]};
     ScStats st{ca.stats != nullptr, {0u, 0u, 0u, 0u, 0u, 0u, 0u}};
     ScBounceStats bs{ca.stats != nullptr, {0u, 0u, 0u, 0u, 0u}};
-
-    const uint32_t tile_x = blockIdx.x % fa.tiles_x, tile_y = blockIdx.x / fa.tiles_x;
-    const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
-    const bool inside = x < fa.width && lr < fa.local_rows;
-    const uint32_t col = x < fa.width ? x : fa.width - 1u;
-    const uint32_t row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
-
+    const SfPixel p = sf_pixel(fa, wave, lane);
+    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
+    const F3 bg{fa.bg[0], fa.bg[1], fa.bg[2]};
     D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
-    D3 d = primary_dir_tab(fa, camx[col], camy[row]);
+    D3 d = primary_dir_tab(fa, camx[p.col], camy[p.row]);
+    // shade_loop's text with ScShade's hooks in place (see the head of this file for why it is written out here)
     F3 res = bg; // a first-segment miss is the background colour
     float cur_ratio = 1.0f;
     bool bouncing = true;
@@ -115,28 +112,11 @@ __global__ __launch_bounds__(256) void stream_cull_bounce_frame_kernel(const Fra
             }
         }
     }
-    if (st.on && lane < 7u) { // one vector atomic per word and wave
-        uint32_t mine = 0u;
-#pragma unroll
-        for (uint32_t i = 0; i < 7u; i++) mine = lane == i ? st.w[i] : mine;
-        if (mine) atomicAdd(ca.stats + lane, (unsigned long long) mine);
-        uint32_t bounce = 0u;
-#pragma unroll
-        for (uint32_t i = 0; i < 5u; i++) bounce = lane == i ? bs.w[i] : bounce;
-        if (lane < 5u && bounce) atomicAdd(bstats + lane, (unsigned long long) bounce);
+    if (st.on) {
+        sc_flush(st.w, ca.stats, lane);
+        sc_flush(bs.w, bstats, lane);
     }
-    if (!inside) return; // (behind the last wave-wide operation)
-    const size_t pix = (size_t) lr * fa.width + x;
-    if (fa.rgba8) { // launch-uniform; the wire format of the render kernels: iround(c * 255), alpha 255
-        uchar4 px;
-        px.x = (unsigned char) (int) (res.x * 255.0f + 0.5f);
-        px.y = (unsigned char) (int) (res.y * 255.0f + 0.5f);
-        px.z = (unsigned char) (int) (res.z * 255.0f + 0.5f);
-        px.w = 255;
-        reinterpret_cast<uchar4 *>(fb)[pix] = px;
-    } else {
-        reinterpret_cast<float4 *>(fb)[pix] = make_float4(res.x, res.y, res.z, 1.0f);
-    }
+    sf_store(fa, fb, p, res);
 }
 
 } // namespace RT_SYM(rtk)
@@ -155,12 +135,9 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_cull_bounce)(const FrameArgs *fa, 
     const dim3 g(fa->n_tiles), block(256);
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     const DevLight *lt = reinterpret_cast<const DevLight *>(lights);
-    if (fa->n_cub) {
-        if (fa->n_gq) hipLaunchKernelGGL((stream_cull_bounce_frame_kernel<true, true>), g, block, 0, stream, *fa, qa, ca, bounce_stats, s, lt, camx, camy, fb);
-        else hipLaunchKernelGGL((stream_cull_bounce_frame_kernel<false, true>), g, block, 0, stream, *fa, qa, ca, bounce_stats, s, lt, camx, camy, fb);
-    } else {
-        if (fa->n_gq) hipLaunchKernelGGL((stream_cull_bounce_frame_kernel<true, false>), g, block, 0, stream, *fa, qa, ca, bounce_stats, s, lt, camx, camy, fb);
-        else hipLaunchKernelGGL((stream_cull_bounce_frame_kernel<false, false>), g, block, 0, stream, *fa, qa, ca, bounce_stats, s, lt, camx, camy, fb);
-    }
+    rq_for_classes(fa, [&](auto gq, auto cub) {
+        hipLaunchKernelGGL((stream_cull_bounce_frame_kernel<decltype(gq)::value, decltype(cub)::value>), g, block, 0, stream, *fa, qa, ca, bounce_stats, s, lt, camx, camy,
+                           fb);
+    });
     return hipGetLastError();
 }

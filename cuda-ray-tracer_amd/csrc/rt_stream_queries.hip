@@ -11,7 +11,7 @@
 // lane without work stays with `use = false`.  Every kernel takes 4 * SQ_SLICE_BYTES = 24 KiB of LDS whatever the tables hold.
 #include <hip/hip_runtime.h>
 #include "rt_launch.h"   // the launchers below, as the host sees them
-#include "rt_stream.hpp" // the streamed object loops; RayQueryArgs, the plain path, the ray and record layouts (rt_rayquery.hpp)
+#include "rt_stream_shade.hpp" // the shading loop and SqShade over rt_stream.hpp: the streamed object loops; RayQueryArgs, the plain path, the ray and record layouts (rt_rayquery.hpp)
 #include "rt_extents.hpp" // the extent record, its merge and the wave reduction
 
 namespace RT_SYM(rtk) {
@@ -63,7 +63,19 @@ __global__ __launch_bounds__(256) void ray_query_stream_kernel(const RayQueryArg
     }
 }
 
-// ---- colour (rt_shade_rays.hip: shade_rays_kernel; the bounce loop is stream_frame_kernel's on caller rays, without a cone) --------------
+// ---- colour (rt_shade_rays.hip: shade_rays_kernel; the shading loop is stream_frame_kernel's on caller rays, without a cone) ------------
+// SqShade, and: segment 0 stores the rt_hit of the lane's ray, as rt_trace_rays writes it (out_rec == NULL: nothing)
+struct SqkShadeRays : SqShade {
+    RqRecord *out_rec;
+    uint64_t i;
+    bool live;
+
+    __device__ __forceinline__ void first_hit(int best, double best_t, const D3 &sp, const D3 &sn) const
+    {
+        if (out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
+    }
+};
+
 template <bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void shade_rays_stream_kernel(const ShadeRaysArgs sa, const unsigned char *__restrict__ scene, const DevLight *__restrict__ lights,
                                                                 const RqRay *__restrict__ rays, float4 *__restrict__ out_rgba, RqRecord *__restrict__ out_rec)
@@ -72,8 +84,6 @@ __global__ __launch_bounds__(256) void shade_rays_stream_kernel(const ShadeRaysA
     const RayQueryArgs &qa = sa.qa;
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
     unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
-    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-    const F3 bg{sa.bg[0], sa.bg[1], sa.bg[2]};
 
     const uint64_t stride = (uint64_t) gridDim.x * 256u;
     for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (workgroup-uniform trip count)
@@ -81,70 +91,8 @@ __global__ __launch_bounds__(256) void shade_rays_stream_kernel(const ShadeRaysA
         const bool live = i < qa.n;
         D3 o, d;
         sqk_load_ray(rays, i, live, o, d);
-        F3 res = bg; // a first-segment miss is the background colour
-        float cur_ratio = 1.0f;
-        bool bouncing = live;
-        for (uint32_t k = 0; __ballot(bouncing) != 0ull; k++) {
-            // get_color_and_object, src/update-cpu.cpp:45-80: the nearest hit ...
-            double best_t = INFINITY;
-            int best = -1;
-            sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best);
-            const bool hit = bouncing && best >= 0;
-            const DevObject *bo = &gobj[hit ? best : 0]; // per-lane index: gathers from global memory, per hit
-            D3 sp{0.0, 0.0, 0.0}, sn{0.0, 0.0, 0.0};
-            if (hit) {
-                sp = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
-                sn = normal_vector(bo->c, sp); // all twenty coefficients; FP64, never flipped
-            }
-            if (k == 0u && out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
-            // ... every light in index order (wave-uniform: scalar loads), shadow_ray from sp + SHADOW_BIAS * sn; a ray the kernel formed, so
-            // sq_query decides anew whether the tables are proven for it
-            const D3 so{sp.x + SHADOW_BIAS * sn.x, sp.y + SHADOW_BIAS * sn.y, sp.z + SHADOW_BIAS * sn.z};
-            F3 acc{0.0f, 0.0f, 0.0f};
-            if (__ballot(hit) != 0ull) {
-                const F3 albedo{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
-                for (uint32_t l = 0; l < sa.n_lights; l++) {
-                    const DevLight *lt = &lights[l];
-                    const bool spherical = lt->spherical != 0;
-                    double max_t;
-                    const D3 sd = shadow_dir(lt->p, spherical, sp, max_t);
-                    double unused_t = INFINITY;
-                    int blocked = 0;
-                    sq_query<HAS_GQ, HAS_CUBIC, true>(qa, scene, slice, lane, so, sd, hit, false, max_t, unused_t, blocked);
-                    if (hit && blocked == 0) {
-                        const F3 c = surface_color(lt->p, lt->color, spherical, sp, sn, albedo);
-                        acc.x += c.x;
-                        acc.y += c.y;
-                        acc.z += c.z;
-                    }
-                }
-            }
-            if (bouncing) {
-                if (!hit) {
-                    if (k != 0u) RT_SYM(rtk)::blend(res, cur_ratio, bg); // a bounce that leaves the scene picks up the background
-                    bouncing = false;
-                } else {
-                    // glm::min(vec3(1.0f), acc)
-                    const F3 oc{(acc.x < 1.0f) ? acc.x : 1.0f, (acc.y < 1.0f) ? acc.y : 1.0f, (acc.z < 1.0f) ? acc.z : 1.0f};
-                    if (k == 0u) res = oc;
-                    else RT_SYM(rtk)::blend(res, cur_ratio, oc);
-                    // the reflection loop, src/update-cpu.cpp:96-117
-                    const float refl = bo->refl;
-                    if (!((double) refl > EPS)) {
-                        bouncing = false;
-                    } else {
-                        cur_ratio *= refl;
-                        if (k == sa.max_refl) {
-                            RT_SYM(rtk)::blend(res, cur_ratio, bg);
-                            bouncing = false;
-                        } else {
-                            d = reflect_ray(d, sn); // of the direction as it is
-                            o = so;
-                        }
-                    }
-                }
-            }
-        }
+        SqkShadeRays pol{{qa, scene, slice, false}, out_rec, i, live};
+        const F3 res = shade_loop<HAS_GQ, HAS_CUBIC>(sa, scene, lights, lane, pol, o, d, live);
         if (live) out_rgba[i] = float4{res.x, res.y, res.z, 1.0f}; // one 16-byte store
     }
 }
@@ -354,17 +302,9 @@ static inline dim3 sqk_ray_grid(uint32_t n, uint32_t max_grid)
     return dim3(need < max_grid ? need : (max_grid ? max_grid : 1u));
 }
 
-// launch kernel<HAS_GQ, HAS_CUBIC, extra...> for the scene's classes
-#define SQK_LAUNCH(fa, kernel, extra, g, stream, ...)                                                                     \
-    do {                                                                                                                  \
-        if ((fa)->n_cub) {                                                                                                \
-            if ((fa)->n_gq) hipLaunchKernelGGL((kernel<true, true extra>), g, dim3(256), 0, stream, __VA_ARGS__);        \
-            else hipLaunchKernelGGL((kernel<false, true extra>), g, dim3(256), 0, stream, __VA_ARGS__);                  \
-        } else {                                                                                                          \
-            if ((fa)->n_gq) hipLaunchKernelGGL((kernel<true, false extra>), g, dim3(256), 0, stream, __VA_ARGS__);       \
-            else hipLaunchKernelGGL((kernel<false, false extra>), g, dim3(256), 0, stream, __VA_ARGS__);                 \
-        }                                                                                                                 \
-    } while (0)
+// launch kernel<HAS_GQ, HAS_CUBIC, extra...> for the scene's classes (rt_rayquery.hpp: rq_for_classes)
+#define SQK_LAUNCH(fa, kernel, extra, g, stream, ...) \
+    rq_for_classes(fa, [&](auto gq, auto cub) { hipLaunchKernelGGL((kernel<decltype(gq)::value, decltype(cub)::value extra>), g, dim3(256), 0, stream, __VA_ARGS__); })
 #define SQK_COMMA ,
 
 static hipError_t sqk_launch_pixels(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, uint32_t grid, int32_t *out_object, double *out_t,

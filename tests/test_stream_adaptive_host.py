@@ -112,15 +112,36 @@ def test_build_report_lists_the_new_kernel_without_spills():
 
 
 def test_the_kernel_file_has_no_workgroup_barrier_and_no_dynamic_lds():
-    text = open(os.path.join(CSRC, "rt_stream_adaptive.hip")).read()
-    code = "\n".join(l.split("//")[0] for l in text.splitlines())
-    assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code and '"workgroup"' not in code
-    assert "extern __shared__" not in code and code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 1
-    # both object loops go through sq_query without a block cone; no lane returns inside the kernel
-    assert code.count("sq_query<HAS_GQ, HAS_CUBIC, false>") == 1 and code.count("sq_query<HAS_GQ, HAS_CUBIC, true>") == 1
-    assert len(re.findall(r"sq_query<[^;]*, (?:bouncing|hit), false, ", code)) == 2
+    def code_of(name):
+        return "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, name)).read().splitlines())
+    # the kernel's file, the shared loop with the policy over sq_query, the items and the resolve
+    codes = {name: code_of(name) for name in ("rt_stream_adaptive.hip", "rt_stream_shade.hpp", "rt_stream_shell.hpp")}
+    for name, code in codes.items():
+        assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code and '"workgroup"' not in code, name
+        assert "extern __shared__" not in code and "HIP_DYNAMIC_SHARED" not in code, name
+    code = codes["rt_stream_adaptive.hip"]
+    assert code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 1
+    assert "__shared__" not in codes["rt_stream_shade.hpp"] and "__shared__" not in codes["rt_stream_shell.hpp"]
+    # both object loops go through sq_query without a block cone: the kernel has no query of its own, it runs the shared loop under the
+    # policy over sq_query with the cone off; that policy has exactly one nearest-hit and one occlusion call, and the only cone argument
+    # that is not the literal false is the policy's `cone`, which this kernel sets to false
+    assert "sq_query<" not in code and "sc_query" not in code
+    assert code.count("SqShade pol{qa, scene, slice, false};") == 1 and code.count("SqShade") == 1
+    assert code.count("shade_loop<HAS_GQ, HAS_CUBIC>(fa, scene, lights, lane, pol, origin, it.dir, it.use);") == 1
+    shade = codes["rt_stream_shade.hpp"]
+    assert shade.count("sq_query<HAS_GQ, HAS_CUBIC, false>") == 1 and shade.count("sq_query<HAS_GQ, HAS_CUBIC, true>") == 1 and shade.count("sq_query<") == 2
+    assert "sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, use, k == 0u && cone, MAX_T, best_t, best);" in shade
+    assert "sq_query<HAS_GQ, HAS_CUBIC, true>(qa, scene, slice, lane, so, sd, use, false, max_t, unused_t, blocked);" in shade
+    # no lane leaves early: none of the three keywords inside the loop function -- except its final `return res;`, the last statement of
+    # its body -- none in the policy's queries, none in the kernel, none in the items and the resolve
+    loop = shade.split("F3 shade_loop(")[1].split("struct ShadeNoSegment")[0]
+    assert loop.count("return") == 1 and re.search(r"\n    return res;\n}\s*$", loop.rstrip() + "\n") and "break" not in loop and "continue" not in loop
+    policy = shade.split("struct SqShade {")[1]
+    assert policy.count("return") == 1 and "return Segment{};" in policy and "break" not in policy and "continue" not in policy
     kernel = code.split("void ray_list_stream_kernel")[1].split("template <int K, bool RGBA8>\nstatic")[0]
     assert "return" not in kernel and "break" not in kernel and "continue" not in kernel
+    lists = codes["rt_stream_shell.hpp"].split("struct SlItem {")[1]
+    assert lists.count("return") == 1 and "    return it;\n" in lists and "break" not in lists and "continue" not in lists
     assert "rt_stream_adaptive" in open(os.path.join(ROOT, "cuda-ray-tracer_amd", "Makefile")).read()
 
 

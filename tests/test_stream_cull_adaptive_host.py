@@ -76,14 +76,21 @@ def test_build_report_lists_the_new_kernel_without_spills_at_two_waves_per_simd(
 
 
 def test_the_new_files_have_no_workgroup_barrier_and_no_dynamic_lds():
-    for name in ("rt_stream_cull_adaptive.hip", "rt_wave_cone.hpp"):
+    for name in ("rt_stream_cull_adaptive.hip", "rt_wave_cone.hpp", "rt_stream_shade.hpp", "rt_stream_shell.hpp"):
         text = open(os.path.join(CSRC, name)).read()
         code = "\n".join(l.split("//")[0] for l in text.splitlines())
         for word in ("__syncthreads", "s_barrier", '"workgroup"', "rq_stage_tables", "extern __shared__", "HIP_DYNAMIC_SHARED"):
             assert word not in code, (name, word)
     text = open(os.path.join(CSRC, "rt_stream_cull_adaptive.hip")).read()
     assert "__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];" in text          # 24 KiB, static
-    assert len(re.findall(r"\), g, block, 0, stream,", text)) == 1 and "sc_hit_ball(" in text and "sc_query_shadow<" in text
+    assert len(re.findall(r"\), g, block, 0, stream,", text)) == 1
+    # the shadow rule: the wave-cone policy is the block policy with two members replaced, so the ball and the culled shadow query are the
+    # block policy's own (rt_stream_cull.hpp: ScShade), the ball read back through lane 0
+    assert "struct ScaShade : ScShade {" in text and "Segment seg = ScShade::segment(hit, sp);" in text and text.count("sq_readlane(seg.ball.") == 4
+    assert "void occluded(" not in text.split("struct ScaShade : ScShade {")[1].split("};")[0]
+    assert "ScaShade pol{{qa, ca, scene, slice, st}, nocone};" in text and "shade_loop<HAS_GQ, HAS_CUBIC>(fa, scene, lights, lane, pol, origin, it.dir, it.use);" in text
+    block = open(os.path.join(CSRC, "rt_stream_cull.hpp")).read().split("struct ScShade {")[1]
+    assert "seg.cull = sc_hit_ball(hit, sp, seg.ball);" in block and block.count("sc_query_shadow<") == 2
     for variant in ("strict", "fast"):
         remarks = open(os.path.join(BUILD, "csrc", f"rt_stream_cull_adaptive_{variant}.o.remarks")).read()
         assert set(re.findall(r"LDS Size \[bytes/block\]: (\d+)", remarks)) == {"24576"}

@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 
 CSRC = os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc")
 N_VERDICTS = 20000   # per family here, a few seconds in all; the full count (100 000 per family) is the lab's main: python tests/tools/bounce_cull_lab.py
-NEW_FILES = ("rt_ray_bound.hpp", "rt_stream_cull_bounce.hpp", "rt_stream_cull_bounce.hip")
+NEW_FILES = ("rt_ray_bound.hpp", "rt_stream_cull_bounce.hpp", "rt_stream_cull_bounce.hip", "rt_stream_shade.hpp", "rt_stream_shell.hpp")
 
 
 @pytest.fixture(autouse=True)
@@ -126,6 +126,7 @@ def test_the_new_files_have_no_workgroup_barrier():
         text = open(os.path.join(CSRC, name)).read()
         code = "\n".join(l.split("//")[0] for l in text.splitlines())
         assert "__syncthreads" not in code and "s_barrier" not in code and '"workgroup"' not in code and "rq_stage_tables" not in code, name
+        assert "extern __shared__" not in code and "HIP_DYNAMIC_SHARED" not in code, name
         assert "__shared__" not in code or name.endswith(".hip"), name      # (nothing of the bounds goes to LDS: only the kernel's own slices)
     query = open(os.path.join(CSRC, "rt_stream_cull_bounce.hpp")).read()
     assert "sq_stage_chunk" in query and "sc_sweep<false>" in query and "ray_reaches" in query
@@ -134,9 +135,17 @@ def test_the_new_files_have_no_workgroup_barrier():
 
 
 def test_the_twin_kernel_file_is_untouched():
-    """rt_stream_cull.hip still sweeps its bounce rays in full: the new kernel is a copy, not an edit."""
+    """The twin still sweeps its bounce rays in full: neither its kernel file nor the header that holds its shading policy (ScShade) can
+    reach sc_query_bounce, even by mistake, and the policy's nearest-hit query of a segment k != 0 is sq_query without a cone."""
+    for name in ("rt_stream_cull.hip", "rt_stream_cull.hpp"):
+        text = open(os.path.join(CSRC, name)).read()
+        assert "sc_query_bounce" not in text and not re.search(r'#\s*include\s*"rt_stream_cull_bounce\.hpp"', text), name
     twin = open(os.path.join(CSRC, "rt_stream_cull.hip")).read()
-    assert "sc_query_bounce" not in twin and "else sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best);" in twin
+    assert "ScShade pol{qa, ca, scene, slice, st};" in twin and "shade_loop<HAS_GQ, HAS_CUBIC>(fa, scene, lights, lane, pol," in twin
+    policy = open(os.path.join(CSRC, "rt_stream_cull.hpp")).read().split("struct ScShade {")[1]
+    nearest = policy.split("void nearest(")[1].split("__device__")[0]
+    assert re.search(r"if \(k == 0u\) sc_query_primary<HAS_GQ, HAS_CUBIC>\([^;]*;[^\n]*\n\s*else sq_query<HAS_GQ, HAS_CUBIC, false>\(qa, scene, slice, lane, o, d, use, false, MAX_T, best_t, best\);",
+                     nearest), nearest
 
 
 # ---- the predicate, asked about bounds ----------------------------------------------------------------------------------------------------

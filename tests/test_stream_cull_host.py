@@ -114,10 +114,11 @@ def test_build_report_lists_the_new_kernel_without_spills():
 
 
 def test_the_new_files_have_no_workgroup_barrier():
-    for name in ("rt_stream_cull.hip", "rt_stream_cull.hpp"):
+    for name in ("rt_stream_cull.hip", "rt_stream_cull.hpp", "rt_stream_shade.hpp", "rt_stream_shell.hpp"):
         text = open(os.path.join(CSRC, name)).read()
         code = "\n".join(l.split("//")[0] for l in text.splitlines())
         assert "__syncthreads" not in code and "s_barrier" not in code and '"workgroup"' not in code and "rq_stage_tables" not in code, name
+        assert "extern __shared__" not in code and "HIP_DYNAMIC_SHARED" not in code, name
     assert "sq_stage_chunk" in open(os.path.join(CSRC, "rt_stream_cull.hpp")).read()
 
 

@@ -101,11 +101,11 @@ def test_build_report_lists_the_new_kernel_without_spills():
 def test_the_kernel_file_has_no_workgroup_barrier():
     """The waves of a workgroup run different numbers of bounces and chunks: nothing in the streamed kernel or its loops may wait for
     the other waves."""
-    for name in ("rt_stream.hip", "rt_stream.hpp"):
+    for name in ("rt_stream.hip", "rt_stream.hpp", "rt_stream_shade.hpp", "rt_stream_shell.hpp"):   # ... the shared loop and shell included
         text = open(os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc", name)).read()
         code = "\n".join(l.split("//")[0] for l in text.splitlines())
         assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code, name
-        assert '"workgroup"' not in code, name
+        assert '"workgroup"' not in code and "extern __shared__" not in code and "HIP_DYNAMIC_SHARED" not in code, name
     assert "__builtin_amdgcn_wave_barrier" in open(os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc", "rt_stream.hpp")).read()
 
 

@@ -97,12 +97,22 @@ def test_build_report_lists_the_new_kernels_without_spills():
 
 
 def test_the_kernel_file_has_no_workgroup_barrier_and_no_dynamic_lds():
+    for name in ("rt_stream_queries.hip", "rt_stream_shade.hpp"):   # ... the shared loop of the colour kernel included
+        text = open(os.path.join(CSRC, name)).read()
+        code = "\n".join(l.split("//")[0] for l in text.splitlines())
+        assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code and '"workgroup"' not in code, name
+        assert "extern __shared__" not in code and "HIP_DYNAMIC_SHARED" not in code and "rq_plain" not in code, name
     text = open(os.path.join(CSRC, "rt_stream_queries.hip")).read()
     code = "\n".join(l.split("//")[0] for l in text.splitlines())
-    assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code and '"workgroup"' not in code
-    assert "extern __shared__" not in code and code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 5
-    # the pixel family goes through sq_tables itself (no plain path), the ray families through sq_query
-    assert "sq_tables<HAS_GQ, HAS_CUBIC, false, true>" in code and code.count("sq_query<") == 4 and "rq_plain" not in code
+    assert code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 5
+    # the pixel family goes through sq_tables itself (no plain path), the ray families through sq_query: the ray-query and the path kernel
+    # call it themselves (2), the colour kernel through the shared loop under the policy over sq_query (2 more, in rt_stream_shade.hpp)
+    assert "sq_tables<HAS_GQ, HAS_CUBIC, false, true>" in code and code.count("sq_query<") == 2
+    shade = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, "rt_stream_shade.hpp")).read().splitlines())
+    assert shade.count("sq_query<") == 2
+    colour = code.split("void shade_rays_stream_kernel")[1].split("void path_query_stream_kernel")[0]
+    assert "SqkShadeRays pol{{qa, scene, slice, false}, out_rec, i, live};" in colour
+    assert "shade_loop<HAS_GQ, HAS_CUBIC>(sa, scene, lights, lane, pol, o, d, live);" in colour and "sq_query<" not in colour
 
 
 # ---- the conditions of the GPU tests, on the composers alone --------------------------------------------------------------------------------
