@@ -198,7 +198,8 @@ def test_streamed_equals_shade_rays_on_primary_rays(pkg, name):
 @pytest.mark.parametrize("name", CUBIC)
 def test_cubic_scenes_to_their_bar(pkg, oracle, name):
     """1e-5 relative per channel; at most max(3, 0.2 % of the pixels) beyond it against the glibc oracle, none against the oracle under
-    the device's cbrt / acos / cos.  The large-count path of degree 3 (the index list in chunks) is the same loop."""
+    the device's cbrt / acos / cos.  The large-count path of degree 3 (the index list in chunks) is taken past its first chunk by
+    tests/test_cubic_chunks_gpu.py, on fields of 64, 65 and 129 degree-3 objects."""
     w, h = 80, 60
     got = frame(pkg, shipped(pkg, name, w, h), flags=pkg.RT_FLAG_STREAM)
     c = compare(got[..., :3], shipped_oracle(name, w, h))
