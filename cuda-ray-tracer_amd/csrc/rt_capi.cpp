@@ -33,7 +33,8 @@
      RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
      RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
      RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V), RT_CAT(rt_launch_stream_cull_bounce, V), \
-     RT_CAT(rt_launch_stream_cull_ray_list, V)}
+     RT_CAT(rt_launch_stream_cull_trace_rays, V), RT_CAT(rt_launch_stream_cull_occluded_rays, V), RT_CAT(rt_launch_stream_cull_shade_rays, V), \
+     RT_CAT(rt_launch_stream_cull_trace_paths, V), RT_CAT(rt_launch_stream_cull_ray_list, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 // the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
 #define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
@@ -238,6 +239,9 @@ struct rt_ctx {
     // ... and the bounce rays of rt_render culled per ray (rt_stream_cull_bounce.hip), with work words of their own
     bool stream_cull_bounce = false; // RT_FLAG_STREAM_CULL_BOUNCE && stream_cull && fa.has_mirror && max_reflections >= 1 && n_chunks >= 2
     DevMem<unsigned long long> d_cull_bounce_stats; // as d_cull_stats
+    // ... and the unit-sphere chunks of caller-supplied rays culled per ray (rt_stream_cull_rays.hip), with work words the four entry points share
+    bool stream_cull_rays = false; // RT_FLAG_STREAM_CULL_RAYS && stream_cull && stream_queries && n_chunks >= 2
+    DevMem<unsigned long long> d_cull_rays_stats; // as d_cull_stats
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -567,6 +571,9 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
     // can bounce at all, and a second chunk.  False: launch for launch the context without the flag.  rt_set_scene keeps has_mirror and the chunk
     // layout, so this holds for the context's life.
     ctx->stream_cull_bounce = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_BOUNCE) && ctx->stream_cull && fa.has_mirror && fa.max_refl >= 1u && ctx->n_chunks >= 2u;
+    // ... and do the ray queries cull the chunks per caller-supplied ray (rt_stream_cull_rays.hip)?  The culling decision, streamed queries and a second
+    // chunk.  False: launch for launch the context without the flag.  rt_set_scene rebuilds the bounds and keeps the layout, so this holds too.
+    ctx->stream_cull_rays = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_RAYS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;
     return RT_OK;
 }
 
@@ -591,6 +598,8 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
             if (int rc = device_table(ctx->d_cull_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull work words")) return rc;
         if (e && !std::strcmp(e, "1") && ctx->stream_cull_bounce)
             if (int rc = device_table(ctx->d_cull_bounce_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-bounce work words")) return rc;
+        if (e && !std::strcmp(e, "1") && ctx->stream_cull_rays)
+            if (int rc = device_table(ctx->d_cull_rays_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-rays work words")) return rc;
         if (e && !std::strcmp(e, "1") && ctx->stream_cull_adaptive && !(fa.n_gq && fa.n_cub))
             if (int rc = device_table(ctx->d_cull_adaptive_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-adaptive work words")) return rc;
     }
@@ -1129,6 +1138,16 @@ static int rays_ready(const char *who, rt_ctx *ctx)
 // workgroups of one ray-query launch: four per CU (the kernels' registers allow three to four resident ones), fewer for few rays
 static uint32_t rays_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
 
+// The ray entry points of a context whose RT_FLAG_STREAM_CULL_RAYS decision is true (rt_ctx::stream_cull_rays, decided once in rt_create) take the culled
+// launchers (rt_stream_cull_rays.hip): the streamed twin's arguments and these.  The pixel queries keep RT_QUERY_KERNEL's.
+#define RT_CULL_RAYS_ARGS(ctx) (ctx)->d_bounds, (ctx)->n_chunks, (ctx)->d_cull_rays_stats
+
+static hipError_t trace_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, void *dev_hits, hipStream_t stream)
+{
+    if (ctx->stream_cull_rays) return ctx->kern->stream_cull_trace_rays(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx), stream);
+    return RT_QUERY_KERNEL(ctx, trace_rays)(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
+}
+
 extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_hit *dev_hits, void *stream_, float *ms)
 {
     static_assert(sizeof(rt_ray) == 48 && sizeof(rt_hit) == 48, "rt_ray / rt_hit layout");
@@ -1140,7 +1159,7 @@ extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt
     hipStream_t stream = (hipStream_t) stream_;
     if (int rc = rays_ready("rt_trace_rays", ctx)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = RT_QUERY_KERNEL(ctx, trace_rays)(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
+    const hipError_t e = trace_launch(ctx, dev_rays, n, dev_hits, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1157,7 +1176,8 @@ extern "C" int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const doubl
     hipStream_t stream = (hipStream_t) stream_;
     if (int rc = rays_ready("rt_occluded_rays", ctx)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = RT_QUERY_KERNEL(ctx, occluded_rays)(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
+    const hipError_t e = ctx->stream_cull_rays ? ctx->kern->stream_cull_occluded_rays(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx), stream)
+                                               : RT_QUERY_KERNEL(ctx, occluded_rays)(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1171,7 +1191,7 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
     if (int rc = rays_ready("rt_trace_rays_host", ctx)) return rc;
     if (int rc = ctx->rq.reserve(n, sizeof(rt_ray), sizeof(rt_hit))) return rc;
     RT_HIP(hipMemcpyAsync(ctx->rq.in, rays, sizeof(rt_ray) * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = RT_QUERY_KERNEL(ctx, trace_rays)(&ctx->fa, ctx->d_obj, ctx->rq.in, n, ctx->rq.out, rays_max_grid(ctx), stream);
+    const hipError_t e = trace_launch(ctx, ctx->rq.in, n, ctx->rq.out, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out, ctx->rq.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1182,6 +1202,8 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
 // Like the ray queries it reads the scene (blob and lights) and nothing of the frame; always 4 x float32 per ray, whatever cfg.format.
 static hipError_t shade_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, float *dev_rgba, void *dev_hits, hipStream_t stream)
 {
+    if (ctx->stream_cull_rays)
+        return ctx->kern->stream_cull_shade_rays(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx), stream);
     return RT_QUERY_KERNEL(ctx, shade_rays)(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
 }
 
@@ -1223,6 +1245,9 @@ extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, f
 // Like the ray queries the path kernel reads the scene blob and nothing of the frame.
 static hipError_t paths_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, uint32_t max_segments, void *dev_segments, void *dev_last, void *dev_ends, hipStream_t stream)
 {
+    if (ctx->stream_cull_rays)
+        return ctx->kern->stream_cull_trace_paths(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx),
+                                                  stream);
     return RT_QUERY_KERNEL(ctx, trace_paths)(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), stream);
 }
 
@@ -1708,6 +1733,22 @@ extern "C" int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8])
         return fail(RT_ERR_INVALID, "rt_debug_stream_cull_bounce: the context keeps no work words (they exist where rt_get_stream_cull_bounce says 1 and MI355RT_STREAM_CULL_STATS=1 "
                                     "was set at rt_create)");
     return read_behind_last_call("rt_debug_stream_cull_bounce", ctx, out, ctx->d_cull_bounce_stats, sizeof(uint64_t) * 8);
+}
+
+extern "C" int rt_get_stream_cull_rays(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_rays: null argument");
+    *on = ctx->stream_cull_rays ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_stream_cull_rays(rt_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_rays: null argument");
+    if (!ctx->d_cull_rays_stats)
+        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_rays: the context keeps no work words (they exist where rt_get_stream_cull_rays says 1 and MI355RT_STREAM_CULL_STATS=1 "
+                                    "was set at rt_create)");
+    return read_behind_last_call("rt_debug_stream_cull_rays", ctx, out, ctx->d_cull_rays_stats, sizeof(uint64_t) * 8);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

@@ -95,6 +95,16 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_cull, const FrameArgs *fa, const voi
 // work words (8, NULL exactly where stats is NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_bounce, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
                const void *bounds, uint32_t n_chunks, unsigned long long *stats, unsigned long long *bounce_stats, hipStream_t stream)
+// rt_stream_cull_rays.hip: the streamed ray launchers with the chunks culled per caller-supplied ray (RT_FLAG_STREAM_CULL_RAYS): each its streamed twin's
+// arguments, the chunk bounds and the work words the four share (8, or NULL)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
+               const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_occluded_rays, const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
+               uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba,
+               void *hits, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
+               void *last, void *ends, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
 // rt_stream_cull_adaptive.hip: rt_launch_stream_ray_list with the same chunks culled (rt_get_stream_cull_adaptive): its arguments, the chunk bounds and
 // work words of its own (8, or NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
@@ -133,6 +143,11 @@ struct Kernels {
     decltype(&rt_launch_stream_cull_strict) stream_cull;
     // rt_render of a context whose RT_FLAG_STREAM_CULL_BOUNCE decision is true (rt_get_stream_cull_bounce)
     decltype(&rt_launch_stream_cull_bounce_strict) stream_cull_bounce;
+    // the ray queries of a context whose RT_FLAG_STREAM_CULL_RAYS decision is true (rt_get_stream_cull_rays)
+    decltype(&rt_launch_stream_cull_trace_rays_strict) stream_cull_trace_rays;
+    decltype(&rt_launch_stream_cull_occluded_rays_strict) stream_cull_occluded_rays;
+    decltype(&rt_launch_stream_cull_shade_rays_strict) stream_cull_shade_rays;
+    decltype(&rt_launch_stream_cull_trace_paths_strict) stream_cull_trace_paths;
     // the halo and refine passes of a context whose streamed adaptive passes cull as well (rt_get_stream_cull_adaptive)
     decltype(&rt_launch_stream_cull_ray_list_strict) stream_cull_ray_list;
 };

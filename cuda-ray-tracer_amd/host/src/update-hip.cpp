@@ -50,6 +50,8 @@
 //                             (RT_FLAG_STREAM_CULL; same frame); nothing changes where the context is not streamed
 //   MI355RT_STREAM_CULL_BOUNCE=1  ... and culls the chunks of its bounce rays per ray (RT_FLAG_STREAM_CULL_BOUNCE; same frame); nothing
 //                             changes without MI355RT_STREAM_CULL, without mirrors or below 65 unit spheres
+//   MI355RT_STREAM_CULL_RAYS=1  ... and the ray-query hooks (trace, shade, pick path) cull the chunks per ray (RT_FLAG_STREAM_CULL_RAYS;
+//                             same answers); nothing changes without MI355RT_STREAM_CULL and MI355RT_STREAM_QUERIES or below 65 unit spheres
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -362,6 +364,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_CULL_BOUNCE")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_BOUNCE;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_BOUNCE", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_CULL_RAYS=1: ... and the chunks of the ray-query hooks' rays, per ray
+    if (const char *f = std::getenv("MI355RT_STREAM_CULL_RAYS")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_RAYS;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_RAYS", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

@@ -283,8 +283,8 @@ typedef struct rt_scene_desc {
  * No refusal of its own; combines with every flag; through rt_create_multi it reaches every context.
  * Known limits: the bounds are spheres around Morton runs of 64 entries, not a hierarchy: a scene whose spheres all overlap gains
  * nothing and pays one decision per chunk, and so does a scene of a single chunk (measured: 20spheres with its 19 lights takes 1.67 x
- * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Bounce rays: RT_FLAG_STREAM_CULL_BOUNCE below.  Out of scope: culling caller-supplied rays; bounds for the other classes;
- * a second level over the chunk bounds; culling in the streamed query kernels (they only read the reordered table); reordering the
+ * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Bounce rays: RT_FLAG_STREAM_CULL_BOUNCE below; caller-supplied rays: RT_FLAG_STREAM_CULL_RAYS below.  Out of scope: bounds for the other classes;
+ * a second level over the chunk bounds; culling in the streamed pixel queries (they only read the reordered table); reordering the
  * refine list for tighter wave cones;
  * counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
 #define RT_FLAG_STREAM_CULL 524288u
@@ -317,9 +317,39 @@ typedef struct rt_scene_desc {
  * 409.5 -> 406.8 us; with spheres 20 pixels across 0.71 x, 0.88 x and 1.002 x (1.1 us more, beyond the 0.8 us spread).  At 10 000
  * spheres a lane reaches 12 % of the bounds ([3] / [2]) while the wave stages 24 % of them ([1] / [0]); at 65 spheres both are one half.
  * Out of scope: pruning by best_t and an ordered traversal; a per-entry level; the bounce rays of the adaptive and query kernels;
- * caller-supplied rays; bounds for the other classes; a hierarchy over the bounds; the flag as a default or as part of
+ * bounds for the other classes; a hierarchy over the bounds; the flag as a default or as part of
  * RT_FLAG_STREAM_CULL. */
 #define RT_FLAG_STREAM_CULL_BOUNCE 1048576u
+
+/* Culled ray queries (csrc/rt_stream_cull_rays.hip): on a streamed-queries context rt_trace_rays,
+ * rt_occluded_rays, rt_shade_rays, rt_trace_paths, rt_pick_paths and the _host forms stage and sweep every chunk of the unit-sphere table
+ * for every wave and every segment, shadow rays included: O(rays x spheres).  With this flag every lane asks about its OWN ray and each
+ * chunk bound (csrc/rt_ray_bound.hpp, the predicate of RT_FLAG_STREAM_CULL_BOUNCE, about the ray's whole half-line), the wave stages a
+ * chunk only if some lane in use reaches its bound, and sweeps it for those lanes alone; an occlusion query stops behind the chunk that
+ * blocks its last undecided lane.  One decision per context, made in rt_create and never revisited (rt_set_scene rebuilds the bounds and
+ * keeps the layout); rt_get_stream_cull_rays reports it:
+ *     stream cull rays = RT_FLAG_STREAM_CULL_RAYS && rt_get_stream_cull && rt_get_streamed_queries && at least 2 chunks (65 unit spheres)
+ * False: the context is, launch for launch and byte for byte, the context without the flag.  There is no refusal of its own, and the flag
+ * combines with every other.  True: the five entry points launch the culling twins of the streamed ray kernels (the same arguments,
+ * grid, loads and stores; one graph node as before).  The shading loop of rt_shade_rays culls the nearest hit of every segment and every
+ * shadow ray as the ray it is; t_max of rt_occluded_rays bounds the roots, not the verdicts.
+ * Not culled for: a ray with |d|^2 <= 1e-7 or not finite (the reference's linear branch is not geometry) -- its WAVE then stages every
+ * chunk; a ray with a component beyond 1e100 (it takes the dense path over all objects); a chunk whose bound is +inf; the other classes'
+ * tables; the pixel queries (rt_render_gbuffer, rt_pick, rt_object_extents), which keep the streamed kernels.
+ * Results are unchanged by definition: every output is bit for bit that of the same context without the flag, strict and RT_FLAG_FAST,
+ * every degree.  ms, capturability, ranks and rt_set_scene are those of the streamed queries.  Through rt_create_multi the flag reaches
+ * every context.  All sixteen instantiations of both builds fit two waves per SIMD without a spill (at most 216 VGPRs), so no scene is
+ * excluded.
+ * Known limits: the chunk level works on the union over a wave's 64 lanes, a wave being 64 CONSECUTIVE rays of the caller's array -- rays
+ * in no spatial order gain little (DESIGN.md section 29 measures row order against a shuffle); no best_t pruning and no near-to-far order;
+ * no per-entry level inside a staged chunk; every lane pays one verdict per chunk and query, which a scene of few chunks does not earn
+ * back.  Measured (profiles/stream_cull_rays.txt; MI355X, strict, the 1920 x 1080 frame's own primary rays as the
+ * rays, against the same context without the flag): in row order 10 000 spheres rt_trace_rays 21 764 -> 4 165 us, rt_shade_rays 61 732 ->
+ * 12 204 us (0.19 - 0.25 x over the four entry points), 1 685 spheres 0.41 - 0.51 x; the same rays shuffled stage 98 - 100 % of the
+ * chunks and take 1.13 - 1.32 x in rt_trace_rays, rt_occluded_rays and rt_trace_paths while rt_shade_rays still gains (0.55 - 0.85 x);
+ * at 65 spheres (two chunks) every entry point is slower, 1.13 - 1.29 x.
+ * Out of scope: the pixel queries; bounds for the other classes; a hierarchy over the bounds; the flag as a default. */
+#define RT_FLAG_STREAM_CULL_RAYS 2097152u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -533,6 +563,10 @@ int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on);
 /* Culled bounce rays (RT_FLAG_STREAM_CULL_BOUNCE above): *on = 1 where rt_render culls the unit-sphere chunks of its bounce rays per ray,
  * else 0.  RT_ERR_INVALID for a NULL argument (before a device is looked for). */
 int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on);
+/* Culled ray queries (RT_FLAG_STREAM_CULL_RAYS above): *on = 1 where rt_trace_rays, rt_occluded_rays, rt_shade_rays, rt_trace_paths and
+ * rt_pick_paths cull the unit-sphere chunks per caller-supplied ray, else 0.  RT_ERR_INVALID for a NULL argument (before a device is
+ * looked for). */
+int rt_get_stream_cull_rays(const rt_ctx *ctx, uint32_t *on);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
@@ -889,6 +923,16 @@ int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8]);
  * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true; otherwise the
  * kernel counts nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
 int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8]);
+/* ... and the work words of the culled ray queries (rt_get_stream_cull_rays), eight words that rt_trace_rays, rt_occluded_rays,
+ * rt_shade_rays, rt_trace_paths and the calls that go through them share, cumulative since rt_create.  Waits as rt_set_scene_status does.
+ *   [0] chunk decisions: one per (wave, query with a lane in use, chunk looked at before an early-out)      [1] chunks staged
+ *   [2] (lane, chunk) pairs asked by lanes that can be culled for      [3] of [2], the pairs that reach
+ *   [4] queries in which no lane in use could be culled for      [5] - [7] 0
+ * A query is one nearest-hit or occlusion query of a wave: one per wave for rt_trace_rays and rt_occluded_rays, one per segment and one
+ * per segment and light for rt_shade_rays, one per segment for rt_trace_paths.  Only an occlusion query has an early-out.
+ * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true; otherwise the
+ * kernels count nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
+int rt_debug_stream_cull_rays(rt_ctx *ctx, uint64_t out[8]);
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
