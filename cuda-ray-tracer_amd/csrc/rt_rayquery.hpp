@@ -1,6 +1,7 @@
 // rt_rayquery.hpp -- what the kernels for caller-supplied rays share (rt_rays.hip: closest hit and occlusion; rt_shade_rays.hip: the
-// reference's colour): the scene-layout argument words, the class tables in LDS, the object loops for one ray per lane -- through the
-// tables where they are proven, through the dense expansion elsewhere -- and the 48-byte ray / record layouts of include/mi355rt.h.
+// reference's colour; rt_paths.hip: the bounces): the scene-layout argument words, the class tables in LDS, the object loops for one ray
+// per lane -- through the tables where they are proven, through the dense expansion elsewhere; as a query object for the kernels' bodies
+// (rt_ray_kernels.hpp): RqStaged -- and the 48-byte ray / record layouts of include/mi355rt.h.
 // Included by files that are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
 #ifndef RT_RAYQUERY_HPP
 #define RT_RAYQUERY_HPP
@@ -141,6 +142,28 @@ __device__ __forceinline__ void rq_plain(const RayQueryArgs &qa, const DevObject
         }
     }
 }
+
+// The query object (rt_ray_kernels.hpp) of a workgroup that holds all class tables in LDS.  One object loop for the ray (o, d) of every
+// lane in `use`: through the tables where rq_tables_proven says so, the plain path for the other lanes.  OCCLUSION: best = 1 once
+// something blocks before t_max.
+struct RqStaged {
+    const RayQueryArgs qa; // (by value, as in ScShade: rt_stream_cull.hpp)
+    const RqTables S;
+    const DevObject *gobj;
+
+    template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+    __device__ __forceinline__ void query(uint32_t, const D3 &o, const D3 &d, bool use, double t_max, double &best_t, int &best) const
+    {
+        constexpr bool NEED_CROSS = HAS_GQ || HAS_CUBIC;
+        const bool proven = rq_tables_proven(o, d);
+        Mono m;
+        mono_set_o<NEED_CROSS>(m, o);
+        mono_set_d<NEED_CROSS>(m, d);
+        mono_set_od<NEED_CROSS>(m);
+        rq_tables<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, S, gobj, m, use && proven, t_max, best_t, best);
+        if (__ballot(use && !proven) != 0ull) rq_plain<OCCLUSION>(qa, gobj, o, d, use && !proven, t_max, best_t, best);
+    }
+};
 
 // One rt_ray / rt_hit (include/mi355rt.h) as three 16-byte words
 struct alignas(16) RqRay {

@@ -202,7 +202,7 @@ __device__ __forceinline__ void sq_tables(const RayQueryArgs &qa, const unsigned
 #undef SQ_ALL_DECIDED
 }
 
-// One object loop for the ray (o, d) of every lane in `use` (rt_shade_rays.hip, shade_query): through the streamed tables where
+// One object loop for the ray (o, d) of every lane in `use` (RqStaged::query of rt_rayquery.hpp, with the tables streamed): through the streamed tables where
 // rq_tables_proven says so, the plain path behind a ballot for the other lanes.  The cone is only used while every ray of the wave is
 // proven: its lanes' directions define it.
 template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
@@ -221,6 +221,20 @@ __device__ __forceinline__ void sq_query(const RayQueryArgs &qa, const unsigned 
     sq_tables<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, slice, lane, m, use && proven, cone, t_max, best_t, best);
     if (plain != 0ull) rq_plain<OCCLUSION>(qa, reinterpret_cast<const DevObject *>(scene), o, d, use && !proven, t_max, best_t, best);
 }
+
+// The query object (rt_ray_kernels.hpp) of a wave that streams the tables: sq_query for unrelated rays, never a cone (qa: the kernel's own
+// argument)
+struct SqQuery {
+    const RayQueryArgs &qa;
+    const unsigned char *scene;
+    unsigned char *slice; // SQ_SLICE_BYTES of LDS that belong to this wave
+
+    template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+    __device__ __forceinline__ void query(uint32_t lane, const D3 &o, const D3 &d, bool use, double t_max, double &best_t, int &best) const
+    {
+        sq_query<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, slice, lane, o, d, use, false, t_max, best_t, best);
+    }
+};
 
 } // namespace RT_SYM(rtk)
 

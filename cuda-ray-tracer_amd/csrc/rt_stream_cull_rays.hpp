@@ -86,35 +86,21 @@ __device__ __forceinline__ void sc_query_ray(const RayQueryArgs &qa, const Strea
     if (plain != 0ull) rq_plain<OCCLUSION>(qa, reinterpret_cast<const DevObject *>(scene), o, d, use && !proven, t_max, best_t, best);
 }
 
-// The shading policy (rt_stream_shade.hpp) of a wave of unrelated rays: every nearest hit, segment 0 included, and every shadow ray is
-// culled for as the ray it is.
-struct ScRayShade {
-    using Segment = ShadeNoSegment;
-    const RayQueryArgs qa; // (by value, as ScShade holds them)
-    const StreamCullArgs ca;
+// The query object (rt_ray_kernels.hpp) of a wave that culls for each of its rays: every query, a shadow ray's included, is sc_query_ray.
+// It owns the wave's work words.  They count a query only if some lane is in use (wave-uniform): a wave of the grid-stride loop's last
+// batch that holds no ray asks nothing and counts nothing.  The kernel adds them up at its end (sc_flush).
+struct ScRayQuery {
+    const RayQueryArgs &qa; // (the kernel's own arguments, by reference: held by value, ray_query_cull_kernel's loops came out at another
+    const StreamCullArgs &ca; // place in the code and 3.6 % slower; DESIGN.md section 30, "Shapes")
     const unsigned char *scene;
     unsigned char *slice; // SQ_SLICE_BYTES of LDS that belong to this wave
-    ScBounceStats &bs;
-    // segment 0 stores the rt_hit of the lane's ray, as SqkShadeRays does (out_rec == NULL: nothing)
-    RqRecord *out_rec;
-    uint64_t i;
-    bool live;
+    ScBounceStats bs;
 
-    template <bool HAS_GQ, bool HAS_CUBIC>
-    __device__ __forceinline__ void nearest(uint32_t, uint32_t lane, const D3 &o, const D3 &d, bool use, double &best_t, int &best) const
+    template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+    __device__ __forceinline__ void query(uint32_t lane, const D3 &o, const D3 &d, bool use, double t_max, double &best_t, int &best)
     {
-        sc_query_ray<HAS_GQ, HAS_CUBIC, false>(qa, ca, scene, slice, lane, o, d, use, MAX_T, best_t, best, bs);
-    }
-    __device__ __forceinline__ Segment segment(bool, const D3 &) const { return Segment{}; }
-    template <bool HAS_GQ, bool HAS_CUBIC>
-    __device__ __forceinline__ void occluded(const Segment &, uint32_t lane, const DevLight &, const D3 &so, const D3 &sd, bool use, double max_t, int &blocked) const
-    {
-        double unused_t = INFINITY;
-        sc_query_ray<HAS_GQ, HAS_CUBIC, true>(qa, ca, scene, slice, lane, so, sd, use, max_t, unused_t, blocked, bs);
-    }
-    __device__ __forceinline__ void first_hit(int best, double best_t, const D3 &sp, const D3 &sn) const
-    {
-        if (out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
+        bs.on = ca.stats != nullptr && __ballot(use) != 0ull;
+        sc_query_ray<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, ca, scene, slice, lane, o, d, use, t_max, best_t, best, bs);
     }
 };
 

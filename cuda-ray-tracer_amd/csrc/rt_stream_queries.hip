@@ -11,93 +11,36 @@
 // lane without work stays with `use = false`.  Every kernel takes 4 * SQ_SLICE_BYTES = 24 KiB of LDS whatever the tables hold.
 #include <hip/hip_runtime.h>
 #include "rt_launch.h"   // the launchers below, as the host sees them
-#include "rt_stream_shade.hpp" // the shading loop and SqShade over rt_stream.hpp: the streamed object loops; RayQueryArgs, the plain path, the ray and record layouts (rt_rayquery.hpp)
+#include "rt_ray_kernels.hpp" // the ray, colour and path kernels' bodies; SqQuery and the streamed object loops (rt_stream.hpp); RayQueryArgs, the ray and record layouts (rt_rayquery.hpp)
 #include "rt_extents.hpp" // the extent record, its merge and the wave reduction
 
 namespace RT_SYM(rtk) {
 
-// one caller-supplied ray per lane: three 16-byte loads (lanes without a ray keep zeroes)
-__device__ __forceinline__ void sqk_load_ray(const RqRay *__restrict__ rays, uint64_t i, bool live, D3 &o, D3 &d)
-{
-    o = D3{0.0, 0.0, 0.0};
-    d = D3{0.0, 0.0, 0.0};
-    if (live) {
-        const double2 *w = reinterpret_cast<const double2 *>(rays + i);
-        const double2 w0 = w[0], w1 = w[1], w2 = w[2];
-        o = D3{w0.x, w0.y, w1.x};
-        d = D3{w1.y, w2.x, w2.y};
-    }
-}
-
-// ---- closest hit and occlusion (rt_rays.hip: ray_query_kernel) ---------------------------------------------------------------------------
+// ---- caller-supplied rays (rt_rays.hip, rt_shade_rays.hip, rt_paths.hip): the twins' bodies (rt_ray_kernels.hpp) over sq_query ---------------------
+// (the slice: this wave's quarter of the workgroup's LDS, never another's)
 template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
 __global__ __launch_bounds__(256) void ray_query_stream_kernel(const RayQueryArgs qa, const unsigned char *__restrict__ scene, const RqRay *__restrict__ rays,
                                                                const double *__restrict__ t_max, RqRecord *__restrict__ out_rec, int32_t *__restrict__ out_blocked)
 {
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    unsigned char *slice = smem + wave * SQ_SLICE_BYTES; // this wave's, never another's
-    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-
-    const uint64_t stride = (uint64_t) gridDim.x * 256u;
-    for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (workgroup-uniform trip count)
-        const uint64_t i = first + tid;
-        const bool live = i < qa.n;
-        D3 o, d;
-        sqk_load_ray(rays, i, live, o, d);
-        double tm = MAX_T;
-        if (OCCLUSION && t_max && live) tm = t_max[i];
-        double best_t = INFINITY;
-        int best = OCCLUSION ? 0 : -1;
-        sq_query<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, slice, lane, o, d, live, false, tm, best_t, best);
-        if (OCCLUSION) {
-            if (live) out_blocked[i] = best;
-        } else if (live) {
-            D3 p{0.0, 0.0, 0.0}, nv{0.0, 0.0, 0.0};
-            if (best >= 0) {
-                p = D3{o.x + best_t * d.x, o.y + best_t * d.y, o.z + best_t * d.z};
-                nv = normal_vector(gobj[best].c, p); // in full for every class, as ray_query_kernel
-            }
-            rq_store_record(out_rec + i, best, best_t, p, nv);
-        }
-    }
+    SqQuery q{qa, scene, smem + (threadIdx.x >> 6) * SQ_SLICE_BYTES};
+    rk_ray_query<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, rays, t_max, out_rec, out_blocked, q);
 }
-
-// ---- colour (rt_shade_rays.hip: shade_rays_kernel; the shading loop is stream_frame_kernel's on caller rays, without a cone) ------------
-// SqShade, and: segment 0 stores the rt_hit of the lane's ray, as rt_trace_rays writes it (out_rec == NULL: nothing)
-struct SqkShadeRays : SqShade {
-    RqRecord *out_rec;
-    uint64_t i;
-    bool live;
-
-    __device__ __forceinline__ void first_hit(int best, double best_t, const D3 &sp, const D3 &sn) const
-    {
-        if (out_rec && live) rq_store_record(out_rec + i, best, best_t, sp, sn);
-    }
-};
 
 template <bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void shade_rays_stream_kernel(const ShadeRaysArgs sa, const unsigned char *__restrict__ scene, const DevLight *__restrict__ lights,
                                                                 const RqRay *__restrict__ rays, float4 *__restrict__ out_rgba, RqRecord *__restrict__ out_rec)
 {
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
-    const RayQueryArgs &qa = sa.qa;
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
-
-    const uint64_t stride = (uint64_t) gridDim.x * 256u;
-    for (uint64_t first = (uint64_t) blockIdx.x * 256u; first < qa.n; first += stride) { // (workgroup-uniform trip count)
-        const uint64_t i = first + tid;
-        const bool live = i < qa.n;
-        D3 o, d;
-        sqk_load_ray(rays, i, live, o, d);
-        SqkShadeRays pol{{qa, scene, slice, false}, out_rec, i, live};
-        const F3 res = shade_loop<HAS_GQ, HAS_CUBIC>(sa, scene, lights, lane, pol, o, d, live);
-        if (live) out_rgba[i] = float4{res.x, res.y, res.z, 1.0f}; // one 16-byte store
-    }
+    SqQuery q{sa.qa, scene, smem + (threadIdx.x >> 6) * SQ_SLICE_BYTES};
+    rk_shade_rays<HAS_GQ, HAS_CUBIC>(sa, scene, lights, rays, out_rgba, out_rec, q);
 }
 
 // ---- paths (rt_paths.hip: path_query_kernel) -------------------------------------------------------------------------------------------------
+// The one kernel of the nine that keeps its own text: rk_path_query's, line for line, with sq_query written in place of the query object
+// (tests/test_stream_shade_host.py holds it to that).  Through the shared body its spheres-only instantiation has the same instructions in
+// every loop, all of them 8 bytes earlier -- one compare hoisted in the entry block -- and took 4 to 5 % longer on every series measured
+// (profiles/ray_kernel_bodies.txt); no shape of the body that was compiled moved them back.
 template <bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void path_query_stream_kernel(const PathArgs pa, const unsigned char *__restrict__ scene, const RqRay *__restrict__ rays,
                                                                 RqRecord *__restrict__ out_seg, RqRecord *__restrict__ out_last, PathEnd *__restrict__ out_end)
@@ -113,7 +56,7 @@ __global__ __launch_bounds__(256) void path_query_stream_kernel(const PathArgs p
         const uint64_t i = first + tid;
         const bool live = i < qa.n;
         D3 o, d;
-        sqk_load_ray(rays, i, live, o, d);
+        rk_load_ray(rays, i, live, o, d);
         float cur_ratio = 1.0f;
         uint32_t segments = 0u, end = PATH_MISS;
         int last = -1; // the last hit: what out_last receives
@@ -296,17 +239,6 @@ __global__ __launch_bounds__(256) void extents_stream_kernel(const FrameArgs fa,
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------
-static inline dim3 sqk_ray_grid(uint32_t n, uint32_t max_grid)
-{
-    const uint32_t need = (uint32_t) (((uint64_t) n + 255u) / 256u);
-    return dim3(need < max_grid ? need : (max_grid ? max_grid : 1u));
-}
-
-// launch kernel<HAS_GQ, HAS_CUBIC, extra...> for the scene's classes (rt_rayquery.hpp: rq_for_classes)
-#define SQK_LAUNCH(fa, kernel, extra, g, stream, ...) \
-    rq_for_classes(fa, [&](auto gq, auto cub) { hipLaunchKernelGGL((kernel<decltype(gq)::value, decltype(cub)::value extra>), g, dim3(256), 0, stream, __VA_ARGS__); })
-#define SQK_COMMA ,
-
 static hipError_t sqk_launch_pixels(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, uint32_t grid, int32_t *out_object, double *out_t,
                                     float *out_normal, const uint32_t *xy, uint32_t n, void *rec, hipStream_t stream)
 {
@@ -314,7 +246,7 @@ static hipError_t sqk_launch_pixels(const FrameArgs *fa, const void *scene, cons
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     float4 *nrm = reinterpret_cast<float4 *>(out_normal);
     RqRecord *r = reinterpret_cast<RqRecord *>(rec);
-    SQK_LAUNCH(fa, gbuffer_stream_kernel, , dim3(grid), stream, *fa, qa, s, camx, camy, out_object, out_t, nrm, xy, n, r);
+    RK_LAUNCH(fa, (gbuffer_stream_kernel<GQ, CUB>), dim3(grid), 0, stream, *fa, qa, s, camx, camy, out_object, out_t, nrm, xy, n, r);
     return hipGetLastError();
 }
 
@@ -351,33 +283,33 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_object_extents)(const FrameArgs *f
     const RayQueryArgs qa = rq_args(fa, 0u);
     const dim3 g(ea.n_tiles < max_grid ? ea.n_tiles : (max_grid ? max_grid : 1u));
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
-    SQK_LAUNCH(fa, extents_stream_kernel, , g, stream, *fa, qa, ea, s, camx, camy, rec);
+    RK_LAUNCH(fa, (extents_stream_kernel<GQ, CUB>), g, 0, stream, *fa, qa, ea, s, camx, camy, rec);
     return hipGetLastError();
 }
+
+namespace RT_SYM(rtk) {
+template <bool OCCLUSION>
+static hipError_t sqk_launch_rays(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, void *out, uint32_t max_grid, hipStream_t stream)
+{
+    const RayQueryArgs qa = rq_args(fa, n);
+    RK_LAUNCH(fa, (ray_query_stream_kernel<GQ, CUB, OCCLUSION>), rk_ray_grid(n, max_grid), 0, stream, qa, reinterpret_cast<const unsigned char *>(scene),
+              reinterpret_cast<const RqRay *>(rays), t_max, OCCLUSION ? nullptr : reinterpret_cast<RqRecord *>(out), OCCLUSION ? reinterpret_cast<int32_t *>(out) : nullptr);
+    return hipGetLastError();
+}
+} // namespace RT_SYM(rtk)
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_trace_rays)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
                                                            hipStream_t stream)
 {
-    using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
-    const RayQueryArgs qa = rq_args(fa, n);
-    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
-    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
-    SQK_LAUNCH(fa, ray_query_stream_kernel, SQK_COMMA false, sqk_ray_grid(n, max_grid), stream, qa, s, r, (const double *) nullptr, reinterpret_cast<RqRecord *>(out),
-               (int32_t *) nullptr);
-    return hipGetLastError();
+    return RT_SYM(rtk)::sqk_launch_rays<false>(fa, scene, rays, nullptr, n, out, max_grid, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_occluded_rays)(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
                                                               uint32_t max_grid, hipStream_t stream)
 {
-    using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
-    const RayQueryArgs qa = rq_args(fa, n);
-    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
-    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
-    SQK_LAUNCH(fa, ray_query_stream_kernel, SQK_COMMA true, sqk_ray_grid(n, max_grid), stream, qa, s, r, t_max, (RqRecord *) nullptr, out);
-    return hipGetLastError();
+    return RT_SYM(rtk)::sqk_launch_rays<true>(fa, scene, rays, t_max, n, out, max_grid, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_shade_rays)(const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
@@ -385,15 +317,9 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_shade_rays)(const FrameArgs *fa, c
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
-    ShadeRaysArgs sa;
-    sa.qa = rq_args(fa, n);
-    sa.n_lights = fa->n_lights;
-    sa.max_refl = fa->max_refl;
-    sa.bg[0] = fa->bg[0]; sa.bg[1] = fa->bg[1]; sa.bg[2] = fa->bg[2];
-    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
-    const DevLight *lt = reinterpret_cast<const DevLight *>(lights);
-    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
-    SQK_LAUNCH(fa, shade_rays_stream_kernel, , sqk_ray_grid(n, max_grid), stream, sa, s, lt, r, reinterpret_cast<float4 *>(rgba), reinterpret_cast<RqRecord *>(hits));
+    const ShadeRaysArgs sa = rk_shade_args(fa, n);
+    RK_LAUNCH(fa, (shade_rays_stream_kernel<GQ, CUB>), rk_ray_grid(n, max_grid), 0, stream, sa, reinterpret_cast<const unsigned char *>(scene),
+              reinterpret_cast<const DevLight *>(lights), reinterpret_cast<const RqRay *>(rays), reinterpret_cast<float4 *>(rgba), reinterpret_cast<RqRecord *>(hits));
     return hipGetLastError();
 }
 
@@ -402,13 +328,8 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_trace_paths)(const FrameArgs *fa, 
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
-    PathArgs pa;
-    pa.qa = rq_args(fa, n);
-    pa.max_refl = fa->max_refl;
-    pa.max_segments = max_segments;
-    const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
-    const RqRay *r = reinterpret_cast<const RqRay *>(rays);
-    SQK_LAUNCH(fa, path_query_stream_kernel, , sqk_ray_grid(n, max_grid), stream, pa, s, r, reinterpret_cast<RqRecord *>(segments), reinterpret_cast<RqRecord *>(last),
-               reinterpret_cast<PathEnd *>(ends));
+    const PathArgs pa = rk_path_args(fa, n, max_segments);
+    RK_LAUNCH(fa, (path_query_stream_kernel<GQ, CUB>), rk_ray_grid(n, max_grid), 0, stream, pa, reinterpret_cast<const unsigned char *>(scene),
+              reinterpret_cast<const RqRay *>(rays), reinterpret_cast<RqRecord *>(segments), reinterpret_cast<RqRecord *>(last), reinterpret_cast<PathEnd *>(ends));
     return hipGetLastError();
 }

@@ -1,5 +1,5 @@
 // rt_stream_shade.hpp -- the reference's render_pixel (src/update-cpu.cpp:82-119) for one ray per lane, once: the loop that
-// shade_rays_kernel (rt_shade_rays.hip), shade_rays_stream_kernel (rt_stream_queries.hip), the three streamed frame kernels
+// the three shade_rays kernels (through their one body, rt_ray_kernels.hpp: rk_shade_rays), the three streamed frame kernels
 // (rt_stream.hip, rt_stream_cull.hip, rt_stream_cull_bounce.hip) and the two streamed ray-list kernels (rt_stream_adaptive.hip,
 // rt_stream_cull_adaptive.hip) all run.  It is the image's definition: nearest hit, normal_vector in full, every light in index order
 // with its occlusion query from sp + SHADOW_BIAS * sn, surface_color, the clamp, the reflection loop with its blends.  No facing-away
@@ -7,7 +7,7 @@
 //   nearest<HAS_GQ, HAS_CUBIC>(k, lane, o, d, use, best_t, best)                the nearest-hit query of segment k (what k == 0 means is the policy's)
 //   segment(hit, sp) -> Policy::Segment                                         once per segment that has a hit: what the light loop shares
 //   occluded<HAS_GQ, HAS_CUBIC>(seg, lane, lt, so, sd, use, max_t, blocked)     the occlusion query towards one light
-//   first_hit(best, best_t, sp, sn)                                             behind the hit point of segment 0 (the shade_rays kernels' record)
+//   first_hit(best, best_t, sp, sn)                                             behind the hit point of segment 0 (the shade_rays kernels' record: RkShade)
 // The wave-level rules are the callers' and the policies' alike: all 64 lanes call; `use` is a predicate; no lane leaves before the
 // wave's last ballot, readlane or staged chunk; nothing is workgroup-wide (no barrier: the waves of a workgroup run different numbers
 // of bounces and chunks); no hook puts divergent control flow around a staging call.
@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "rt_stream.hpp" // sq_query, for SqShade alone: shade_loop itself needs nothing of the streamed loops, only rt_rayquery.hpp's types and
-                         // rt_shade.hpp's arithmetic (so rt_shade_rays.hip, which stages all tables, reads rt_stream.hpp without using it)
+                         // rt_shade.hpp's arithmetic (so the files that stage all tables read rt_stream.hpp without using it)
 
 namespace RT_SYM(rtk) {
 

@@ -22,8 +22,7 @@ NEW_FILES = ("rt_stream_cull_rays.hpp", "rt_stream_cull_rays.hip")
 KERNELS = {"ray_query_cull_kernel": 8, "shade_rays_cull_kernel": 4, "path_query_cull_kernel": 4}   # instantiations per build
 LAUNCHERS = ("rt_launch_stream_cull_trace_rays", "rt_launch_stream_cull_occluded_rays", "rt_launch_stream_cull_shade_rays", "rt_launch_stream_cull_trace_paths")
 # the files the feature calls into or stands beside, as they were before it (sha256)
-UNTOUCHED = {"rt_stream_queries.hip": "c5718e524603544303010092957b8a36c0c2978e8e534fa2110124ae2aa988d6",
-             "rt_stream_cull_bounce.hpp": "f4f6b3c4d618b80feda7186228001dad1adc4eabb48d844fcc57158034ac5c8e",
+UNTOUCHED = {"rt_stream_cull_bounce.hpp": "f4f6b3c4d618b80feda7186228001dad1adc4eabb48d844fcc57158034ac5c8e",
              "rt_ray_bound.hpp": "32c17c9aa85ae82b2add30121c1149e19d87f38e81a145cc2354c45140e0df4c"}
 
 
@@ -151,16 +150,37 @@ def test_the_new_files_have_no_workgroup_barrier():
     code = "\n".join(l.split("//")[0] for l in kernel.splitlines())
     assert "sq_query<" not in code      # no instantiation keeps the full sweep
     assert code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 3
-    assert "ScRayShade pol{" in code and "shade_loop<HAS_GQ, HAS_CUBIC>(sa, scene, lights, lane, pol, o, d, live)" in code      # the shading loop is the shared one
+    # every kernel's query object is the one over sc_query_ray, on the wave's own slice, and its work words leave through sc_flush
+    assert code.count("smem + (threadIdx.x >> 6) * SQ_SLICE_BYTES, {false, {0u, 0u, 0u, 0u, 0u}}};") == 3 == len(re.findall(r"\bScRayQuery q\{(qa|sa\.qa|pa\.qa), ca, scene, ", code))
+    assert code.count("if (ca.stats) sc_flush(q.bs.w, ca.stats, threadIdx.x & 63u);") == 3 and "atomicAdd" not in code
+    obj = body.split("struct ScRayQuery {")[1].split("\n};\n")[0]
+    assert "bs.on = ca.stats != nullptr && __ballot(use) != 0ull;" in obj and obj.count("sc_query_ray<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, ca, scene, slice, lane, o, d, use, t_max, best_t, best, bs);") == 1
+    assert body.count("sc_query_ray<") == 1 and "const StreamCullArgs &ca;" in obj and "const RayQueryArgs &qa;" in obj      # (the kernel's own arguments: DESIGN.md section 30, "Shapes")
+    # the shading loop is the shared one, under the one policy over a query object (rt_ray_kernels.hpp), which this file's colour kernel runs
+    bodies = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, "rt_ray_kernels.hpp")).read().splitlines())
+    assert "RkShade<Query> pol{q, out_rec, i, live};" in bodies and "shade_loop<HAS_GQ, HAS_CUBIC>(sa, scene, lights, lane, pol, o, d, live)" in bodies
+    assert "rk_shade_rays<HAS_GQ, HAS_CUBIC>(sa, scene, lights, rays, out_rgba, out_rec, q);" in code.split("void shade_rays_cull_kernel(")[1].split("\n}\n")[0]
+    assert "sq_query<" not in bodies and "sc_query_ray" not in bodies      # the bodies know no family
 
 
 def test_the_neighbours_are_untouched():
-    """rt_stream_queries.hip (the twins), rt_stream_cull_bounce.hpp (the nearest-hit query this feature calls) and rt_ray_bound.hpp (the
-    predicate) are what they were before the feature."""
+    """rt_stream_cull_bounce.hpp (the nearest-hit query this feature calls) and rt_ray_bound.hpp (the predicate) are what they were before
+    the feature.  rt_stream_queries.hip (the twins) was pinned too while this feature's kernels restated its ray loader, grid and bodies; now
+    there is no copy to keep in step: this feature's kernels run the bodies of rt_ray_kernels.hpp, as the twins do
+    (but for the one that keeps the path body's text, held to it line by line), and this feature's files hold no ray load, grid rule,
+    record store or loop of their own (tests/test_stream_shade_host.py says so of all five kernel files).  The twins still know nothing of
+    culling."""
     for name, digest in UNTOUCHED.items():
         assert hashlib.sha256(open(os.path.join(CSRC, name), "rb").read()).hexdigest() == digest, name
     twin = open(os.path.join(CSRC, "rt_stream_queries.hip")).read()
     assert "rt_stream_cull" not in twin and "ray_reaches" not in twin
+    import test_stream_shade_host as shared
+    shared.test_the_ray_kernels_bodies_exist_once()
+    shared.test_the_path_kernel_that_keeps_its_copy_is_the_bodys_text()
+    for name in NEW_FILES:
+        code = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, name)).read().splitlines())
+        for word in ("double2", "rq_store_record", "normal_vector", "reflect_ray", "__ballot(bouncing)", "max_grid ?", "gridDim"):
+            assert word not in code, (name, word)
 
 
 def test_the_launch_sites_pick_by_the_one_decision():

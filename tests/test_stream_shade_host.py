@@ -1,5 +1,8 @@
 """The shading loop of the streamed kernels and of rt_shade_rays (csrc/rt_stream_shade.hpp: shade_loop), host side:
 the loop's text exists once, every kernel that shades a ray runs it under a policy of its own, and the helpers around it exist once.
+So do the bodies of the kernels for caller-supplied rays (csrc/rt_ray_kernels.hpp): the staged, the streamed and the
+culled kernel of each query run one body over a query object, and what was written out per family -- the ray loads, the grid rule, the
+records, the path loop, the shading policy -- is in one file.
 One kernel is the stated exception: stream_cull_bounce_frame_kernel holds the loop's text itself, because through the shared loop its
 strict <true, true> instantiation needs 258 registers and loses its second wave per SIMD (profiles/stream_shared_loop.txt)."""
 import glob
@@ -12,16 +15,25 @@ CSRC = os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc")
 MARKER = "the reflection loop, src/update-cpu.cpp:96-117"
 LOOP = "rt_stream_shade.hpp"
 KEEPS_ITS_COPY = "rt_stream_cull_bounce.hip"
-# file -> (kernel, its policy): the sites that run the shared loop
+BODIES = "rt_ray_kernels.hpp"
+# file -> (kernel or body, its policy): the sites that run the shared loop.  The three shade_rays kernels are one site: their body
 SITES = {
-    "rt_shade_rays.hip": ("shade_rays_kernel", "ShadeRaysStaged"),
-    "rt_stream_queries.hip": ("shade_rays_stream_kernel", "SqkShadeRays"),
+    BODIES: ("rk_shade_rays", "RkShade<Query>"),
     "rt_stream.hip": ("stream_frame_kernel", "SqShade"),
     "rt_stream_adaptive.hip": ("ray_list_stream_kernel", "SqShade"),
     "rt_stream_cull.hip": ("stream_cull_frame_kernel", "ScShade"),
     "rt_stream_cull_adaptive.hip": ("ray_list_cull_kernel", "ScaShade"),
 }
-STREAMED = sorted(glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", "rt_shade.hpp", "rt_rayquery.hpp", "rt_adaptive.hip")])
+STREAMED = sorted(glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", "rt_shade.hpp", "rt_rayquery.hpp", "rt_adaptive.hip", BODIES)])
+# One of the nine kernels for caller-supplied rays keeps the text of its body, as stream_cull_bounce_frame_kernel keeps the loop's:
+# through rk_path_query path_query_stream_kernel took 4 to 5 % longer on every series measured (profiles/ray_kernel_bodies.txt)
+PATHS_KEEPS_ITS_COPY = ("rt_stream_queries.hip", "path_query_stream_kernel")
+# the other eight: file -> {kernel: the body it runs}
+RAY_KERNELS = {
+    "rt_rays.hip": {"ray_query_kernel": "rk_ray_query"}, "rt_shade_rays.hip": {"shade_rays_kernel": "rk_shade_rays"}, "rt_paths.hip": {"path_query_kernel": "rk_path_query"},
+    "rt_stream_queries.hip": {"ray_query_stream_kernel": "rk_ray_query", "shade_rays_stream_kernel": "rk_shade_rays"},
+    "rt_stream_cull_rays.hip": {"ray_query_cull_kernel": "rk_ray_query", "shade_rays_cull_kernel": "rk_shade_rays", "path_query_cull_kernel": "rk_path_query"},
+}
 
 
 def read(name):
@@ -33,16 +45,18 @@ def code_of(name):
 
 
 def test_the_loops_text_exists_once():
-    """The marker comment of the reflection loop: in the shared loop, in the two path kernels (rt_paths.hip, and once in
-    rt_stream_queries.hip for path_query_stream_kernel: no lights, a store per segment -- another loop), and in the one kernel that keeps
-    its copy.  Nowhere else under csrc/."""
+    """The marker comment of the reflection loop: in the shared loop, in the one body of the path kernels (rk_path_query: no lights, a
+    store per segment -- another loop), and in the two kernels that keep a copy: stream_cull_bounce_frame_kernel the shared loop's,
+    path_query_stream_kernel the path body's.  Nowhere else under csrc/."""
     have = {os.path.basename(p): open(p).read().count(MARKER) for p in glob.glob(os.path.join(CSRC, "*")) if MARKER in open(p).read()}
-    assert have == {LOOP: 1, "rt_paths.hip": 1, "rt_stream_queries.hip": 1, KEEPS_ITS_COPY: 1}, have
-    paths = read("rt_stream_queries.hip").split("void path_query_stream_kernel")[1].split("// ---- pixels")[0]
+    assert have == {LOOP: 1, BODIES: 1, PATHS_KEEPS_ITS_COPY[0]: 1, KEEPS_ITS_COPY: 1}, have
+    paths = read(BODIES).split("void rk_path_query(")[1].split("// ---- colour")[0]
     assert MARKER in paths
+    assert MARKER in read(PATHS_KEEPS_ITS_COPY[0]).split(f"void {PATHS_KEEPS_ITS_COPY[1]}(")[1].split("// ---- pixels")[0]
     # what goes with the loop: the light loop's colour, the clamp and the blends are written in the same files only
     for word in ("surface_color(lt->p, lt->color, spherical, sp, sn, albedo)", "glm::min(vec3(1.0f), acc)", "RT_SYM(rtk)::blend(res, cur_ratio, bg)"):
-        files = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, "rt_shade_rays.hip")] if word in open(p).read())
+        files = sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", BODIES)]
+                       if word in open(p).read())
         assert files == sorted([LOOP, KEEPS_ITS_COPY]), (word, files)
 
 
@@ -87,14 +101,19 @@ def test_the_policies_state_the_four_points_and_nothing_workgroup_wide():
     assert loop.count("pol.") == 4
     # the per-segment hook sits behind the wave-uniform ballot, in front of the light loop
     assert re.search(r"if \(__ballot\(hit\) != 0ull\) \{\n[^\n]*albedo[^\n]*\n[^\n]*pol\.segment\(hit, sp\);\n\s*for \(uint32_t l = 0; l < a\.n_lights; l\+\+\)", loop)
-    where = {"SqShade": LOOP, "ScShade": "rt_stream_cull.hpp", "ScaShade": "rt_stream_cull_adaptive.hip", "ShadeRaysStaged": "rt_shade_rays.hip",
-             "SqkShadeRays": "rt_stream_queries.hip"}
+    # (RkShade: the one policy of the three shade_rays kernels, a template over the query object)
+    where = {"SqShade": LOOP, "ScShade": "rt_stream_cull.hpp", "ScaShade": "rt_stream_cull_adaptive.hip", "RkShade": BODIES}
     for policy, name in where.items():
         assert len(re.findall(rf"\bstruct {policy}\b[^;]*{{", code_of(name))) == 1, policy
-        for other in set(where.values()) | {"rt_stream_shell.hpp", "rt_stream.hpp", "rt_stream_cull_bounce.hpp"}:
+        for other in set(where.values()) | {"rt_stream_shell.hpp", "rt_stream.hpp", "rt_stream_cull_bounce.hpp", "rt_shade_rays.hip", "rt_stream_queries.hip",
+                                            "rt_stream_cull_rays.hpp", "rt_stream_cull_rays.hip", "rt_rayquery.hpp"}:
             if other != name:
                 assert not re.search(rf"\bstruct {policy}\b", code_of(other)), (policy, other)
-    for name in (LOOP, "rt_stream_shell.hpp"):
+    assert "template <typename Query>\nstruct RkShade {" in code_of(BODIES)
+    for p in glob.glob(os.path.join(CSRC, "*")):      # the three policies it replaces are gone
+        for gone in ("ShadeRaysStaged", "SqkShadeRays", "ScRayShade"):
+            assert gone not in open(p).read(), (gone, p)
+    for name in (LOOP, "rt_stream_shell.hpp", BODIES):
         code = code_of(name)
         for word in ("__syncthreads", "s_barrier", '"workgroup"', "rq_stage_tables", "__shared__", "HIP_DYNAMIC_SHARED"):
             assert word not in code, (name, word)
@@ -117,6 +136,63 @@ def test_the_helpers_around_the_loop_exist_once():
     for name in ("rt_stream_cull.hip", "rt_stream_cull_bounce.hip", "rt_stream_cull_adaptive.hip"):
         code = code_of(name)
         assert "sc_flush(st.w, ca.stats, lane" in code and "atomicAdd" not in code, name
-    for name in list(SITES) + [KEEPS_ITS_COPY]:
+    # (the ray kernels' files and rt_stream_queries.hip's pixel family through the one macro over it, RK_LAUNCH)
+    macro = read(BODIES).split("#define RK_LAUNCH(fa, kernel, g, lds, stream, ...)")[1].split("\n\n")[0]
+    assert "rq_for_classes(fa, [&](auto gq, auto cub) {" in macro and "hipLaunchKernelGGL(kernel, g, dim3(256), lds, stream, __VA_ARGS__);" in macro
+    assert "#define" not in read("rt_stream_queries.hip") and "#define" not in read("rt_stream_cull_rays.hip")      # (no launch macro of their own)
+    for name in list(SITES) + [KEEPS_ITS_COPY] + list(RAY_KERNELS):
         code = code_of(name)
-        assert "rq_for_classes(fa, [&](auto gq, auto cub)" in code and not re.search(r"kernel<(true|false), (true|false)", code), name
+        if name in RAY_KERNELS:
+            assert len(re.findall(r"\bRK_LAUNCH\(fa, \(\w+<GQ, CUB[,>]", code)) >= len(RAY_KERNELS[name]) and "rq_for_classes" not in code, name
+        else:
+            assert "rq_for_classes(fa, [&](auto gq, auto cub)" in code, name
+        assert not re.search(r"kernel<(true|false), (true|false)", code) and "if (fa->n_cub)" not in code, name
+
+
+def test_the_ray_kernels_bodies_exist_once():
+    """each of the kernels (eight of the nine) takes its LDS, builds its query object and calls its body exactly
+    once, with no loop of its own; the three-load ray read, the grid rule and the ray query's stores are written in one file, a path's
+    stores in that file and in the one kernel that keeps the path body's text."""
+    for name, kernels in RAY_KERNELS.items():
+        code = code_of(name)
+        for kernel, body_fn in kernels.items():
+            body = code.split(f"void {kernel}(")[1].split("\n}\n")[0]
+            assert len(re.findall(r"\brk_\w+<", body)) == 1 and len(re.findall(rf"\b{body_fn}<HAS_GQ, HAS_CUBIC(, OCCLUSION)?>\(", body)) == 1, (kernel, body)
+            assert "for (" not in body and "while (" not in body and "shade_loop" not in body, kernel
+            assert len(re.findall(r"\b(RqStaged|SqQuery|ScRayQuery) q\{", body)) == 1, kernel      # one query object, built here
+        assert len(re.findall(r"\brk_(ray_query|shade_rays|path_query)<", code)) == len(kernels), name
+    assert sum(len(k) for k in RAY_KERNELS.values()) == 8
+    for body_fn in ("rk_ray_query", "rk_shade_rays", "rk_path_query"):
+        assert len(re.findall(rf"void {body_fn}\(", code_of(BODIES))) == 1, body_fn
+    # a query object offers one call
+    for struct, name in (("RqStaged", "rt_rayquery.hpp"), ("SqQuery", "rt_stream.hpp"), ("ScRayQuery", "rt_stream_cull_rays.hpp")):
+        text = code_of(name).split(f"struct {struct} {{")[1].split("\n};\n")[0]
+        assert text.count("__device__") == 1 and "void query(uint32_t" in text and "template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>" in text, struct
+    everything = {os.path.basename(p): "\n".join(l.split("//")[0] for l in open(p).read().splitlines()) for p in glob.glob(os.path.join(CSRC, "*"))}
+    only_in_bodies = ("const double2 w0 = w[0], w1 = w[1], w2 = w[2];",                       # the three-load ray read
+                      "need < max_grid ? need : (max_grid ? max_grid : 1u)",                  # the grid rule
+                      "out_blocked[i] = best;", "nv = normal_vector(gobj[best].c, p);", "RkShade<Query> pol{")
+    for word in only_in_bodies:
+        assert sorted(n for n, code in everything.items() if word in code) == [BODIES], word
+    for word in ("rq_store_record(out_seg +", "out_end[i] = PathEnd{segments, end, cur_ratio, last};"):      # a path's stores
+        assert sorted(n for n, code in everything.items() if word in code) == sorted([BODIES, PATHS_KEEPS_ITS_COPY[0]]), word
+        assert everything[PATHS_KEEPS_ITS_COPY[0]].count(word) == everything[BODIES].count(word), word
+    assert everything[BODIES].count("const double2 w0 = w[0], w1 = w[1], w2 = w[2];") == 1 and everything[BODIES].count("need < max_grid ?") == 1
+
+
+def test_the_path_kernel_that_keeps_its_copy_is_the_bodys_text():
+    """path_query_stream_kernel is rk_path_query line for line -- code and order -- from the grid-stride loop to its end, with the query
+    object's one call written in place as sq_query without a cone; in front of the loop it takes its wave's slice as its twins do."""
+    def lines(text):
+        return [l.strip() for l in text.splitlines() if l.strip()]
+    body = lines(code_of(BODIES).split("void rk_path_query(")[1].split("template <typename Query>")[0].split("const uint64_t stride =")[1])
+    kernel = lines(code_of(PATHS_KEEPS_ITS_COPY[0]).split(f"void {PATHS_KEEPS_ITS_COPY[1]}(")[1].split("\n}\n")[0].split("const uint64_t stride =")[1])
+    call = "q.template query<HAS_GQ, HAS_CUBIC, false>(lane, o, d, bouncing, MAX_T, best_t, best);"
+    assert body.count(call) == 1 and len(body) >= 55
+    want = [("sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best);" if l == call else l) for l in body]
+    assert kernel + ["}"] == want, [(a, b) for a, b in zip(kernel, want) if a != b][:3]      # (the body's text ends with its closing brace)
+    head = code_of(PATHS_KEEPS_ITS_COPY[0]).split(f"void {PATHS_KEEPS_ITS_COPY[1]}(")[1].split("const uint64_t stride =")[0]
+    for l in ("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];", "const RayQueryArgs &qa = pa.qa;", "const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;",
+              "unsigned char *slice = smem + wave * SQ_SLICE_BYTES;", "const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);"):
+        assert l in head, l
+    assert "rk_" not in head.replace("rk_load_ray", "")
