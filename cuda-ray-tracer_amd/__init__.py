@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
+    "rt_sort_rays_work_bytes", "rt_sort_rays", "rt_permute",
     "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_debug_wave_box", "rt_destroy",
 ]
@@ -256,6 +257,11 @@ def lib():
         L.rt_debug_scene_blob.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_assemble_planes.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp]
         L.rt_merge_object_extents.argtypes = [vp, vp, C.c_uint32, vp, vp]
+        if LIB_PATH != os.environ.get("MI355RT_LIB") or hasattr(L, "rt_sort_rays"):   # (an earlier build of this ABI under MI355RT_LIB: calling them raises)
+            L.rt_sort_rays_work_bytes.argtypes = [C.c_uint32]
+            L.rt_sort_rays_work_bytes.restype = C.c_size_t
+            L.rt_sort_rays.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp, C.c_size_t, vp, fp]
+            L.rt_permute.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint32, C.c_uint32, C.c_int, vp, fp]
         _lib = L
     return _lib
 
@@ -419,6 +425,70 @@ def desc_from_arrays(width, height, vertical_fov, bg_color, max_reflections, coe
 
 from .sharding import (band_rows_of_rank, max_local_rows, assemble_index, gather_to_root, assemble_torch, sparse_words, bg_rgba8,  # noqa: E402,F401
                        bg_rgba32f, pack_sparse_numpy, assemble_sparse_numpy)
+
+
+class _SortedRays:
+    """What the sort=True keywords share: the rays uploaded and sorted on the device (rt_sort_rays), buffers on that device, gathers into
+    the sorted order and scatters back into the caller's (rt_permute).  Everything is enqueued on `stream` (None: the default stream);
+    sync() waits for it."""
+
+    def __init__(self, r, rays, stream, keys=False):
+        import torch
+        self.r, self.n, self.stream = r, len(rays), stream
+        self.dev = torch.device("cuda", torch.cuda.current_device())
+        self._torch = torch
+        if self.n == 0:
+            raise RtError(-1, "rt_sort_rays: n is 0")
+        d_rays = torch.from_numpy(np.ascontiguousarray(rays).view(np.float64).reshape(-1, 6)).to(self.dev)
+        self.sorted = torch.empty((self.n, 6), dtype=torch.float64, device=self.dev)
+        self.perm = torch.empty((self.n,), dtype=torch.int32, device=self.dev)
+        self.keys = torch.empty((self.n,), dtype=torch.int32, device=self.dev) if keys else None
+        nbytes = r.sort_work_bytes(self.n)
+        work = torch.empty((nbytes,), dtype=torch.uint8, device=self.dev)
+        torch.cuda.current_stream().synchronize()   # the upload ran on torch's current stream
+        self._t0, self._t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        self._t0.record(self._ext())
+        r.sort_rays_into(d_rays.data_ptr(), self.n, self.sorted.data_ptr(), self.perm.data_ptr(), None if self.keys is None else self.keys.data_ptr(),
+                         work.data_ptr(), nbytes, stream=stream, timed=False)
+        self._keep = [d_rays, work]
+        self.sorted_ptr = self.sorted.data_ptr()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.sync()
+        self._keep = []
+        return False
+
+    def _ext(self):
+        return self._torch.cuda.ExternalStream(self.stream) if self.stream else self._torch.cuda.default_stream()
+
+    def sync(self):
+        self._ext().synchronize()
+
+    def result(self, shape, dtype):
+        return self._torch.empty(shape, dtype=getattr(self._torch, dtype), device=self.dev)
+
+    def gathered(self, host, elem_bytes):
+        """A host array of one record per ray, on the device in the sorted order."""
+        src = self._torch.from_numpy(host).to(self.dev)
+        self._torch.cuda.current_stream().synchronize()
+        dst = self._torch.empty_like(src)
+        self.r.permute_into(self.perm.data_ptr(), self.n, src.data_ptr(), dst.data_ptr(), elem_bytes, stream=self.stream, timed=False)
+        self._keep.append(src)
+        return dst
+
+    def scattered(self, t, elem_bytes, planes=1):
+        """A device tensor of planes x n records in the sorted order, back in the caller's order (waits for it)."""
+        out = self._torch.empty_like(t)
+        self.r.permute_into(self.perm.data_ptr(), self.n, t.data_ptr(), out.data_ptr(), elem_bytes, planes=planes, scatter=True, stream=self.stream, timed=False)
+        self._t1.record(self._ext())
+        self.sync()
+        return out
+
+    def elapsed(self):
+        return self._t0.elapsed_time(self._t1)
 
 
 class Renderer:
@@ -642,10 +712,17 @@ class Renderer:
         out["d"] = d.reshape(-1, 3)
         return out
 
-    def trace(self, origins, dirs, stream=None):
+    def trace(self, origins, dirs, stream=None, sort=False):
         """The closest hit of every ray (rt_trace_rays_host; blocks): a structured numpy array of HIT_DTYPE records.  Directions are
-        used as given (t is in units of |d|); a miss is object -1, t +inf, point and normal 0.  Works in every context kind."""
+        used as given (t is in units of |d|); a miss is object -1, t +inf, point and normal 0.  Works in every context kind.
+        sort=True: the same records by way of rt_sort_rays -- the rays are sorted on the device, traced in that order and the hits
+        scattered back (worth it for rays in no useful order on an RT_FLAG_STREAM_CULL_RAYS context)."""
         rays = self.rays(origins, dirs)
+        if sort:
+            with self._sorted(rays, stream) as q:
+                hits = q.result((q.n, 6), "float64")
+                self.trace_into(q.sorted_ptr, q.n, hits.data_ptr(), stream=stream, timed=False)
+                return q.scattered(hits, 48).cpu().numpy().view(HIT_DTYPE).reshape(-1)
         out = np.zeros(len(rays), dtype=HIT_DTYPE)
         _check(lib().rt_trace_rays_host(self._h, rays.ctypes.data_as(C.POINTER(Ray)), len(rays), out.ctypes.data_as(C.POINTER(Hit)),
                                         C.c_void_p(stream) if stream else None))
@@ -659,12 +736,19 @@ class Renderer:
                                    C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
 
-    def occluded(self, origins, dirs, t_max=None, stream=None, timed=True):
+    def occluded(self, origins, dirs, t_max=None, stream=None, timed=True, sort=False):
         """Is each ray blocked by some object at EPS < t < t_max (rt_occluded_rays; t_max: one value per ray, None = 1e6 for all)?
-        Returns (torch int32 device tensor [n] of 1 / 0, device milliseconds or None)."""
+        Returns (torch int32 device tensor [n] of 1 / 0, device milliseconds or None).  sort=True: the same flags by way of rt_sort_rays
+        (t_max gathered into the sorted order, the flags scattered back; the milliseconds then cover sort, query and scatter)."""
         import torch
         dev = torch.device("cuda", torch.cuda.current_device())
         rays = self.rays(origins, dirs)
+        if sort:
+            with self._sorted(rays, stream) as q:
+                tm = None if t_max is None else q.gathered(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (q.n,)).copy(), 8)
+                flags = q.result((q.n,), "int32")
+                self.occluded_into(q.sorted_ptr, None if tm is None else tm.data_ptr(), q.n, flags.data_ptr(), stream=stream, timed=False)
+                return q.scattered(flags, 4), (q.elapsed() if timed else None)
         d_rays = torch.from_numpy(rays.view(np.float64).reshape(-1, 6)).to(dev)
         d_tmax = None if t_max is None else torch.from_numpy(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (len(rays),)).copy()).to(dev)
         out = torch.empty((len(rays),), dtype=torch.int32, device=dev)
@@ -680,10 +764,16 @@ class Renderer:
                                       C.c_void_p(blocked_ptr) if blocked_ptr else None, C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
         return ms.value if timed else None
 
-    def shade(self, origins, dirs, stream=None):
+    def shade(self, origins, dirs, stream=None, sort=False):
         """The reference's colour of every ray (rt_shade_rays_host; blocks): an [n, 4] float32 numpy array of (r, g, b, 1) -- what an
-        RGBA32F pixel holds whose primary ray this is.  Directions are used as given.  Works in every context kind and format."""
+        RGBA32F pixel holds whose primary ray this is.  Directions are used as given.  Works in every context kind and format.
+        sort=True: the same colours by way of rt_sort_rays, as trace() does it."""
         rays = self.rays(origins, dirs)
+        if sort:
+            with self._sorted(rays, stream) as q:
+                rgba = q.result((q.n, 4), "float32")
+                self.shade_into(q.sorted_ptr, q.n, rgba.data_ptr(), stream=stream, timed=False)
+                return q.scattered(rgba, 16).cpu().numpy()
         out = np.zeros((len(rays), 4), dtype=np.float32)
         _check(lib().rt_shade_rays_host(self._h, rays.ctypes.data_as(C.POINTER(Ray)), len(rays), out.ctypes.data_as(C.POINTER(C.c_float)),
                                         C.c_void_p(stream) if stream else None))
@@ -700,13 +790,20 @@ class Renderer:
     def _max_segments(self, max_segments):
         return min(self._desc.max_reflections + 1, RT_PATH_MAX_SEGMENTS) if max_segments is None else int(max_segments)
 
-    def paths(self, origins, dirs, max_segments=None, stream=None):
+    def paths(self, origins, dirs, max_segments=None, stream=None, sort=False):
         """The hits along every ray's mirror bounces (rt_trace_paths_host; blocks): (segments, last, ends) -- HIT_DTYPE records [M, n]
         of the segments (a segment the path did not reach is a miss record), HIT_DTYPE records [n] of the last hits, PATH_END_DTYPE
         records [n].  M = max_segments, by default max_reflections + 1 (every segment a path can have), at most 64; it limits what is
-        stored, not how far a path is followed.  Works in every context kind."""
+        stored, not how far a path is followed.  Works in every context kind.  sort=True: the same records by way of rt_sort_rays, as
+        trace() does it (the segment planes scattered plane by plane)."""
         rays = self.rays(origins, dirs)
         m, n = self._max_segments(max_segments), len(rays)
+        if sort:
+            with self._sorted(rays, stream) as q:
+                seg, last, ends = q.result((max(m, 1) * n, 6), "float64"), q.result((n, 6), "float64"), q.result((n, 4), "int32")
+                self.paths_into(q.sorted_ptr, n, m, seg.data_ptr() if m else None, last.data_ptr(), ends.data_ptr(), stream=stream, timed=False)
+                seg = q.scattered(seg, 48, planes=m).cpu().numpy().view(HIT_DTYPE).reshape(m, n) if m else np.zeros((0, n), dtype=HIT_DTYPE)
+                return seg, q.scattered(last, 48).cpu().numpy().view(HIT_DTYPE).reshape(-1), q.scattered(ends, 16).cpu().numpy().view(PATH_END_DTYPE).reshape(-1)
         seg, last, ends = np.zeros((m, n), dtype=HIT_DTYPE), np.zeros(n, dtype=HIT_DTYPE), np.zeros(n, dtype=PATH_END_DTYPE)
         _check(lib().rt_trace_paths_host(self._h, rays.ctypes.data_as(C.POINTER(Ray)), n, m, seg.ctypes.data_as(C.POINTER(Hit)) if m else None,
                                          last.ctypes.data_as(C.POINTER(Hit)), ends.ctypes.data_as(C.POINTER(PathEnd)), C.c_void_p(stream) if stream else None))
@@ -721,6 +818,38 @@ class Renderer:
                                     C.c_void_p(last_ptr) if last_ptr else None, C.c_void_p(ends_ptr) if ends_ptr else None, C.c_void_p(stream) if stream else None,
                                     C.byref(ms) if timed else None))
         return ms.value if timed else None
+
+    @staticmethod
+    def sort_work_bytes(n):
+        """rt_sort_rays_work_bytes: the device work space rt_sort_rays needs for n rays."""
+        return int(lib().rt_sort_rays_work_bytes(int(n)))
+
+    def sort_rays_into(self, ray_ptr, n, sorted_ptr, perm_ptr, keys_ptr, work_ptr, work_bytes, stream=None, timed=True):
+        """rt_sort_rays on the caller's device memory (raw pointers to n rt_ray / optionally n rt_ray / n uint32 / optionally n uint32 /
+        work_bytes >= sort_work_bytes(n) of work space): device milliseconds, or None unless timed (then the call only enqueues kernels)."""
+        ms = C.c_float(0.0)
+        _check(lib().rt_sort_rays(self._h, C.c_void_p(ray_ptr) if ray_ptr else None, int(n), C.c_void_p(sorted_ptr) if sorted_ptr else None,
+                                  C.c_void_p(perm_ptr) if perm_ptr else None, C.c_void_p(keys_ptr) if keys_ptr else None, C.c_void_p(work_ptr) if work_ptr else None,
+                                  int(work_bytes), C.c_void_p(stream) if stream else None, C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def permute_into(self, perm_ptr, n, src_ptr, dst_ptr, elem_bytes, planes=1, scatter=False, stream=None, timed=True):
+        """rt_permute on the caller's device memory: planes x n records of elem_bytes, dst[i] = src[perm[i]], or with scatter
+        dst[perm[i]] = src[i].  Device milliseconds, or None unless timed (then the call only enqueues one kernel)."""
+        ms = C.c_float(0.0)
+        _check(lib().rt_permute(self._h, C.c_void_p(perm_ptr) if perm_ptr else None, int(n), C.c_void_p(src_ptr) if src_ptr else None,
+                                C.c_void_p(dst_ptr) if dst_ptr else None, int(elem_bytes), int(planes), 1 if scatter else 0, C.c_void_p(stream) if stream else None,
+                                C.byref(ms) if timed else None))
+        return ms.value if timed else None
+
+    def sort_rays(self, origins, dirs, stream=None):
+        """The rays in rt_sort_rays' order: (sorted RAY_DTYPE array, perm uint32 [n], keys uint32 [n]); sorted == rays[perm]."""
+        with self._sorted(self.rays(origins, dirs), stream, keys=True) as q:
+            q.sync()
+            return (q.sorted.cpu().numpy().view(RAY_DTYPE).reshape(-1), q.perm.cpu().numpy().view(np.uint32), q.keys.cpu().numpy().view(np.uint32))
+
+    def _sorted(self, rays, stream=None, keys=False):
+        return _SortedRays(self, rays, stream, keys)
 
     def primary_rays(self, cam=None, rect=None, stream=None, timed=True):
         """The context's own primary rays of rect = (x0, y0, x1, y1) (inclusive, global coordinates, row 0 = bottom; None = the whole

@@ -1582,6 +1582,53 @@ extern "C" int rt_merge_object_extents(rt_ctx *ctx, const rt_object_extent *dev_
     return RT_OK;
 }
 
+// ---- sorting caller-supplied rays (rt_sort_rays.hip) ----------------------------------------------------------
+// No scene state: the context selects the device, the grid bound and the error conventions, as in rt_assemble_planes.  Everything is decided
+// from the arguments before a device is looked for.
+extern "C" size_t rt_sort_rays_work_bytes(uint32_t n) { return rt_sort_rays_work_size(n); }
+
+extern "C" int rt_sort_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_ray *dev_sorted, uint32_t *dev_perm, uint32_t *dev_keys, void *dev_work, size_t work_bytes,
+                            void *stream_, float *ms)
+{
+    if (!ctx || !dev_rays || !dev_perm || !dev_work) return fail(RT_ERR_INVALID, "rt_sort_rays: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_sort_rays: n is 0");
+    if (((uintptr_t) dev_rays | (uintptr_t) dev_sorted) & 15u) return fail(RT_ERR_INVALID, "rt_sort_rays: rays and sorted rays must be 16-byte aligned");
+    if (((uintptr_t) dev_perm | (uintptr_t) dev_keys) & 3u) return fail(RT_ERR_INVALID, "rt_sort_rays: perm / keys are not aligned to their type");
+    const size_t need = rt_sort_rays_work_size(n);
+    if (work_bytes < need) return fail(RT_ERR_INVALID, "rt_sort_rays: %zu bytes of work space offered, %u rays take %zu (rt_sort_rays_work_bytes)", work_bytes, n, need);
+    const struct { const void *p; size_t bytes; } range[5] = {{dev_rays, sizeof(rt_ray) * (size_t) n}, {dev_sorted, sizeof(rt_ray) * (size_t) n}, {dev_perm, sizeof(uint32_t) * (size_t) n},
+                                                             {dev_keys, sizeof(uint32_t) * (size_t) n}, {dev_work, work_bytes}};
+    for (int a = 0; a < 5; a++)
+        for (int b = a + 1; b < 5; b++)
+            if (range[a].p && range[b].p && ranges_overlap(range[a].p, range[a].bytes, range[b].p, range[b].bytes))
+                return fail(RT_ERR_INVALID, "rt_sort_rays: two of the rays, sorted rays, perm, keys and work space ranges overlap");
+    hipStream_t stream = (hipStream_t) stream_;
+    if (int rc = use_device(ctx)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = rt_launch_sort_rays(dev_rays, n, dev_sorted, dev_perm, dev_keys, dev_work, rays_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_sort_rays: kernel launch failed: %s", hipGetErrorString(e));
+    return timer_end(ctx, stream, ms);
+}
+
+extern "C" int rt_permute(rt_ctx *ctx, const uint32_t *dev_perm, uint32_t n, const void *dev_src, void *dev_dst, uint32_t elem_bytes, uint32_t planes, int scatter,
+                          void *stream_, float *ms)
+{
+    if (!ctx || !dev_perm || !dev_src || !dev_dst) return fail(RT_ERR_INVALID, "rt_permute: null argument");
+    if (n == 0) return fail(RT_ERR_INVALID, "rt_permute: n is 0");
+    if (elem_bytes == 0u || (elem_bytes & 3u) || elem_bytes > 256u) return fail(RT_ERR_INVALID, "rt_permute: elem_bytes is %u (a multiple of 4, at most 256)", elem_bytes);
+    if (planes == 0u) return fail(RT_ERR_INVALID, "rt_permute: planes is 0");
+    if (((uintptr_t) dev_perm | (uintptr_t) dev_src | (uintptr_t) dev_dst) & 3u) return fail(RT_ERR_INVALID, "rt_permute: perm, src and dst must be 4-byte aligned");
+    const size_t bytes = (size_t) n * elem_bytes * planes;
+    if (ranges_overlap(dev_src, bytes, dev_dst, bytes)) return fail(RT_ERR_INVALID, "rt_permute: src overlaps dst");
+    if (ranges_overlap(dev_perm, sizeof(uint32_t) * (size_t) n, dev_dst, bytes)) return fail(RT_ERR_INVALID, "rt_permute: perm overlaps dst");
+    hipStream_t stream = (hipStream_t) stream_;
+    if (int rc = use_device(ctx)) return rc;
+    if (int rc = timer_begin(ctx, stream, ms)) return rc;
+    const hipError_t e = rt_launch_permute(dev_perm, n, dev_src, dev_dst, elem_bytes, planes, scatter, rays_max_grid(ctx), stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_permute: kernel launch failed: %s", hipGetErrorString(e));
+    return timer_end(ctx, stream, ms);
+}
+
 extern "C" size_t rt_sparse_bytes(uint32_t capacity_tiles)
 {
     return ((size_t) ((4u + capacity_tiles + 3u) & ~3u) + (size_t) capacity_tiles * 256u) * sizeof(uint32_t);

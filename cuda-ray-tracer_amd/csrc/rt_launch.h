@@ -160,5 +160,12 @@ extern "C" hipError_t rt_launch_merge_extents(const void *parts, uint32_t n_part
 // rt_wave_box.hip, built once: the box helper of rt_wavefront.hip (rt_wave_box.hpp) alone, one wave per entry (rt_debug_wave_box); pts = [n_waves][64][3],
 // use_masks = [n_waves], out = [n_waves][6]
 extern "C" hipError_t rt_launch_wave_box(const double *pts, const unsigned long long *use_masks, uint32_t n_waves, float *out, hipStream_t stream);
+// rt_sort_rays.hip, built once (the key is the order's definition, not a variant's): the bytes of work space n rays take (0 for n == 0); the
+// sort -- sorted and keys may be NULL, work holds at least rt_sort_rays_work_size(n) bytes, n > 0 --; planes x n records of elem_bytes (a
+// multiple of 4) gathered (dst[i] = src[perm[i]]) or scattered (dst[perm[i]] = src[i])
+extern "C" size_t rt_sort_rays_work_size(uint32_t n);
+extern "C" hipError_t rt_launch_sort_rays(const void *rays, uint32_t n, void *sorted, uint32_t *perm, uint32_t *keys, void *work, uint32_t max_grid, hipStream_t stream);
+extern "C" hipError_t rt_launch_permute(const uint32_t *perm, uint32_t n, const void *src, void *dst, uint32_t elem_bytes, uint32_t planes, int scatter, uint32_t max_grid,
+                                        hipStream_t stream);
 
 #endif

@@ -826,6 +826,66 @@ int rt_pick_paths(rt_ctx *ctx, const double cam[16], const uint32_t *xy, uint32_
                   rt_hit *segments_host /* [max_segments][n] or NULL iff 0 */, rt_path_end *ends_host, void *stream); /* blocks */
 
 /* ---------------------------------------------------------------------------------------------------
+ * Sorting rays: order caller-supplied rays on the device for culling (csrc/rt_sort_rays.hip)
+ *
+ * RT_FLAG_STREAM_CULL_RAYS culls per wave, and a wave is 64 consecutive rays of the caller's array: rays in an unrelated order make every
+ * wave stage nearly every chunk (above: 98.5 % staged for the shuffled frame).  A caller cannot produce a good order itself -- it depends
+ * on which chunk bounds a ray reaches -- so rt_sort_rays does, from the rays alone:
+ *     rt_sort_rays(rays -> sorted, perm); rt_permute(perm, t_max -> t_max', gather); <any ray query on sorted>; rt_permute(perm, result ->
+ *     result in the caller's order, scatter).
+ * The two calls take no scene state (ctx selects the device, the grid bound and the error conventions, as in rt_assemble_planes; every
+ * context kind), allocate nothing, read nothing back, and launch what n alone decides: with ms == NULL they only enqueue kernels and can
+ * be captured into a graph that stays valid for other rays of the same count.  They change nothing about any other call; per-ray results
+ * do not depend on a ray's neighbours, so the scattered result is bit for bit the result of the query on the caller's order.
+ *
+ * The key (csrc/rt_ray_sort_key.hpp is its definition; FP64, never contracted, the same in strict and RT_FLAG_FAST contexts):
+ *   class 0 = a ray the culled kernels can cull for (the predicate of RT_FLAG_STREAM_CULL_RAYS: finite, every |component| <= 1e100,
+ *   1e-7 < |d|^2 < inf), class 1 = every other ray: key 0x80000000, so those stand together at the end, in input order, and spoil at most
+ *   one mixed wave.  Class 0: key = mo << 18 | md.  mo = the 12-bit Morton code of the origin in a 16^3 grid over the box of the class-0
+ *   origins (q = clamp(floor((o - lo) / (hi - lo) * 16), 0, 15) per axis, 0 where hi == lo; -0.0 counts as +0.0); md = the 18-bit Morton
+ *   code of the direction in a 512^2 grid over the octahedral map of d / (|dx| + |dy| + |dz|) (where n.z < 0: (u, v) = ((1 - |n.y|)
+ *   sign(n.x), (1 - |n.x|) sign(n.y)), sign(0) = +1; q = clamp(floor((u / 2 + 1 / 2) * 512), 0, 511)).
+ * perm[i] = the index in dev_rays of the ray at place i: a STABLE sort by that key (equal keys keep their input order), deterministic --
+ * a radix sort whose only atomics are integer sums and the box's minima and maxima.  dev_sorted (may be NULL): sorted[i] = rays[perm[i]].
+ * dev_keys (may be NULL): the key of sorted[i], non-decreasing.
+ *
+ * Limits.  The key helps rays that share origins or directions (a camera's, a lens model's, a light's, bounce rays of one surface); rays
+ * with unrelated origins AND directions stay as they were (CPU proxy: 3 072 random probes aimed at random clusters, 0 of 240 (wave, chunk)
+ * pairs left unstaged before and after).  n up to 2^32 - 1; work space about 16.5 bytes per ray (rt_sort_rays_work_bytes).
+ *
+ * RT_ERR_INVALID, before a device is looked for: a NULL ctx / dev_rays / dev_perm / dev_work / dev_src / dev_dst; n == 0; rays or sorted
+ * rays that are not 16-byte aligned; perm, keys, src or dst that are not 4-byte aligned; work_bytes below rt_sort_rays_work_bytes(n); any
+ * overlap among the rays, the sorted rays, perm, keys and the work space; for rt_permute elem_bytes of 0, not a multiple of 4 or above
+ * 256, planes == 0, src or perm overlapping dst.
+ *
+ * Measured (one MI355X; the 1080p frame's own 2 073 600 primary rays, the four-flag context, strict; medians of five series of 31
+ * synchronised calls, us; tools/sort_rays_bench.py, profiles/sort_rays.txt), rt_trace_rays:
+ *   spheres  rays      unsorted   rt_sort_rays  sorted call  rt_permute  sum      sum / unsorted  staged [1]/[0]
+ *   10 000   shuffled  25 043.6   279.4         3 725.1      51.4        4 056.0  0.162           0.985 -> 0.113
+ *   10 000   row        4 160.3   224.2         3 701.7      37.0        3 962.8  0.953           0.120 -> 0.113
+ *   10 000   8x8 block  3 793.1   224.1         3 706.9      37.1        3 968.1  1.046           0.111 -> 0.112
+ *    1 685   shuffled   4 240.1   279.9         1 572.0      51.3        1 903.1  0.449           1.000 -> 0.290
+ *    1 685   row        1 498.8   225.7         1 572.1      37.0        1 834.9  1.224           0.300 -> 0.289
+ *       65   shuffled     189.5   280.1           190.8      51.0          521.9  2.754           0.500 -> 0.500
+ * rt_occluded_rays and rt_trace_paths follow rt_trace_rays (shuffled 0.16 - 0.17 x at 10 000 spheres, 0.44 x at 1 685); rt_shade_rays
+ * 42.4 -> 11.2 ms shuffled and 11.9 -> 10.6 ms in row order at 10 000 spheres.  So: sort rays that come in no spatial order; leave rays
+ * alone that a camera produced in scan-line or block order unless the scene has thousands of spheres; never at two chunks, where the sort
+ * costs more than the query.  The CPU proxy of DESIGN.md section 31 (a distance rule, not a measurement) had predicted 0.997 -> 0.199
+ * staged for shuffled rays at 10 000 spheres on a 128 x 96 frame.
+ * ------------------------------------------------------------------------------------------------- */
+/* bytes of device work space rt_sort_rays needs for n rays (0 for n == 0); non-decreasing in n */
+size_t rt_sort_rays_work_bytes(uint32_t n);
+/* ms as in rt_trace_rays (NULL: enqueue only, capturable) */
+int rt_sort_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_ray *dev_sorted, uint32_t *dev_perm, uint32_t *dev_keys,
+                 void *dev_work, size_t work_bytes, void *stream, float *ms);
+/* planes x n records of elem_bytes each (plane stride n * elem_bytes; 16-byte vectors where elem_bytes % 16 == 0 and both pointers allow):
+ *   scatter == 0: dst[p][i] = src[p][perm[i]]   (bring t_max into the sorted order)
+ *   scatter != 0: dst[p][perm[i]] = src[p][i]   (bring hits, flags, colours, path records back into the caller's order)
+ * perm must be a permutation of 0 .. n - 1 (rt_sort_rays' output): its entries are not checked. */
+int rt_permute(rt_ctx *ctx, const uint32_t *dev_perm, uint32_t n, const void *dev_src, void *dev_dst, uint32_t elem_bytes,
+               uint32_t planes, int scatter, void *stream, float *ms);
+
+/* ---------------------------------------------------------------------------------------------------
  * Scene updates: move objects and lights of a live context (csrc/rt_set_scene.hip)
  *
  * rt_create uploads the scene once; rt_set_scene rewrites it in stream order, without a new context: one kernel of one workgroup reads
