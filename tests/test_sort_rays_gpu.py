@@ -2,7 +2,10 @@
 csrc/rt_ray_sort_key.hpp compiled for the host (tests/tools/ray_sort_lab.py) and numpy's stable argsort, bit for bit; the results of the ray
 queries by way of sort, query and scatter are held to the direct call on the caller's order, bit for bit.  "Four flags" is RT_FLAG_STREAM |
 RT_FLAG_STREAM_QUERIES | RT_FLAG_STREAM_CULL | RT_FLAG_STREAM_CULL_RAYS.  T = the sort's tile (pairs per workgroup and pass), W = the tiles one
-scan workgroup covers in one step, both from the header's constants.  The host-side conditions are in tests/test_sort_rays_host.py."""
+scan workgroup covers in one step, both from the header's constants.  The host-side conditions are in tests/test_sort_rays_host.py.
+Sections 8 and 9 take every loop of the file past the cap of its grid (G workgroups: the tile loop two and three times, permute_kernel three
+trips and more, the scan with three levels) against a reference formed on the device, and the key to the values where one rounding decides
+the cell (SL.edge_rays; DESIGN.md section 8, "Past one grid trip")."""
 import functools
 import os
 import sys
@@ -374,3 +377,160 @@ def test_one_graph_of_sort_trace_and_scatter(pkg):
     finally:
         torch.cuda.synchronize()
         r.cleanup_update()
+
+
+# ---- 8. past one trip of the bounded grids -------------------------------------------------------------------------------------------------
+# Every kernel of csrc/rt_sort_rays.hip runs at most G workgroups and loops over the rest; G = 4 per CU, as tests/test_rays_gpu.py computes
+# it.  The sizes below are derived from G, never from a CU count.
+def cap():
+    import torch
+    return 4 * torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def big_sizes():
+    """T G + T + 1: G + 2 tiles, so workgroups 0 and 1 of histogram_kernel and scatter_kernel make two trips of their tile loop and the
+    others one; 8 G + 9 workgroups of 256 rays, so the per-ray kernels (box, keys, gather) make nine and eight trips; two scan levels.
+    2 T G + T + 1: 2 G + 2 tiles, three and two trips."""
+    return [T * cap() + T + 1, 2 * T * cap() + T + 1]
+
+
+def tiled_on_the_device(base, n):
+    """[n, 6] float64 on the device: the rays `base` tiled.  Every copy is the same rays, so the box is base's and the keys are
+    SL.keys(base) tiled: P keys are uploaded and tiled on the device as well (int64, as torch sorts them)."""
+    import torch
+    assert n >= len(base)
+    reps = -(-n // len(base))
+    d_base = to_device(base)
+    d_keys = torch.from_numpy(SL.keys(base).astype(np.int64)).to("cuda:0")
+    return d_base.repeat(reps, 1)[:n].contiguous(), d_keys.repeat(reps)[:n].contiguous()
+
+
+def check_big_sort(r, base, n, want_sorted, host_argsort=False):
+    """rt_sort_rays of n tiled rays against torch's own stable device sort of the tiled host keys; returns the wall seconds of the call."""
+    import time
+    import torch
+    d_rays, d_keys = tiled_on_the_device(base, n)
+    want_keys, want_perm = torch.sort(d_keys, stable=True)
+    if host_argsort:      # the torch reference itself, once, against numpy's stable argsort
+        k = np.tile(SL.keys(base), -(-n // len(base)))[:n]
+        assert np.array_equal(want_perm.cpu().numpy(), np.argsort(k, kind="stable")), "torch.sort(stable=True) is numpy's stable argsort"
+    b_sorted, b_perm, b_keys = (guarded(48 * n) if want_sorted else None), guarded(4 * n), guarded(4 * n)
+    need = r.sort_work_bytes(n)
+    b_work = guarded(need)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    r.sort_rays_into(d_rays.data_ptr(), n, b_sorted.data_ptr() if want_sorted else None, b_perm.data_ptr(), b_keys.data_ptr(), b_work.data_ptr(), need, timed=False)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    perm = b_perm[:4 * n].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    keys = b_keys[:4 * n].view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    assert torch.equal(keys, want_keys), (n, "keys", int((keys != want_keys).sum()))
+    assert torch.equal(perm, want_perm), (n, "perm", int((perm != want_perm).sum()))
+    assert guard_untouched(b_perm, 4 * n) and guard_untouched(b_keys, 4 * n) and guard_untouched(b_work, need), (n, "guard bands")
+    if want_sorted:
+        at = torch.arange(0, n, max(1, n // (1 << 16)), device="cuda:0")[:1 << 16]
+        got = b_sorted[:48 * n].view(torch.int64).reshape(n, 6)[at]
+        assert torch.equal(got, d_rays.view(torch.int64)[want_perm[at]]), (n, "sorted == rays[perm] on a strided sample")
+        assert guard_untouched(b_sorted, 48 * n), (n, "guard band of sorted")
+    return seconds
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_sizes_past_the_cap(any_ctx, which):
+    """big_sizes(): the tile loop of histogram_kernel and scatter_kernel iterates twice (which = 0) and three times (1) in the first
+    workgroups and once less in the rest, its trailing barrier and the re-zeroed LDS counts are needed; the per-ray loops make more than
+    eight trips.  The base is the "quarter odd" set (2 T + 1 rays, a quarter of them class 1), so every key recurs in every copy and a
+    stable order has to hold across tiles and trips.  Reference: torch's stable device sort of the tiled host keys, at the first size held
+    to numpy's stable argsort."""
+    n = big_sizes()[which]
+    G = cap()
+    tiles = -(-n // T)
+    assert n % 2 == 1 and tiles == (which + 1) * G + 2 and -(-tiles // G) == which + 2 and tiles // G == which + 1
+    assert W < 256 * tiles <= W * W      # the table of 256 x tiles entries takes two scan levels
+    base = SL.adversarial("quarter odd")
+    assert (T * G) % len(base) != 0      # (a copy does not start where a trip does)
+    seconds = check_big_sort(any_ctx, base, n, want_sorted=True, host_argsort=which == 0)
+    print(f"rt_sort_rays of {n} rays ({tiles} tiles, cap {G}): {seconds:.3f} s")
+
+
+def test_three_scan_levels(any_ctx):
+    """16 384 T + 1 rays = 16 385 tiles: the digit-major table has 16 385 x 256 entries = 2 049 scan chunks, which is more than one chunk of
+    sums -- the first size at which the levelled scan has three levels (reduce_chunks_kernel twice, scan_chunks_kernel three times per pass,
+    the middle level with a partial second chunk).  The tile loop makes ceil(16 385 / G) trips and the scan's chunk loop ceil(2 049 / G).
+    sorted = NULL (the rays alone are 1.6 GB); the host uploads the 2 T + 1 base rays and keys, everything else is formed on the device."""
+    n = 16384 * T + 1
+    assert -(-n // T) == 16385
+    chunk = W      # RS_SCAN_CHUNK: the entries of the digit-major table one scan workgroup covers in one step
+    level0 = 16385 * 256
+    level1 = -(-level0 // chunk)
+    assert level1 == 2049 > chunk and -(-level1 // chunk) == 2      # three levels: 4 194 560 -> 2 049 -> 2
+    seconds = check_big_sort(any_ctx, SL.adversarial("quarter odd"), n, want_sorted=False)
+    print(f"rt_sort_rays of {n} rays (16385 tiles, three scan levels, cap {cap()}): {seconds:.3f} s")
+
+
+@pytest.mark.parametrize("elem", (4, 8, 16, 48))
+def test_permute_past_the_cap(any_ctx, elem):
+    """n = 2 x 256 G + 257 records: permute_kernel's grid is capped at G workgroups of 256 lanes and one lane moves one 4-byte or 16-byte
+    element, so its loop makes three trips for 4-byte records (2 G + 2 workgroups of work: workgroups 0 and 1 three, the others two), about
+    2 per x that many for records of `per` elements, the last one partial.  Gather == numpy's fancy indexing, gather then scatter == the
+    identity, guard bands untouched, planes 1 and 3; 48-byte records also on pointers that only allow words (per = 12, > 24 trips)."""
+    import torch
+    r, G = any_ctx, cap()
+    n = 2 * 256 * G + 257
+    assert -(-n // 256) == 2 * G + 2 and n % 64 != 0
+    rng = np.random.default_rng(700 + elem)
+    perm = rng.permutation(n).astype(np.uint32)
+    d_perm = torch.from_numpy(perm.view(np.int32)).to("cuda:0")
+    pool = rng.integers(0, 256, 3 * n * elem + 4, dtype=np.uint8)
+    for planes in (1, 3):
+        src = pool[:planes * n * elem].reshape(planes, n, elem)
+        nbytes = src.size
+        d_src = torch.from_numpy(src).to("cuda:0")
+        mid, back = guarded(nbytes), guarded(nbytes)
+        torch.cuda.synchronize()
+        r.permute_into(d_perm.data_ptr(), n, d_src.data_ptr(), mid.data_ptr(), elem, planes=planes)
+        r.permute_into(d_perm.data_ptr(), n, mid.data_ptr(), back.data_ptr(), elem, planes=planes, scatter=True, timed=False)
+        torch.cuda.synchronize()
+        assert np.array_equal(mid[:nbytes].cpu().numpy().reshape(planes, n, elem), src[:, perm]), (elem, planes, "gather is numpy's fancy indexing")
+        assert torch.equal(back[:nbytes], d_src.reshape(-1)), (elem, planes, "gather then scatter")
+        assert guard_untouched(mid, nbytes) and guard_untouched(back, nbytes), (elem, planes)
+    if elem == 48:      # the uint32_t path with per = 12
+        src = pool[4:4 + 48 * n].reshape(n, 48)
+        d_src, out = guarded(48 * n + 4), guarded(48 * n + 4)
+        d_src[4:4 + 48 * n] = torch.from_numpy(src.reshape(-1)).to("cuda:0")
+        torch.cuda.synchronize()
+        r.permute_into(d_perm.data_ptr(), n, d_src.data_ptr() + 4, out.data_ptr() + 4, 48)
+        torch.cuda.synchronize()
+        assert np.array_equal(out[4:4 + 48 * n].cpu().numpy().reshape(n, 48), src[perm]) and guard_untouched(out, 48 * n + 4) and (out[:4] == FILL).all().item()
+
+
+def test_the_sort_keywords_past_the_cap(pkg):
+    """r.trace(o, d, sort=True) and r.shade(o, d, sort=True) on the four-flag statistics scene for 2 x 256 G + 613 shuffled tiled rays:
+    rt_sort_rays (per-ray loops: workgroups 0 .. 2 three trips, the others two; 2 G / 8 + 1 tiles), the culled kernel (three and two
+    trips, the last workgroup with a full wave, a wave of 37 rays and two waves without a ray) and the scatter of rt_permute (48-byte and
+    16-byte records), in one chain: the bytes are the unsorted call's."""
+    G = cap()
+    n = 2 * 256 * G + 613
+    assert n > 2 * 256 * G + 256 and n % 64 == 37
+    rays = SL.tiled_shuffled(n, 43)
+    o, d = rays["o"], rays["d"]
+    r = pkg.Renderer(BL.bounce_scene(pkg), device=0, flags=four(pkg))
+    try:
+        assert r.stream_cull_rays
+        a, b = r.trace(o, d), r.trace(o, d, sort=True)
+        assert a.dtype == b.dtype and a.shape == b.shape == (n,) and a.tobytes() == b.tobytes() and (a["object"] >= 0).any() and (a["object"] < 0).any()
+        a, b = r.shade(o, d), r.shade(o, d, sort=True)
+        assert a.dtype == b.dtype and a.shape == b.shape == (n, 4) and a.tobytes() == b.tobytes()
+    finally:
+        r.cleanup_update()
+
+
+# ---- 9. the key where one rounding decides the cell -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("seed", [3, 4])
+def test_edge_values(any_ctx, seed):
+    """SL.edge_rays: origins one representable value around every sixteenth of a box with an axis from 0.0, one 2e-300 wide and one of
+    sub-normal width, directions one value around the cell boundaries of the octahedral map, the clamp, the fold at n.z == +-0.0.  The
+    device's key (FP64 division, floor, no contraction on gfx950) is the header's compiled for the host, bit for bit."""
+    rays = SL.edge_rays(2 * T + 1, seed)
+    assert SL.class0(rays).all()
+    check_sort(any_ctx, rays, ("edge values", seed))

@@ -1,6 +1,6 @@
 """rt_sort_rays and rt_permute (csrc/rt_sort_rays.hip), host side: the prototypes, what the entry points answer before
 they look for a device, the work-space size, the key of csrc/rt_ray_sort_key.hpp against its numpy restatement on every ray set of
-tests/test_sort_rays_gpu.py, the class rule, the device's sort as tests/tools/ray_sort_lab.cpp restates it against numpy's stable argsort
+tests/test_sort_rays_gpu.py (the edge values of ray_sort_lab.edge_rays among them, and that they are what they are said to be), the class rule, the device's sort as tests/tools/ray_sort_lab.cpp restates it against numpy's stable argsort
 (and, as a stand-alone program, under AddressSanitizer and UBSan), the build report's lines for the new kernels, and the condition that keeps
 the GPU test of the work words from being vacuous."""
 import ctypes as C
@@ -26,6 +26,7 @@ PROTOTYPES = (
     r"void \*dev_work, size_t work_bytes, void \*stream, float \*ms\);",
     r"int rt_permute\(rt_ctx \*ctx, const uint32_t \*dev_perm, uint32_t n, const void \*dev_src, void \*dev_dst, uint32_t elem_bytes,\s*"
     r"uint32_t planes, int scatter, void \*stream, float \*ms\);")
+EDGE_SEEDS = (3, 4)      # the seeds of tests/test_sort_rays_gpu.py::test_edge_values
 
 
 @functools.lru_cache(maxsize=None)
@@ -131,6 +132,8 @@ def ray_sets():
         yield name, SL.adversarial(name)
     for order in ("row", "block", "shuffled"):
         yield f"statistics scene, {order}", SL.stats_rays(order)
+    for seed in EDGE_SEEDS:
+        yield f"edge values, seed {seed}", SL.edge_rays(2 * SL.constants()["T"] + 1, seed)
 
 
 def test_header_and_restatement_give_the_same_keys():
@@ -146,9 +149,36 @@ def test_header_and_restatement_give_the_same_keys():
         if ok.any():
             assert np.array_equal(lo, (rays["o"][ok] + 0.0).min(axis=0)) and np.array_equal(hi, (rays["o"][ok] + 0.0).max(axis=0)), what
         count += 1
-    assert count == 9 + 9 + 3
+    assert count == 9 + 9 + 3 + len(EDGE_SEEDS)
     c = SL.constants()
     assert 3 * c["origin_bits"] + 2 * c["dir_bits"] == 30 and c["class1"] == 0x80000000
+
+
+def test_the_edge_values_are_what_they_are_said_to_be():
+    """SL.edge_rays: every ray of class 0 (so every key is computed), the box SL.EDGE_BOX with both corners present, -0.0 among the origins,
+    the sixty fixed directions, and a set that does not collapse into a few cells: more than n / 2 distinct keys, more than 1 000 of the
+    4 096 origin cells.  Every origin coordinate is at most one representable value off a sixteenth of its axis, every direction's
+    octahedral coordinates at most a few off a 512th."""
+    SL = lab()
+    c = SL.constants()
+    n = 2 * c["T"] + 1
+    for seed in EDGE_SEEDS:
+        rays = SL.edge_rays(n, seed)
+        assert len(rays) == n and SL.class0(rays).all()
+        k = SL.keys(rays)
+        assert (k < (1 << 30)).all() and len(np.unique(k)) > n // 2 and len(np.unique(k >> (2 * c["dir_bits"]))) > 1000, (seed, len(np.unique(k)))
+        lo, hi = SL.box(rays)
+        assert np.array_equal(lo, SL.EDGE_BOX[0]) and np.array_equal(hi, SL.EDGE_BOX[1]) and lo[0] == 0.0 and abs((hi[1] - lo[1]) / 2e-300 - 1.0) < 1e-15
+        assert 0.0 < hi[2] - lo[2] < 2.3e-308 and (hi[2] - lo[2]) / 5e-324 % 16 == 0      # a sub-normal width, whole sixteenths of it representable
+        assert np.array_equal(rays["o"][0], lo) and np.array_equal(rays["o"][1], hi)
+        assert np.signbit(rays["o"][:, 0]).any() and not (rays["o"][:, 0] < 0.0).any()      # -0.0
+        assert np.array_equal(rays["d"][:60:6], np.array(SL.EDGE_FIXED)) and np.signbit(rays["d"][42, 2]) and np.signbit(rays["d"][48, 0])
+        assert k[0] >> (2 * c["dir_bits"]) == 0 and k[1] >> (2 * c["dir_bits"]) == (1 << (3 * c["origin_bits"])) - 1      # the corners' cells
+        with np.errstate(all="ignore"):
+            sixteenths = (rays["o"] - lo) / (hi - lo) * 16.0
+            steps = (rays["o"][:, 2] - lo[2]) / 5e-324      # on the sub-normal axis a sixteenth is seven representable values
+        assert (np.abs(sixteenths - np.round(sixteenths))[:, :2] < 1e-9).all() and (np.abs(steps - 7.0 * np.round(steps / 7.0)) <= 1.0).all()
+        assert len(np.unique(SL.keys(rays[60:]) & ((1 << (2 * c["dir_bits"])) - 1))) > 1000      # ... nor do the directions
 
 
 def test_the_adversarial_sets_are_what_their_names_say():

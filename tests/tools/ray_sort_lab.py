@@ -199,6 +199,47 @@ def tiled_shuffled(n, seed=31):
     return np.ascontiguousarray(r[idx])
 
 
+EDGE_BOX = (np.array([0.0, 1e-300, -48 * 5e-324]), np.array([3.0, 3e-300, 64 * 5e-324]))      # an axis from 0.0, one 2e-300 wide, one 112 sub-normal steps wide
+EDGE_FIXED = ([1.0, 0.0, 0.0], [-1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, -1.0, 0.0], [0.0, 0.0, 1.0], [0.0, 0.0, -1.0],
+              [0.3, -0.2, 0.0], [0.3, -0.2, -0.0], [-0.0, 0.0, -1.0], [3.2e-4, 0.0, 0.0])
+
+
+def _ulp_moved(x, move):
+    """x one representable value down, where it is, or one up (move = -1, 0, +1 per element)."""
+    return np.where(move < 0, np.nextafter(x, -np.inf), np.where(move > 0, np.nextafter(x, np.inf), x))
+
+
+def edge_rays(n, seed):
+    """n class-0 rays at the values where one rounding decides the key's cell (csrc/rt_ray_sort_key.hpp claims host and device agree there).
+    Origins: every coordinate on lo + (hi - lo) k / 16 of EDGE_BOX, k in 0 .. 16, one value down, as it is or one up, clipped to the box;
+    rays 0 and 1 are the two corners; -0.0 stands among the zeroes of the axis that starts at 0.0.  Directions: the octahedral
+    coordinates (a / 256 - 1, b / 256 - 1), a, b in 0 .. 512 -- the cell boundaries of the direction's 512 x 512 grid -- unfolded (to the
+    lower hemisphere where |u| + |v| > 1), scaled by 10^U(-3, 90), every component moved as the origins' are; the first sixty rows have the
+    directions of EDGE_FIXED instead, six each: the axes (u or v * 0.5 + 0.5 == 1.0, the clamp), n.z == +-0.0 against the fold, |d|^2 just
+    above 1e-7."""
+    rng = np.random.default_rng(seed)
+    lo, hi = EDGE_BOX
+    r = np.zeros(n, dtype=RAY_DTYPE)
+    k = rng.integers(0, 17, (n, 3))
+    k[0], k[1] = 0, 16
+    move = rng.integers(-1, 2, (n, 3))
+    move[:2] = 0
+    with np.errstate(under="ignore"):
+        o = np.clip(_ulp_moved(lo + (hi - lo) * k / 16.0, move), lo, hi)
+    o[:, 0] = np.where((k[:, 0] == 0) & (move[:, 0] < 0), -0.0, o[:, 0])
+    r["o"] = o
+    a, b = rng.integers(0, 513, n), rng.integers(0, 513, n)
+    u, v = a / 256.0 - 1.0, b / 256.0 - 1.0
+    z = 1.0 - np.abs(u) - np.abs(v)
+    x = np.where(z < 0.0, (1.0 - np.abs(v)) * np.where(u < 0.0, -1.0, 1.0), u)
+    y = np.where(z < 0.0, (1.0 - np.abs(u)) * np.where(v < 0.0, -1.0, 1.0), v)
+    d = np.stack([x, y, z], axis=1) * (10.0 ** rng.uniform(-3.0, 90.0, n))[:, None]
+    r["d"] = _ulp_moved(d, rng.integers(-1, 2, (n, 3)))
+    fixed = np.repeat(np.array(EDGE_FIXED), 6, axis=0)
+    r["d"][:len(fixed)] = fixed[:n]
+    return r
+
+
 ADVERSARIAL = ("all equal", "two alternating", "top digit", "lowest digit", "sorted", "reversed", "one origin", "quarter odd", "all odd")
 
 
