@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256) void classify_kernel(const float4 *__restrict_
     if (refine) list[base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = (lr << 16) | x;
 }
 
-// One rt_hit record as gbuffer_kernel's coordinate-list mode writes it (rt_gbuffer.hip, GbRecord): the halo rows' object and normal
+// One rt_hit record as gbuffer_kernel's coordinate-list mode writes it (rt_pixel_kernels.hpp: pk_gbuffer; rt_rayquery.hpp: RqRecord): the halo rows' object and normal
 struct GeoHalo {
     double t, p[3];
     float n[3];

@@ -28,7 +28,7 @@
 // the launchers a context calls per floating-point contraction mode (rt_launch.h, struct Kernels); rt_create picks one from RT_FLAG_FAST
 #define RT_KERNELS(V)                                                                                                                              \
     {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
-     RT_CAT(rt_launch_gbuffer_edges, V), RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
+     RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
      RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
      RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
      RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
@@ -953,12 +953,11 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             // the primary-hit object (and, for a finite min_cos, normal) of this rank's rows and of the halo rows: gbuffer_kernel itself, which
             // reads no frame state and books no rays; then the classifier with the geometric term
             float *nrm = ctx->min_cos == -INFINITY ? nullptr : ctx->d_geo_nrm.p;
-            if (ctx->stream_adaptive) { // gbuffer_stream_kernel in its two modes, as rt_render_gbuffer / rt_pick launch it: two nodes with several ranks
-                RT_HIP(ctx->kern->stream_gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, stream));
-                RT_HIP(ctx->kern->stream_pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
-            } else {
-                RT_HIP(ctx->kern->gbuffer_edges(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nrm, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
-            }
+            // (the kernel in its two modes, as rt_render_gbuffer / rt_pick launch it: two nodes with several ranks -- the launchers skip an empty grid --;
+            // so the adaptive frame's edges are the ones those two report, in the FAST build too)
+            const Kernels *k = ctx->kern;
+            RT_HIP((ctx->stream_adaptive ? k->stream_gbuffer : k->gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, stream));
+            RT_HIP((ctx->stream_adaptive ? k->stream_pick : k->pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
             RT_HIP(rt_launch_classify_geometry_strict(fb, ctx->d_halo, ctx->d_geo_obj, nrm, ctx->d_geo_halo, ctx->width, ctx->height, ctx->local_rows,
                                                       ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau, ctx->min_cos, dest, out8, ctx->d_list,
                                                       ctx->d_list + px, stream));

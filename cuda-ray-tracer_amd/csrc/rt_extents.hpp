@@ -1,7 +1,8 @@
 // rt_extents.hpp -- what the two object-extents kernels share (rt_gbuffer.hip: extents_kernel, the class tables staged in LDS;
-// rt_stream_queries.hip: extents_stream_kernel, the tables streamed): the record as the kernels update it, the merge, the reduction of a
-// wave's 8 x 8 block into the output records, and what a launcher derives from the caller's rectangle.  Included behind rt_shade.hpp (global_row) by files that
-// are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
+// rt_stream_queries.hip: extents_stream_kernel, the tables streamed) besides their body (rt_pixel_kernels.hpp: pk_extents): the record
+// as the kernels update it, its identity and the kernel that writes it, the merge, the reduction of a wave's 8 x 8 block into the
+// accumulators or the output records, and what a launcher derives from the caller's rectangle.  Included behind rt_shade.hpp
+// (global_row) by files that are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
 #ifndef RT_EXTENTS_HPP
 #define RT_EXTENTS_HPP
 
@@ -20,6 +21,18 @@ struct ExtRecord {
 };
 static_assert(sizeof(ExtRecord) == 40, "rt_object_extent layout");
 #define RT_EXT_INF_BITS 0x7FF0000000000000ull
+
+// the record of an object no pixel shows: the identity of ext_merge
+__device__ __forceinline__ ExtRecord ext_identity() { return ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull}; }
+
+// The kernel that sets the n output records to the identity, one record per thread, 256-thread workgroups.  Written once; each of the
+// two files defines it under the name its launcher and the build's resource report use.
+#define EXT_INIT_KERNEL(name)                                                                      \
+    __global__ __launch_bounds__(256) void name(ExtRecord *__restrict__ out, uint32_t n)           \
+    {                                                                                              \
+        const uint32_t i = blockIdx.x * 256u + threadIdx.x;                                        \
+        if (i < n) out[i] = ext_identity();                                                        \
+    }
 
 // what the launcher derives from the rectangle: its columns, this rank's LOCAL rows inside it, and the tiles that meet both
 struct ExtArgs {
@@ -45,11 +58,10 @@ __device__ __forceinline__ void ext_merge(ExtRecord *r, unsigned long long n, ui
 
 // One wave, one 8 x 8 block whose first column is bx and first local row blr: the lanes in `counted` hit object `best` at best_t.  One
 // turn per distinct object among them (wave-uniform): count = popcount of their ballot, the box from the ballot's rows and columns, t by
-// a butterfly; lane 0 merges that into `out` itself.  Every lane of the wave must call.  (extents_kernel keeps its own copy of this
-// loop, with the LDS accumulators in front of `out`: as a call of this function its machine code came out different from what it was --
-// four commuted operands -- and the kernels that exist are kept as they are, to the instruction.)
+// a butterfly; lane 0 merges that into the workgroup's accumulators in LDS (acc != NULL, launch-uniform: one record per object, which
+// the workgroup adds to `out` at its end) or into `out` itself.  Every lane of the wave must call.
 __device__ __forceinline__ void ext_reduce_wave(const FrameArgs &fa, uint32_t bx, uint32_t blr, uint32_t lane, bool counted, int best, double best_t,
-                                                ExtRecord *__restrict__ out)
+                                                ExtRecord *__restrict__ out, ExtRecord *acc)
 {
     const unsigned long long tb = (unsigned long long) __double_as_longlong(best_t);
     unsigned long long todo = __ballot(counted);
@@ -73,7 +85,8 @@ __device__ __forceinline__ void ext_reduce_wave(const FrameArgs &fa, uint32_t bx
             const uint32_t y_min = global_row(fa, blr + ((uint32_t) __builtin_ctzll(mask) >> 3)); // (global_row rises with the local row)
             const uint32_t y_max = global_row(fa, blr + ((63u - (uint32_t) __builtin_clzll(mask)) >> 3));
             const unsigned long long n = (unsigned long long) __builtin_popcountll(mask);
-            ext_merge<__HIP_MEMORY_SCOPE_AGENT>(out + id, n, x_min, y_min, x_max, y_max, lo, hi);
+            if (acc) ext_merge<__HIP_MEMORY_SCOPE_WORKGROUP>(acc + id, n, x_min, y_min, x_max, y_max, lo, hi);
+            else ext_merge<__HIP_MEMORY_SCOPE_AGENT>(out + id, n, x_min, y_min, x_max, y_max, lo, hi);
         }
     }
 }

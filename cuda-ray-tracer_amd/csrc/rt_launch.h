@@ -41,14 +41,12 @@ RT_PER_VARIANT(hipError_t, rt_launch_classify, const void *p, const void *halo, 
 RT_PER_VARIANT(hipError_t, rt_launch_classify_geometry, const void *p, const void *halo, const int32_t *obj, const float *nrm, const void *ghalo, uint32_t width,
                uint32_t height, uint32_t local_rows, uint32_t band_rows, uint32_t world, uint32_t rank, float tau, float min_cos, void *out, int rgba8,
                uint32_t *list, uint32_t *count, hipStream_t stream)
-// rt_gbuffer.hip: primary-hit G-buffer, picking, and the G pass of an RT_FLAG_SSAA_GEOMETRY frame
+// rt_gbuffer.hip: primary-hit G-buffer and picking (the two together: the G pass of an RT_FLAG_SSAA_GEOMETRY frame)
 RT_PER_VARIANT(size_t, rt_gbuffer_lds_bytes, const FrameArgs *fa)
 RT_PER_VARIANT(hipError_t, rt_launch_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
                float *out_normal, hipStream_t stream)
 RT_PER_VARIANT(hipError_t, rt_launch_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
                hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_gbuffer_edges, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object,
-               float *out_normal, const uint32_t *halo_xy, uint32_t n_halo, void *halo_rec, hipStream_t stream)
 // ... and the object extents: the same rays reduced per object instead of stored (rect = x0, y0, x1, y1 inclusive, validated by the caller)
 RT_PER_VARIANT(int, rt_extents_lds_accumulators, size_t table_bytes, uint32_t n_obj)
 RT_PER_VARIANT(size_t, rt_extents_lds_bytes, const FrameArgs *fa)
@@ -121,7 +119,6 @@ struct Kernels {
     decltype(&rt_launch_ray_list_strict) ray_list;
     decltype(&rt_launch_gbuffer_strict) gbuffer;
     decltype(&rt_launch_pick_strict) pick;
-    decltype(&rt_launch_gbuffer_edges_strict) gbuffer_edges;
     decltype(&rt_launch_trace_rays_strict) trace_rays;
     decltype(&rt_launch_occluded_rays_strict) occluded_rays;
     decltype(&rt_launch_shade_rays_strict) shade_rays;

@@ -223,14 +223,6 @@ static inline PathArgs rk_path_args(const FrameArgs *fa, uint32_t n, uint32_t ma
     return pa;
 }
 
-// Launch `kernel` -- a parenthesised instantiation that names its first two template arguments GQ and CUB -- for the scene's classes
-// (rt_rayquery.hpp: rq_for_classes), 256 threads per workgroup.  (A macro: a kernel template cannot be handed to a function.)
-#define RK_LAUNCH(fa, kernel, g, lds, stream, ...)                                    \
-    rq_for_classes(fa, [&](auto gq, auto cub) {                                       \
-        constexpr bool GQ = decltype(gq)::value, CUB = decltype(cub)::value;          \
-        hipLaunchKernelGGL(kernel, g, dim3(256), lds, stream, __VA_ARGS__);           \
-    })
-
 } // namespace RT_SYM(rtk)
 
 #endif

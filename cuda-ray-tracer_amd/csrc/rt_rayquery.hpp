@@ -1,7 +1,9 @@
 // rt_rayquery.hpp -- what the kernels for caller-supplied rays share (rt_rays.hip: closest hit and occlusion; rt_shade_rays.hip: the
 // reference's colour; rt_paths.hip: the bounces): the scene-layout argument words, the class tables in LDS, the object loops for one ray
 // per lane -- through the tables where they are proven, through the dense expansion elsewhere; as a query object for the kernels' bodies
-// (rt_ray_kernels.hpp): RqStaged -- and the 48-byte ray / record layouts of include/mi355rt.h.
+// (rt_ray_kernels.hpp): RqStaged -- and the 48-byte ray / record layouts of include/mi355rt.h.  The pixel queries (rt_gbuffer.hip; their
+// bodies: rt_pixel_kernels.hpp) run the same object loop from the frame's origin, with the block's cone and the host's degree-3 records
+// switched on (rq_tables<..., PRIMARY = true>); their query object over the tables in LDS is RqPixels.
 // Included by files that are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
 #ifndef RT_RAYQUERY_HPP
 #define RT_RAYQUERY_HPP
@@ -42,6 +44,54 @@ __device__ __forceinline__ bool rq_tables_proven(const D3 &o, const D3 &d)
            fabs(d.y) <= RQ_PLAIN_ABOVE && fabs(d.z) <= RQ_PLAIN_ABOVE;
 }
 
+// The ray's monomials (rt_wavefront_math.hpp) for one object loop; NEED_CROSS: the scene holds a class that reads the cross terms
+template <bool NEED_CROSS>
+__device__ __forceinline__ Mono rq_mono(const D3 &o, const D3 &d)
+{
+    Mono m;
+    mono_set_o<NEED_CROSS>(m, o);
+    mono_set_d<NEED_CROSS>(m, d);
+    mono_set_od<NEED_CROSS>(m);
+    return m;
+}
+
+// A wave's cone for the culling of primary rays against the unit spheres: on = false culls nothing.
+struct SqCone {
+    bool on;
+    D3 axis;
+    double cos_t;
+};
+
+__device__ __forceinline__ double sq_readlane(double v, int l)
+{
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
+    return __hiloint2double(hi, lo);
+}
+
+// the cone of a wave whose lanes are the pixels of one 8 x 8 block, all from one origin: the axis from the central lane 36, the
+// opening from the four corner lanes (the angle to the axis is quasi-convex on the image plane)
+__device__ __forceinline__ SqCone sq_block_cone(const D3 &d)
+{
+    SqCone c;
+    c.on = true;
+    c.axis = D3{sq_readlane(d.x, 36), sq_readlane(d.y, 36), sq_readlane(d.z, 36)};
+    const double ca = dot3(c.axis, d);
+    const double c0 = sq_readlane(ca, 0), c1 = sq_readlane(ca, 7), c2 = sq_readlane(ca, 56), c3 = sq_readlane(ca, 63);
+    const double m01 = c0 < c1 ? c0 : c1, m23 = c2 < c3 ? c2 : c3;
+    c.cos_t = m01 < m23 ? m01 : m23;
+    return c;
+}
+
+// The cone of a pixel query's wave (launch-uniform): the block's where the context culls and the lanes are the pixels of a block; for
+// unrelated pixels (picking) a cone that culls nothing, through the same loop -- planes and picks share their kernel, so a picked pixel
+// is the planes' entry in the FMA-contracted build too.  (sphere_in_cone: no cone wider than a half-space culls anything)
+__device__ __forceinline__ SqCone sq_pixel_cone(bool cull, bool block, const D3 &d)
+{
+    SqCone cone{cull, D3{0.0, 0.0, 1.0}, block ? 1.0 : -1.0};
+    if (cone.on && block) cone = sq_block_cone(d);
+    return cone;
+}
+
 // One candidate's root against the query's acceptance rule.  Closest hit: rtm::accept (t >= EPS, t < MAX_T, nearest, lowest index on a
 // tie).  Occlusion: t > EPS && t < t_max, both strict; a NaN on either side blocks nothing.
 template <bool OCCLUSION>
@@ -54,14 +104,19 @@ __device__ __forceinline__ void rq_take(double t, int k, double t_max, double &b
     }
 }
 
-// The object loops for one ray per lane, wave-uniform as the non-cone branch of the G-buffer's nearest_hit: t1 / t0 and the sign of
-// the discriminant first, the root and the division only in the lanes that need them (us_needs_solve / needs_solve say when the
-// reference's solver returns nothing that `t >= EPS`, hence `t > EPS`, can accept); planes take their one division; degree 3 goes
-// through the guarded Taylor test with the surface's data at the lane's own origin.  `use`: the lane has a ray whose answer comes from
-// the tables.  OCCLUSION: best = 1 once something blocks; the wave leaves as soon as no lane is left undecided.
-template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION>
+// The object loops for one ray per lane, wave-uniform: the reference's loop (src/update-cpu.cpp:50-56) over the class tables, as phase A
+// of the wavefront kernel runs it.  t1 / t0 and the sign of the discriminant first, the root and the division only in the lanes that
+// need them (us_needs_solve / needs_solve say when the reference's solver returns nothing that `t >= EPS`, hence `t > EPS`, can
+// accept); planes take their one division; degree 3 goes through the guarded Taylor test with the surface's data at the lane's own
+// origin.  `use`: the lane has a ray whose answer comes from the tables.  OCCLUSION: best = 1 once something blocks; the wave leaves as
+// soon as no lane is left undecided.
+// PRIMARY (the pixel queries: every ray starts at the frame's origin; off for everyone else, who then passes none of the last three
+// arguments): with cone.on the unit spheres are first culled against the wave's cone, one lane per sphere, and the wave sweeps only
+// the survivors; the first RT_CUB_AT_MAX degree-3 objects take their data at the origin from the host's records (prim:
+// FrameArgs::cub_rec, then FrameArgs::cub_abs), indexed by the wave-uniform table position.
+template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION, bool PRIMARY = false>
 __device__ __forceinline__ void rq_tables(const RayQueryArgs &qa, const RqTables &S, const DevObject *__restrict__ gobj, const Mono &m, bool use, double t_max,
-                                          double &best_t, int &best)
+                                          double &best_t, int &best, uint32_t lane = 0u, const SqCone &cone = SqCone{}, const double *prim = nullptr)
 {
 #define RQ_ALL_DECIDED() (OCCLUSION && __ballot(use && best == 0) == 0ull)
     const bool quad = fabs(m.u2) > EPS; // unit spheres share t2 = u2: one degree decision per ray
@@ -69,11 +124,27 @@ __device__ __forceinline__ void rq_tables(const RayQueryArgs &qa, const RqTables
     for (uint32_t base = 0; base < qa.n_us; base += 64) {
         const uint32_t end = (base + 64 < qa.n_us) ? base + 64 : qa.n_us;
         unsigned long long cand = 0;
+        if (PRIMARY && cone.on) {
+            bool rel = false;
+            if (base + lane < end) {
+                const UsEntry e = S.us[base + lane];
+                rel = sphere_in_cone(e.kx, e.ky, e.kz, e.r, e.inv_r, m.o, cone.axis, cone.cos_t);
+            }
+            unsigned long long it = __ballot(rel);
+            while (it) { // wave-uniform loop over the spheres that reach into the wave's cone
+                const int b = __builtin_ctzll(it);
+                it &= it - 1;
+                const UsEntry e = S.us[base + b];
+                const bool need = us_needs_solve(quad, four_t2, us_t1(e, m), us_t0(e, m));
+                cand |= need ? (1ull << b) : 0ull;
+            }
+        } else {
 #pragma unroll 4
-        for (uint32_t j = base; j < end; j++) {
-            const UsEntry e = S.us[j];
-            const bool need = us_needs_solve(quad, four_t2, us_t1(e, m), us_t0(e, m));
-            cand |= need ? (1ull << (j - base)) : 0ull;
+            for (uint32_t j = base; j < end; j++) {
+                const UsEntry e = S.us[j];
+                const bool need = us_needs_solve(quad, four_t2, us_t1(e, m), us_t0(e, m));
+                cand |= need ? (1ull << (j - base)) : 0ull;
+            }
         }
         if (!use) cand = 0;
         while (cand && !(OCCLUSION && best != 0)) { // per lane: the few spheres whose root must actually be computed
@@ -115,8 +186,16 @@ __device__ __forceinline__ void rq_tables(const RayQueryArgs &qa, const RqTables
             if (use && !(OCCLUSION && best != 0)) {
                 // the guarded Taylor test of the render kernels (rt_math.hpp: cubic_guarded, dense expansion where it refuses); the surface's
                 // data at the ray's origin is formed per lane: there is no host record for arbitrary origins
-                const CubicAt ca = cubic_at(gobj[k].c, m.o);
-                const CubicAbs ab = cubic_abs(gobj[k].c);
+                CubicAt ca;
+                CubicAbs ab;
+                if (PRIMARY && j < RT_CUB_AT_MAX) { // ... but for the frame's, as in rt_render
+                    const double *r = prim + j * RT_CUB_REC, *a = prim + RT_CUB_AT_MAX * RT_CUB_REC + j * 4u;
+                    ca = CubicAt{r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9]};
+                    ab = CubicAbs{a[0], a[1], a[2], a[3]};
+                } else {
+                    ca = cubic_at(gobj[k].c, m.o);
+                    ab = cubic_abs(gobj[k].c);
+                }
                 bool refused;
                 const double t = intersect_cubic_taylor<false>(gobj[k].c, ca, cubic_mag_origin(ab, m.o), m.o, m.d, OCCLUSION ? t_max : MAX_T, OCCLUSION, refused);
                 rq_take<OCCLUSION>(t, (int) k, t_max, best_t, best);
@@ -156,10 +235,7 @@ struct RqStaged {
     {
         constexpr bool NEED_CROSS = HAS_GQ || HAS_CUBIC;
         const bool proven = rq_tables_proven(o, d);
-        Mono m;
-        mono_set_o<NEED_CROSS>(m, o);
-        mono_set_d<NEED_CROSS>(m, d);
-        mono_set_od<NEED_CROSS>(m);
+        const Mono m = rq_mono<NEED_CROSS>(o, d);
         rq_tables<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, S, gobj, m, use && proven, t_max, best_t, best);
         if (__ballot(use && !proven) != 0ull) rq_plain<OCCLUSION>(qa, gobj, o, d, use && !proven, t_max, best_t, best);
     }
@@ -192,7 +268,7 @@ __device__ __forceinline__ RqTables rq_stage_tables(const RayQueryArgs &qa, cons
 }
 
 // the scene-layout words of a context's FrameArgs for n rays
-static inline RayQueryArgs rq_args(const FrameArgs *fa, uint32_t n)
+__host__ __device__ static inline RayQueryArgs rq_args(const FrameArgs *fa, uint32_t n)
 {
     RayQueryArgs qa;
     qa.n_obj = fa->n_obj; qa.n_us = fa->n_us; qa.n_gq = fa->n_gq; qa.n_lin = fa->n_lin; qa.n_cub = fa->n_cub;
@@ -201,6 +277,40 @@ static inline RayQueryArgs rq_args(const FrameArgs *fa, uint32_t n)
     qa.tab_bytes = fa->off_mat - fa->off_us;
     qa.n = n;
     return qa;
+}
+
+// The query object of the pixel kernels (rt_pixel_kernels.hpp) of a workgroup that holds all class tables in LDS: the nearest hit of
+// the primary ray (m: from the frame's origin) of every lane in `live`.  block: the wave's lanes are the pixels of one 8 x 8 block.
+// The pixel family has no plain path: its rays are the camera's.
+struct RqPixels {
+    const bool cull; // FrameArgs::cull
+    const RayQueryArgs qa;
+    const RqTables S;
+    const double *prim; // FrameArgs::cub_rec, then FrameArgs::cub_abs, in LDS
+    const DevObject *gobj;
+
+    template <bool HAS_GQ, bool HAS_CUBIC>
+    __device__ __forceinline__ void nearest(uint32_t lane, const Mono &m, bool live, bool block, double &best_t, int &best) const
+    {
+        best = -1;
+        best_t = INFINITY;
+        rq_tables<HAS_GQ, HAS_CUBIC, false, true>(qa, S, gobj, m, live, MAX_T, best_t, best, lane, sq_pixel_cone(cull, block, m.d), prim);
+    }
+};
+
+// LDS bytes of the host's degree-3 records behind the staged tables (a multiple of 16)
+constexpr uint32_t RQ_PRIM_BYTES = (uint32_t) sizeof(double) * (RT_CUB_REC + 4) * RT_CUB_AT_MAX;
+
+// RqPixels for this workgroup: rq_stage_tables, and behind the tables the host's records of the first RT_CUB_AT_MAX degree-3 objects at
+// the frame's origin (cub_rec[4][10], then cub_abs[4][4]: contiguous in FrameArgs).  Whatever else the caller wrote to LDS in front of
+// this call is visible behind it: it ends with rq_stage_tables' barrier.
+template <bool HAS_CUBIC>
+__device__ __forceinline__ RqPixels rq_stage_pixels(const FrameArgs &fa, const unsigned char *__restrict__ scene, unsigned char *smem)
+{
+    const RayQueryArgs qa = rq_args(&fa, 0u);
+    double *prim = reinterpret_cast<double *>(smem + qa.tab_bytes);
+    if (HAS_CUBIC && threadIdx.x < (RT_CUB_REC + 4) * RT_CUB_AT_MAX) prim[threadIdx.x] = (&fa.cub_rec[0][0])[threadIdx.x];
+    return RqPixels{fa.cull != 0u, qa, rq_stage_tables(qa, scene, smem), prim, reinterpret_cast<const DevObject *>(scene)};
 }
 
 // The launch ladder over the classes the scene of `fa` holds: calls launch(gq, cub) once, with std::true_type / std::false_type for
@@ -216,6 +326,14 @@ static inline void rq_for_classes(const FrameArgs *fa, Launch &&launch)
         else launch(std::false_type{}, std::false_type{});
     }
 }
+
+// Launch `kernel` -- a parenthesised instantiation that names its first two template arguments GQ and CUB -- for the scene's classes
+// (rq_for_classes), 256 threads per workgroup.  (A macro: a kernel template cannot be handed to a function.)
+#define RK_LAUNCH(fa, kernel, g, lds, stream, ...)                                    \
+    rq_for_classes(fa, [&](auto gq, auto cub) {                                       \
+        constexpr bool GQ = decltype(gq)::value, CUB = decltype(cub)::value;          \
+        hipLaunchKernelGGL(kernel, g, dim3(256), lds, stream, __VA_ARGS__);           \
+    })
 
 // the argument words of the colour kernels (rt_shade_rays.hip, rt_stream_queries.hip) and of the path kernels (rt_paths.hip, rt_stream_queries.hip)
 struct ShadeRaysArgs {

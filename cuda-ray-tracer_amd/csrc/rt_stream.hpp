@@ -4,47 +4,20 @@
 // for the same ray -- whatever the scene's size.  One ray per lane; the caller owns the whole wave (all 64 lanes call, `use` says which
 // of them have a ray).  Nothing here is workgroup-wide: no barrier, no shared state between waves, so the waves of a workgroup may run
 // any number of queries each.  Used by the streamed frame kernel (rt_stream.hip) and by the streamed query kernels
-// (rt_stream_queries.hip).
+// (rt_stream_queries.hip), the latter through the query objects at the end: SqQuery for caller-supplied rays, SqPixels for pixels.
 // Included by files that are compiled once per variant (-DRT_VARIANT=strict|fast); everything lives in that variant's namespace.
 #ifndef RT_STREAM_HPP
 #define RT_STREAM_HPP
 
 #include <hip/hip_runtime.h>
 
-#include "rt_rayquery.hpp" // RayQueryArgs, rq_take, rq_tables_proven, rq_plain
+#include "rt_rayquery.hpp" // RayQueryArgs, rq_take, rq_tables_proven, rq_plain, rq_mono, SqCone and the block's cone
 
 namespace RT_SYM(rtk) {
 
 constexpr uint32_t SQ_CHUNK = 64;                                    // entries per chunk: one per lane
 constexpr uint32_t SQ_SLICE_BYTES = SQ_CHUNK * (uint32_t) sizeof(GqEntry); // a wave's slice, sized for the largest entry kind
 static_assert(sizeof(GqEntry) >= sizeof(UsEntry) && sizeof(GqEntry) >= sizeof(LinEntry) && sizeof(GqEntry) >= sizeof(uint32_t), "slice size");
-
-// The block's cone for the culling of primary rays (rt_gbuffer.hip, nearest_hit): on = false culls nothing.
-struct SqCone {
-    bool on;
-    D3 axis;
-    double cos_t;
-};
-
-__device__ __forceinline__ double sq_readlane(double v, int l)
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
-// the cone of a wave whose lanes are the pixels of one 8 x 8 block, all from one origin: the axis from the central lane 36, the
-// opening from the four corner lanes (the angle to the axis is quasi-convex on the image plane)
-__device__ __forceinline__ SqCone sq_block_cone(const D3 &d)
-{
-    SqCone c;
-    c.on = true;
-    c.axis = D3{sq_readlane(d.x, 36), sq_readlane(d.y, 36), sq_readlane(d.z, 36)};
-    const double ca = dot3(c.axis, d);
-    const double c0 = sq_readlane(ca, 0), c1 = sq_readlane(ca, 7), c2 = sq_readlane(ca, 56), c3 = sq_readlane(ca, 63);
-    const double m01 = c0 < c1 ? c0 : c1, m23 = c2 < c3 ? c2 : c3;
-    c.cos_t = m01 < m23 ? m01 : m23;
-    return c;
-}
 
 // One chunk: lane j copies entry base + j of a table in global memory to the wave's slice (16-byte pieces; 4-byte ones for the index
 // list) and keeps it; lanes beyond the table's end keep zeroes and store nothing.  Behind the stores the wave-level LDS idiom of
@@ -91,7 +64,7 @@ __device__ __forceinline__ void sq_stage_indices(const uint32_t *__restrict__ ta
 // rq_tables with the tables streamed.  scene: the blob (DevObject records first, the tables from qa.off_us on); slice: SQ_SLICE_BYTES of
 // LDS that belong to this wave.  All control flow around the staging is wave-uniform; `use` stays a predicate.  cone.on (primary rays
 // of a block, wave-uniform): the lane that loaded a sphere tests it against the block's cone, and the wave sweeps only the survivors.
-// HOST_CUB (rays from the frame's origin: the G-buffer family, rt_gbuffer.hip: nearest_hit): the first RT_CUB_AT_MAX degree-3 objects
+// HOST_CUB (rays from the frame's origin: the pixel family, as rq_tables' PRIMARY): the first RT_CUB_AT_MAX degree-3 objects
 // take their data at the origin from the host's records in `frame` (cub_rec, cub_abs), indexed by the wave-uniform table position --
 // kernel arguments, read by scalar loads, nothing in LDS.
 template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION, bool HOST_CUB = false>
@@ -211,10 +184,7 @@ __device__ __forceinline__ void sq_query(const RayQueryArgs &qa, const unsigned 
 {
     constexpr bool NEED_CROSS = HAS_GQ || HAS_CUBIC;
     const bool proven = rq_tables_proven(o, d);
-    Mono m;
-    mono_set_o<NEED_CROSS>(m, o);
-    mono_set_d<NEED_CROSS>(m, d);
-    mono_set_od<NEED_CROSS>(m);
+    const Mono m = rq_mono<NEED_CROSS>(o, d);
     const unsigned long long plain = __ballot(use && !proven);
     SqCone cone{false, D3{0.0, 0.0, 1.0}, 1.0};
     if (block_cone && plain == 0ull) cone = sq_block_cone(d); // (wave-uniform)
@@ -233,6 +203,24 @@ struct SqQuery {
     __device__ __forceinline__ void query(uint32_t lane, const D3 &o, const D3 &d, bool use, double t_max, double &best_t, int &best) const
     {
         sq_query<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, slice, lane, o, d, use, false, t_max, best_t, best);
+    }
+};
+
+// The query object of the pixel kernels (rt_pixel_kernels.hpp) of a wave that streams the tables (RqPixels of rt_rayquery.hpp, with
+// the tables streamed): the nearest hit of the primary ray (m: from the frame's origin) of every lane in `live`, the cone as there, the
+// host's degree-3 records from the kernel's own arguments.  The pixel family has no plain path: sq_tables directly, not sq_query.
+struct SqPixels {
+    const FrameArgs &fa; // (fa, qa: the kernel's own arguments)
+    const RayQueryArgs &qa;
+    const unsigned char *scene;
+    unsigned char *slice; // SQ_SLICE_BYTES of LDS that belong to this wave
+
+    template <bool HAS_GQ, bool HAS_CUBIC>
+    __device__ __forceinline__ void nearest(uint32_t lane, const Mono &m, bool live, bool block, double &best_t, int &best) const
+    {
+        best = -1;
+        best_t = INFINITY;
+        sq_tables<HAS_GQ, HAS_CUBIC, false, true>(qa, scene, slice, lane, m, live, sq_pixel_cone(fa.cull != 0u, block, m.d), MAX_T, best_t, best, &fa);
     }
 };
 

@@ -5,14 +5,15 @@
 // rt_shade_rays.hip, rt_paths.hip) and differs from it in one thing: the object loops read the tables from the scene blob in global
 // memory through a wave-private LDS slice, 64 entries at a time (rt_stream.hpp), as the streamed frame kernel does (rt_stream.hip).  The
 // chunks are the staged loops' chunks and a chunk's body is theirs, so in a strict context a streamed kernel returns what its twin
-// returns, bit for bit.  Rays, work geometry, loads, stores and launch bounds are the twin's.
+// returns, bit for bit.  Rays, work geometry, loads, stores and launch bounds are the twin's: the twins share their bodies (rt_ray_kernels.hpp,
+// DESIGN.md section 30; rt_pixel_kernels.hpp, section 32).
 // Compiled twice like rt_stream.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).
 // There is no workgroup barrier anywhere in this file, and no lane leaves before its wave's last ballot, readlane or staged chunk: a
 // lane without work stays with `use = false`.  Every kernel takes 4 * SQ_SLICE_BYTES = 24 KiB of LDS whatever the tables hold.
 #include <hip/hip_runtime.h>
 #include "rt_launch.h"   // the launchers below, as the host sees them
-#include "rt_ray_kernels.hpp" // the ray, colour and path kernels' bodies; SqQuery and the streamed object loops (rt_stream.hpp); RayQueryArgs, the ray and record layouts (rt_rayquery.hpp)
-#include "rt_extents.hpp" // the extent record, its merge and the wave reduction
+#include "rt_ray_kernels.hpp" // the ray, colour and path kernels' bodies; SqQuery, SqPixels and the streamed object loops (rt_stream.hpp); RayQueryArgs, the ray and record layouts (rt_rayquery.hpp)
+#include "rt_pixel_kernels.hpp" // the pixel kernels' bodies; the extent record and its init kernel (rt_extents.hpp)
 
 namespace RT_SYM(rtk) {
 
@@ -115,33 +116,8 @@ __global__ __launch_bounds__(256) void path_query_stream_kernel(const PathArgs p
 }
 
 // ---- pixels: the G-buffer, picking, object extents (rt_gbuffer.hip) --------------------------------------------------------------------------
-// nearest_hit with the tables streamed.  The G-buffer family has no plain path, and this one has none either: sq_tables directly, not
-// sq_query.  The cone is nearest_hit's: the block's where the context culls and the wave is a block; for unrelated pixels (picking) a
-// cone that culls nothing, through the same loop -- planes and picks share the kernel, so a picked pixel is the planes' entry in the
-// FMA-contracted build too.  The first RT_CUB_AT_MAX degree-3 objects take the host's records at the frame's origin.
-template <bool HAS_GQ, bool HAS_CUBIC>
-__device__ __forceinline__ void sqk_nearest_hit(const FrameArgs &fa, const RayQueryArgs &qa, const unsigned char *__restrict__ scene, unsigned char *slice, uint32_t lane,
-                                                const Mono &m, bool live, bool block, double &best_t, int &best)
-{
-    best = -1;
-    best_t = INFINITY;
-    SqCone cone{fa.cull != 0u, D3{0.0, 0.0, 1.0}, block ? 1.0 : -1.0}; // (sphere_in_cone: no cone wider than a half-space culls anything)
-    if (cone.on && block) cone = sq_block_cone(m.d);                     // launch-uniform
-    sq_tables<HAS_GQ, HAS_CUBIC, false, true>(qa, scene, slice, lane, m, live, cone, MAX_T, best_t, best, &fa);
-}
-
-template <bool NEED_CROSS>
-__device__ __forceinline__ Mono sqk_mono(const D3 &o, const D3 &dir)
-{
-    Mono m;
-    mono_set_o<NEED_CROSS>(m, o);
-    mono_set_d<NEED_CROSS>(m, dir);
-    mono_set_od<NEED_CROSS>(m);
-    return m;
-}
-
-// gbuffer_kernel's two launch modes, work geometry and stores: planes (xy == NULL; one workgroup per 16 x 16 tile, one wave per 8 x 8
-// block, lanes outside the image trace a clamped pixel's ray and store nothing) and picking (one lane per query, no cone).
+// The twins' bodies (rt_pixel_kernels.hpp) over SqPixels (rt_stream.hpp): sq_tables itself, without a plain path, as the staged family
+// has none.  extents_stream_kernel has no accumulators in LDS: every wave merges into `out` itself.
 template <bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void gbuffer_stream_kernel(const FrameArgs fa, const RayQueryArgs qa, const unsigned char *__restrict__ scene,
                                                              const double *__restrict__ camx, const double *__restrict__ camy, int32_t *__restrict__ out_object,
@@ -149,93 +125,19 @@ __global__ __launch_bounds__(256) void gbuffer_stream_kernel(const FrameArgs fa,
                                                              uint32_t n_query, RqRecord *__restrict__ out_rec)
 {
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
-    const DevObject *gobj = reinterpret_cast<const DevObject *>(scene);
-
-    const bool pick = xy != nullptr; // launch-uniform
-    uint32_t col, row, lr = 0, x = 0; // camera-table indices: pixel column, GLOBAL image row
-    bool live;
-    if (pick) {
-        const uint32_t q = blockIdx.x * 256u + tid;
-        live = q < n_query;
-        col = live ? xy[2u * q] : 0u; // (validated by the host: col < width, row < height)
-        row = live ? xy[2u * q + 1u] : 0u;
-    } else {
-        const uint32_t tile_x = blockIdx.x % fa.tiles_x, tile_y = blockIdx.x / fa.tiles_x;
-        x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
-        lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
-        live = x < fa.width && lr < fa.local_rows;
-        col = x < fa.width ? x : fa.width - 1u;
-        row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
-    }
-    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
-    const D3 dir = primary_dir_tab(fa, camx[col], camy[row]);
-    const Mono m = sqk_mono<HAS_GQ || HAS_CUBIC>(o, dir);
-    double best_t;
-    int best;
-    sqk_nearest_hit<HAS_GQ, HAS_CUBIC>(fa, qa, scene, slice, lane, m, live, !pick, best_t, best);
-    // (behind the last wave-wide operation) primary_hit's record: object = -1, t = +inf, point = normal = 0 on a miss
-    RqRecord r{INFINITY, {0.0, 0.0, 0.0}, {0.0f, 0.0f, 0.0f}, -1};
-    if (live && best >= 0) {
-        r.object = best;
-        r.t = best_t;
-        const D3 p{o.x + best_t * dir.x, o.y + best_t * dir.y, o.z + best_t * dir.z};
-        r.p[0] = p.x; r.p[1] = p.y; r.p[2] = p.z;
-        const DevObject *bo = &gobj[best]; // per-lane index: a gather from global memory, per hit
-        D3 n;
-        if (bo->cls & RT_CLS_UNITSQ) { // the pixel family's own normal: three coefficients instead of twenty (sphere_normal)
-            UsEntry e{};
-            e.kx = bo->c[K_X];
-            e.ky = bo->c[K_Y];
-            e.kz = bo->c[K_Z];
-            n = sphere_normal(e, p);
-        } else {
-            n = normal_vector(bo->c, p);
-        }
-        r.n[0] = (float) n.x; r.n[1] = (float) n.y; r.n[2] = (float) n.z;
-    }
-    if (live && pick) {
-        out_rec[blockIdx.x * 256u + tid] = r;
-    } else if (live) {
-        const size_t at = (size_t) lr * fa.width + x;
-        if (out_object) out_object[at] = r.object;
-        if (out_t) out_t[at] = r.t;
-        if (out_normal) out_normal[at] = make_float4(r.n[0], r.n[1], r.n[2], 0.0f);
-    }
+    SqPixels q{fa, qa, scene, smem + (threadIdx.x >> 6) * SQ_SLICE_BYTES};
+    pk_gbuffer<HAS_GQ, HAS_CUBIC>(fa, scene, camx, camy, out_object, out_t, out_normal, xy, n_query, out_rec, q);
 }
 
-__global__ __launch_bounds__(256) void extents_init_stream_kernel(ExtRecord *__restrict__ out, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) out[i] = ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull};
-}
+EXT_INIT_KERNEL(extents_init_stream_kernel)
 
-// extents_kernel without accumulators in LDS: the wave reduces the lanes of each distinct object and lane 0 merges into `out` itself.
 template <bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void extents_stream_kernel(const FrameArgs fa, const RayQueryArgs qa, const ExtArgs ea, const unsigned char *__restrict__ scene,
                                                              const double *__restrict__ camx, const double *__restrict__ camy, ExtRecord *__restrict__ out)
 {
     __shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];
-    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
-    unsigned char *slice = smem + wave * SQ_SLICE_BYTES;
-    const D3 o{fa.origin[0], fa.origin[1], fa.origin[2]};
-
-    for (uint32_t tile = blockIdx.x; tile < ea.n_tiles; tile += gridDim.x) { // workgroup-uniform
-        const uint32_t tile_x = ea.tx0 + tile % ea.ntx, tile_y = ea.ty0 + tile / ea.ntx;
-        const uint32_t bx = tile_x * 16u + (wave & 1u) * 8u, blr = tile_y * 16u + (wave >> 1) * 8u; // the block's first column and local row
-        const uint32_t x = bx + (lane & 7u), lr = blr + (lane >> 3);
-        const bool live = x < fa.width && lr < fa.local_rows;
-        const uint32_t col = x < fa.width ? x : fa.width - 1u;
-        const uint32_t row = global_row(fa, lr < fa.local_rows ? lr : fa.local_rows - 1u);
-        const D3 dir = primary_dir_tab(fa, camx[col], camy[row]);
-        const Mono m = sqk_mono<HAS_GQ || HAS_CUBIC>(o, dir);
-        double best_t;
-        int best;
-        sqk_nearest_hit<HAS_GQ, HAS_CUBIC>(fa, qa, scene, slice, lane, m, live, true, best_t, best);
-        const bool counted = live && best >= 0 && x >= ea.x0 && x <= ea.x1 && lr >= ea.lr0 && lr <= ea.lr1;
-        ext_reduce_wave(fa, bx, blr, lane, counted, best, best_t, out);
-    }
+    SqPixels q{fa, qa, scene, smem + (threadIdx.x >> 6) * SQ_SLICE_BYTES};
+    pk_extents<HAS_GQ, HAS_CUBIC>(fa, ea, camx, camy, out, nullptr, q);
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------

@@ -97,7 +97,7 @@ def test_build_report_lists_the_new_kernels_without_spills():
 
 
 def test_the_kernel_file_has_no_workgroup_barrier_and_no_dynamic_lds():
-    for name in ("rt_stream_queries.hip", "rt_stream_shade.hpp", "rt_ray_kernels.hpp"):   # ... the shared loop of the colour kernel and the ray kernels' bodies included
+    for name in ("rt_stream_queries.hip", "rt_stream_shade.hpp", "rt_ray_kernels.hpp", "rt_pixel_kernels.hpp"):   # ... the shared loop of the colour kernel and the kernels' bodies included
         text = open(os.path.join(CSRC, name)).read()
         code = "\n".join(l.split("//")[0] for l in text.splitlines())
         assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code and '"workgroup"' not in code, name
@@ -106,19 +106,26 @@ def test_the_kernel_file_has_no_workgroup_barrier_and_no_dynamic_lds():
     text = open(os.path.join(CSRC, "rt_stream_queries.hip")).read()
     code = "\n".join(l.split("//")[0] for l in text.splitlines())
     assert code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 5
-    # the pixel family goes through sq_tables itself (no plain path), the ray families through sq_query: the ray-query and the colour kernel
-    # through their bodies (rt_ray_kernels.hpp) over the one query object that calls it, without a cone (SqQuery, next to sq_query in
+    # the pixel family goes through sq_tables itself (no plain path) -- in its one query object, SqPixels, next to the loop in rt_stream.hpp, with
+    # the cone of the staged twin (sq_pixel_cone) and the host's degree-3 records (HOST_CUB) --, the ray families through sq_query: the ray-query
+    # and the colour kernel through their bodies (rt_ray_kernels.hpp) over the one query object that calls it, without a cone (SqQuery, next to sq_query in
     # rt_stream.hpp: 1), the path kernel, which keeps its body's text, itself (1); the frame kernels' policy over
     # sq_query keeps its two calls (rt_stream_shade.hpp)
-    assert "sq_tables<HAS_GQ, HAS_CUBIC, false, true>" in code and code.count("sq_query<") == 1
+    assert "sq_tables" not in code and "sq_query<" not in code.split("void gbuffer_stream_kernel(")[1] and code.count("sq_query<") == 1
+    assert len(re.findall(r"SqPixels q\{fa, qa, scene, smem \+ \(threadIdx\.x >> 6\) \* SQ_SLICE_BYTES\};", code.split("void gbuffer_stream_kernel(")[1])) == 2      # the wave's own slice
     assert "sq_query<HAS_GQ, HAS_CUBIC, false>(qa, scene, slice, lane, o, d, bouncing, false, MAX_T, best_t, best);" in code.split("void path_query_stream_kernel")[1].split("// ---- pixels")[0]
     shade = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, "rt_stream_shade.hpp")).read().splitlines())
     assert shade.count("sq_query<") == 2
     stream = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, "rt_stream.hpp")).read().splitlines())
     assert stream.count("sq_query<") == 1
     assert "sq_query<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, scene, slice, lane, o, d, use, false, t_max, best_t, best);" in stream.split("struct SqQuery {")[1].split("\n};\n")[0]
+    pixels = stream.split("struct SqPixels {")[1].split("\n};\n")[0]
+    assert "sq_tables<HAS_GQ, HAS_CUBIC, false, true>(qa, scene, slice, lane, m, live, sq_pixel_cone(fa.cull != 0u, block, m.d), MAX_T, best_t, best, &fa);" in pixels
+    assert "sq_query" not in pixels and "rq_plain" not in pixels and stream.count("sq_tables<HAS_GQ, HAS_CUBIC, false, true>") == 1
     bodies = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, "rt_ray_kernels.hpp")).read().splitlines())
     assert "sq_query" not in bodies and "sq_tables" not in bodies
+    pixel_bodies = "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, "rt_pixel_kernels.hpp")).read().splitlines())
+    assert "sq_query" not in pixel_bodies and "sq_tables" not in pixel_bodies and "rq_tables" not in pixel_bodies
     assert len(re.findall(r"SqQuery q\{(qa|sa\.qa|pa\.qa), scene, smem \+ \(threadIdx\.x >> 6\) \* SQ_SLICE_BYTES\};", code)) == 2      # the wave's own slice
     colour = code.split("void shade_rays_stream_kernel")[1].split("void path_query_stream_kernel")[0]
     assert "SqQuery q{sa.qa, scene, smem + (threadIdx.x >> 6) * SQ_SLICE_BYTES};" in colour

@@ -3,6 +3,8 @@ the loop's text exists once, every kernel that shades a ray runs it under a poli
 So do the bodies of the kernels for caller-supplied rays (csrc/rt_ray_kernels.hpp): the staged, the streamed and the
 culled kernel of each query run one body over a query object, and what was written out per family -- the ray loads, the grid rule, the
 records, the path loop, the shading policy -- is in one file.
+And so do the bodies of the pixel queries (csrc/rt_pixel_kernels.hpp): the staged and the streamed kernel of the
+G-buffer / picking and of the object extents run one body over a pixel query object, and each table path has one object loop.
 One kernel is the stated exception: stream_cull_bounce_frame_kernel holds the loop's text itself, because through the shared loop its
 strict <true, true> instantiation needs 258 registers and loses its second wave per SIMD (profiles/stream_shared_loop.txt)."""
 import glob
@@ -16,6 +18,7 @@ MARKER = "the reflection loop, src/update-cpu.cpp:96-117"
 LOOP = "rt_stream_shade.hpp"
 KEEPS_ITS_COPY = "rt_stream_cull_bounce.hip"
 BODIES = "rt_ray_kernels.hpp"
+PIXEL_BODIES = "rt_pixel_kernels.hpp"
 # file -> (kernel or body, its policy): the sites that run the shared loop.  The three shade_rays kernels are one site: their body
 SITES = {
     BODIES: ("rk_shade_rays", "RkShade<Query>"),
@@ -24,10 +27,15 @@ SITES = {
     "rt_stream_cull.hip": ("stream_cull_frame_kernel", "ScShade"),
     "rt_stream_cull_adaptive.hip": ("ray_list_cull_kernel", "ScaShade"),
 }
-STREAMED = sorted(glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", "rt_shade.hpp", "rt_rayquery.hpp", "rt_adaptive.hip", BODIES)])
+STREAMED = sorted(glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", "rt_shade.hpp", "rt_rayquery.hpp", "rt_adaptive.hip", "rt_gbuffer.hip", BODIES, PIXEL_BODIES)])
 # One of the nine kernels for caller-supplied rays keeps the text of its body, as stream_cull_bounce_frame_kernel keeps the loop's:
 # through rk_path_query path_query_stream_kernel took 4 to 5 % longer on every series measured (profiles/ray_kernel_bodies.txt)
 PATHS_KEEPS_ITS_COPY = ("rt_stream_queries.hip", "path_query_stream_kernel")
+# the four pixel kernels: file -> ({kernel: the body it runs}, the query object it builds)
+PIXEL_KERNELS = {
+    "rt_gbuffer.hip": ({"gbuffer_kernel": "pk_gbuffer", "extents_kernel": "pk_extents"}, r"RqPixels q = rq_stage_pixels<HAS_CUBIC>\(fa, scene, smem\);"),
+    "rt_stream_queries.hip": ({"gbuffer_stream_kernel": "pk_gbuffer", "extents_stream_kernel": "pk_extents"}, r"SqPixels q\{fa, qa, scene, smem \+ \(threadIdx\.x >> 6\) \* SQ_SLICE_BYTES\};"),
+}
 # the other eight: file -> {kernel: the body it runs}
 RAY_KERNELS = {
     "rt_rays.hip": {"ray_query_kernel": "rk_ray_query"}, "rt_shade_rays.hip": {"shade_rays_kernel": "rk_shade_rays"}, "rt_paths.hip": {"path_query_kernel": "rk_path_query"},
@@ -126,8 +134,9 @@ def test_the_helpers_around_the_loop_exist_once():
     found = {what: sorted(os.path.basename(p) for p in STREAMED for _ in re.findall(rx, "\n".join(l.split("//")[0] for l in open(p).read().splitlines())))
              for what, rx in defs.items()}
     assert found["quantise"] == ["rt_shade.hpp"] and found["xor_add"] == ["rt_shade.hpp"], found
-    # (gbuffer_stream_kernel maps pixels too, with picking beside it, and so do the two classify kernels of rt_adaptive.hip: other kernels)
-    assert found["pixel mapping"] == ["rt_adaptive.hip", "rt_adaptive.hip", "rt_stream_queries.hip", "rt_stream_shell.hpp"], found
+    # (the pixel queries map pixels too -- once, for the staged and the streamed kernels and for both bodies: pk_block_pixel --, and so do the
+    # two classify kernels of rt_adaptive.hip: other kernels)
+    assert found["pixel mapping"] == ["rt_adaptive.hip", "rt_adaptive.hip", PIXEL_BODIES, "rt_stream_shell.hpp"], found
     assert found["frame store"] == ["rt_stream_shell.hpp"], found
     # (ray_list_kernel, the twin over all records in LDS, keeps its own items: it counts, and skips by `live`)
     assert found["halo item"] == ["rt_adaptive.hip", "rt_stream_shell.hpp"] and found["resolve scale"] == ["rt_adaptive.hip", "rt_stream_shell.hpp"], found
@@ -136,15 +145,17 @@ def test_the_helpers_around_the_loop_exist_once():
     for name in ("rt_stream_cull.hip", "rt_stream_cull_bounce.hip", "rt_stream_cull_adaptive.hip"):
         code = code_of(name)
         assert "sc_flush(st.w, ca.stats, lane" in code and "atomicAdd" not in code, name
-    # (the ray kernels' files and rt_stream_queries.hip's pixel family through the one macro over it, RK_LAUNCH)
-    macro = read(BODIES).split("#define RK_LAUNCH(fa, kernel, g, lds, stream, ...)")[1].split("\n\n")[0]
+    # (the ray kernels' files and the pixel family's two through the one macro over it, RK_LAUNCH, next to it in rt_rayquery.hpp)
+    assert sorted(os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*")) if "#define RK_LAUNCH" in open(p).read()) == ["rt_rayquery.hpp"]
+    macro = read("rt_rayquery.hpp").split("#define RK_LAUNCH(fa, kernel, g, lds, stream, ...)")[1].split("\n\n")[0]
     assert "rq_for_classes(fa, [&](auto gq, auto cub) {" in macro and "hipLaunchKernelGGL(kernel, g, dim3(256), lds, stream, __VA_ARGS__);" in macro
     assert "#define" not in read("rt_stream_queries.hip") and "#define" not in read("rt_stream_cull_rays.hip")      # (no launch macro of their own)
-    for name in list(SITES) + [KEEPS_ITS_COPY] + list(RAY_KERNELS):
+    for name in list(SITES) + [KEEPS_ITS_COPY] + list(RAY_KERNELS) + list(PIXEL_KERNELS):
         code = code_of(name)
-        if name in RAY_KERNELS:
-            assert len(re.findall(r"\bRK_LAUNCH\(fa, \(\w+<GQ, CUB[,>]", code)) >= len(RAY_KERNELS[name]) and "rq_for_classes" not in code, name
-        else:
+        if name in RAY_KERNELS or name in PIXEL_KERNELS:
+            want = len(RAY_KERNELS.get(name, ())) + len(PIXEL_KERNELS.get(name, ((),))[0])
+            assert len(re.findall(r"\bRK_LAUNCH\(fa, \(\w+<GQ, CUB[,>]", code)) >= want and "rq_for_classes" not in code, name
+        elif name != BODIES:      # (the bodies' file launches nothing: the macro's text, held above, moved next to rq_for_classes)
             assert "rq_for_classes(fa, [&](auto gq, auto cub)" in code, name
         assert not re.search(r"kernel<(true|false), (true|false)", code) and "if (fa->n_cub)" not in code, name
 
@@ -178,6 +189,77 @@ def test_the_ray_kernels_bodies_exist_once():
         assert sorted(n for n, code in everything.items() if word in code) == sorted([BODIES, PATHS_KEEPS_ITS_COPY[0]]), word
         assert everything[PATHS_KEEPS_ITS_COPY[0]].count(word) == everything[BODIES].count(word), word
     assert everything[BODIES].count("const double2 w0 = w[0], w1 = w[1], w2 = w[2];") == 1 and everything[BODIES].count("need < max_grid ?") == 1
+
+
+def test_the_pixel_kernels_bodies_exist_once():
+    """each of the four pixel kernels takes its LDS, builds its query object and calls its body exactly once, with no
+    loop of its own but the accumulator init and flush of extents_kernel; a pixel query object offers one call; the record assembly, the
+    sphere-normal special case, the block-cone formation, the extents wave reduction and the extents init kernel are written once under
+    csrc/; what the copies were called is gone."""
+    for name, (kernels, query) in PIXEL_KERNELS.items():
+        code = code_of(name)
+        for kernel, body_fn in kernels.items():
+            body = code.split(f"void {kernel}(")[1].split("\n}\n")[0]
+            assert len(re.findall(r"\bpk_\w+<", body)) == 1 and len(re.findall(rf"\b{body_fn}<HAS_GQ, HAS_CUBIC>\(", body)) == 1, (kernel, body)
+            assert len(re.findall(query, body)) == 1 and len(re.findall(r"\b(RqPixels|SqPixels) q\b", body)) == 1, kernel      # one query object, built here
+            loops = re.findall(r"for \([^\n]*", body)
+            assert "while (" not in body and "nearest" not in body and "rq_tables" not in body and "sq_tables" not in body, kernel
+            if kernel == "extents_kernel":      # the accumulators' identities and their flush, each with a barrier between it and the body
+                assert len(loops) == 2 and all(l.startswith("for (uint32_t i = threadIdx.x; i < fa.n_obj; i += 256u)") for l in loops), loops
+                at = [body.index(w) for w in ("rq_stage_pixels<", "acc[i] = ext_identity();", "__syncthreads();", "pk_extents<", "__syncthreads();\n        for (", "ext_merge<__HIP_MEMORY_SCOPE_AGENT>")]
+                assert at == sorted(at) and len(set(at)) == 6 and body.count("__syncthreads()") == 2, at
+            else:
+                assert not loops and "__syncthreads" not in body, kernel
+        assert len(re.findall(r"\bpk_(gbuffer|extents)<", code)) == len(kernels), name
+    bodies = code_of(PIXEL_BODIES)
+    for body_fn in ("pk_gbuffer", "pk_extents", "pk_block_pixel"):
+        assert len(re.findall(rf"\b{body_fn}\(const FrameArgs &fa", bodies)) == 1, body_fn
+    assert bodies.count("q.template nearest<HAS_GQ, HAS_CUBIC>(lane, m, ") == 2 and bodies.count("q.") == 2 and bodies.count("pk_block_pixel(fa, ") == 2
+    # a pixel query object offers one call, and each lives next to the loop it calls
+    for struct, name, loop in (("RqPixels", "rt_rayquery.hpp", "rq_tables<HAS_GQ, HAS_CUBIC, false, true>("), ("SqPixels", "rt_stream.hpp", "sq_tables<HAS_GQ, HAS_CUBIC, false, true>(")):
+        text = code_of(name).split(f"struct {struct} {{")[1].split("\n};\n")[0]
+        assert text.count("__device__") == 1 and "template <bool HAS_GQ, bool HAS_CUBIC>\n" in text, struct
+        assert "void nearest(uint32_t lane, const Mono &m, bool live, bool block, double &best_t, int &best) const" in text and text.count(loop) == 1, struct
+        assert "sq_pixel_cone(" in text and "rq_plain" not in text and "sq_query" not in text, struct
+        assert sorted(n for n in os.listdir(CSRC) if re.search(rf"\bstruct {struct}\b", code_of(n))) == [name], struct
+    # one object loop per table path: the staged one takes the cone and the host's records behind a switch that is off for everyone else
+    staged = code_of("rt_rayquery.hpp")
+    assert len(re.findall(r"void rq_tables\(", staged)) == 1 and "template <bool HAS_GQ, bool HAS_CUBIC, bool OCCLUSION, bool PRIMARY = false>\n__device__ __forceinline__ void rq_tables(" in staged
+    assert staged.count("if (PRIMARY && cone.on) {") == 1 and staged.count("if (PRIMARY && j < RT_CUB_AT_MAX) {") == 1 and staged.count("PRIMARY") == 3
+    assert len(re.findall(r"void sq_tables\(", code_of("rt_stream.hpp"))) == 1
+    everything = {n: code_of(n) for n in os.listdir(CSRC)}
+    users = {n: c.count("rq_tables<") for n, c in everything.items() if "rq_tables<" in c}
+    assert users == {"rt_rayquery.hpp": 2}, users      # RqStaged::query, without the switch, and RqPixels::nearest
+    assert "rq_tables<HAS_GQ, HAS_CUBIC, OCCLUSION>(qa, S, gobj, m, use && proven, t_max, best_t, best);" in staged
+    once = {"r.n[0] = (float) n.x; r.n[1] = (float) n.y; r.n[2] = (float) n.z;": PIXEL_BODIES,                      # the record assembly
+            "n = sphere_normal(e, p);": PIXEL_BODIES, "if (bo->cls & RT_CLS_UNITSQ) {": PIXEL_BODIES,                  # the sphere-normal special case
+            "out_rec[blockIdx.x * 256u + tid] = r;": PIXEL_BODIES, "out_normal[at] = make_float4(": PIXEL_BODIES,      # the stores
+            "sq_readlane(ca, 0), c1 = sq_readlane(ca, 7), c2 = sq_readlane(ca, 56), c3 = sq_readlane(ca, 63);": "rt_rayquery.hpp",      # the block-cone formation
+            "if (cone.on && block) cone = sq_block_cone(d);": "rt_rayquery.hpp", "SqCone sq_block_cone(": "rt_rayquery.hpp", "double sq_readlane(": "rt_rayquery.hpp",
+            "Mono rq_mono(": "rt_rayquery.hpp",                                                                        # the Mono set-up (below)
+            "void ext_reduce_wave(": "rt_extents.hpp", "const unsigned long long l2 = __shfl_xor(lo, s), h2 = __shfl_xor(hi, s);": "rt_extents.hpp",      # the wave reduction
+            "ExtRecord{0ull, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, RT_EXT_INF_BITS, 0ull}": "rt_extents.hpp",               # the identity, and the init kernel
+            "void name(ExtRecord *__restrict__ out, uint32_t n)": "rt_extents.hpp",
+            "(&fa.cub_rec[0][0])[threadIdx.x]": "rt_rayquery.hpp"}                                                       # the host's records behind the staged tables
+    for word, where in once.items():
+        assert sorted(n for n, c in everything.items() if word in c) == [where] and everything[where].count(word) == 1, word
+    for n in ("rt_rayquery.hpp", "rt_stream.hpp", "rt_gbuffer.hip", "rt_stream_queries.hip", BODIES, PIXEL_BODIES):      # (the frame kernels' own set-ups: not this family's)
+        assert everything[n].count("mono_set_od<NEED_CROSS>(m);") == (n == "rt_rayquery.hpp"), n
+    assert sorted(n for n, c in everything.items() if "EXT_INIT_KERNEL(" in c) == ["rt_extents.hpp", "rt_gbuffer.hip", "rt_stream_queries.hip"]
+    assert "EXT_INIT_KERNEL(extents_init_kernel)" in everything["rt_gbuffer.hip"] and "EXT_INIT_KERNEL(extents_init_stream_kernel)" in everything["rt_stream_queries.hip"]
+    assert sum(c.count("extents_init") for c in everything.values()) == 4      # (each file: the definition and its launch)
+    # the header has the standing of rt_ray_kernels.hpp: nothing workgroup-wide
+    for word in ("__syncthreads", "s_barrier", '"workgroup"', "rq_stage_tables", "rq_stage_pixels", "__shared__", "HIP_DYNAMIC_SHARED"):
+        assert word not in bodies, word
+    for gone in ("GbRecord", "GbHit", "GbTables", "gb_readlane", "sqk_mono", "sqk_nearest_hit", "nearest_hit", "primary_hit", "rt_launch_gbuffer_edges", "gbuffer_edges"):
+        for n in os.listdir(CSRC):
+            assert gone not in read(n), (gone, n)
+    # the G pass of an adaptive frame with the geometric term: the two launchers rt_render_gbuffer / rt_pick call, chosen by the context's one decision
+    capi = code_of("rt_capi.cpp")
+    g = capi.split("if (ctx->geometry) {")[1].split("RT_HIP(rt_launch_classify_geometry_strict(")[0]
+    assert "(ctx->stream_adaptive ? k->stream_gbuffer : k->gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, stream)" in g
+    assert "(ctx->stream_adaptive ? k->stream_pick : k->pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream)" in g
+    assert g.count("RT_HIP(") == 2
 
 
 def test_the_path_kernel_that_keeps_its_copy_is_the_bodys_text():

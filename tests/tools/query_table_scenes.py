@@ -1,7 +1,7 @@
 """Scenes, aimed rays and oracle-side conditions of the query kernels' table tests (tests/test_query_tables_host.py and
 tests/test_query_tables_gpu.py) -- test infrastructure.  The seven query entry points (rt_render_gbuffer, rt_pick, rt_object_extents,
 rt_trace_rays, rt_occluded_rays, rt_shade_rays, rt_trace_paths) copy the class tables into LDS and walk them 64 entries at a time
-(csrc/rt_gbuffer.hip: nearest_hit, csrc/rt_rayquery.hpp: rq_tables), so the scenes are the fields of tests/tools/stream_scenes.py with
+(csrc/rt_rayquery.hpp: rq_tables, for pixels and for rays), so the scenes are the fields of tests/tools/stream_scenes.py with
 a count next to a multiple of 64 or next to the 160 KiB limit, and the rays are AIMED: one per chosen table entry, so that a test reaches
 that entry on purpose, which the primary rays of a small frame cannot.
 

@@ -87,10 +87,12 @@ def main(parent, tree):
             same.append(base[:-2])
             continue
         differ.append(base[:-2])
-        ka, kb = kernels(os.path.join(parent, base), a), kernels(obj, b)
-        assert list(ka) == list(kb), base
+        # paired by kernel name and template arguments, not by the mangled name: that one also spells the parameters' types
+        ka = {demangled(name): k for name, k in kernels(os.path.join(parent, base), a).items()}
+        kb = {demangled(name): k for name, k in kernels(obj, b).items()}
+        assert sorted(ka) == sorted(kb), (base, sorted(set(ka) ^ set(kb)))
         for name in kb:
-            rows.append((base[:-2], demangled(name), ka[name], kb[name]))
+            rows.append((base[:-2], name, ka[name], kb[name]))
     print(f"byte-identical .text ({len(same)}): {' '.join(same)}")
     print(f"differ ({len(differ)}): {' '.join(differ)}")
     print()
