@@ -68,7 +68,10 @@ typedef struct rt_scene_desc {
                                  A near-tie is a decision (|t2| or |t1| against EPS, the discriminant's sign, a root against
                                  EPS, MAX_T or t_max, two objects' roots against each other) closer to its threshold than
                                  2^20 times its bound; only such rays may differ ("The FAST build against exact
-                                 arithmetic"; tests/test_fast_truth_gpu.py).  Degree 3: within the bars of the degree-3 tests */
+                                 arithmetic"; tests/test_fast_truth_gpu.py).  Degree 3, in this and in the strict build: the
+                                 same, with t within B3 + 1e-8 |t| of the exact root the reference's rule selects -- B3 the
+                                 first-order bound of the reference's own cubic solver, 1e-8 what cubic_guarded (csrc/rt_math.hpp)
+                                 allows itself -- and two objects' roots a near-tie also within 1e-8 of their sizes */
 #define RT_FLAG_COUNT 2u      /* also count rays / intersection tests on the device (slower; for accounting) */
 #define RT_FLAG_SIMPLE 4u     /* use the simple one-thread-per-pixel kernel (rt_kernels.hip) instead of the
                                  workgroup wavefront kernel (rt_wavefront.hip); same results, kept for A/B runs */

@@ -235,3 +235,61 @@ def test_device_special_functions_against_mpmath(pkg, oracle, lab):
         worst = int(np.argmax(err))
         print(f"{f}: {len(x)} distinct arguments, worst {err[worst]:.3f} ulp at {x[worst]!r} (device {y[worst]!r})")
         assert err.max() <= ULP_BOUND[f], (f, x[worst], y[worst], err[worst])
+
+
+# ---- the same lab in the RT_FLAG_FAST variant's flags (-ffp-contract=fast) ------------------------------------------------------------------
+FAST_KEYS = ["clebsch", "dingdong", "many_cubic"]
+FAST_DENSE_SAMPLE = 600   # refused records per scene whose contracted dense root is held to exact arithmetic (some 2 ms each on the host)
+
+
+@pytest.mark.parametrize("key", FAST_KEYS)
+def test_degree3_rays_on_the_device_in_the_fast_variants_flags(pkg, oracle, lab, key):
+    """cubic_at, cubic_coefs, cubic_guarded and the dense fall-back as the compiler contracts them for the FAST kernels.  Where the guard
+    answers, the strict run's assertions: no decision differs from the oracle's, accepted roots within CUB_TOL.  Where it refuses, the
+    contracted dense root is held to exact arithmetic within B3 on decided pairs (tests/tools/fast_ref.py) -- the bit-for-bit comparison
+    under the device's libm stays with the strict build.  The refused shares of both builds are printed side by side."""
+    import fast_ref as F
+    strict = _run(pkg, oracle, lab, key)
+    osc, cam, _, _ = _scene(pkg, oracle, key)
+    rays, where = D.enumerate_rays(osc, cam)
+    out = D.device_rays(D.lib(pkg, "fast"), osc.coefs, rays)
+    out_strict = D.device_rays(lab, osc.coefs, rays)
+    t_ref, _, _ = D.oracle_rays(osc, rays)
+    refused = out["refused"] != 0
+    answered = ~refused
+    decide = (rays["flags"] & D.LAB_DECIDE) != 0
+    max_t = rays["max_t"]
+    differ = int((out["t_dense"].view(np.uint64) != out_strict["t_dense"].view(np.uint64)).sum())
+    assert differ > 0, "this build of the lab is not contracted: it says nothing about the FAST variant"
+    assert np.array_equal(out["guard_ok"] != 0, answered)
+    with np.errstate(invalid="ignore"):
+        acc = np.where(decide, (out["t"] > EPS) & (out["t"] < max_t), (out["t"] >= EPS) & (out["t"] < max_t))
+        acc_ref = np.where(decide, (t_ref > EPS) & (t_ref < max_t), (t_ref >= EPS) & (t_ref < max_t))
+        decision_diff = answered & (acc != acc_ref)
+        assert not decision_diff.any(), f"{key}: {int(decision_diff.sum())} decisions differ from the oracle's; first record {int(np.flatnonzero(decision_diff)[0])}"
+        used = answered & ~decide & acc_ref
+        rel = np.abs(out["t"][used] - t_ref[used]) / np.abs(t_ref[used])
+        worst_rel = float(rel.max()) if rel.size else 0.0
+        assert worst_rel <= CUB_TOL, f"{key}: an accepted root is {worst_rel:.3g} relative off the oracle's"
+    # the contracted dense path where the guard refused, against exact arithmetic
+    coefs = np.ascontiguousarray(osc.coefs, dtype=np.float64).reshape(-1, 20)
+    idx = np.flatnonzero(refused)
+    idx = idx[:: max(1, len(idx) // FAST_DENSE_SAMPLE)]
+    judged, worst_rho = 0, 0.0
+    import mpmath
+    for k in np.unique(rays["obj"][idx]).tolist():
+        sel = idx[rays["obj"][idx] == k]
+        pr = F.pairs(coefs[k:k + 1], rays["o"][sel], rays["d"][sel])
+        for j, i in enumerate(sel.tolist()):
+            if not pr["ok"][j, 0]:
+                continue
+            te = F.exact_t(coefs[k], rays["o"][i], rays["d"][i])
+            rho = float(abs(mpmath.mpf(float(out["t_dense"][i])) - te) / mpmath.mpf(float(pr["B"][j, 0])))
+            judged, worst_rho = judged + 1, max(worst_rho, rho)
+            assert rho <= 1.0, (f"{key}: record {i} (object {k}, o {rays['o'][i].tolist()}, d {rays['d'][i].tolist()}): contracted dense t {float(out['t_dense'][i])!r}, "
+                                f"exact {mpmath.nstr(te, 25)}, B3 {pr['B'][j, 0]:.3e}, rho {rho:.3g}")
+    assert np.array_equal(out["t"][refused].view(np.uint64), out["t_dense"][refused].view(np.uint64))
+    print(f"{key}: tests {len(rays)}; refused strict {strict['refused']} ({100.0 * strict['refused'] / len(rays):.3f} %), FAST flags {int(refused.sum())} "
+          f"({100.0 * refused.sum() / len(rays):.3f} %); dense roots that differ in bits between the builds {differ}; decision diffs 0, worst answered root "
+          f"{worst_rel:.2e}; {judged} of {len(idx)} sampled refused records decided, worst rho {worst_rho:.3g}")
+    assert judged > 0 or not len(idx)

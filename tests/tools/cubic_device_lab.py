@@ -51,34 +51,35 @@ def devflags():
     return r.stdout.split()
 
 
-def build(force=False):
-    """Compile the lab for gfx950 with the strict kernels' flags into tests/tools/bin (on demand, like cubic_guard_lab.build)."""
-    if force or not os.path.exists(SO) or any(os.path.getmtime(d) > os.path.getmtime(SO) for d in DEPS):
-        os.makedirs(os.path.dirname(SO), exist_ok=True)
+def build(force=False, contract="off"):
+    """Compile the lab for gfx950 with the strict kernels' flags (contract "off") or the RT_FLAG_FAST variant's ("fast") into
+    tests/tools/bin (on demand, like cubic_guard_lab.build)."""
+    so = SO if contract == "off" else SO.replace(".so", f"_{contract}.so")
+    if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in DEPS):
+        os.makedirs(os.path.dirname(so), exist_ok=True)
         hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-        tmp = SO + ".tmp"
-        subprocess.run([hipcc] + devflags() + ["-ffp-contract=off", "-shared", "-I" + HERE, SRC, "-o", tmp], check=True)
-        os.replace(tmp, SO)
-    return SO
+        tmp = so + ".tmp"
+        subprocess.run([hipcc] + devflags() + ["-ffp-contract=" + contract, "-shared", "-I" + HERE, SRC, "-o", tmp], check=True)
+        os.replace(tmp, so)
+    return so
 
 
-_LIB = None
+_LIB = {}
 
 
-def lib(pkg):
+def lib(pkg, contract="off"):
     """The lab, loaded after pkg.lib() (which loads torch's HIP runtime first: a second runtime in the process would see no device)."""
-    global _LIB
-    if _LIB is None:
+    if contract not in _LIB:
         pkg.lib()
-        L = C.CDLL(build())
+        L = C.CDLL(build(contract=contract))
         vp = C.c_void_p
         L.lab_libm.argtypes = [C.c_int, vp, C.c_uint64, vp]
         L.lab_rays.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp]
         L.lab_guard.argtypes = [vp, C.c_uint64, vp]
         for f in (L.lab_libm, L.lab_rays, L.lab_guard):
             f.restype = C.c_int
-        _LIB = L
-    return _LIB
+        _LIB[contract] = L
+    return _LIB[contract]
 
 
 def _check(status, what):
