@@ -10,27 +10,16 @@
 #include <hip/hip_runtime.h>
 #include "rt_launch.h" // the launchers below, as the host sees them
 #include "rt_shade.hpp"
+#include "rt_ray_list.hpp"       // the ray-list kernels' items, resolve and launch ladder
+#include "rt_wave_ball.hpp"      // the ball around a wave's hit points
 #include "rt_wavefront_math.hpp" // Ball, sphere_relevant: the wavefront kernel's conservative shadow culling
 
 namespace RT_SYM(rtk) {
 
 constexpr uint32_t WAVES = 4; // waves per workgroup of the ray kernel
 
-__device__ __forceinline__ double wave_min(double v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmin(v, __shfl_xor(v, m));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) v = fmax(v, __shfl_xor(v, m));
-    return v;
-}
-
 // render_ray (rt_shade.hpp) for a wave whose lanes trace nearby rays, with the wavefront kernel's exact shadow culling: after each
-// round of nearest hits the wave forms one ball around its lanes' hit points (Ball, rt_wavefront_math.hpp: box centre, half
+// round of nearest hits the wave forms one ball around its lanes' hit points (wave_hit_ball, rt_wave_ball.hpp: box centre, half
 // diagonal plus the 1e-2 shadow bias) and, per light, one wave-wide verdict per object (sphere_relevant, one object per lane); only
 // objects that could block some lane's shadow ray are tested.  A culled object cannot block (that is the culling's contract), so
 // every lane's in_shadow -- and with it every colour -- is what render_ray computes.  Lanes stay resident (a `live` flag instead of
@@ -80,17 +69,7 @@ __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevOb
         if (__ballot(hit)) { // wave-uniform
             bool cull = fa.cull != 0u;
             Ball ball{0.0, 0.0, 0.0, INFINITY};
-            if (cull) {
-                const bool finite = !hit || (isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z));
-                if (__ballot(!finite)) cull = false; // (a NaN / inf hit point: test everything)
-                const double lx = wave_min(hit ? sp.x : INFINITY), ly = wave_min(hit ? sp.y : INFINITY), lz = wave_min(hit ? sp.z : INFINITY);
-                const double hx = wave_max(hit ? sp.x : -INFINITY), hy = wave_max(hit ? sp.y : -INFINITY), hz = wave_max(hit ? sp.z : -INFINITY);
-                const double dx = hx - lx, dy = hy - ly, dz = hz - lz;
-                ball.cx = 0.5 * (lx + hx);
-                ball.cy = 0.5 * (ly + hy);
-                ball.cz = 0.5 * (lz + hz);
-                ball.R = 0.5 * sqrt(dx * dx + dy * dy + dz * dz) * (1.0 + 1e-9) + 1.01e-2; // as the wavefront kernel forms it
-            }
+            if (cull) cull = wave_hit_ball<true>(hit, sp, ball); // (false: a NaN / inf hit point, test everything)
             for (uint32_t l = 0; l < fa.n_lights; l++) {
                 const DevLight *lt = &glight[l];
                 const bool spherical = lt->spherical != 0;
@@ -166,17 +145,10 @@ __device__ __forceinline__ F3 render_ray_culled(const FrameArgs &fa, const DevOb
     return res;
 }
 
-// (quantise, the RGBA8 store, and xor_add, one level of the resolve's tree: rt_shade.hpp, shared with the streamed ray-list kernels)
-
-// One lane = one sample ray; a wave = 64 / K^2 pixels (K = 4: 4 pixels of 16 lanes; K = 2: 16 pixels of 4 lanes).  Lane bits: i =
-// sub-column (K = 4: bits 0-1, K = 2: bit 0), j = sub-row (the next bits).  Workgroups of four waves stage the scene into LDS once
-// and then take pixels by a grid-stride loop over the device-side count, so the grid size never depends on the frame.
-//   K = 2 / 4: item q is list[q] = (local row << 16) | x; sample (i, j) is the ray of sample (K x + i, K y + j) of the K-times
-//              finer frame (camx / camy: its camera-plane tables); the lanes reduce with the resolve's tree, multiply by 1/K^2 and
-//              store one pixel of the output (RGBA8 quantised as the render kernels do).
-//   K = 1:     halo rows.  Item q = pixel x of halo slot h = q / width: band b = h / 2 of this rank, side 0 = the global row just
-//              below the band, 1 = just above it (nothing when that row lies outside the image); camx / camy: the output frame's
-//              tables.  Stores RGBA32F into halo[h][x].
+// One lane = one sample ray; a wave = 64 / K^2 pixels (K = 4: 4 pixels of 16 lanes; K = 2: 16 pixels of 4 lanes; K = 1: 64 pixels of the
+// halo rows).  Workgroups of four waves stage the scene into LDS once and then take items by a grid-stride loop over the device-side
+// count, so the grid size never depends on the frame.  The items, the resolve and the store are the streamed twins' (rt_ray_list.hpp:
+// sl_item, sl_resolve_store); what is this kernel's own is the staging prologue, the counters and render_ray_culled.
 template <int K, bool COUNT, bool RGBA8>
 __global__ __launch_bounds__(256) void ray_list_kernel(const FrameArgs fa, const DevObject *__restrict__ gobj, const DevLight *__restrict__ glight,
                                                        const double *__restrict__ camx, const double *__restrict__ camy,
@@ -213,100 +185,12 @@ __global__ __launch_bounds__(256) void ray_list_kernel(const FrameArgs fa, const
     const D3 origin{fa.origin[0], fa.origin[1], fa.origin[2]};
     Cnt<COUNT> cnt;
     for (uint32_t base = (blockIdx.x * WAVES + wave) * PPW; base < n; base += gridDim.x * WAVES * PPW) { // wave-uniform
-        const uint32_t q = base + lane / LANES;
-        bool live = q < n;
-        uint32_t x = 0, lr = 0, y = 0;
-        D3 dir{0.0, 0.0, 1.0};
-        if (K == 1) {
-            if (live) {
-                const uint32_t h = q / fa.width, b = h >> 1;
-                x = q - h * fa.width;
-                lr = h; // (halo slot)
-                const uint32_t start = b * fa.band_rows, rows = min(fa.band_rows, fa.local_rows - start);
-                const int64_t g0 = ((int64_t) b * fa.world + fa.rank) * fa.band_rows;
-                const int64_t gy = (h & 1u) ? g0 + rows : g0 - 1;
-                live = gy >= 0 && gy < (int64_t) fa.height;
-                if (live) dir = primary_dir_tab(fa, camx[x], camy[(uint32_t) gy]);
-            }
-        } else {
-            if (live) {
-                const uint32_t v = list[q];
-                lr = v >> 16;
-                x = v & 0xFFFFu;
-                y = global_row(fa, lr);
-                dir = primary_dir_tab(fa, camx[(size_t) K * x + i], camy[(size_t) K * y + j]);
-            }
-        }
-        if (live) cnt.primary();
-        F3 c = render_ray_culled<COUNT>(fa, gobj, glight, sobj, scull, origin, dir, live, cnt);
-        if (K == 1) {
-            if (live) reinterpret_cast<float4 *>(out)[(size_t) lr * fa.width + x] = make_float4(c.x, c.y, c.z, 1.0f);
-        } else {
-            // (s0 + s1) [+ (s2 + s3)] over i, then the same over j: lanes i ^ 1, i ^ 2, then j's bits
-            c = xor_add(c, 1);
-            if (K == 4) c = xor_add(c, 2);
-            c = xor_add(c, K);
-            if (K == 4) c = xor_add(c, 2 * K);
-            if (live && sub == 0u) {
-                constexpr float inv = 1.0f / (float) (K * K); // exact
-                const float vx = __fmul_rn(c.x, inv), vy = __fmul_rn(c.y, inv), vz = __fmul_rn(c.z, inv);
-                const size_t o = (size_t) lr * fa.width + x;
-                if (RGBA8) reinterpret_cast<uchar4 *>(out)[o] = quantise(vx, vy, vz);
-                else reinterpret_cast<float4 *>(out)[o] = make_float4(vx, vy, vz, 1.0f);
-            }
-        }
+        const SlItem it = sl_item<K>(fa, camx, camy, list, base + lane / LANES, n, i, j);
+        if (it.use) cnt.primary();
+        const F3 c = render_ray_culled<COUNT>(fa, gobj, glight, sobj, scull, origin, it.dir, it.use, cnt);
+        sl_resolve_store<K, RGBA8>(fa, out, it, sub, c);
     }
     cnt.flush(counters);
-}
-
-// One lane per output pixel, a wave per 8 x 8 block (a workgroup per 16 x 16 tile), so that the list keeps locality.  refine(x, y):
-// tau < 0, or some 8-neighbour n inside the image and channel c with !(fabsf(P(x,y).c - P(n).c) <= tau).  Neighbour rows come from
-// P (the same band) or from the halo (a row of another rank).  Unrefined pixels are written to `out` in the context's format
-// (nothing to write when out is P itself); refined ones are appended to the list, one atomicAdd per wave.
-template <bool RGBA8>
-__global__ __launch_bounds__(256) void classify_kernel(const float4 *__restrict__ p, const float4 *__restrict__ halo, uint32_t width, uint32_t height,
-                                                       uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world, uint32_t rank, float tau,
-                                                       void *out, uint32_t *__restrict__ list, uint32_t *__restrict__ count)
-{
-    const uint32_t tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
-    const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
-    const bool in = x < width && lr < local_rows;
-    bool refine = false;
-    float4 c = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    if (in) {
-        c = p[(size_t) lr * width + x];
-        refine = tau < 0.0f;
-        const uint32_t b = lr / band_rows, t = lr - b * band_rows;
-        const int64_t gy = ((int64_t) b * world + rank) * band_rows + t;
-        for (int dy = -1; dy <= 1 && !refine; dy++) {
-            const int64_t ny = gy + dy;
-            if (ny < 0 || ny >= (int64_t) height) continue;
-            const float4 *row;
-            if (dy == 0) row = p + (size_t) lr * width;
-            else if (world == 1u) row = p + (size_t) (lr + dy) * width;
-            else if (dy < 0) row = t > 0u ? p + (size_t) (lr - 1u) * width : halo + (size_t) (2u * b) * width;
-            else row = (t + 1u < band_rows && lr + 1u < local_rows) ? p + (size_t) (lr + 1u) * width : halo + (size_t) (2u * b + 1u) * width;
-            for (int dx = -1; dx <= 1; dx++) {
-                const int64_t nx = (int64_t) x + dx;
-                if ((dx == 0 && dy == 0) || nx < 0 || nx >= (int64_t) width) continue;
-                const float4 v = row[nx];
-                if (!(fabsf(c.x - v.x) <= tau) || !(fabsf(c.y - v.y) <= tau) || !(fabsf(c.z - v.z) <= tau)) refine = true;
-            }
-        }
-    }
-    const unsigned long long m = __ballot(refine);
-    if (in && !refine) {
-        const size_t o = (size_t) lr * width + x;
-        if (RGBA8) reinterpret_cast<uchar4 *>(out)[o] = quantise(c.x, c.y, c.z);
-        else if (out != (const void *) p) reinterpret_cast<float4 *>(out)[o] = make_float4(c.x, c.y, c.z, 1.0f);
-    }
-    if (m == 0ull) return; // wave-uniform
-    uint32_t base = 0;
-    if (lane == 0u) base = atomicAdd(count, (uint32_t) __popcll(m));
-    base = __builtin_amdgcn_readfirstlane(base);
-    if (refine) list[base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = (lr << 16) | x;
 }
 
 // One rt_hit record as gbuffer_kernel's coordinate-list mode writes it (rt_pixel_kernels.hpp: pk_gbuffer; rt_rayquery.hpp: RqRecord): the halo rows' object and normal
@@ -323,39 +207,45 @@ __device__ __forceinline__ float geo_dot(float ax, float ay, float az, float bx,
     return __fadd_rn(__fadd_rn(__fmul_rn(ax, bx), __fmul_rn(ay, by)), __fmul_rn(az, bz));
 }
 
-// classify_kernel with the geometric term of RT_FLAG_SSAA_GEOMETRY: refine(x, y) also when some 8-neighbour inside the image has
-// another primary-hit object, or the same object (>= 0) and !(dotf(N(x, y), N(n)) >= min_cos).  obj / nrm: this rank's planes
-// ([local_rows][width], gbuffer_kernel's plane mode; nrm = NULL: ids only, launch-uniform), ghalo: [2 * bands][width] records of the
-// halo rows (world > 1; the slots of `halo`).  Every neighbour is read where it lies: with bands of any height a block's
-// neighbour rows are per lane (a plane row or a halo slot), so there is no rectangular apron to stage.
-template <bool RGBA8>
-__global__ __launch_bounds__(256) void classify_geometry_kernel(const float4 *__restrict__ p, const float4 *__restrict__ halo, const int32_t *__restrict__ obj,
-                                                                const float4 *__restrict__ nrm, const GeoHalo *__restrict__ ghalo, uint32_t width,
-                                                                uint32_t height, uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world,
-                                                                uint32_t rank, float tau, float min_cos, void *out, uint32_t *__restrict__ list,
-                                                                uint32_t *__restrict__ count)
+// The body of both classifiers.  One lane per output pixel, a wave per 8 x 8 block (a workgroup per 16 x 16 tile), so that the list keeps
+// locality.  refine(x, y): tau < 0, or some 8-neighbour n inside the image and channel c with !(fabsf(P(x,y).c - P(n).c) <= tau); with
+// GEOMETRY (RT_FLAG_SSAA_GEOMETRY) also when that neighbour has another primary-hit object, or the same object (>= 0) and
+// !(dotf(N(x, y), N(n)) >= min_cos).  obj / nrm: this rank's planes ([local_rows][width], gbuffer_kernel's plane mode; nrm = NULL: ids
+// only, launch-uniform), ghalo: [2 * bands][width] records of the halo rows (world > 1; the slots of `halo`); none of the three is read
+// without GEOMETRY.  Every neighbour is read where it lies: a neighbour row is local row r of P and the planes (the same band) or halo
+// slot r (a row of another rank) -- with bands of any height per lane, so there is no rectangular apron to stage.
+// Unrefined pixels are written to `out` in the context's format (nothing to write when out is P itself); refined ones are appended to
+// the list, one atomicAdd per wave.
+template <bool RGBA8, bool GEOMETRY>
+__device__ __forceinline__ void classify_body(const float4 *__restrict__ p, const float4 *__restrict__ halo, const int32_t *__restrict__ obj,
+                                              const float4 *__restrict__ nrm, const GeoHalo *__restrict__ ghalo, uint32_t width, uint32_t height,
+                                              uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world, uint32_t rank, float tau,
+                                              float min_cos, void *out, uint32_t *__restrict__ list, uint32_t *__restrict__ count)
 {
     const uint32_t tile_x = blockIdx.x % tiles_x, tile_y = blockIdx.x / tiles_x;
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t x = tile_x * 16u + (wave & 1u) * 8u + (lane & 7u);
     const uint32_t lr = tile_y * 16u + (wave >> 1) * 8u + (lane >> 3);
     const bool in = x < width && lr < local_rows;
-    const bool normals = nrm != nullptr; // launch-uniform
+    const bool normals = GEOMETRY && nrm != nullptr; // launch-uniform
     bool refine = false;
     float4 c = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     if (in) {
         const size_t at = (size_t) lr * width + x;
         c = p[at];
         refine = tau < 0.0f;
-        const int32_t id = obj[at];
+        int32_t id = -1;
         float4 n0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (normals && id >= 0) n0 = nrm[at];
+        if constexpr (GEOMETRY) {
+            id = obj[at];
+            if (normals && id >= 0) n0 = nrm[at];
+        }
         const uint32_t b = lr / band_rows, t = lr - b * band_rows;
         const int64_t gy = ((int64_t) b * world + rank) * band_rows + t;
         for (int dy = -1; dy <= 1 && !refine; dy++) {
             const int64_t ny = gy + dy;
             if (ny < 0 || ny >= (int64_t) height) continue;
-            // the neighbour row: local row r of the planes, or halo slot r (the existing classifier's rule)
+            // the neighbour row: local row r of P and the planes, or halo slot r
             bool from_halo = false;
             uint32_t r = lr;
             if (dy != 0) {
@@ -369,19 +259,21 @@ __global__ __launch_bounds__(256) void classify_geometry_kernel(const float4 *__
                 if ((dx == 0 && dy == 0) || nx < 0 || nx >= (int64_t) width) continue;
                 const float4 v = from_halo ? halo[row + nx] : p[row + nx];
                 if (!(fabsf(c.x - v.x) <= tau) || !(fabsf(c.y - v.y) <= tau) || !(fabsf(c.z - v.z) <= tau)) refine = true;
-                const int32_t idn = from_halo ? ghalo[row + nx].object : obj[row + nx];
-                if (idn != id) {
-                    refine = true;
-                } else if (normals && id >= 0) {
-                    float bx, by, bz;
-                    if (from_halo) {
-                        const GeoHalo *g = &ghalo[row + nx];
-                        bx = g->n[0]; by = g->n[1]; bz = g->n[2];
-                    } else {
-                        const float4 n1 = nrm[row + nx];
-                        bx = n1.x; by = n1.y; bz = n1.z;
+                if constexpr (GEOMETRY) {
+                    const int32_t idn = from_halo ? ghalo[row + nx].object : obj[row + nx];
+                    if (idn != id) {
+                        refine = true;
+                    } else if (normals && id >= 0) {
+                        float bx, by, bz;
+                        if (from_halo) {
+                            const GeoHalo *g = &ghalo[row + nx];
+                            bx = g->n[0]; by = g->n[1]; bz = g->n[2];
+                        } else {
+                            const float4 n1 = nrm[row + nx];
+                            bx = n1.x; by = n1.y; bz = n1.z;
+                        }
+                        if (!(geo_dot(n0.x, n0.y, n0.z, bx, by, bz) >= min_cos)) refine = true;
                     }
-                    if (!(geo_dot(n0.x, n0.y, n0.z, bx, by, bz) >= min_cos)) refine = true;
                 }
             }
         }
@@ -399,15 +291,32 @@ __global__ __launch_bounds__(256) void classify_geometry_kernel(const float4 *__
     if (refine) list[base + (uint32_t) __popcll(m & ((1ull << lane) - 1ull))] = (lr << 16) | x;
 }
 
-template <int K, bool COUNT>
-hipError_t launch_rays(const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, const double *camx, const double *camy, const uint32_t *list,
-                       const uint32_t *count_ptr, uint32_t n_items, uint32_t grid, void *out, int rgba8, unsigned long long *counters, hipStream_t stream)
+// The classifier of the colour term alone: classify_body with everything geometric compiled out.
+template <bool RGBA8>
+__global__ __launch_bounds__(256) void classify_kernel(const float4 *__restrict__ p, const float4 *__restrict__ halo, uint32_t width, uint32_t height,
+                                                       uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world, uint32_t rank, float tau,
+                                                       void *out, uint32_t *__restrict__ list, uint32_t *__restrict__ count)
+{
+    classify_body<RGBA8, false>(p, halo, nullptr, nullptr, nullptr, width, height, local_rows, tiles_x, band_rows, world, rank, tau, 0.0f, out, list, count);
+}
+
+// ... and with the geometric term of RT_FLAG_SSAA_GEOMETRY.
+template <bool RGBA8>
+__global__ __launch_bounds__(256) void classify_geometry_kernel(const float4 *__restrict__ p, const float4 *__restrict__ halo, const int32_t *__restrict__ obj,
+                                                                const float4 *__restrict__ nrm, const GeoHalo *__restrict__ ghalo, uint32_t width,
+                                                                uint32_t height, uint32_t local_rows, uint32_t tiles_x, uint32_t band_rows, uint32_t world,
+                                                                uint32_t rank, float tau, float min_cos, void *out, uint32_t *__restrict__ list,
+                                                                uint32_t *__restrict__ count)
+{
+    classify_body<RGBA8, true>(p, halo, obj, nrm, ghalo, width, height, local_rows, tiles_x, band_rows, world, rank, tau, min_cos, out, list, count);
+}
+
+template <int K, bool COUNT, bool RGBA8>
+static hipError_t launch_rays(const FrameArgs *fa, const DevObject *gobj, const DevLight *glight, const double *camx, const double *camy, const uint32_t *list,
+                              const uint32_t *count_ptr, uint32_t n_items, uint32_t grid, void *out, unsigned long long *counters, hipStream_t stream)
 {
     const size_t lds = (size_t) fa->n_obj * (sizeof(DevObject) + sizeof(UsEntry));
-    if (rgba8)
-        hipLaunchKernelGGL((ray_list_kernel<K, COUNT, true>), dim3(grid), dim3(256), lds, stream, *fa, gobj, glight, camx, camy, list, count_ptr, n_items, out, counters);
-    else
-        hipLaunchKernelGGL((ray_list_kernel<K, COUNT, false>), dim3(grid), dim3(256), lds, stream, *fa, gobj, glight, camx, camy, list, count_ptr, n_items, out, counters);
+    hipLaunchKernelGGL((ray_list_kernel<K, COUNT, RGBA8>), dim3(grid), dim3(256), lds, stream, *fa, gobj, glight, camx, camy, list, count_ptr, n_items, out, counters);
     return hipGetLastError();
 }
 
@@ -422,13 +331,12 @@ extern "C" hipError_t RT_SYM(rt_launch_ray_list)(const FrameArgs *fa, const DevO
 {
     using namespace RT_SYM(rtk);
     if (grid == 0u) return hipSuccess;
-    if (k == 1u) return count ? launch_rays<1, true>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, 0, counters, stream)
-                              : launch_rays<1, false>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, 0, counters, stream);
-    if (k == 2u) return count ? launch_rays<2, true>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream)
-                              : launch_rays<2, false>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream);
-    if (k == 4u) return count ? launch_rays<4, true>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream)
-                              : launch_rays<4, false>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, rgba8, counters, stream);
-    return hipErrorInvalidValue;
+    return sl_for_shapes(k, rgba8, [&](auto kk, auto r8) {
+        constexpr int K = decltype(kk)::value;
+        constexpr bool RGBA8 = decltype(r8)::value;
+        return count ? launch_rays<K, true, RGBA8>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, counters, stream)
+                     : launch_rays<K, false, RGBA8>(fa, gobj, glight, camx, camy, list, count_ptr, n_items, grid, out, counters, stream);
+    });
 }
 
 // p = [local_rows][width] RGBA32F plain frame, halo = [2 * bands][width] (world > 1), out = [local_rows][width] pixels (may be p

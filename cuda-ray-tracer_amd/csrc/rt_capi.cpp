@@ -883,6 +883,20 @@ static int rotate_launch_order(rt_ctx *ctx, FrameArgs &fa, hipStream_t stream)
     return RT_OK;
 }
 
+// One pass of an adaptive frame over a ray list (the halo rows: k = 1, n_items slots; the refine pass: k = the context's, the device-side count): the
+// staged kernel (rt_adaptive.hip) or, on a context whose adaptive passes are streamed -- rt_ctx::stream_adaptive, rt_ctx::stream_cull_adaptive, decided once
+// in rt_create --, that pass's streamed or culled twin.  The streamed passes book no counters.  One graph node.
+static hipError_t ray_list_launch(rt_ctx *ctx, const double *camx, const double *camy, const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid,
+                                  void *out, int rgba8, int count, hipStream_t stream)
+{
+    const Kernels *kern = ctx->kern;
+    if (ctx->stream_cull_adaptive)
+        return kern->stream_cull_ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, ctx->d_bounds, ctx->n_chunks,
+                                          ctx->d_cull_adaptive_stats, stream);
+    if (ctx->stream_adaptive) return kern->stream_ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, stream);
+    return kern->ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, count, ctx->d_counters, stream);
+}
+
 static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *stream_, float *ms, bool sparse, uint32_t sparse_cap)
 {
     hipStream_t stream = (hipStream_t) stream_;
@@ -938,16 +952,8 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         // halo rows -> clear the list -> classify (unrefined pixels written out) -> the k^2 sample rays of the listed pixels; the next
         // frame's plain pass overwrites what these read, and the ordering event below is recorded behind the last of them
         const size_t px = (size_t) ctx->local_rows * ctx->width;
-        // (a context whose adaptive passes are streamed -- rt_ctx::stream_adaptive, decided once in rt_create -- launches each pass's streamed twin)
-        if (ctx->halo_slots && ctx->stream_cull_adaptive)
-            RT_HIP(ctx->kern->stream_cull_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid,
-                                                   ctx->d_halo, 0, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_adaptive_stats, stream));
-        else if (ctx->halo_slots && ctx->stream_adaptive)
-            RT_HIP(ctx->kern->stream_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid,
-                                              ctx->d_halo, 0, stream));
-        else if (ctx->halo_slots)
-            RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo,
-                                       0, count, ctx->d_counters, stream));
+        if (ctx->halo_slots)
+            RT_HIP(ray_list_launch(ctx, ctx->d_camx, ctx->d_camy, nullptr, nullptr, ctx->halo_slots * ctx->width, 1u, ctx->halo_grid, ctx->d_halo, 0, count, stream));
         RT_HIP(hipMemsetAsync(ctx->d_list + px, 0, sizeof(uint32_t), stream));
         if (ctx->geometry) {
             // the primary-hit object (and, for a finite min_cos, normal) of this rank's rows and of the halo rows: gbuffer_kernel itself, which
@@ -965,15 +971,7 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             RT_HIP(rt_launch_classify_strict(fb, ctx->d_halo, ctx->width, ctx->height, ctx->local_rows, ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau,
                                              dest, out8, ctx->d_list, ctx->d_list + px, stream));
         }
-        if (ctx->stream_cull_adaptive)
-            RT_HIP(ctx->kern->stream_cull_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest,
-                                                   out8, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_adaptive_stats, stream));
-        else if (ctx->stream_adaptive)
-            RT_HIP(ctx->kern->stream_ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8,
-                                              stream));
-        else
-            RT_HIP(ctx->kern->ray_list(&fa, ctx->d_obj, ctx->d_light, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count,
-                                       ctx->d_counters, stream));
+        RT_HIP(ray_list_launch(ctx, ctx->d_camxk, ctx->d_camyk, ctx->d_list, ctx->d_list + px, 0u, ctx->ssaa, ctx->ray_grid, dest, out8, count, stream));
     }
     if (ss) // the next frame's render overwrites the internal frame this reads, so the ordering event below is recorded behind it
         RT_HIP(rt_launch_resolve(ctx->d_ss, dest, ctx->width, ctx->local_rows, ctx->ssaa, out8, ctx->resolve_nt, stream));

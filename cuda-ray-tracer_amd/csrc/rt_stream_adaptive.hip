@@ -14,14 +14,14 @@
 // rays test every object, as in every streamed kernel.  No counters.
 #include <hip/hip_runtime.h>
 #include "rt_launch.h"   // the launcher below, as the host sees it
-#include "rt_stream_shell.hpp" // the items and the resolve; the shading loop and SqShade (rt_stream_shade.hpp) over rt_stream.hpp
+#include "rt_stream_shell.hpp" // the items, the resolve and the launch ladder (rt_ray_list.hpp); the shading loop and SqShade (rt_stream_shade.hpp) over rt_stream.hpp
 
 namespace RT_SYM(rtk) {
 
 // ray_list_kernel's items (rt_adaptive.hip).  One lane = one sample ray; a wave = 64 / K^2 items.  Lane bits: i = sub-column (the low
 // ones), j = sub-row (the next ones).  The waves take items by a grid-stride loop over the device-side count, so the grid size never
 // depends on the frame; the loop's trip count is wave-uniform and nothing in it is workgroup-wide.
-// The items and what is stored for them: rt_stream_shell.hpp (sl_item, sl_resolve_store).
+// The items and what is stored for them: rt_ray_list.hpp (sl_item, sl_resolve_store).
 // Lanes past the list's end, and lanes of an off-image halo row, stay in the wave with use = false and skip only the store.
 template <int K, bool RGBA8, bool HAS_GQ, bool HAS_CUBIC>
 __global__ __launch_bounds__(256) void ray_list_stream_kernel(const FrameArgs fa, const RayQueryArgs qa, const unsigned char *__restrict__ scene,
@@ -71,10 +71,7 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_ray_list)(const FrameArgs *fa, con
 {
     using namespace RT_SYM(rtk);
     if (grid == 0u) return hipSuccess;
-    if (k == 1u) return sa_launch<1, false>(fa, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream);
-    if (k == 2u) return rgba8 ? sa_launch<2, true>(fa, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream)
-                              : sa_launch<2, false>(fa, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream);
-    if (k == 4u) return rgba8 ? sa_launch<4, true>(fa, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream)
-                              : sa_launch<4, false>(fa, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream);
-    return hipErrorInvalidValue;
+    return sl_for_shapes(k, rgba8, [&](auto kk, auto r8) {
+        return sa_launch<decltype(kk)::value, decltype(r8)::value>(fa, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream);
+    });
 }

@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "rt_wave_ball.hpp"    // the ball around the wave's hit points (wave_hit_ball), wave_min and wave_max
 #include "rt_stream_shade.hpp" // the shading loop whose policy ends this file; sq_query and the staging idiom (rt_stream.hpp)
 
 namespace RT_SYM(rtk) {
@@ -39,40 +40,6 @@ __device__ __forceinline__ void sc_flush(const uint32_t (&w)[N], unsigned long l
 #pragma unroll
     for (uint32_t i = 0; i < N; i++) mine = lane == i ? w[i] : mine;
     if (mine) atomicAdd(dst + lane, (unsigned long long) mine);
-}
-
-__device__ __forceinline__ double sc_wave_min(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off, 64);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-__device__ __forceinline__ double sc_wave_max(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double o = __shfl_xor(v, off, 64);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// The ball around the wave's hit points, as rt_adaptive.hip forms it (the 1e-2 shadow bias included).  Returns false -- cull nothing in
-// this segment -- when a hit point is not finite.
-__device__ __forceinline__ bool sc_hit_ball(bool hit, const D3 &sp, Ball &ball)
-{
-    const bool finite = !hit || (isfinite(sp.x) && isfinite(sp.y) && isfinite(sp.z));
-    const double lx = sc_wave_min(hit ? sp.x : INFINITY), ly = sc_wave_min(hit ? sp.y : INFINITY), lz = sc_wave_min(hit ? sp.z : INFINITY);
-    const double hx = sc_wave_max(hit ? sp.x : -INFINITY), hy = sc_wave_max(hit ? sp.y : -INFINITY), hz = sc_wave_max(hit ? sp.z : -INFINITY);
-    const double dx = hx - lx, dy = hy - ly, dz = hz - lz;
-    ball.cx = 0.5 * (lx + hx);
-    ball.cy = 0.5 * (ly + hy);
-    ball.cz = 0.5 * (lz + hz);
-    ball.R = 0.5 * sqrt(dx * dx + dy * dy + dz * dz) * (1.0 + 1e-9) + 1.01e-2;
-    return __ballot(!finite) == 0ull;
 }
 
 struct ScBound { // what the predicates read of a bound
@@ -237,7 +204,7 @@ struct ScShade {
     __device__ __forceinline__ Segment segment(bool hit, const D3 &sp) const
     {
         Segment seg;
-        seg.cull = sc_hit_ball(hit, sp, seg.ball);
+        seg.cull = wave_hit_ball(hit, sp, seg.ball);
         return seg;
     }
     // Not culled for: a directional light with |d|^2 <= EPS (the reference's linear branch is not geometry).

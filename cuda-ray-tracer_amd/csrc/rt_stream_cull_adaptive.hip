@@ -3,13 +3,13 @@
 // DESIGN.md section 26).
 //
 // The twin of ray_list_stream_kernel (rt_stream_adaptive.hip): the same items, lane layout, grid-stride loop, resolve tree, exact 1 / K^2
-// and RGBA8 store (rt_stream_shell.hpp), the same shading loop (rt_stream_shade.hpp: shade_loop).  What differs is the loop's policy
+// and RGBA8 store (rt_ray_list.hpp), the same shading loop (rt_stream_shade.hpp: shade_loop).  What differs is the loop's policy
 // (ScaShade below, over rt_stream_cull.hpp's ScShade), that is, which 64-entry chunks of the unit-sphere table a query stages:
 //   * segment 0, nearest hit: the sample (or halo centre) rays of a wave all leave the frame's origin, so they have a cone -- not a block's
 //     (the lanes are 64 / K^2 listed pixels, anywhere in the classifier's append order), but the wave's own: rt_wave_cone.hpp.  Lane j
 //     asks sphere_in_cone about chunk bound g * 64 + j, only the surviving chunks are staged, and inside a staged chunk the per-entry cone
 //     test and sc_sweep run, as in sc_query_primary.  A wave with an unproven lane, or with no lane in use, takes sq_query;
-//   * shadow rays: sc_hit_ball once per segment and sc_query_shadow per light, under stream_cull_frame_kernel's conditions;
+//   * shadow rays: wave_hit_ball (rt_wave_ball.hpp) once per segment and sc_query_shadow per light, under stream_cull_frame_kernel's conditions;
 //   * bounce rays (nearest hit of segments >= 1): sq_query, a full sweep, as in the frame kernel.
 // The colours are ray_list_stream_kernel's: the same arithmetic per tested object, and no dropped object's root could have been accepted.
 // Compiled twice like rt_stream.hip (-DRT_VARIANT=strict -ffp-contract=off / -DRT_VARIANT=fast -ffp-contract=fast).
@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "rt_launch.h"          // the launcher below, as the host sees it
 #include "rt_stream_cull.hpp"   // the culled unit-sphere loops over rt_stream.hpp, and their shading policy
-#include "rt_stream_shell.hpp"  // the items and the resolve
+#include "rt_stream_shell.hpp"  // the items, the resolve and the launch ladder (rt_ray_list.hpp)
 #include "rt_wave_cone.hpp"     // the lanes' parts of the wave cone
 
 namespace RT_SYM(rtk) {
@@ -37,13 +37,13 @@ __device__ __forceinline__ SqCone sca_wave_cone(const D3 &d, bool use)
         s.z += __shfl_xor(s.z, off, 64);
     }
     const double score = wc_score(s, d, use);
-    unsigned long long pick = __ballot(wc_is_pick(score, sc_wave_max(score), use));
+    unsigned long long pick = __ballot(wc_is_pick(score, wave_max<false>(score), use));
     if (pick == 0ull) pick = __ballot(use);
     const int l = __builtin_ctzll(pick);
     SqCone c;
     c.on = true;
     c.axis = D3{sq_readlane(d.x, l), sq_readlane(d.y, l), sq_readlane(d.z, l)};
-    c.cos_t = sq_readlane(sc_wave_min(wc_cos(c.axis, d, use)), 0);
+    c.cos_t = sq_readlane(wave_min<false>(wc_cos(c.axis, d, use)), 0);
     return c;
 }
 
@@ -112,7 +112,7 @@ struct ScaShade : ScShade {
 
 // ray_list_stream_kernel's items (rt_stream_adaptive.hip).  ca: the chunk bounds and the work words.  One lane = one sample ray; a wave
 // = 64 / K^2 items.  The waves take items by a grid-stride loop over the device-side count, so the grid size never depends on the frame;
-// the loop's trip count is wave-uniform and nothing in it is workgroup-wide.  The items and what is stored for them: rt_stream_shell.hpp
+// the loop's trip count is wave-uniform and nothing in it is workgroup-wide.  The items and what is stored for them: rt_ray_list.hpp
 // (sl_item, sl_resolve_store).
 // Lanes past the list's end, and lanes of an off-image halo row, stay in the wave with use = false and skip only the store.
 // STATS: the work words are counted (a template parameter: counting costs some twenty registers).  Two waves per SIMD are asked of the
@@ -175,12 +175,10 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_cull_ray_list)(const FrameArgs *fa
     if (grid == 0u) return hipSuccess;
     if (n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (n_chunks && !bounds)) return hipErrorInvalidValue;
     const StreamCullArgs ca{reinterpret_cast<const UsEntry *>(bounds), stats, n_chunks, 0u};
-#define SCA_LAUNCH(K, RGBA8) \
-    (stats ? sca_launch<K, RGBA8, true>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream) \
-           : sca_launch<K, RGBA8, false>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream))
-    if (k == 1u) return SCA_LAUNCH(1, false);
-    if (k == 2u) return rgba8 ? SCA_LAUNCH(2, true) : SCA_LAUNCH(2, false);
-    if (k == 4u) return rgba8 ? SCA_LAUNCH(4, true) : SCA_LAUNCH(4, false);
-#undef SCA_LAUNCH
-    return hipErrorInvalidValue;
+    return sl_for_shapes(k, rgba8, [&](auto kk, auto r8) {
+        constexpr int K = decltype(kk)::value;
+        constexpr bool RGBA8 = decltype(r8)::value;
+        return stats ? sca_launch<K, RGBA8, true>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream)
+                     : sca_launch<K, RGBA8, false>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream);
+    });
 }

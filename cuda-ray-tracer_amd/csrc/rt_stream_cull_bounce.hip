@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void stream_cull_bounce_frame_kernel(const Fra
         if (__ballot(hit) != 0ull) {
             const F3 albedo{bo->albedo[0], bo->albedo[1], bo->albedo[2]};
             Ball ball;
-            const bool cull_seg = sc_hit_ball(hit, sp, ball); // once per segment; false: a non-finite hit point, test everything
+            const bool cull_seg = wave_hit_ball(hit, sp, ball); // once per segment; false: a non-finite hit point, test everything
             for (uint32_t l = 0; l < fa.n_lights; l++) {
                 const DevLight *lt = &lights[l];
                 const bool spherical = lt->spherical != 0;

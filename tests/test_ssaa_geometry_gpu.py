@@ -420,3 +420,57 @@ def test_update_driver(pkg, tmp_path):
         got = np.fromfile(out, dtype=np.float32).reshape(h, w, 4)
         want = want_frame(p, s, k, 1.0 / 32.0, obj, nrm, c, F32)
         assert identical(got, want), (val, mismatch(got, want))
+
+
+# 7. one classifier body (rt_adaptive.hip: classify_body): the neighbour-row rule of the geometric classifier is the plain one's
+ONE_W, ONE_H = 37, 23
+ONE_LAYOUTS = [(1, 0, 8)] + [(3, rank, band) for band in (1, 5) for rank in range(3)]   # band 1: both neighbour rows of every row are halo slots; band 5: the last band is partial
+
+
+def one_object_scene(pkg):
+    """The camera inside a single sphere, lit through its wall by two lights outside it (from inside, a light inside faces no
+    normal): every primary ray hits object 0, so with min_cos = -inf the geometric term can refine nothing, and the colours vary smoothly."""
+    s = pkg.Scene.new(ONE_W, ONE_H, 60.0, 0, (0.1, 0.1, 0.1))
+    s.add_object(pkg.surface_make("sphere", [0, 0, 0], [50.0]), (0.9, 0.8, 0.7))
+    s.add_light("spherical", [30, 40, 120], (1, 1, 1), 60000.0)
+    s.add_light("spherical", [-60, -20, 90], (1.0, 0.6, 0.3), 40000.0)
+    return s
+
+
+def test_both_classifiers_follow_one_neighbour_row_rule(pkg):
+    """A context with RT_FLAG_SSAA_GEOMETRY and min_cos = -inf on a frame whose every pixel shows object 0 must return the frame, and
+    the refined count, of the same context without the flag, bit for bit: for tau = -1 (everything refines), +inf (nothing does) and a
+    tau taken from the plain frame at which some pixels do; as the only rank and as every rank of 3 with bands of 1 and 5 rows."""
+    sc = one_object_scene(pkg)
+    plain = pkg.Renderer(sc, device=0)
+    try:
+        plain.update()
+        p = plain.download()
+        po, _, _, _ = plain.gbuffer(t=False, normal=False)
+        assert po.shape == (ONE_H, ONE_W) and bool((po == 0).all())   # rt_render_gbuffer: object 0 in every pixel
+    finally:
+        plain.cleanup_update()
+    counts = {e: int(ada.refine_mask(p, 2.0 ** -e).sum()) for e in range(1, 25)}
+    mid = 2.0 ** -min(counts, key=lambda e: abs(counts[e] - ONE_W * ONE_H // 2))
+    assert 0 < int(ada.refine_mask(p, mid).sum()) < ONE_W * ONE_H, counts
+    for fmt in (F32, U8):
+        for world, rank, band in ONE_LAYOUTS:
+            pair = [pkg.Renderer(sc, device=0, rank=rank, world=world, band_rows=band, flags=flags, fmt=fmt, **kw)
+                    for flags, kw in ((ada_flags(pkg, 2), {}), (gflags(pkg, 2), {"ssaa_min_cos": -INF}))]
+            try:
+                assert pair[0].local_rows == pair[1].local_rows > 0
+                for tau in (-1.0, INF, mid):
+                    got = []
+                    for r in pair:
+                        r.set_ssaa_threshold(tau)
+                        r.update()
+                        got.append((r.download(), r.refined))
+                    (a, na), (b, nb) = got
+                    print(f"fmt {fmt} world {world} rank {rank} band {band} tau {tau}: refined {na} / {nb} of {a.shape[0] * ONE_W}, differing pixels {mismatch(b, a)}")
+                    assert identical(b, a) and nb == na, (fmt, world, rank, band, tau, na, nb, mismatch(b, a))
+                    assert na == {-1.0: a.shape[0] * ONE_W, INF: 0}.get(tau, na)
+                    if world == 1 and tau == mid:
+                        assert 0 < na < ONE_W * ONE_H, na
+            finally:
+                for r in pair:
+                    r.cleanup_update()

@@ -115,13 +115,13 @@ def test_the_kernel_file_has_no_workgroup_barrier_and_no_dynamic_lds():
     def code_of(name):
         return "\n".join(l.split("//")[0] for l in open(os.path.join(CSRC, name)).read().splitlines())
     # the kernel's file, the shared loop with the policy over sq_query, the items and the resolve
-    codes = {name: code_of(name) for name in ("rt_stream_adaptive.hip", "rt_stream_shade.hpp", "rt_stream_shell.hpp")}
+    codes = {name: code_of(name) for name in ("rt_stream_adaptive.hip", "rt_stream_shade.hpp", "rt_stream_shell.hpp", "rt_ray_list.hpp")}
     for name, code in codes.items():
         assert "__syncthreads" not in code and "s_barrier" not in code and "rq_stage_tables" not in code and '"workgroup"' not in code, name
         assert "extern __shared__" not in code and "HIP_DYNAMIC_SHARED" not in code, name
     code = codes["rt_stream_adaptive.hip"]
     assert code.count("__shared__ __align__(16) unsigned char smem[4u * SQ_SLICE_BYTES];") == 1
-    assert "__shared__" not in codes["rt_stream_shade.hpp"] and "__shared__" not in codes["rt_stream_shell.hpp"]
+    assert "__shared__" not in codes["rt_stream_shade.hpp"] and "__shared__" not in codes["rt_stream_shell.hpp"] and "__shared__" not in codes["rt_ray_list.hpp"]
     # both object loops go through sq_query without a block cone: the kernel has no query of its own, it runs the shared loop under the
     # policy over sq_query with the cone off; that policy has exactly one nearest-hit and one occlusion call, and the only cone argument
     # that is not the literal false is the policy's `cone`, which this kernel sets to false
@@ -140,7 +140,8 @@ def test_the_kernel_file_has_no_workgroup_barrier_and_no_dynamic_lds():
     assert policy.count("return") == 1 and "return Segment{};" in policy and "break" not in policy and "continue" not in policy
     kernel = code.split("void ray_list_stream_kernel")[1].split("template <int K, bool RGBA8>\nstatic")[0]
     assert "return" not in kernel and "break" not in kernel and "continue" not in kernel
-    lists = codes["rt_stream_shell.hpp"].split("struct SlItem {")[1]
+    assert "struct SlItem" not in codes["rt_stream_shell.hpp"] and '#include "rt_ray_list.hpp"' in codes["rt_stream_shell.hpp"]
+    lists = codes["rt_ray_list.hpp"].split("struct SlItem {")[1]
     assert lists.count("return") == 1 and "    return it;\n" in lists and "break" not in lists and "continue" not in lists
     assert "rt_stream_adaptive" in open(os.path.join(ROOT, "cuda-ray-tracer_amd", "Makefile")).read()
 

@@ -38,7 +38,12 @@ def test_symbols_and_prototypes(pkg):
     assert len(re.findall(r"RT_PER_VARIANT\(hipError_t, rt_launch_stream_cull_ray_list,", launch)) == 1
     assert re.search(r"decltype\(&rt_launch_stream_cull_ray_list_strict\) stream_cull_ray_list;", launch)   # the Kernels member
     capi = open(os.path.join(CSRC, "rt_capi.cpp")).read()
-    assert "RT_CAT(rt_launch_stream_cull_ray_list, V)}" in capi and capi.count("kern->stream_cull_ray_list(") == 2   # the halo and the refine launch
+    assert "RT_CAT(rt_launch_stream_cull_ray_list, V)}" in capi
+    # the halo and the refine launch go through one function, which holds the one call of each of the three launchers
+    one = capi.split("static hipError_t ray_list_launch(")[1].split("\n}\n")[0]
+    for launcher in ("kern->stream_cull_ray_list(", "kern->stream_ray_list(", "kern->ray_list("):
+        assert one.count(launcher) == 1 and capi.count(launcher) == 1, launcher
+    assert capi.split("static int render_impl(")[1].split("\n}\n")[0].count("ray_list_launch(") == 2 and capi.count("ray_list_launch(") == 3
 
 
 def test_null_arguments_are_refused_before_a_device_is_looked_for(pkg):
@@ -76,7 +81,7 @@ def test_build_report_lists_the_new_kernel_without_spills_at_two_waves_per_simd(
 
 
 def test_the_new_files_have_no_workgroup_barrier_and_no_dynamic_lds():
-    for name in ("rt_stream_cull_adaptive.hip", "rt_wave_cone.hpp", "rt_stream_shade.hpp", "rt_stream_shell.hpp"):
+    for name in ("rt_stream_cull_adaptive.hip", "rt_wave_cone.hpp", "rt_stream_shade.hpp", "rt_stream_shell.hpp", "rt_ray_list.hpp", "rt_wave_ball.hpp"):
         text = open(os.path.join(CSRC, name)).read()
         code = "\n".join(l.split("//")[0] for l in text.splitlines())
         for word in ("__syncthreads", "s_barrier", '"workgroup"', "rq_stage_tables", "extern __shared__", "HIP_DYNAMIC_SHARED"):
@@ -90,7 +95,7 @@ def test_the_new_files_have_no_workgroup_barrier_and_no_dynamic_lds():
     assert "void occluded(" not in text.split("struct ScaShade : ScShade {")[1].split("};")[0]
     assert "ScaShade pol{{qa, ca, scene, slice, st}, nocone};" in text and "shade_loop<HAS_GQ, HAS_CUBIC>(fa, scene, lights, lane, pol, origin, it.dir, it.use);" in text
     block = open(os.path.join(CSRC, "rt_stream_cull.hpp")).read().split("struct ScShade {")[1]
-    assert "seg.cull = sc_hit_ball(hit, sp, seg.ball);" in block and block.count("sc_query_shadow<") == 2
+    assert "seg.cull = wave_hit_ball(hit, sp, seg.ball);" in block and block.count("sc_query_shadow<") == 2
     for variant in ("strict", "fast"):
         remarks = open(os.path.join(BUILD, "csrc", f"rt_stream_cull_adaptive_{variant}.o.remarks")).read()
         assert set(re.findall(r"LDS Size \[bytes/block\]: (\d+)", remarks)) == {"24576"}

@@ -5,6 +5,9 @@ culled kernel of each query run one body over a query object, and what was writt
 records, the path loop, the shading policy -- is in one file.
 And so do the bodies of the pixel queries (csrc/rt_pixel_kernels.hpp): the staged and the streamed kernel of the
 G-buffer / picking and of the object extents run one body over a pixel query object, and each table path has one object loop.
+And so do the adaptive passes (csrc/rt_ray_list.hpp, csrc/rt_wave_ball.hpp, csrc/rt_adaptive.hip): the three ray-list
+kernels take their items, their resolve and their launch ladder from one header, the two classifiers run one body, and the ball around
+a wave's hit points is formed in one place.
 One kernel is the stated exception: stream_cull_bounce_frame_kernel holds the loop's text itself, because through the shared loop its
 strict <true, true> instantiation needs 258 registers and loses its second wave per SIMD (profiles/stream_shared_loop.txt)."""
 import glob
@@ -19,6 +22,8 @@ LOOP = "rt_stream_shade.hpp"
 KEEPS_ITS_COPY = "rt_stream_cull_bounce.hip"
 BODIES = "rt_ray_kernels.hpp"
 PIXEL_BODIES = "rt_pixel_kernels.hpp"
+RAY_LIST = "rt_ray_list.hpp"      # the three ray-list kernels' items, resolve and launch ladder
+WAVE_BALL = "rt_wave_ball.hpp"    # the ball around a wave's hit points
 # file -> (kernel or body, its policy): the sites that run the shared loop.  The three shade_rays kernels are one site: their body
 SITES = {
     BODIES: ("rk_shade_rays", "RkShade<Query>"),
@@ -27,7 +32,7 @@ SITES = {
     "rt_stream_cull.hip": ("stream_cull_frame_kernel", "ScShade"),
     "rt_stream_cull_adaptive.hip": ("ray_list_cull_kernel", "ScaShade"),
 }
-STREAMED = sorted(glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", "rt_shade.hpp", "rt_rayquery.hpp", "rt_adaptive.hip", "rt_gbuffer.hip", BODIES, PIXEL_BODIES)])
+STREAMED = sorted(glob.glob(os.path.join(CSRC, "rt_stream*")) + [os.path.join(CSRC, n) for n in ("rt_shade_rays.hip", "rt_shade.hpp", "rt_rayquery.hpp", "rt_adaptive.hip", "rt_gbuffer.hip", BODIES, PIXEL_BODIES, RAY_LIST, WAVE_BALL)])
 # One of the nine kernels for caller-supplied rays keeps the text of its body, as stream_cull_bounce_frame_kernel keeps the loop's:
 # through rk_path_query path_query_stream_kernel took 4 to 5 % longer on every series measured (profiles/ray_kernel_bodies.txt)
 PATHS_KEEPS_ITS_COPY = ("rt_stream_queries.hip", "path_query_stream_kernel")
@@ -121,7 +126,7 @@ def test_the_policies_state_the_four_points_and_nothing_workgroup_wide():
     for p in glob.glob(os.path.join(CSRC, "*")):      # the three policies it replaces are gone
         for gone in ("ShadeRaysStaged", "SqkShadeRays", "ScRayShade"):
             assert gone not in open(p).read(), (gone, p)
-    for name in (LOOP, "rt_stream_shell.hpp", BODIES):
+    for name in (LOOP, "rt_stream_shell.hpp", RAY_LIST, BODIES):
         code = code_of(name)
         for word in ("__syncthreads", "s_barrier", '"workgroup"', "rq_stage_tables", "__shared__", "HIP_DYNAMIC_SHARED"):
             assert word not in code, (name, word)
@@ -134,12 +139,48 @@ def test_the_helpers_around_the_loop_exist_once():
     found = {what: sorted(os.path.basename(p) for p in STREAMED for _ in re.findall(rx, "\n".join(l.split("//")[0] for l in open(p).read().splitlines())))
              for what, rx in defs.items()}
     assert found["quantise"] == ["rt_shade.hpp"] and found["xor_add"] == ["rt_shade.hpp"], found
-    # (the pixel queries map pixels too -- once, for the staged and the streamed kernels and for both bodies: pk_block_pixel --, and so do the
-    # two classify kernels of rt_adaptive.hip: other kernels)
-    assert found["pixel mapping"] == ["rt_adaptive.hip", "rt_adaptive.hip", PIXEL_BODIES, "rt_stream_shell.hpp"], found
+    # (the pixel queries map pixels too -- once, for the staged and the streamed kernels and for both bodies: pk_block_pixel --, and so does the
+    # one body of the two classify kernels of rt_adaptive.hip, classify_body: other kernels)
+    assert found["pixel mapping"] == ["rt_adaptive.hip", PIXEL_BODIES, "rt_stream_shell.hpp"], found
     assert found["frame store"] == ["rt_stream_shell.hpp"], found
-    # (ray_list_kernel, the twin over all records in LDS, keeps its own items: it counts, and skips by `live`)
-    assert found["halo item"] == ["rt_adaptive.hip", "rt_stream_shell.hpp"] and found["resolve scale"] == ["rt_adaptive.hip", "rt_stream_shell.hpp"], found
+    # (ray_list_kernel, the twin over all records in LDS, takes its items and stores through the same header as the streamed twins)
+    assert found["halo item"] == [RAY_LIST] and found["resolve scale"] == [RAY_LIST], found
+    adaptive, ray_list = code_of("rt_adaptive.hip"), code_of(RAY_LIST)
+    loop = adaptive.split("void ray_list_kernel(")[1].split("cnt.flush(counters);")[0].split("base += gridDim.x * WAVES * PPW) {")[1]
+    assert [l.strip() for l in loop.splitlines() if l.strip()] == [
+        "const SlItem it = sl_item<K>(fa, camx, camy, list, base + lane / LANES, n, i, j);", "if (it.use) cnt.primary();",
+        "const F3 c = render_ray_culled<COUNT>(fa, gobj, glight, sobj, scull, origin, it.dir, it.use, cnt);", "sl_resolve_store<K, RGBA8>(fa, out, it, sub, c);", "}"], loop
+    # the two classifiers run one body, which holds the walk, the ballot and the append; everything geometric sits behind its constant
+    assert len(re.findall(r"void classify_body\(", adaptive)) == 1 and "template <bool RGBA8, bool GEOMETRY>\n__device__ __forceinline__ void classify_body(" in adaptive
+    for kernel, call in (("classify_kernel", "classify_body<RGBA8, false>("), ("classify_geometry_kernel", "classify_body<RGBA8, true>(")):
+        body = adaptive.split(f"void {kernel}(")[1].split("\n}\n")[0]
+        assert body.count("classify_body<") == 1 and body.count(call) == 1 and "for (" not in body and "__ballot" not in body and "atomicAdd" not in body, kernel
+    body = adaptive.split("void classify_body(")[1].split("\n}\n")[0]
+    assert body.count("__ballot(") == 1 and body.count("atomicAdd(") == 1 and body.count("from_halo = ") == 3 and adaptive.count("from_halo = ") == 3
+    plain = re.sub(r"\n( *)if constexpr \(GEOMETRY\) \{\n.*?\n\1\}\n", "\n", body, flags=re.S)      # the body without its two geometric blocks
+    assert body.count("if constexpr (GEOMETRY) {") == 2 and "if constexpr" not in plain
+    for word in ("obj[", "nrm[", "ghalo", "geo_dot", "min_cos)"):
+        assert word in body and word not in plain.split("{", 1)[1], word
+    # the ball around a wave's hit points is formed in one place (the wavefront kernel's own two sites apart)
+    assert not re.search(r"\bwave_m(in|ax)\(double", adaptive) and "fmin(" not in adaptive and "fmax(" not in adaptive
+    assert adaptive.count("wave_hit_ball<true>(hit, sp, ball)") == 1 and adaptive.count("wave_hit_ball") == 1 and "isfinite" not in adaptive
+    everything = {os.path.basename(q): "\n".join(l.split("//")[0] for l in open(q).read().splitlines()) for q in glob.glob(os.path.join(CSRC, "*"))}
+    assert {n: c.count("1.01e-2") for n, c in everything.items() if "1.01e-2" in c} == {"rt_wavefront.hip": 8, WAVE_BALL: 1}
+    for fn in ("double wave_min(double", "double wave_max(double", "bool wave_hit_ball("):
+        assert {n: c.count(fn) for n, c in everything.items() if fn in c} == {WAVE_BALL: 1}, fn
+    ball = open(os.path.join(CSRC, WAVE_BALL)).read()
+    assert "no colour and no RT_FLAG_COUNT counter depends on it" in ball
+    # the (k, rgba8) ladder is written once, and all three launch files go through it
+    assert sorted(n for n, c in everything.items() if "k == 4u" in c) == [RAY_LIST] and everything[RAY_LIST].count("k == 4u") == 1
+    for name in ("rt_adaptive.hip", "rt_stream_adaptive.hip", "rt_stream_cull_adaptive.hip"):
+        assert everything[name].count("return sl_for_shapes(k, rgba8, [&](auto kk, auto r8) {") == 1 and "#define" not in everything[name], name
+    # the header has the standing of rt_stream_shell.hpp: nothing workgroup-wide, and no lane leaves sl_item early
+    for name in (RAY_LIST, WAVE_BALL):
+        for word in ("__syncthreads", "s_barrier", '"workgroup"', "rq_stage_tables", "__shared__", "HIP_DYNAMIC_SHARED"):
+            assert word not in everything[name], (name, word)
+    lists = ray_list.split("struct SlItem {")[1]
+    assert lists.count("return") == 1 and "    return it;\n" in lists and "break" not in lists and "continue" not in lists
+    assert '#include "rt_shade.hpp"' in ray_list and ray_list.count('#include "') == 1      # needs rt_shade.hpp alone
     # the work words leave through one function, and the class ladder of every launcher of these files is rq_for_classes
     assert len(re.findall(r"void sc_flush\(", code_of("rt_stream_cull.hpp"))) == 1
     for name in ("rt_stream_cull.hip", "rt_stream_cull_bounce.hip", "rt_stream_cull_adaptive.hip"):

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Two builds of libmi355rt.so on the kernels for caller-supplied rays (results: profiles/ray_kernel_bodies.txt) and
-on the pixel queries (section 32; profiles/pixel_kernel_bodies.txt).
+"""Two builds of libmi355rt.so on the kernels for caller-supplied rays (results: profiles/ray_kernel_bodies.txt), on
+the pixel queries (section 32; profiles/pixel_kernel_bodies.txt) and on the adaptive passes (section 33; profiles/adaptive_passes.txt).
 
   python tools/ray_kernels_ab.py --parent <another build's libmi355rt.so> [--out FILE] [--only staged,streamed,culled] [--rounds 4] [--runs 31]
   python tools/ray_kernels_ab.py --parent <another build's libmi355rt.so> --only pixels,geometry [--fast] [--out FILE]
+  python tools/ray_kernels_ab.py --parent <another build's libmi355rt.so> --only adaptive,geometry [--fast] [--out FILE]
 
 The other library is selected with MI355RT_LIB; the Python binding and the scenes are this tree's for both.  Per configuration (a scene
 and the context's flags) one child process per library, each holding one context and its buffers: the frame's own primary rays
@@ -21,7 +22,11 @@ the call has no event pair) -- the scenes of tools/gbuffer_bench.py and extents_
 stream_queries_bench.py (its field at 2 560 spheres staged and streamed, with and without RT_FLAG_NOCULL, and at 10 000 streamed) --;
 and the frame of an RT_FLAG_SSAA4 | RT_FLAG_SSAA_ADAPTIVE | RT_FLAG_SSAA_GEOMETRY context (min_cos 0.999, tau 1/32: the G pass writes
 ids and normals) as the only rank and as rank 0 of 2 (the halo rows' records: the kernel's picking mode), the scenes of
-tools/ssaa_geometry_bench.py staged and the culled field at 1 685 spheres with the adaptive passes streamed."""
+tools/ssaa_geometry_bench.py staged and the culled field at 1 685 spheres with the adaptive passes streamed.
+The adaptive passes (--only adaptive): the frame (rt_render) of RT_FLAG_SSAA2 | RT_FLAG_SSAA_ADAPTIVE and RT_FLAG_SSAA4 | RT_FLAG_SSAA_ADAPTIVE
+contexts at the default threshold, RGBA32F and RGBA8, as the only rank and as rank 0 of 2 (the halo pass), the scenes of
+tools/ssaa_adaptive_bench.py (20spheres, clebsch); and the field at 1 685 spheres with the passes streamed (RT_FLAG_STREAM |
+RT_FLAG_STREAM_ADAPTIVE) and with RT_FLAG_STREAM_CULL added.  Compared outputs: the frame and the refined count."""
 import argparse
 import hashlib
 import os
@@ -34,7 +39,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, WARM = 1920, 1080, 5
 ENTRY_POINTS = ("rt_trace_rays", "rt_occluded_rays", "rt_shade_rays", "rt_trace_paths")
 GEOMETRY = ("RT_FLAG_SSAA4", "RT_FLAG_SSAA_ADAPTIVE", "RT_FLAG_SSAA_GEOMETRY")
-# name -> (family, scene, flag names[, world])
+ADAPTIVE = {2: ("RT_FLAG_SSAA2", "RT_FLAG_SSAA_ADAPTIVE"), 4: ("RT_FLAG_SSAA4", "RT_FLAG_SSAA_ADAPTIVE")}
+# name -> (family, scene, flag names[, world[, format]])
 CONFIGS = {
     "20spheres": ("staged", ("file", "20spheres", -1), ()),
     "clebsch": ("staged", ("file", "clebsch", -1), ()),
@@ -60,6 +66,14 @@ CONFIGS = {
     "geo field 1685 str": ("geometry", ("cull_field", 1685, False), GEOMETRY + ("RT_FLAG_STREAM", "RT_FLAG_STREAM_ADAPTIVE"), 1),
     "geo field 1685 str 0/2": ("geometry", ("cull_field", 1685, False), GEOMETRY + ("RT_FLAG_STREAM", "RT_FLAG_STREAM_ADAPTIVE"), 2),
 }
+# the adaptive passes: family "adaptive" -> the adaptive frame without the geometric term, per k, format and layout
+for _scene in ("20spheres", "clebsch"):
+    for _k in (2, 4):
+        for _fmt in ("RGBA32F", "RGBA8"):
+            for _world in (1, 2):
+                CONFIGS[f"ada{_k} {_scene} {_fmt[4:].lower()}" + (" 0/2" if _world == 2 else "")] = ("adaptive", ("file", _scene, -1), ADAPTIVE[_k], _world, _fmt)
+CONFIGS["ada4 field 1685 str"] = ("adaptive", ("cull_field", 1685, False), ADAPTIVE[4] + ("RT_FLAG_STREAM", "RT_FLAG_STREAM_ADAPTIVE"), 1, "RGBA32F")
+CONFIGS["ada4 field 1685 cull"] = ("adaptive", ("cull_field", 1685, False), ADAPTIVE[4] + ("RT_FLAG_STREAM", "RT_FLAG_STREAM_ADAPTIVE", "RT_FLAG_STREAM_CULL"), 1, "RGBA32F")
 PIXEL_SERIES = (("rt_render_gbuffer", "planes"), ("rt_object_extents", "frame"), ("rt_object_extents", "64x64"), ("rt_pick", "4096px"))
 UNTIMED = ("rt_pick",)      # (blocks and copies to the host: no event pair of its own; its outputs are compared)
 
@@ -89,6 +103,11 @@ def child(config, runs, fast=False):
     for name in flag_names:
         flags |= getattr(pkg, name)
     n, dev = W * H, "cuda:0"
+    if family == "adaptive":
+        r = pkg.Renderer(sc, device=0, rank=0, world=world, flags=flags, fmt=getattr(pkg, "RT_FMT_" + CONFIGS[config][4]))
+        assert r.streamed_adaptive == ("RT_FLAG_STREAM_ADAPTIVE" in flag_names) and r.stream_cull_adaptive == ("RT_FLAG_STREAM_CULL" in flag_names), config
+        assert (world == 1) == (r.local_rows == H)
+        return serve(torch, r, {("rt_render", "frame"): (lambda: r.update(), ())}, runs, refined=True)
     if family in ("pixels", "geometry"):
         return pixel_child(pkg, torch, family, sc, flags, flag_names, world, runs)
     r = pkg.Renderer(sc, device=0, flags=flags)
@@ -139,7 +158,7 @@ def pixel_child(pkg, torch, family, sc, flags, flag_names, world, runs):
                      ("rt_pick", "4096px"): (pick, picked)}, runs)
 
 
-def serve(torch, r, calls, runs):
+def serve(torch, r, calls, runs, refined=False):
     warm = set()
     print("ready", flush=True)
     for line in sys.stdin:
@@ -155,6 +174,8 @@ def serve(torch, r, calls, runs):
                 h.update(o.tobytes() if isinstance(o, np.ndarray) else o.cpu().numpy().tobytes())
             if not outputs:
                 h.update(np.ascontiguousarray(r.download()).tobytes())      # (the control and the adaptive frames: the frame)
+            if refined:
+                h.update(str(int(r.refined)).encode())      # (... and the refined count)
             print(h.hexdigest(), flush=True)
             continue
         if key not in warm:
@@ -212,7 +233,7 @@ def main():
             for p in procs:
                 if p.stdout.readline().strip() != "ready":
                     raise RuntimeError(f"{config}: a child did not start ({p.poll()})")
-            if family == "geometry":
+            if family in ("geometry", "adaptive"):
                 series = [("rt_render", "frame")]
             elif family == "pixels":
                 series = list(PIXEL_SERIES)
@@ -222,7 +243,7 @@ def main():
             for entry, which in series:
                 if entry in UNTIMED:
                     same = ask(procs[0], f"out {entry} {which}") == ask(procs[1], f"out {entry} {which}")
-                    emit(f"{family:9s}{config:22s}{entry:19s}{which:9s} outputs only: same result {same}")
+                    emit(f"{family:9s}{config:24s}{entry:19s}{which:9s} outputs only: same result {same}")
                     continue
                 a, b = [], []
                 for _ in range(args.rounds):
@@ -232,7 +253,7 @@ def main():
                 ma, mb, spread = float(np.median(a)), float(np.median(b)), max(a) - min(a)
                 verdict = "faster beyond the spread" if ma - mb > spread else ("SLOWER beyond the spread" if mb - ma > spread else "within the spread")
                 name = "control: rt_render" if (entry, which) == ("rt_render", "row") else entry
-                emit(f"{family:9s}{config:22s}{name:19s}{which:9s} parent {ma:10.1f} [{min(a):10.1f} .. {max(a):10.1f}]  this tree {mb:10.1f} [{min(b):10.1f} .. {max(b):10.1f}]  "
+                emit(f"{family:9s}{config:24s}{name:19s}{which:9s} parent {ma:10.1f} [{min(a):10.1f} .. {max(a):10.1f}]  this tree {mb:10.1f} [{min(b):10.1f} .. {max(b):10.1f}]  "
                      f"x {mb / ma:6.4f}  spread {spread:8.1f} ({100.0 * spread / ma:5.2f} %)  {verdict:25s} same result {same}")
         finally:
             for p in procs:
