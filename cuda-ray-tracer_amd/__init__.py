@@ -37,6 +37,7 @@ RT_FLAG_STREAM_ADAPTIVE = 32768             # adaptive supersampling takes its s
 RT_FLAG_STREAM_CULL = 524288                # a streamed context keeps its unit spheres in a spatial order and culls them by 64-entry chunk (same frame)
 RT_FLAG_STREAM_CULL_BOUNCE = 1048576        # ... and culls the chunks of its bounce rays per ray (with RT_FLAG_STREAM_CULL, mirrors and at least two chunks; same frame)
 RT_FLAG_STREAM_CULL_RAYS = 2097152          # ... and culls the chunks per caller-supplied ray in the ray queries (with RT_FLAG_STREAM_CULL, streamed queries and at least two chunks; same outputs)
+RT_FLAG_STREAM_CULL_PIXELS = 4194304        # ... and culls the chunks by the block's cone in the pixel queries (with RT_FLAG_STREAM_CULL, streamed queries and at least two chunks; same outputs)
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -51,6 +52,7 @@ ABI_SYMBOLS = [
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries", "rt_get_streamed_adaptive",
     "rt_get_stream_cull", "rt_debug_stream_bounds", "rt_debug_stream_cull", "rt_get_stream_cull_adaptive", "rt_debug_stream_cull_adaptive",
     "rt_get_stream_cull_bounce", "rt_debug_stream_cull_bounce", "rt_get_stream_cull_rays", "rt_debug_stream_cull_rays",
+    "rt_get_stream_cull_pixels", "rt_debug_stream_cull_pixels",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
@@ -238,6 +240,9 @@ def lib():
         L.rt_debug_stream_cull_bounce.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_get_stream_cull_rays.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_debug_stream_cull_rays.argtypes = [vp, C.POINTER(C.c_uint64)]
+        if LIB_PATH != os.environ.get("MI355RT_LIB") or hasattr(L, "rt_get_stream_cull_pixels"):   # (an earlier build under MI355RT_LIB: as rt_sort_rays below)
+            L.rt_get_stream_cull_pixels.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.rt_debug_stream_cull_pixels.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
@@ -625,6 +630,22 @@ class Renderer:
         only where stream_cull_rays is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
         w = (C.c_uint64 * 8)()
         _check(lib().rt_debug_stream_cull_rays(self._h, w))
+        return [int(v) for v in w]
+
+    @property
+    def stream_cull_pixels(self):
+        """True where the pixel queries (gbuffer, pick, object_extents) cull the unit-sphere chunks by the block's cone:
+        RT_FLAG_STREAM_CULL_PIXELS on a context whose stream_cull and streamed_queries are True, with at least two chunks
+        (rt_get_stream_cull_pixels)."""
+        n = C.c_uint32()
+        _check(lib().rt_get_stream_cull_pixels(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def stream_cull_pixels_stats(self):
+        """The eight work words the culled pixel queries share, since the context was created (rt_debug_stream_cull_pixels; waits).  They
+        exist only where stream_cull_pixels is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
+        w = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_stream_cull_pixels(self._h, w))
         return [int(v) for v in w]
 
     @property
@@ -1168,6 +1189,11 @@ class MultiRenderer:
     def stream_cull_rays(self):
         """Renderer.stream_cull_rays of rt_multi_query_ctx's context: the one that answers the ray queries."""
         return self.query.stream_cull_rays
+
+    @property
+    def stream_cull_pixels(self):
+        """Renderer.stream_cull_pixels of rt_multi_query_ctx's context (the contexts share scene and flags, hence the decision)."""
+        return self.query.stream_cull_pixels
 
     @property
     def query(self):

@@ -34,7 +34,9 @@
      RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
      RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V), RT_CAT(rt_launch_stream_cull_bounce, V), \
      RT_CAT(rt_launch_stream_cull_trace_rays, V), RT_CAT(rt_launch_stream_cull_occluded_rays, V), RT_CAT(rt_launch_stream_cull_shade_rays, V), \
-     RT_CAT(rt_launch_stream_cull_trace_paths, V), RT_CAT(rt_launch_stream_cull_ray_list, V)}
+     RT_CAT(rt_launch_stream_cull_trace_paths, V), \
+     RT_CAT(rt_launch_pixel_cull_gbuffer, V), RT_CAT(rt_launch_pixel_cull_pick, V), RT_CAT(rt_launch_pixel_cull_object_extents, V), \
+     RT_CAT(rt_launch_stream_cull_ray_list, V)}
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
 // the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
 #define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
@@ -242,6 +244,9 @@ struct rt_ctx {
     // ... and the unit-sphere chunks of caller-supplied rays culled per ray (rt_stream_cull_rays.hip), with work words the four entry points share
     bool stream_cull_rays = false; // RT_FLAG_STREAM_CULL_RAYS && stream_cull && stream_queries && n_chunks >= 2
     DevMem<unsigned long long> d_cull_rays_stats; // as d_cull_stats
+    // ... and the unit-sphere chunks of the pixel queries culled by the block's cone (rt_stream_cull_pixels.hip), with work words the three entry points share
+    bool stream_cull_pixels = false; // RT_FLAG_STREAM_CULL_PIXELS && stream_cull && stream_queries && n_chunks >= 2
+    DevMem<unsigned long long> d_cull_pixels_stats; // as d_cull_stats
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -574,6 +579,9 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
     // ... and do the ray queries cull the chunks per caller-supplied ray (rt_stream_cull_rays.hip)?  The culling decision, streamed queries and a second
     // chunk.  False: launch for launch the context without the flag.  rt_set_scene rebuilds the bounds and keeps the layout, so this holds too.
     ctx->stream_cull_rays = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_RAYS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;
+    // ... and do the pixel queries cull the chunks by the block's cone (rt_stream_cull_pixels.hip)?  The same three conditions under a flag of its own.
+    // False: launch for launch the context without the flag.  (stream_cull implies fa.cull: the cone exists.)
+    ctx->stream_cull_pixels = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_PIXELS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;
     return RT_OK;
 }
 
@@ -600,6 +608,8 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
             if (int rc = device_table(ctx->d_cull_bounce_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-bounce work words")) return rc;
         if (e && !std::strcmp(e, "1") && ctx->stream_cull_rays)
             if (int rc = device_table(ctx->d_cull_rays_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-rays work words")) return rc;
+        if (e && !std::strcmp(e, "1") && ctx->stream_cull_pixels)
+            if (int rc = device_table(ctx->d_cull_pixels_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-pixels work words")) return rc;
         if (e && !std::strcmp(e, "1") && ctx->stream_cull_adaptive && !(fa.n_gq && fa.n_cub))
             if (int rc = device_table(ctx->d_cull_adaptive_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-adaptive work words")) return rc;
     }
@@ -999,6 +1009,10 @@ extern "C" int rt_render_sparse(rt_ctx *ctx, const double cam[16], void *dev_msg
 }
 
 // ---- G-buffer (rt_gbuffer.hip) ---------------------------------------------------------------------------
+// The pixel entry points of a context whose RT_FLAG_STREAM_CULL_PIXELS decision is true (rt_ctx::stream_cull_pixels, decided once in rt_create) take the
+// culled launchers (rt_stream_cull_pixels.hip): the streamed twin's arguments and these.  The G pass of an adaptive frame keeps its own two.
+#define RT_CULL_PIXELS_ARGS(ctx) (ctx)->d_bounds, (ctx)->n_chunks, (ctx)->d_cull_pixels_stats
+
 // The frame arguments of a G-buffer pass: a COPY of the context's (geometry, scene layout) with this call's camera -- the context's own
 // FrameArgs, which carry the render kernels' frame-to-frame state, are neither read for that state nor written.
 static int gbuffer_args(const char *who, rt_ctx *ctx, const double cam[16], FrameArgs &fa)
@@ -1023,7 +1037,8 @@ extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev
     FrameArgs fa;
     if (int rc = gbuffer_args("rt_render_gbuffer", ctx, cam, fa)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = RT_QUERY_KERNEL(ctx, gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
+    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, RT_CULL_PIXELS_ARGS(ctx), stream)
+                                                 : RT_QUERY_KERNEL(ctx, gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "G-buffer kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1048,7 +1063,8 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
     if (int rc = gbuffer_args("rt_pick", ctx, cam, fa)) return rc;
     if (int rc = ctx->pick.reserve(n, sizeof(uint32_t) * 2, sizeof(rt_hit))) return rc;
     RT_HIP(hipMemcpyAsync(ctx->pick.in, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = RT_QUERY_KERNEL(ctx, pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
+    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, RT_CULL_PIXELS_ARGS(ctx), stream)
+                                                 : RT_QUERY_KERNEL(ctx, pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pick kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out_host, ctx->pick.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1092,7 +1108,8 @@ extern "C" int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32
     if (int rc = extents_args("rt_object_extents", ctx, cam, rect, dev_out, true, fa, r)) return rc;
     if (fa.n_obj == 0u) return RT_OK;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), stream);
+    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), RT_CULL_PIXELS_ARGS(ctx), stream)
+                                                 : RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents: kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1109,7 +1126,8 @@ extern "C" int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const u
         return fail(RT_ERR_INVALID, "rt_object_extents_host: the stream is capturing, and this call allocates and waits; capture rt_object_extents (device memory) instead");
     if (fa.n_obj == 0u) return RT_OK;
     if (int rc = ctx->ext.reserve(fa.n_obj, 8, sizeof(rt_object_extent))) return rc;
-    const hipError_t e = RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), stream);
+    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), RT_CULL_PIXELS_ARGS(ctx), stream)
+                                                 : RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents_host: kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out_host, ctx->ext.out, sizeof(rt_object_extent) * (size_t) fa.n_obj, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1136,7 +1154,7 @@ static int rays_ready(const char *who, rt_ctx *ctx)
 static uint32_t rays_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
 
 // The ray entry points of a context whose RT_FLAG_STREAM_CULL_RAYS decision is true (rt_ctx::stream_cull_rays, decided once in rt_create) take the culled
-// launchers (rt_stream_cull_rays.hip): the streamed twin's arguments and these.  The pixel queries keep RT_QUERY_KERNEL's.
+// launchers (rt_stream_cull_rays.hip): the streamed twin's arguments and these.  The pixel queries have a decision of their own (RT_CULL_PIXELS_ARGS).
 #define RT_CULL_RAYS_ARGS(ctx) (ctx)->d_bounds, (ctx)->n_chunks, (ctx)->d_cull_rays_stats
 
 static hipError_t trace_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, void *dev_hits, hipStream_t stream)
@@ -1793,6 +1811,22 @@ extern "C" int rt_debug_stream_cull_rays(rt_ctx *ctx, uint64_t out[8])
         return fail(RT_ERR_INVALID, "rt_debug_stream_cull_rays: the context keeps no work words (they exist where rt_get_stream_cull_rays says 1 and MI355RT_STREAM_CULL_STATS=1 "
                                     "was set at rt_create)");
     return read_behind_last_call("rt_debug_stream_cull_rays", ctx, out, ctx->d_cull_rays_stats, sizeof(uint64_t) * 8);
+}
+
+extern "C" int rt_get_stream_cull_pixels(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_pixels: null argument");
+    *on = ctx->stream_cull_pixels ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_stream_cull_pixels(rt_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_pixels: null argument");
+    if (!ctx->d_cull_pixels_stats)
+        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_pixels: the context keeps no work words (they exist where rt_get_stream_cull_pixels says 1 and MI355RT_STREAM_CULL_STATS=1 "
+                                    "was set at rt_create)");
+    return read_behind_last_call("rt_debug_stream_cull_pixels", ctx, out, ctx->d_cull_pixels_stats, sizeof(uint64_t) * 8);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

@@ -103,6 +103,14 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_shade_rays, const FrameArgs *fa
                void *hits, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
                void *last, void *ends, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+// rt_stream_cull_pixels.hip: the streamed pixel launchers with the chunks culled by the block's cone (RT_FLAG_STREAM_CULL_PIXELS): each its streamed twin's
+// arguments, the chunk bounds and the work words the three share (8, or NULL)
+RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
+               float *out_normal, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n,
+               void *out, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_object_extents, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect,
+               void *out, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
 // rt_stream_cull_adaptive.hip: rt_launch_stream_ray_list with the same chunks culled (rt_get_stream_cull_adaptive): its arguments, the chunk bounds and
 // work words of its own (8, or NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
@@ -145,6 +153,10 @@ struct Kernels {
     decltype(&rt_launch_stream_cull_occluded_rays_strict) stream_cull_occluded_rays;
     decltype(&rt_launch_stream_cull_shade_rays_strict) stream_cull_shade_rays;
     decltype(&rt_launch_stream_cull_trace_paths_strict) stream_cull_trace_paths;
+    // the pixel queries of a context whose RT_FLAG_STREAM_CULL_PIXELS decision is true (rt_get_stream_cull_pixels)
+    decltype(&rt_launch_pixel_cull_gbuffer_strict) pixel_cull_gbuffer;
+    decltype(&rt_launch_pixel_cull_pick_strict) pixel_cull_pick;
+    decltype(&rt_launch_pixel_cull_object_extents_strict) pixel_cull_object_extents;
     // the halo and refine passes of a context whose streamed adaptive passes cull as well (rt_get_stream_cull_adaptive)
     decltype(&rt_launch_stream_cull_ray_list_strict) stream_cull_ray_list;
 };

@@ -52,6 +52,8 @@
 //                             changes without MI355RT_STREAM_CULL, without mirrors or below 65 unit spheres
 //   MI355RT_STREAM_CULL_RAYS=1  ... and the ray-query hooks (trace, shade, pick path) cull the chunks per ray (RT_FLAG_STREAM_CULL_RAYS;
 //                             same answers); nothing changes without MI355RT_STREAM_CULL and MI355RT_STREAM_QUERIES or below 65 unit spheres
+//   MI355RT_STREAM_CULL_PIXELS=1  ... and the pixel hooks (pick, extents) cull the chunks by the block's cone (RT_FLAG_STREAM_CULL_PIXELS;
+//                             same answers); nothing changes without MI355RT_STREAM_CULL and MI355RT_STREAM_QUERIES or below 65 unit spheres
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -369,6 +371,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_CULL_RAYS")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_RAYS;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_RAYS", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_CULL_PIXELS=1: ... and the chunks of the pixel hooks (pick, extents), by the block's cone
+    if (const char *f = std::getenv("MI355RT_STREAM_CULL_PIXELS")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_PIXELS;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_PIXELS", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

@@ -149,8 +149,9 @@ typedef struct rt_scene_desc {
  * exactly the meaning the definition gives c = -inf.  No default crease angle is chosen: nobody has measured one.
  * In strict contexts obj and N are the G-buffer definition's values for surfaces of degree <= 2; in RT_FLAG_FAST contexts (and for
  * degree 3) they are bit for bit what rt_render_gbuffer / rt_pick report on a context without supersampling and otherwise equal flags
- * (the same kernel computes them).  rt_render adds, on `stream`, that kernel for this rank's rows (and, world > 1, for the rows just
- * outside each band) in front of the classify kernel; still nothing is read back and frames can be captured into a graph.
+ * (the same kernel computes them, or -- RT_FLAG_STREAM_CULL_PIXELS -- its culling twin, bit-equal by that flag's rule).  rt_render
+ * adds, on `stream`, that kernel for this rank's rows (and, world > 1, for the rows just outside each band) in front of the classify
+ * kernel; still nothing is read back and frames can be captured into a graph.
  * rt_get_ssaa_refined and rt_render_sparse work as in every adaptive context.  RT_FLAG_COUNT does not book the rays of that pass (as
  * rt_render_gbuffer books none): primary_rays = width * local_rows + halo rays + k^2 * refined, with the new refined count.
  * Known limits: two sheets of ONE object at different depths whose normals agree are not told apart (there is no depth term), and a
@@ -226,7 +227,9 @@ typedef struct rt_scene_desc {
  * stores: the plain pass keeps the rule of rt_get_streamed (at 569 ... 1 684 spheres it is still the wavefront kernel).  S(X, Y) is
  * the colour of sample (X, Y) of the k-times finer grid by the arithmetic of the streamed frame kernel, i.e. of rt_shade_rays, resolved
  * with the fixed pairwise tree, times 1/k^2, quantised for RGBA8 as everywhere.  obj / N of RT_FLAG_SSAA_GEOMETRY are bit for bit what
- * rt_render_gbuffer / rt_pick report on a streamed-queries context (the same kernel computes them).
+ * rt_render_gbuffer / rt_pick report on a streamed-queries context (the same kernel computes them; where that context's
+ * RT_FLAG_STREAM_CULL_PIXELS decision is true its two calls run the culling twin while the G pass keeps the streamed kernel, and the
+ * equality holds by that flag's rule -- the same spheres tested, an order-independent acceptance -- not by identity of kernel).
  * Accuracy: in strict contexts, for surfaces of degree <= 2, the frame and rt_get_ssaa_refined are bit-identical to the CPU reference's
  * composition and to the context without the flag wherever that one is accepted; for every degree tau < 0 gives bit for bit the frame of
  * a RT_FLAG_STREAM | RT_FLAG_SSAAk context.  RT_FLAG_FAST is its own arithmetic, held to 1e-5 relative like every RT_FLAG_FAST frame.
@@ -286,10 +289,10 @@ typedef struct rt_scene_desc {
  * No refusal of its own; combines with every flag; through rt_create_multi it reaches every context.
  * Known limits: the bounds are spheres around Morton runs of 64 entries, not a hierarchy: a scene whose spheres all overlap gains
  * nothing and pays one decision per chunk, and so does a scene of a single chunk (measured: 20spheres with its 19 lights takes 1.67 x
- * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Bounce rays: RT_FLAG_STREAM_CULL_BOUNCE below; caller-supplied rays: RT_FLAG_STREAM_CULL_RAYS below.  Out of scope: bounds for the other classes;
- * a second level over the chunk bounds; culling in the streamed pixel queries (they only read the reordered table); reordering the
- * refine list for tighter wave cones;
- * counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
+ * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Bounce
+ * rays: RT_FLAG_STREAM_CULL_BOUNCE below; caller-supplied rays: RT_FLAG_STREAM_CULL_RAYS below; the pixel queries:
+ * RT_FLAG_STREAM_CULL_PIXELS below.  Out of scope: bounds for the other classes; a second level over the chunk bounds; reordering the
+ * refine list for tighter wave cones; counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
 #define RT_FLAG_STREAM_CULL 524288u
 
 /* Culled bounce rays (csrc/rt_stream_cull_bounce.hip): in a culled streamed frame the nearest-hit query of a bounce
@@ -338,7 +341,7 @@ typedef struct rt_scene_desc {
  * shadow ray as the ray it is; t_max of rt_occluded_rays bounds the roots, not the verdicts.
  * Not culled for: a ray with |d|^2 <= 1e-7 or not finite (the reference's linear branch is not geometry) -- its WAVE then stages every
  * chunk; a ray with a component beyond 1e100 (it takes the dense path over all objects); a chunk whose bound is +inf; the other classes'
- * tables; the pixel queries (rt_render_gbuffer, rt_pick, rt_object_extents), which keep the streamed kernels.
+ * tables; the pixel queries (rt_render_gbuffer, rt_pick, rt_object_extents), which have a flag of their own (RT_FLAG_STREAM_CULL_PIXELS below).
  * Results are unchanged by definition: every output is bit for bit that of the same context without the flag, strict and RT_FLAG_FAST,
  * every degree.  ms, capturability, ranks and rt_set_scene are those of the streamed queries.  Through rt_create_multi the flag reaches
  * every context.  All sixteen instantiations of both builds fit two waves per SIMD without a spill (at most 216 VGPRs), so no scene is
@@ -351,8 +354,41 @@ typedef struct rt_scene_desc {
  * 12 204 us (0.19 - 0.25 x over the four entry points), 1 685 spheres 0.41 - 0.51 x; the same rays shuffled stage 98 - 100 % of the
  * chunks and take 1.13 - 1.32 x in rt_trace_rays, rt_occluded_rays and rt_trace_paths while rt_shade_rays still gains (0.55 - 0.85 x);
  * at 65 spheres (two chunks) every entry point is slower, 1.13 - 1.29 x.
- * Out of scope: the pixel queries; bounds for the other classes; a hierarchy over the bounds; the flag as a default. */
+ * Out of scope: bounds for the other classes; a hierarchy over the bounds; the flag as a default. */
 #define RT_FLAG_STREAM_CULL_RAYS 2097152u
+
+/* Culled pixel queries (csrc/rt_stream_cull_pixels.hip): on a streamed-queries context rt_render_gbuffer, rt_pick
+ * and rt_object_extents (and through them rt_render_gbuffer_multi, rt_object_extents_multi[_host], mi355rt_update_pick and
+ * mi355rt_update_extents) stage and sweep every chunk of the unit-sphere table for every 8 x 8 block: O(pixels x spheres).  With this flag
+ * a wave asks sphere_in_cone -- the predicate its block's cone already asks about every sphere -- about the chunk bounds first, lane =
+ * chunk, and stages only the chunks whose bound reaches into the cone; inside a staged chunk the per-sphere cone runs as before.  One
+ * decision per context, made in rt_create and never revisited (rt_set_scene rebuilds the bounds and keeps the layout);
+ * rt_get_stream_cull_pixels reports it:
+ *     stream cull pixels = RT_FLAG_STREAM_CULL_PIXELS && rt_get_stream_cull && rt_get_streamed_queries && at least 2 chunks (65 unit spheres)
+ * False: the context is, launch for launch and byte for byte, the context without the flag.  There is no refusal of its own, and the flag
+ * combines with every other.  True: the entry points launch the culling twins of the streamed pixel kernels (the same arguments, grid,
+ * loads and stores; graph nodes as before: planes 1, picks 1, extents 2).
+ * Not culled: the other classes' tables (general quadrics, planes, degree 3), streamed in full; a chunk whose bound is +inf (a sphere
+ * without a radius in it); picks -- rt_pick's pixels are unrelated, so its waves run the same loop under a cone that culls nothing and
+ * stage every chunk; the G pass of an RT_FLAG_SSAA_GEOMETRY frame, which keeps the streamed kernels.
+ * Results are unchanged by definition: a skipped bound implies that every member is skipped by the same predicate, and the per-sphere cone
+ * skips exactly those members already, so the spheres tested are the unflagged kernels' and the acceptance rule does not depend on their
+ * order (nearest, lowest object index on a tie).  Every output is bit for bit that of the same context without the flag, strict and
+ * RT_FLAG_FAST, every degree; a picked pixel is the planes' entry (one kernel, two launch modes, as before), and extents are the
+ * reduction of the planes.  ms, capturability, ranks and rt_set_scene are those of the streamed queries.  Through rt_create_multi the
+ * flag reaches every context.  All eight instantiations of both builds fit two waves per SIMD without a spill, so no scene is excluded.
+ * Known limits: picks gain nothing from culling and pay one verdict per chunk; a scene of two chunks can remove little and pays the
+ * verdicts per block; chunks are not pruned against the nearest hit found so far and not visited near to far; the bounds are spheres
+ * around Morton runs of 64 entries, not a hierarchy.  Measured (profiles/stream_cull_pixels.txt; MI355X,
+ * 1920 x 1080, strict, the sphere field, against the same context without the flag): 10 000 spheres rt_render_gbuffer 1 112 -> 157 us
+ * (0.14 x), rt_object_extents 1 134 -> 172 us (0.15 x), 11 % of the chunks staged; 1 685 spheres 203 -> 73 us and 204 -> 79 us
+ * (0.36 x, 0.39 x); 65 spheres (two chunks) both inside the unflagged series' spread (27.2 / 27.3 us, 31.6 / 31.5 us).  rt_pick of 1
+ * and of 4 096 pixels stages every chunk and saves not one test; by the host's clock around the blocking call it measured 0.91 - 0.97 x
+ * at all three sizes (1 630 -> 1 481 us for one pixel at 10 000 spheres).  That figure is unexplained -- the two kernels' code was not
+ * compared -- and promises nothing: expect the unflagged time, neither a gain nor a guaranteed absence of overhead.
+ * Out of scope: per-lane culling for picks; the adaptive G pass; best_t pruning, near-to-far order, a hierarchy over the bounds; bounds
+ * for the other classes; the flag as a default.  Supersampling contexts stay refused by the G-buffer family as before. */
+#define RT_FLAG_STREAM_CULL_PIXELS 4194304u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -570,6 +606,9 @@ int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on);
  * rt_pick_paths cull the unit-sphere chunks per caller-supplied ray, else 0.  RT_ERR_INVALID for a NULL argument (before a device is
  * looked for). */
 int rt_get_stream_cull_rays(const rt_ctx *ctx, uint32_t *on);
+/* Culled pixel queries (RT_FLAG_STREAM_CULL_PIXELS above): *on = 1 where rt_render_gbuffer, rt_pick and rt_object_extents cull the
+ * unit-sphere chunks by the block's cone, else 0.  RT_ERR_INVALID for a NULL argument (before a device is looked for). */
+int rt_get_stream_cull_pixels(const rt_ctx *ctx, uint32_t *on);
 
 /* ---------------------------------------------------------------------------------------------------
  * G-buffer: what is under a pixel (object, depth, normal of the PRIMARY hit) and pixel picking
@@ -996,6 +1035,15 @@ int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8]);
  * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true; otherwise the
  * kernels count nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
 int rt_debug_stream_cull_rays(rt_ctx *ctx, uint64_t out[8]);
+/* ... and the work words of the culled pixel queries (rt_get_stream_cull_pixels), eight words that rt_render_gbuffer, rt_pick,
+ * rt_object_extents and the calls that go through them share, cumulative since rt_create.  Waits as rt_set_scene_status does.
+ *   [0] chunk decisions: one per (wave, nearest-hit call with a live pixel, chunk)      [1] chunks staged
+ *   [2] entries asked inside staged chunks      [3] entries swept      [4] - [7] 0
+ * A wave makes one call per 8 x 8 block of the planes, per block of each tile of an extents rectangle, per 64 picked pixels; a pick's
+ * cone culls nothing, so there [1] == [0].
+ * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true; otherwise the
+ * kernels count nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
+int rt_debug_stream_cull_pixels(rt_ctx *ctx, uint64_t out[8]);
 
 /* Replaces cleanup_update (include/update.h:8). */
 int rt_destroy(rt_ctx *ctx);
