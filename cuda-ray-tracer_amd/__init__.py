@@ -561,13 +561,6 @@ class Renderer:
         _check(lib().rt_get_streamed_adaptive(self._h, C.byref(n)))
         return bool(n.value)
 
-    @property
-    def stream_cull(self):
-        """True where update() culls whole chunks of the unit-sphere table: RT_FLAG_STREAM_CULL on a streamed context whose culling is on."""
-        n = C.c_uint32()
-        _check(lib().rt_get_stream_cull(self._h, C.byref(n)))
-        return bool(n.value)
-
     def stream_bounds(self):
         """Diagnostics: the chunk-bound table as the device holds it, as bytes (64 per chunk; rt_debug_stream_bounds; waits).  Empty
         where stream_cull is False."""
@@ -577,76 +570,6 @@ class Renderer:
         if n.value:
             _check(lib().rt_debug_stream_bounds(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
         return out
-
-    def stream_cull_stats(self):
-        """The culling kernel's eight work words since the context was created (rt_debug_stream_cull; waits).  They exist only where
-        stream_cull is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
-        w = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_stream_cull(self._h, w))
-        return [int(v) for v in w]
-
-    @property
-    def stream_cull_adaptive(self):
-        """True where the halo and refine passes of an adaptive frame cull whole chunks of the unit-sphere table as well: stream_cull and
-        streamed_adaptive on a scene of at least two chunks (rt_get_stream_cull_adaptive)."""
-        n = C.c_uint32()
-        _check(lib().rt_get_stream_cull_adaptive(self._h, C.byref(n)))
-        return bool(n.value)
-
-    def stream_cull_adaptive_stats(self):
-        """The eight work words of the culling halo and refine kernels since the context was created (rt_debug_stream_cull_adaptive;
-        waits).  They exist only where stream_cull_adaptive is True, MI355RT_STREAM_CULL_STATS=1 was in the environment when the context
-        was created, and the scene does not hold both general quadrics and degree-3 objects."""
-        w = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_stream_cull_adaptive(self._h, w))
-        return [int(v) for v in w]
-
-    @property
-    def stream_cull_bounce(self):
-        """True where update() culls the unit-sphere chunks of its bounce rays per ray as well: RT_FLAG_STREAM_CULL_BOUNCE on a context whose
-        stream_cull is True, with a mirror in the scene, max_reflections >= 1 and at least two chunks (rt_get_stream_cull_bounce)."""
-        n = C.c_uint32()
-        _check(lib().rt_get_stream_cull_bounce(self._h, C.byref(n)))
-        return bool(n.value)
-
-    def stream_cull_bounce_stats(self):
-        """The eight work words of the bounce queries since the context was created (rt_debug_stream_cull_bounce; waits).  They exist only
-        where stream_cull_bounce is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
-        w = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_stream_cull_bounce(self._h, w))
-        return [int(v) for v in w]
-
-    @property
-    def stream_cull_rays(self):
-        """True where the ray queries (trace_rays, occluded_rays, shade_rays, trace_paths, pick_paths) cull the unit-sphere chunks per
-        caller-supplied ray: RT_FLAG_STREAM_CULL_RAYS on a context whose stream_cull and streamed_queries are True, with at least two
-        chunks (rt_get_stream_cull_rays)."""
-        n = C.c_uint32()
-        _check(lib().rt_get_stream_cull_rays(self._h, C.byref(n)))
-        return bool(n.value)
-
-    def stream_cull_rays_stats(self):
-        """The eight work words the culled ray queries share, since the context was created (rt_debug_stream_cull_rays; waits).  They exist
-        only where stream_cull_rays is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
-        w = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_stream_cull_rays(self._h, w))
-        return [int(v) for v in w]
-
-    @property
-    def stream_cull_pixels(self):
-        """True where the pixel queries (gbuffer, pick, object_extents) cull the unit-sphere chunks by the block's cone:
-        RT_FLAG_STREAM_CULL_PIXELS on a context whose stream_cull and streamed_queries are True, with at least two chunks
-        (rt_get_stream_cull_pixels)."""
-        n = C.c_uint32()
-        _check(lib().rt_get_stream_cull_pixels(self._h, C.byref(n)))
-        return bool(n.value)
-
-    def stream_cull_pixels_stats(self):
-        """The eight work words the culled pixel queries share, since the context was created (rt_debug_stream_cull_pixels; waits).  They
-        exist only where stream_cull_pixels is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
-        w = (C.c_uint64 * 8)()
-        _check(lib().rt_debug_stream_cull_pixels(self._h, w))
-        return [int(v) for v in w]
 
     @property
     def samples(self):
@@ -1072,6 +995,61 @@ class Renderer:
         d["cubic_points"] = int(x.cubic_points)
         d["cubic_refused"] = int(x.cubic_refused)
         return d
+
+
+# The culling families of a context (csrc/rt_capi.cpp: CullFamily), one row each: the Renderer property that reads the decision and the
+# Renderer method <property>_stats that reads the family's eight work words -- name, getter, debug reader, the two docstrings.
+_CULL_FAMILIES = (
+    ("stream_cull", "rt_get_stream_cull", "rt_debug_stream_cull",
+     """True where update() culls whole chunks of the unit-sphere table: RT_FLAG_STREAM_CULL on a streamed context whose culling is on.""",
+     """The culling kernel's eight work words since the context was created (rt_debug_stream_cull; waits).  They exist only where
+        stream_cull is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""),
+    ("stream_cull_adaptive", "rt_get_stream_cull_adaptive", "rt_debug_stream_cull_adaptive",
+     """True where the halo and refine passes of an adaptive frame cull whole chunks of the unit-sphere table as well: stream_cull and
+        streamed_adaptive on a scene of at least two chunks (rt_get_stream_cull_adaptive).""",
+     """The eight work words of the culling halo and refine kernels since the context was created (rt_debug_stream_cull_adaptive;
+        waits).  They exist only where stream_cull_adaptive is True, MI355RT_STREAM_CULL_STATS=1 was in the environment when the context
+        was created, and the scene does not hold both general quadrics and degree-3 objects."""),
+    ("stream_cull_bounce", "rt_get_stream_cull_bounce", "rt_debug_stream_cull_bounce",
+     """True where update() culls the unit-sphere chunks of its bounce rays per ray as well: RT_FLAG_STREAM_CULL_BOUNCE on a context whose
+        stream_cull is True, with a mirror in the scene, max_reflections >= 1 and at least two chunks (rt_get_stream_cull_bounce).""",
+     """The eight work words of the bounce queries since the context was created (rt_debug_stream_cull_bounce; waits).  They exist only
+        where stream_cull_bounce is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""),
+    ("stream_cull_rays", "rt_get_stream_cull_rays", "rt_debug_stream_cull_rays",
+     """True where the ray queries (trace_rays, occluded_rays, shade_rays, trace_paths, pick_paths) cull the unit-sphere chunks per
+        caller-supplied ray: RT_FLAG_STREAM_CULL_RAYS on a context whose stream_cull and streamed_queries are True, with at least two
+        chunks (rt_get_stream_cull_rays).""",
+     """The eight work words the culled ray queries share, since the context was created (rt_debug_stream_cull_rays; waits).  They exist
+        only where stream_cull_rays is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""),
+    ("stream_cull_pixels", "rt_get_stream_cull_pixels", "rt_debug_stream_cull_pixels",
+     """True where the pixel queries (gbuffer, pick, object_extents) cull the unit-sphere chunks by the block's cone:
+        RT_FLAG_STREAM_CULL_PIXELS on a context whose stream_cull and streamed_queries are True, with at least two chunks
+        (rt_get_stream_cull_pixels).""",
+     """The eight work words the culled pixel queries share, since the context was created (rt_debug_stream_cull_pixels; waits).  They
+        exist only where stream_cull_pixels is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""),
+)
+
+
+def _cull_family_members(name, getter, debug, flag_doc, stats_doc):
+    def flag(self):
+        n = C.c_uint32()
+        _check(getattr(lib(), getter)(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def stats(self):
+        w = (C.c_uint64 * 8)()
+        _check(getattr(lib(), debug)(self._h, w))
+        return [int(v) for v in w]
+
+    flag.__name__, stats.__name__ = name, name + "_stats"
+    flag.__qualname__, stats.__qualname__ = "Renderer." + name, "Renderer." + name + "_stats"
+    flag.__doc__, stats.__doc__ = flag_doc, stats_doc
+    setattr(Renderer, name, property(flag))
+    setattr(Renderer, name + "_stats", stats)
+
+
+for _row in _CULL_FAMILIES:
+    _cull_family_members(*_row)
 
 
 class MultiRenderer:

@@ -26,20 +26,43 @@
 #include "camera.h"
 
 // the launchers a context calls per floating-point contraction mode (rt_launch.h, struct Kernels); rt_create picks one from RT_FLAG_FAST
-#define RT_KERNELS(V)                                                                                                                              \
-    {RT_CAT(rt_launch_trace, V), RT_CAT(rt_launch_wavefront, V),  RT_CAT(rt_launch_ray_list, V),      RT_CAT(rt_launch_gbuffer, V),   RT_CAT(rt_launch_pick, V), \
-     RT_CAT(rt_launch_trace_rays, V), RT_CAT(rt_launch_occluded_rays, V), RT_CAT(rt_launch_shade_rays, V), \
-     RT_CAT(rt_launch_object_extents, V), RT_CAT(rt_launch_trace_paths, V), RT_CAT(rt_launch_primary_rays, V), RT_CAT(rt_launch_stream, V), \
-     RT_CAT(rt_launch_stream_gbuffer, V), RT_CAT(rt_launch_stream_pick, V), RT_CAT(rt_launch_stream_object_extents, V), RT_CAT(rt_launch_stream_trace_rays, V), \
-     RT_CAT(rt_launch_stream_occluded_rays, V), RT_CAT(rt_launch_stream_shade_rays, V), RT_CAT(rt_launch_stream_trace_paths, V), \
-     RT_CAT(rt_launch_stream_ray_list, V), RT_CAT(rt_launch_stream_cull, V), RT_CAT(rt_launch_stream_cull_bounce, V), \
-     RT_CAT(rt_launch_stream_cull_trace_rays, V), RT_CAT(rt_launch_stream_cull_occluded_rays, V), RT_CAT(rt_launch_stream_cull_shade_rays, V), \
-     RT_CAT(rt_launch_stream_cull_trace_paths, V), \
-     RT_CAT(rt_launch_pixel_cull_gbuffer, V), RT_CAT(rt_launch_pixel_cull_pick, V), RT_CAT(rt_launch_pixel_cull_object_extents, V), \
-     RT_CAT(rt_launch_stream_cull_ray_list, V)}
+// Every slot is filled by its name: the seven queries' launchers have one type on all three paths, so a list by position would compile with two of them swapped.
+#define RT_KERNELS(V)                                                                               \
+    [] {                                                                                            \
+        Kernels k{};                                                                                \
+        k.trace = RT_CAT(rt_launch_trace, V);                                                       \
+        k.wavefront = RT_CAT(rt_launch_wavefront, V);                                               \
+        k.stream = RT_CAT(rt_launch_stream, V);                                                     \
+        k.stream_cull = RT_CAT(rt_launch_stream_cull, V);                                           \
+        k.stream_cull_bounce = RT_CAT(rt_launch_stream_cull_bounce, V);                             \
+        k.ray_list = RT_CAT(rt_launch_ray_list, V);                                                 \
+        k.stream_ray_list = RT_CAT(rt_launch_stream_ray_list, V);                                   \
+        k.stream_cull_ray_list = RT_CAT(rt_launch_stream_cull_ray_list, V);                         \
+        k.primary_rays = RT_CAT(rt_launch_primary_rays, V);                                         \
+        k.query[PATH_STAGED].gbuffer = RT_CAT(rt_launch_gbuffer, V);                                \
+        k.query[PATH_STAGED].pick = RT_CAT(rt_launch_pick, V);                                      \
+        k.query[PATH_STAGED].object_extents = RT_CAT(rt_launch_object_extents, V);                  \
+        k.query[PATH_STAGED].trace_rays = RT_CAT(rt_launch_trace_rays, V);                          \
+        k.query[PATH_STAGED].occluded_rays = RT_CAT(rt_launch_occluded_rays, V);                    \
+        k.query[PATH_STAGED].shade_rays = RT_CAT(rt_launch_shade_rays, V);                          \
+        k.query[PATH_STAGED].trace_paths = RT_CAT(rt_launch_trace_paths, V);                        \
+        k.query[PATH_STREAMED].gbuffer = RT_CAT(rt_launch_stream_gbuffer, V);                       \
+        k.query[PATH_STREAMED].pick = RT_CAT(rt_launch_stream_pick, V);                             \
+        k.query[PATH_STREAMED].object_extents = RT_CAT(rt_launch_stream_object_extents, V);         \
+        k.query[PATH_STREAMED].trace_rays = RT_CAT(rt_launch_stream_trace_rays, V);                 \
+        k.query[PATH_STREAMED].occluded_rays = RT_CAT(rt_launch_stream_occluded_rays, V);           \
+        k.query[PATH_STREAMED].shade_rays = RT_CAT(rt_launch_stream_shade_rays, V);                 \
+        k.query[PATH_STREAMED].trace_paths = RT_CAT(rt_launch_stream_trace_paths, V);               \
+        k.query[PATH_CULLED].gbuffer = RT_CAT(rt_launch_pixel_cull_gbuffer, V);                     \
+        k.query[PATH_CULLED].pick = RT_CAT(rt_launch_pixel_cull_pick, V);                           \
+        k.query[PATH_CULLED].object_extents = RT_CAT(rt_launch_pixel_cull_object_extents, V);       \
+        k.query[PATH_CULLED].trace_rays = RT_CAT(rt_launch_stream_cull_trace_rays, V);              \
+        k.query[PATH_CULLED].occluded_rays = RT_CAT(rt_launch_stream_cull_occluded_rays, V);        \
+        k.query[PATH_CULLED].shade_rays = RT_CAT(rt_launch_stream_cull_shade_rays, V);              \
+        k.query[PATH_CULLED].trace_paths = RT_CAT(rt_launch_stream_cull_trace_paths, V);            \
+        return k;                                                                                   \
+    }()
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
-// the launcher of a query entry point: the streamed twin where the context's queries are streamed (rt_ctx::stream_queries, decided once in rt_create)
-#define RT_QUERY_KERNEL(ctx, name) ((ctx)->stream_queries ? (ctx)->kern->stream_##name : (ctx)->kern->name)
 
 namespace {
 
@@ -177,6 +200,29 @@ struct rt_scene {
     }
 };
 
+// What culls whole chunks of the unit-sphere table, by family: each has a decision of its own (create_scene), work words of its own, and a getter and
+// a debug reader in the ABI.  `also`: what else the work words need, as rt_debug_<name> says it when the context keeps none.
+enum CullFamily {
+    CULL_FRAME,    // rt_render (rt_stream_cull.hip; RT_FLAG_STREAM_CULL)
+    CULL_BOUNCE,   // ... its bounce rays per ray as well (rt_stream_cull_bounce.hip; RT_FLAG_STREAM_CULL_BOUNCE)
+    CULL_ADAPTIVE, // the halo and refine passes of an adaptive frame (rt_stream_cull_adaptive.hip)
+    CULL_RAYS,     // caller-supplied rays, per ray (rt_stream_cull_rays.hip; RT_FLAG_STREAM_CULL_RAYS): four entry points share the words
+    CULL_PIXELS,   // the pixel queries, by the block's cone (rt_stream_cull_pixels.hip; RT_FLAG_STREAM_CULL_PIXELS): three entry points share the words
+    N_CULL_FAMILIES
+};
+static const char STATS_SET[] = " and MI355RT_STREAM_CULL_STATS=1 was set at rt_create";
+static const struct {
+    const char *get, *debug, *also;
+} cull_family[N_CULL_FAMILIES] = {
+    {"rt_get_stream_cull", "rt_debug_stream_cull", STATS_SET},
+    {"rt_get_stream_cull_bounce", "rt_debug_stream_cull_bounce", STATS_SET},
+    // (the kernel that counts for both classes is not built: rt_stream_cull_adaptive.hip)
+    {"rt_get_stream_cull_adaptive", "rt_debug_stream_cull_adaptive",
+     ", MI355RT_STREAM_CULL_STATS=1 was set at rt_create and the scene does not hold both general quadrics and degree-3 objects"},
+    {"rt_get_stream_cull_rays", "rt_debug_stream_cull_rays", STATS_SET},
+    {"rt_get_stream_cull_pixels", "rt_debug_stream_cull_pixels", STATS_SET},
+};
+
 struct rt_ctx {
     int device = 0;
     const Kernels *kern = &kernels_strict; // RT_FLAG_FAST: &kernels_fast
@@ -230,23 +276,15 @@ struct rt_ctx {
     bool stream_queries = false;  // the queries are the streamed kernels (rt_stream_queries.hip): RT_FLAG_STREAM_QUERIES on a streamed context or on a scene whose tables the staged query kernels cannot hold in LDS
     bool stream_adaptive = false; // the halo, G and refine passes of an adaptive frame are the streamed kernels (rt_stream_adaptive.hip, rt_stream_queries.hip): RT_FLAG_STREAM_ADAPTIVE on a scene or context the staged passes refuse
     bool streamed = false;        // rt_render is the streamed frame kernel (rt_stream.hip): RT_FLAG_STREAM, or a scene whose tables the context's own kernel cannot hold in LDS
-    // RT_FLAG_STREAM_CULL (rt_stream_cull.hip): the decision, the bounds of the 64-entry chunks of the (ordered) unit-sphere table, the work words
-    bool stream_cull = false;     // RT_FLAG_STREAM_CULL && streamed && fa.cull: rt_render is the culling streamed kernel
+    // Chunk culling, per family (CullFamily): the decision (create_scene) and what its launchers take -- the bounds of the 64-entry chunks of the (ordered)
+    // unit-sphere table, and the family's 8 of d_cull_words (NULL where it keeps none: create_device_state); all zero where the family does not cull
+    bool cull[N_CULL_FAMILIES] = {};
+    ChunkTables chunks[N_CULL_FAMILIES] = {};
     uint32_t n_chunks = 0;
     DevMem<UsEntry> d_bounds;
-    DevMem<unsigned long long> d_cull_stats; // only with MI355RT_STREAM_CULL_STATS=1 in the environment at rt_create
-    // ... and the same chunks culled in the halo and refine passes (rt_stream_cull_adaptive.hip), with work words of their own
-    bool stream_cull_adaptive = false; // stream_cull && stream_adaptive && n_chunks >= 2
-    DevMem<unsigned long long> d_cull_adaptive_stats; // as d_cull_stats; not for scenes with both general quadrics and degree-3 objects (that counting kernel is not built)
-    // ... and the bounce rays of rt_render culled per ray (rt_stream_cull_bounce.hip), with work words of their own
-    bool stream_cull_bounce = false; // RT_FLAG_STREAM_CULL_BOUNCE && stream_cull && fa.has_mirror && max_reflections >= 1 && n_chunks >= 2
-    DevMem<unsigned long long> d_cull_bounce_stats; // as d_cull_stats
-    // ... and the unit-sphere chunks of caller-supplied rays culled per ray (rt_stream_cull_rays.hip), with work words the four entry points share
-    bool stream_cull_rays = false; // RT_FLAG_STREAM_CULL_RAYS && stream_cull && stream_queries && n_chunks >= 2
-    DevMem<unsigned long long> d_cull_rays_stats; // as d_cull_stats
-    // ... and the unit-sphere chunks of the pixel queries culled by the block's cone (rt_stream_cull_pixels.hip), with work words the three entry points share
-    bool stream_cull_pixels = false; // RT_FLAG_STREAM_CULL_PIXELS && stream_cull && stream_queries && n_chunks >= 2
-    DevMem<unsigned long long> d_cull_pixels_stats; // as d_cull_stats
+    DevMem<unsigned long long> d_cull_words; // [N_CULL_FAMILIES][8]; only with MI355RT_STREAM_CULL_STATS=1 in the environment at rt_create
+    // the launchers of the pixel and the ray entry points: the staged, the streamed (stream_queries) or the culled (cull[CULL_PIXELS], cull[CULL_RAYS]) path of kern->query
+    const QueryLaunchers *pixel_q = nullptr, *ray_q = nullptr;
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
     bool lean_now = true;         // ... and it renders the current frames (it does not while few tiles have hits: see choose_schedule)
     uint32_t wg_slots = 1536;     // workgroup slots of the device for these kernels (six per CU)
@@ -564,24 +602,29 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
         return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
     // Does rt_render cull whole chunks of the unit-sphere table (rt_stream_cull.hip)?  One decision, as above.  True: the table takes the
     // context's spatial order and every chunk gets its bound (rt_scene_image.hpp); false: nothing of the context differs from one without the flag.
-    ctx->stream_cull = (ctx->cfg.flags & RT_FLAG_STREAM_CULL) && ctx->streamed && fa.cull;
-    if (ctx->stream_cull) {
+    bool *cull = ctx->cull;
+    cull[CULL_FRAME] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL) && ctx->streamed && fa.cull;
+    if (cull[CULL_FRAME]) {
         im.bounds = rtp::stream_cull_image(im, fa);
         ctx->n_chunks = (uint32_t) im.bounds.size();
     }
     // ... and do the halo and refine passes cull them too (rt_stream_cull_adaptive.hip)?  Both decisions above, and a second chunk: with one,
     // the chunk level can remove nothing and is paid per query.
-    ctx->stream_cull_adaptive = ctx->stream_cull && ctx->stream_adaptive && ctx->n_chunks >= 2u;
+    cull[CULL_ADAPTIVE] = cull[CULL_FRAME] && ctx->stream_adaptive && ctx->n_chunks >= 2u;
     // ... and does rt_render cull its bounce rays per ray (rt_stream_cull_bounce.hip)?  The decision above, a scene and a context in which a ray
     // can bounce at all, and a second chunk.  False: launch for launch the context without the flag.  rt_set_scene keeps has_mirror and the chunk
     // layout, so this holds for the context's life.
-    ctx->stream_cull_bounce = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_BOUNCE) && ctx->stream_cull && fa.has_mirror && fa.max_refl >= 1u && ctx->n_chunks >= 2u;
+    cull[CULL_BOUNCE] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_BOUNCE) && cull[CULL_FRAME] && fa.has_mirror && fa.max_refl >= 1u && ctx->n_chunks >= 2u;
     // ... and do the ray queries cull the chunks per caller-supplied ray (rt_stream_cull_rays.hip)?  The culling decision, streamed queries and a second
     // chunk.  False: launch for launch the context without the flag.  rt_set_scene rebuilds the bounds and keeps the layout, so this holds too.
-    ctx->stream_cull_rays = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_RAYS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;
+    cull[CULL_RAYS] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_RAYS) && cull[CULL_FRAME] && ctx->stream_queries && ctx->n_chunks >= 2u;
     // ... and do the pixel queries cull the chunks by the block's cone (rt_stream_cull_pixels.hip)?  The same three conditions under a flag of its own.
-    // False: launch for launch the context without the flag.  (stream_cull implies fa.cull: the cone exists.)
-    ctx->stream_cull_pixels = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_PIXELS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;
+    // False: launch for launch the context without the flag.  (cull[CULL_FRAME] implies fa.cull: the cone exists.)
+    cull[CULL_PIXELS] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_PIXELS) && cull[CULL_FRAME] && ctx->stream_queries && ctx->n_chunks >= 2u;
+    // So the launchers the query entry points call, for the context's life: the culled path where the family culls, else the streamed or the staged one.
+    const TablePath plain = ctx->stream_queries ? PATH_STREAMED : PATH_STAGED;
+    ctx->pixel_q = &ctx->kern->query[cull[CULL_PIXELS] ? PATH_CULLED : plain];
+    ctx->ray_q = &ctx->kern->query[cull[CULL_RAYS] ? PATH_CULLED : plain];
     return RT_OK;
 }
 
@@ -599,19 +642,17 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
     RT_TRY("hipMalloc(framebuffer)", ctx->d_fb.alloc((size_t) (ctx->local_rows ? ctx->local_rows : 1) * ctx->width * ctx->pixel_bytes));
     if (int rc = device_table(ctx->d_counters, nullptr, sizeof(unsigned long long) * 64, "counters")) return rc;
     if (int rc = device_table(ctx->d_ss_status, nullptr, sizeof(SetSceneStatus), "scene-update status")) return rc;
-    if (ctx->stream_cull) {
+    if (ctx->cull[CULL_FRAME]) {
         if (int rc = device_table(ctx->d_bounds, im.bounds.data(), sizeof(UsEntry) * im.bounds.size(), "chunk bounds")) return rc;
         const char *e = std::getenv("MI355RT_STREAM_CULL_STATS");
         if (e && !std::strcmp(e, "1"))
-            if (int rc = device_table(ctx->d_cull_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull work words")) return rc;
-        if (e && !std::strcmp(e, "1") && ctx->stream_cull_bounce)
-            if (int rc = device_table(ctx->d_cull_bounce_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-bounce work words")) return rc;
-        if (e && !std::strcmp(e, "1") && ctx->stream_cull_rays)
-            if (int rc = device_table(ctx->d_cull_rays_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-rays work words")) return rc;
-        if (e && !std::strcmp(e, "1") && ctx->stream_cull_pixels)
-            if (int rc = device_table(ctx->d_cull_pixels_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-pixels work words")) return rc;
-        if (e && !std::strcmp(e, "1") && ctx->stream_cull_adaptive && !(fa.n_gq && fa.n_cub))
-            if (int rc = device_table(ctx->d_cull_adaptive_stats, nullptr, sizeof(unsigned long long) * 8, "stream-cull-adaptive work words")) return rc;
+            if (int rc = device_table(ctx->d_cull_words, nullptr, sizeof(unsigned long long) * 8 * N_CULL_FAMILIES, "stream-cull work words")) return rc;
+        // a family that culls takes the bounds, and its own 8 words where there are any (the adaptive kernel that counts for a scene with both general
+        // quadrics and degree-3 objects is not built: no words there)
+        for (int f = 0; f < N_CULL_FAMILIES; f++) {
+            const bool words = ctx->d_cull_words && !(f == CULL_ADAPTIVE && fa.n_gq && fa.n_cub);
+            if (ctx->cull[f]) ctx->chunks[f] = ChunkTables{ctx->d_bounds.p, ctx->n_chunks, words ? ctx->d_cull_words + 8 * f : nullptr};
+        }
     }
     RT_TRY("hipEventCreate", ctx->ev0.create());
     RT_TRY("hipEventCreate", ctx->ev1.create());
@@ -894,15 +935,14 @@ static int rotate_launch_order(rt_ctx *ctx, FrameArgs &fa, hipStream_t stream)
 }
 
 // One pass of an adaptive frame over a ray list (the halo rows: k = 1, n_items slots; the refine pass: k = the context's, the device-side count): the
-// staged kernel (rt_adaptive.hip) or, on a context whose adaptive passes are streamed -- rt_ctx::stream_adaptive, rt_ctx::stream_cull_adaptive, decided once
+// staged kernel (rt_adaptive.hip) or, on a context whose adaptive passes are streamed -- rt_ctx::stream_adaptive, rt_ctx::cull[CULL_ADAPTIVE], decided once
 // in rt_create --, that pass's streamed or culled twin.  The streamed passes book no counters.  One graph node.
 static hipError_t ray_list_launch(rt_ctx *ctx, const double *camx, const double *camy, const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid,
                                   void *out, int rgba8, int count, hipStream_t stream)
 {
     const Kernels *kern = ctx->kern;
-    if (ctx->stream_cull_adaptive)
-        return kern->stream_cull_ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, ctx->d_bounds, ctx->n_chunks,
-                                          ctx->d_cull_adaptive_stats, stream);
+    if (ctx->cull[CULL_ADAPTIVE])
+        return kern->stream_cull_ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, &ctx->chunks[CULL_ADAPTIVE], stream);
     if (ctx->stream_adaptive) return kern->stream_ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, stream);
     return kern->ray_list(&ctx->fa, ctx->d_obj, ctx->d_light, camx, camy, list, count_ptr, n_items, k, grid, out, rgba8, count, ctx->d_counters, stream);
 }
@@ -950,9 +990,9 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
     if (fa.order_state)
         if (int rc = rotate_launch_order(ctx, fa, stream)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->stream_cull_bounce ? ctx->kern->stream_cull_bounce(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_stats,
-                                                                                 ctx->d_cull_bounce_stats, stream)
-                         : ctx->stream_cull ? ctx->kern->stream_cull(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, ctx->d_bounds, ctx->n_chunks, ctx->d_cull_stats, stream)
+    const ChunkTables *frame_chunks = &ctx->chunks[CULL_FRAME]; // (the bounce kernel books the frame's words as well as its own)
+    const hipError_t e = ctx->cull[CULL_BOUNCE] ? ctx->kern->stream_cull_bounce(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, frame_chunks, ctx->chunks[CULL_BOUNCE].stats, stream)
+                         : ctx->cull[CULL_FRAME] ? ctx->kern->stream_cull(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, frame_chunks, stream)
                          : ctx->streamed ? ctx->kern->stream(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, stream)
                          : (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
                                                            : ctx->kern->wavefront(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, count, ctx->d_camx, ctx->d_camy, stream);
@@ -971,9 +1011,11 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
             float *nrm = ctx->min_cos == -INFINITY ? nullptr : ctx->d_geo_nrm.p;
             // (the kernel in its two modes, as rt_render_gbuffer / rt_pick launch it: two nodes with several ranks -- the launchers skip an empty grid --;
             // so the adaptive frame's edges are the ones those two report, in the FAST build too)
-            const Kernels *k = ctx->kern;
-            RT_HIP((ctx->stream_adaptive ? k->stream_gbuffer : k->gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, stream));
-            RT_HIP((ctx->stream_adaptive ? k->stream_pick : k->pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream));
+            // The path is named here and is never the pixel entry points': streamed where the adaptive passes are, and never culled (its planes equal
+            // rt_render_gbuffer's of a culling context by the rule of DESIGN.md section 34, not by identity of kernel).
+            const QueryLaunchers &g = ctx->kern->query[ctx->stream_adaptive ? PATH_STREAMED : PATH_STAGED];
+            RT_HIP(g.gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, nullptr, stream));
+            RT_HIP(g.pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, nullptr, stream));
             RT_HIP(rt_launch_classify_geometry_strict(fb, ctx->d_halo, ctx->d_geo_obj, nrm, ctx->d_geo_halo, ctx->width, ctx->height, ctx->local_rows,
                                                       ctx->cfg.band_rows, ctx->cfg.world, ctx->cfg.rank, ctx->tau, ctx->min_cos, dest, out8, ctx->d_list,
                                                       ctx->d_list + px, stream));
@@ -1009,10 +1051,8 @@ extern "C" int rt_render_sparse(rt_ctx *ctx, const double cam[16], void *dev_msg
 }
 
 // ---- G-buffer (rt_gbuffer.hip) ---------------------------------------------------------------------------
-// The pixel entry points of a context whose RT_FLAG_STREAM_CULL_PIXELS decision is true (rt_ctx::stream_cull_pixels, decided once in rt_create) take the
-// culled launchers (rt_stream_cull_pixels.hip): the streamed twin's arguments and these.  The G pass of an adaptive frame keeps its own two.
-#define RT_CULL_PIXELS_ARGS(ctx) (ctx)->d_bounds, (ctx)->n_chunks, (ctx)->d_cull_pixels_stats
-
+// The pixel entry points call the launchers rt_create decided on (rt_ctx::pixel_q): the staged, the streamed, or -- RT_FLAG_STREAM_CULL_PIXELS -- the culled
+// ones (rt_stream_cull_pixels.hip), which read the family's chunks.  The G pass of an adaptive frame keeps its own two.
 // The frame arguments of a G-buffer pass: a COPY of the context's (geometry, scene layout) with this call's camera -- the context's own
 // FrameArgs, which carry the render kernels' frame-to-frame state, are neither read for that state nor written.
 static int gbuffer_args(const char *who, rt_ctx *ctx, const double cam[16], FrameArgs &fa)
@@ -1037,8 +1077,7 @@ extern "C" int rt_render_gbuffer(rt_ctx *ctx, const double cam[16], int32_t *dev
     FrameArgs fa;
     if (int rc = gbuffer_args("rt_render_gbuffer", ctx, cam, fa)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, RT_CULL_PIXELS_ARGS(ctx), stream)
-                                                 : RT_QUERY_KERNEL(ctx, gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, stream);
+    const hipError_t e = ctx->pixel_q->gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, dev_object, dev_t, dev_normal, &ctx->chunks[CULL_PIXELS], stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "G-buffer kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1063,8 +1102,7 @@ extern "C" int rt_pick(rt_ctx *ctx, const double cam[16], const uint32_t *xy, ui
     if (int rc = gbuffer_args("rt_pick", ctx, cam, fa)) return rc;
     if (int rc = ctx->pick.reserve(n, sizeof(uint32_t) * 2, sizeof(rt_hit))) return rc;
     RT_HIP(hipMemcpyAsync(ctx->pick.in, xy, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice, stream));
-    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, RT_CULL_PIXELS_ARGS(ctx), stream)
-                                                 : RT_QUERY_KERNEL(ctx, pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, stream);
+    const hipError_t e = ctx->pixel_q->pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, (const uint32_t *) ctx->pick.in.p, n, ctx->pick.out, &ctx->chunks[CULL_PIXELS], stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "pick kernel launch failed: %s", hipGetErrorString(e));
     RT_HIP(hipMemcpyAsync(out_host, ctx->pick.out, sizeof(rt_hit) * (size_t) n, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
@@ -1099,6 +1137,14 @@ static int extents_args(const char *who, rt_ctx *ctx, const double cam[16], cons
 // workgroups of one extents launch: four per CU, each striding over the tiles (rt_gbuffer.hip, extents_kernel)
 static uint32_t extents_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
 
+// the launch behind both entry points; `who` names the one that called
+static int extents_launch(const char *who, rt_ctx *ctx, const FrameArgs &fa, const uint32_t r[4], void *dev_out, hipStream_t stream)
+{
+    const hipError_t e = ctx->pixel_q->object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), &ctx->chunks[CULL_PIXELS], stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
+    return RT_OK;
+}
+
 extern "C" int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32_t rect[4], rt_object_extent *dev_out, void *stream_, float *ms)
 {
     static_assert(sizeof(rt_object_extent) == 40 && alignof(rt_object_extent) == 8, "rt_object_extent layout");
@@ -1108,9 +1154,7 @@ extern "C" int rt_object_extents(rt_ctx *ctx, const double cam[16], const uint32
     if (int rc = extents_args("rt_object_extents", ctx, cam, rect, dev_out, true, fa, r)) return rc;
     if (fa.n_obj == 0u) return RT_OK;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), RT_CULL_PIXELS_ARGS(ctx), stream)
-                                                 : RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, dev_out, extents_max_grid(ctx), stream);
-    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents: kernel launch failed: %s", hipGetErrorString(e));
+    if (int rc = extents_launch("rt_object_extents", ctx, fa, r, dev_out, stream)) return rc;
     return timer_end(ctx, stream, ms);
 }
 
@@ -1126,9 +1170,7 @@ extern "C" int rt_object_extents_host(rt_ctx *ctx, const double cam[16], const u
         return fail(RT_ERR_INVALID, "rt_object_extents_host: the stream is capturing, and this call allocates and waits; capture rt_object_extents (device memory) instead");
     if (fa.n_obj == 0u) return RT_OK;
     if (int rc = ctx->ext.reserve(fa.n_obj, 8, sizeof(rt_object_extent))) return rc;
-    const hipError_t e = ctx->stream_cull_pixels ? ctx->kern->pixel_cull_object_extents(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), RT_CULL_PIXELS_ARGS(ctx), stream)
-                                                 : RT_QUERY_KERNEL(ctx, object_extents)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, r, ctx->ext.out, extents_max_grid(ctx), stream);
-    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_object_extents_host: kernel launch failed: %s", hipGetErrorString(e));
+    if (int rc = extents_launch("rt_object_extents_host", ctx, fa, r, ctx->ext.out, stream)) return rc;
     RT_HIP(hipMemcpyAsync(out_host, ctx->ext.out, sizeof(rt_object_extent) * (size_t) fa.n_obj, hipMemcpyDeviceToHost, stream));
     RT_HIP(hipStreamSynchronize(stream));
     return RT_OK;
@@ -1153,14 +1195,11 @@ static int rays_ready(const char *who, rt_ctx *ctx)
 // workgroups of one ray-query launch: four per CU (the kernels' registers allow three to four resident ones), fewer for few rays
 static uint32_t rays_max_grid(const rt_ctx *ctx) { return ctx->wg_slots / 6u * 4u; }
 
-// The ray entry points of a context whose RT_FLAG_STREAM_CULL_RAYS decision is true (rt_ctx::stream_cull_rays, decided once in rt_create) take the culled
-// launchers (rt_stream_cull_rays.hip): the streamed twin's arguments and these.  The pixel queries have a decision of their own (RT_CULL_PIXELS_ARGS).
-#define RT_CULL_RAYS_ARGS(ctx) (ctx)->d_bounds, (ctx)->n_chunks, (ctx)->d_cull_rays_stats
-
+// The ray entry points call the launchers rt_create decided on (rt_ctx::ray_q): the staged, the streamed, or -- RT_FLAG_STREAM_CULL_RAYS -- the culled ones
+// (rt_stream_cull_rays.hip), which read the family's chunks.  The pixel queries have a decision of their own (rt_ctx::pixel_q).
 static hipError_t trace_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, void *dev_hits, hipStream_t stream)
 {
-    if (ctx->stream_cull_rays) return ctx->kern->stream_cull_trace_rays(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx), stream);
-    return RT_QUERY_KERNEL(ctx, trace_rays)(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), stream);
+    return ctx->ray_q->trace_rays(&ctx->fa, ctx->d_obj, dev_rays, n, dev_hits, rays_max_grid(ctx), &ctx->chunks[CULL_RAYS], stream);
 }
 
 extern "C" int rt_trace_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, rt_hit *dev_hits, void *stream_, float *ms)
@@ -1191,8 +1230,7 @@ extern "C" int rt_occluded_rays(rt_ctx *ctx, const rt_ray *dev_rays, const doubl
     hipStream_t stream = (hipStream_t) stream_;
     if (int rc = rays_ready("rt_occluded_rays", ctx)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
-    const hipError_t e = ctx->stream_cull_rays ? ctx->kern->stream_cull_occluded_rays(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx), stream)
-                                               : RT_QUERY_KERNEL(ctx, occluded_rays)(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), stream);
+    const hipError_t e = ctx->ray_q->occluded_rays(&ctx->fa, ctx->d_obj, dev_rays, dev_t_max, n, dev_blocked, rays_max_grid(ctx), &ctx->chunks[CULL_RAYS], stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "ray-query kernel launch failed: %s", hipGetErrorString(e));
     return timer_end(ctx, stream, ms);
 }
@@ -1217,9 +1255,7 @@ extern "C" int rt_trace_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, r
 // Like the ray queries it reads the scene (blob and lights) and nothing of the frame; always 4 x float32 per ray, whatever cfg.format.
 static hipError_t shade_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, float *dev_rgba, void *dev_hits, hipStream_t stream)
 {
-    if (ctx->stream_cull_rays)
-        return ctx->kern->stream_cull_shade_rays(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx), stream);
-    return RT_QUERY_KERNEL(ctx, shade_rays)(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), stream);
+    return ctx->ray_q->shade_rays(&ctx->fa, ctx->d_obj, ctx->d_light, dev_rays, n, dev_rgba, dev_hits, rays_max_grid(ctx), &ctx->chunks[CULL_RAYS], stream);
 }
 
 extern "C" int rt_shade_rays(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, float *dev_rgba, rt_hit *dev_hits, void *stream_, float *ms)
@@ -1260,10 +1296,7 @@ extern "C" int rt_shade_rays_host(rt_ctx *ctx, const rt_ray *rays, uint32_t n, f
 // Like the ray queries the path kernel reads the scene blob and nothing of the frame.
 static hipError_t paths_launch(rt_ctx *ctx, const void *dev_rays, uint32_t n, uint32_t max_segments, void *dev_segments, void *dev_last, void *dev_ends, hipStream_t stream)
 {
-    if (ctx->stream_cull_rays)
-        return ctx->kern->stream_cull_trace_paths(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), RT_CULL_RAYS_ARGS(ctx),
-                                                  stream);
-    return RT_QUERY_KERNEL(ctx, trace_paths)(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), stream);
+    return ctx->ray_q->trace_paths(&ctx->fa, ctx->d_obj, dev_rays, n, max_segments, dev_segments, dev_last, dev_ends, rays_max_grid(ctx), &ctx->chunks[CULL_RAYS], stream);
 }
 
 extern "C" int rt_trace_paths(rt_ctx *ctx, const rt_ray *dev_rays, uint32_t n, uint32_t max_segments, rt_hit *dev_segments, rt_hit *dev_last, rt_path_end *dev_ends,
@@ -1438,8 +1471,8 @@ static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update
     a.off_lin = fa.off_lin;
     a.off_mat = fa.off_mat;
     a.has_mirror = fa.has_mirror;
-    a.n_chunks = ctx->stream_cull ? ctx->n_chunks : 0u; // (the chunk bounds follow the rebuilt entries; the order chosen at rt_create stays)
-    a.bounds = ctx->stream_cull ? ctx->d_bounds.p : nullptr;
+    a.n_chunks = ctx->cull[CULL_FRAME] ? ctx->n_chunks : 0u; // (the chunk bounds follow the rebuilt entries; the order chosen at rt_create stays)
+    a.bounds = ctx->cull[CULL_FRAME] ? ctx->d_bounds.p : nullptr;
     const hipError_t e = rt_launch_set_scene(&a, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
     return order_end(ctx, stream, capturing);
@@ -1739,94 +1772,43 @@ extern "C" int rt_get_streamed_adaptive(const rt_ctx *ctx, uint32_t *streamed)
     return RT_OK;
 }
 
-extern "C" int rt_get_stream_cull(const rt_ctx *ctx, uint32_t *on)
+// The getter and the debug reader of a culling family (cull_family[] holds their names and what the refusal says)
+static int get_cull(CullFamily f, const rt_ctx *ctx, uint32_t *on)
 {
-    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull: null argument");
-    *on = ctx->stream_cull ? 1u : 0u;
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "%s: null argument", cull_family[f].get);
+    *on = ctx->cull[f] ? 1u : 0u;
     return RT_OK;
 }
+
+static int debug_cull(CullFamily f, rt_ctx *ctx, uint64_t out[8])
+{
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "work words");
+    const char *who = cull_family[f].debug;
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "%s: null argument", who);
+    if (!ctx->chunks[f].stats)
+        return fail(RT_ERR_INVALID, "%s: the context keeps no work words (they exist where %s says 1%s)", who, cull_family[f].get, cull_family[f].also);
+    return read_behind_last_call(who, ctx, out, ctx->chunks[f].stats, sizeof(uint64_t) * 8);
+}
+
+extern "C" int rt_get_stream_cull(const rt_ctx *ctx, uint32_t *on) { return get_cull(CULL_FRAME, ctx, on); }
+extern "C" int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8]) { return debug_cull(CULL_FRAME, ctx, out); }
+extern "C" int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on) { return get_cull(CULL_ADAPTIVE, ctx, on); }
+extern "C" int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8]) { return debug_cull(CULL_ADAPTIVE, ctx, out); }
+extern "C" int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on) { return get_cull(CULL_BOUNCE, ctx, on); }
+extern "C" int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8]) { return debug_cull(CULL_BOUNCE, ctx, out); }
+extern "C" int rt_get_stream_cull_rays(const rt_ctx *ctx, uint32_t *on) { return get_cull(CULL_RAYS, ctx, on); }
+extern "C" int rt_debug_stream_cull_rays(rt_ctx *ctx, uint64_t out[8]) { return debug_cull(CULL_RAYS, ctx, out); }
+extern "C" int rt_get_stream_cull_pixels(const rt_ctx *ctx, uint32_t *on) { return get_cull(CULL_PIXELS, ctx, on); }
+extern "C" int rt_debug_stream_cull_pixels(rt_ctx *ctx, uint64_t out[8]) { return debug_cull(CULL_PIXELS, ctx, out); }
 
 extern "C" int rt_debug_stream_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes)
 {
     if (!ctx || !bytes) return fail(RT_ERR_INVALID, "rt_debug_stream_bounds: null argument");
-    const size_t need = ctx->stream_cull ? sizeof(UsEntry) * (size_t) ctx->n_chunks : 0u;
+    const size_t need = ctx->cull[CULL_FRAME] ? sizeof(UsEntry) * (size_t) ctx->n_chunks : 0u;
     *bytes = need;
     if (!out || !need) return RT_OK;
     if (cap < need) return fail(RT_ERR_INVALID, "rt_debug_stream_bounds: %zu bytes offered, the bounds take %zu", cap, need);
     return read_behind_last_call("rt_debug_stream_bounds", ctx, out, ctx->d_bounds, need);
-}
-
-extern "C" int rt_debug_stream_cull(rt_ctx *ctx, uint64_t out[8])
-{
-    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull: null argument");
-    if (!ctx->d_cull_stats)
-        return fail(RT_ERR_INVALID, "rt_debug_stream_cull: the context keeps no work words (they exist where rt_get_stream_cull says 1 and MI355RT_STREAM_CULL_STATS=1 was set at rt_create)");
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "work words");
-    return read_behind_last_call("rt_debug_stream_cull", ctx, out, ctx->d_cull_stats, sizeof(uint64_t) * 8);
-}
-
-extern "C" int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on)
-{
-    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_adaptive: null argument");
-    *on = ctx->stream_cull_adaptive ? 1u : 0u;
-    return RT_OK;
-}
-
-extern "C" int rt_debug_stream_cull_adaptive(rt_ctx *ctx, uint64_t out[8])
-{
-    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_adaptive: null argument");
-    if (!ctx->d_cull_adaptive_stats)
-        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_adaptive: the context keeps no work words (they exist where rt_get_stream_cull_adaptive says 1, MI355RT_STREAM_CULL_STATS=1 was "
-                                    "set at rt_create and the scene does not hold both general quadrics and degree-3 objects)");
-    return read_behind_last_call("rt_debug_stream_cull_adaptive", ctx, out, ctx->d_cull_adaptive_stats, sizeof(uint64_t) * 8);
-}
-
-extern "C" int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on)
-{
-    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_bounce: null argument");
-    *on = ctx->stream_cull_bounce ? 1u : 0u;
-    return RT_OK;
-}
-
-extern "C" int rt_debug_stream_cull_bounce(rt_ctx *ctx, uint64_t out[8])
-{
-    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_bounce: null argument");
-    if (!ctx->d_cull_bounce_stats)
-        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_bounce: the context keeps no work words (they exist where rt_get_stream_cull_bounce says 1 and MI355RT_STREAM_CULL_STATS=1 "
-                                    "was set at rt_create)");
-    return read_behind_last_call("rt_debug_stream_cull_bounce", ctx, out, ctx->d_cull_bounce_stats, sizeof(uint64_t) * 8);
-}
-
-extern "C" int rt_get_stream_cull_rays(const rt_ctx *ctx, uint32_t *on)
-{
-    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_rays: null argument");
-    *on = ctx->stream_cull_rays ? 1u : 0u;
-    return RT_OK;
-}
-
-extern "C" int rt_debug_stream_cull_rays(rt_ctx *ctx, uint64_t out[8])
-{
-    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_rays: null argument");
-    if (!ctx->d_cull_rays_stats)
-        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_rays: the context keeps no work words (they exist where rt_get_stream_cull_rays says 1 and MI355RT_STREAM_CULL_STATS=1 "
-                                    "was set at rt_create)");
-    return read_behind_last_call("rt_debug_stream_cull_rays", ctx, out, ctx->d_cull_rays_stats, sizeof(uint64_t) * 8);
-}
-
-extern "C" int rt_get_stream_cull_pixels(const rt_ctx *ctx, uint32_t *on)
-{
-    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_pixels: null argument");
-    *on = ctx->stream_cull_pixels ? 1u : 0u;
-    return RT_OK;
-}
-
-extern "C" int rt_debug_stream_cull_pixels(rt_ctx *ctx, uint64_t out[8])
-{
-    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_cull_pixels: null argument");
-    if (!ctx->d_cull_pixels_stats)
-        return fail(RT_ERR_INVALID, "rt_debug_stream_cull_pixels: the context keeps no work words (they exist where rt_get_stream_cull_pixels says 1 and MI355RT_STREAM_CULL_STATS=1 "
-                                    "was set at rt_create)");
-    return read_behind_last_call("rt_debug_stream_cull_pixels", ctx, out, ctx->d_cull_pixels_stats, sizeof(uint64_t) * 8);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

@@ -44,7 +44,7 @@ static hipError_t launch(const FrameArgs *fa, const void *scene, const double *c
 
 // planes = [local_rows][width] each; any of them may be NULL
 extern "C" hipError_t RT_SYM(rt_launch_gbuffer)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
-                                                 float *out_normal, hipStream_t stream)
+                                                 float *out_normal, const ChunkTables *, hipStream_t stream)
 {
     if (fa->n_tiles == 0u) return hipSuccess;
     return RT_SYM(rtk)::launch(fa, scene, camx, camy, fa->n_tiles, out_object, out_t, out_normal, nullptr, 0u, nullptr, stream);
@@ -52,7 +52,7 @@ extern "C" hipError_t RT_SYM(rt_launch_gbuffer)(const FrameArgs *fa, const void 
 
 // xy = n coordinate pairs and out = n records (16-byte aligned), both in device memory: the planes' kernel in its picking mode
 extern "C" hipError_t RT_SYM(rt_launch_pick)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
-                                              hipStream_t stream)
+                                              const ChunkTables *, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::launch(fa, scene, camx, camy, (n + 255u) / 256u, nullptr, nullptr, nullptr, xy, n, out, stream);
@@ -105,7 +105,7 @@ extern "C" size_t RT_SYM(rt_extents_lds_bytes)(const FrameArgs *fa)
 // rect = x0, y0, x1, y1 (inclusive, inside the image, GLOBAL rows); out = n_obj records in device memory.  Two nodes on `stream`: the
 // identities, then -- when this rank owns a row of the rectangle -- the kernel, at most max_grid workgroups.
 extern "C" hipError_t RT_SYM(rt_launch_object_extents)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out,
-                                                        uint32_t max_grid, hipStream_t stream)
+                                                        uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (fa->n_obj == 0u) return hipSuccess;

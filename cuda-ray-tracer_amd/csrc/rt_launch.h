@@ -41,124 +41,118 @@ RT_PER_VARIANT(hipError_t, rt_launch_classify, const void *p, const void *halo, 
 RT_PER_VARIANT(hipError_t, rt_launch_classify_geometry, const void *p, const void *halo, const int32_t *obj, const float *nrm, const void *ghalo, uint32_t width,
                uint32_t height, uint32_t local_rows, uint32_t band_rows, uint32_t world, uint32_t rank, float tau, float min_cos, void *out, int rgba8,
                uint32_t *list, uint32_t *count, hipStream_t stream)
-// rt_gbuffer.hip: primary-hit G-buffer and picking (the two together: the G pass of an RT_FLAG_SSAA_GEOMETRY frame)
+// The chunk bounds of a culling context, as the culled launchers take them: [n_chunks] UsEntry for the n_chunks = ceil(n_us / 64) chunks of the blob's
+// (ordered) unit-sphere table, and the 8 work words the launch adds to (or NULL: nothing is counted)
+struct ChunkTables {
+    const void *bounds;
+    uint32_t n_chunks;
+    unsigned long long *stats;
+};
+// The seven queries.  Each has one signature for its three launchers -- the tables staged in LDS (rt_gbuffer.hip, rt_rays.hip, rt_shade_rays.hip,
+// rt_paths.hip), streamed through a slice (rt_stream_queries.hip, RT_FLAG_STREAM_QUERIES) and streamed with chunks culled (rt_stream_cull_pixels.hip,
+// RT_FLAG_STREAM_CULL_PIXELS; rt_stream_cull_rays.hip, RT_FLAG_STREAM_CULL_RAYS) --, so an entry point calls whichever the context decided on
+// (struct QueryLaunchers below).  The staged and the streamed launchers ignore `chunks`.
+// primary-hit G-buffer and picking (the two together: the G pass of an RT_FLAG_SSAA_GEOMETRY frame)
+#define RT_GBUFFER_ARGS                                                                                                                              \
+    const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t, float *out_normal, const ChunkTables *chunks, \
+        hipStream_t stream
+#define RT_PICK_ARGS \
+    const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out, const ChunkTables *chunks, hipStream_t stream
+// the object extents: the same rays reduced per object instead of stored (rect = x0, y0, x1, y1 inclusive, validated by the caller)
+#define RT_OBJECT_EXTENTS_ARGS                                                                                                                        \
+    const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out, uint32_t max_grid, const ChunkTables *chunks, \
+        hipStream_t stream
+// caller-supplied rays: closest hit, occlusion, colour
+#define RT_TRACE_RAYS_ARGS const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid, const ChunkTables *chunks, hipStream_t stream
+#define RT_OCCLUDED_RAYS_ARGS \
+    const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out, uint32_t max_grid, const ChunkTables *chunks, hipStream_t stream
+#define RT_SHADE_RAYS_ARGS                                                                                                                            \
+    const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits, uint32_t max_grid, const ChunkTables *chunks, \
+        hipStream_t stream
+// the hits along a ray's mirror bounces
+#define RT_TRACE_PATHS_ARGS                                                                                                                           \
+    const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments, void *last, void *ends, uint32_t max_grid, \
+        const ChunkTables *chunks, hipStream_t stream
+// rt_gbuffer.hip (and what sizes its LDS)
 RT_PER_VARIANT(size_t, rt_gbuffer_lds_bytes, const FrameArgs *fa)
-RT_PER_VARIANT(hipError_t, rt_launch_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
-               float *out_normal, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
-               hipStream_t stream)
-// ... and the object extents: the same rays reduced per object instead of stored (rect = x0, y0, x1, y1 inclusive, validated by the caller)
 RT_PER_VARIANT(int, rt_extents_lds_accumulators, size_t table_bytes, uint32_t n_obj)
 RT_PER_VARIANT(size_t, rt_extents_lds_bytes, const FrameArgs *fa)
-RT_PER_VARIANT(hipError_t, rt_launch_object_extents, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out,
-               uint32_t max_grid, hipStream_t stream)
-// rt_rays.hip, rt_shade_rays.hip: caller-supplied rays
+RT_PER_VARIANT(hipError_t, rt_launch_gbuffer, RT_GBUFFER_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_pick, RT_PICK_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_object_extents, RT_OBJECT_EXTENTS_ARGS)
+// rt_rays.hip, rt_shade_rays.hip, rt_paths.hip
 RT_PER_VARIANT(size_t, rt_rays_lds_bytes, const FrameArgs *fa)
-RT_PER_VARIANT(hipError_t, rt_launch_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_occluded_rays, const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
-               uint32_t max_grid, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
-               uint32_t max_grid, hipStream_t stream)
-// rt_paths.hip: the hits along a ray's mirror bounces; the context's own primary rays as explicit rays (rect = x0, y0, x1, y1 inclusive, or a pixel list)
-RT_PER_VARIANT(hipError_t, rt_launch_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments, void *last,
-               void *ends, uint32_t max_grid, hipStream_t stream)
+RT_PER_VARIANT(hipError_t, rt_launch_trace_rays, RT_TRACE_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_occluded_rays, RT_OCCLUDED_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_shade_rays, RT_SHADE_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_trace_paths, RT_TRACE_PATHS_ARGS)
+// rt_stream_queries.hip
+RT_PER_VARIANT(hipError_t, rt_launch_stream_gbuffer, RT_GBUFFER_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_pick, RT_PICK_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_object_extents, RT_OBJECT_EXTENTS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_rays, RT_TRACE_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_occluded_rays, RT_OCCLUDED_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_shade_rays, RT_SHADE_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_paths, RT_TRACE_PATHS_ARGS)
+// rt_stream_cull_pixels.hip (the chunks culled by the block's cone), rt_stream_cull_rays.hip (per caller-supplied ray): the work words are the family's
+RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_gbuffer, RT_GBUFFER_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_pick, RT_PICK_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_object_extents, RT_OBJECT_EXTENTS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_rays, RT_TRACE_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_occluded_rays, RT_OCCLUDED_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_shade_rays, RT_SHADE_RAYS_ARGS)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_paths, RT_TRACE_PATHS_ARGS)
+// rt_paths.hip: the context's own primary rays as explicit rays (rect = x0, y0, x1, y1 inclusive, or a pixel list)
 RT_PER_VARIANT(hipError_t, rt_launch_primary_rays, const FrameArgs *fa, const double *camx, const double *camy, const uint32_t *rect, const uint32_t *xy, uint32_t n_list,
                void *out, uint32_t max_grid, hipStream_t stream)
 // rt_stream.hip: the streamed frame kernel (scenes of any size)
 RT_PER_VARIANT(hipError_t, rt_launch_stream, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
                hipStream_t stream)
-// rt_stream_queries.hip: the streamed twins of the query launchers above (RT_FLAG_STREAM_QUERIES), each with its twin's signature
-RT_PER_VARIANT(hipError_t, rt_launch_stream_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
-               float *out_normal, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n,
-               void *out, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_object_extents, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect,
-               void *out, uint32_t max_grid, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
-               hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_occluded_rays, const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
-               uint32_t max_grid, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba,
-               void *hits, uint32_t max_grid, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
-               void *last, void *ends, uint32_t max_grid, hipStream_t stream)
 // rt_stream_adaptive.hip: the streamed twin of rt_launch_ray_list (RT_FLAG_STREAM_ADAPTIVE): its arguments without the counters, scene = the blob
 RT_PER_VARIANT(hipError_t, rt_launch_stream_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
                const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, hipStream_t stream)
-// rt_stream_cull.hip: the streamed frame kernel with whole chunks of the unit-sphere table culled (RT_FLAG_STREAM_CULL): rt_launch_stream's arguments, the
-// chunk bounds ([n_chunks] UsEntry, n_chunks = ceil(n_us / 64)) and the work words (8, or NULL)
+// rt_stream_cull.hip: the streamed frame kernel with whole chunks of the unit-sphere table culled (RT_FLAG_STREAM_CULL): rt_launch_stream's arguments and the chunks
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
-               const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+               const ChunkTables *chunks, hipStream_t stream)
 // rt_stream_cull_bounce.hip: rt_launch_stream_cull with the bounce rays culled per ray as well (RT_FLAG_STREAM_CULL_BOUNCE): its arguments and the bounce
-// work words (8, NULL exactly where stats is NULL)
+// work words (8, NULL exactly where chunks->stats is NULL)
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_bounce, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
-               const void *bounds, uint32_t n_chunks, unsigned long long *stats, unsigned long long *bounce_stats, hipStream_t stream)
-// rt_stream_cull_rays.hip: the streamed ray launchers with the chunks culled per caller-supplied ray (RT_FLAG_STREAM_CULL_RAYS): each its streamed twin's
-// arguments, the chunk bounds and the work words the four share (8, or NULL)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_rays, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
-               const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_occluded_rays, const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
-               uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_shade_rays, const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba,
-               void *hits, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_trace_paths, const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
-               void *last, void *ends, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-// rt_stream_cull_pixels.hip: the streamed pixel launchers with the chunks culled by the block's cone (RT_FLAG_STREAM_CULL_PIXELS): each its streamed twin's
-// arguments, the chunk bounds and the work words the three share (8, or NULL)
-RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_gbuffer, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
-               float *out_normal, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_pick, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n,
-               void *out, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-RT_PER_VARIANT(hipError_t, rt_launch_pixel_cull_object_extents, const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect,
-               void *out, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
-// rt_stream_cull_adaptive.hip: rt_launch_stream_ray_list with the same chunks culled (rt_get_stream_cull_adaptive): its arguments, the chunk bounds and
-// work words of its own (8, or NULL)
+               const ChunkTables *chunks, unsigned long long *bounce_stats, hipStream_t stream)
+// rt_stream_cull_adaptive.hip: rt_launch_stream_ray_list with the same chunks culled (rt_get_stream_cull_adaptive): its arguments and the chunks, with work
+// words of its own
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
-               const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, const void *bounds,
-               uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+               const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, const ChunkTables *chunks,
+               hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
 
-// the launchers a context calls per variant; rt_create picks one of the two instances (rt_capi.cpp) from RT_FLAG_FAST
-struct Kernels {
-    decltype(&rt_launch_trace_strict) trace;
-    decltype(&rt_launch_wavefront_strict) wavefront;
-    decltype(&rt_launch_ray_list_strict) ray_list;
+// how a query reads the class tables: staged in LDS, streamed through a slice, or streamed with whole chunks culled
+enum TablePath { PATH_STAGED, PATH_STREAMED, PATH_CULLED };
+// the seven query launchers of one path (the types are the same on every path)
+struct QueryLaunchers {
     decltype(&rt_launch_gbuffer_strict) gbuffer;
     decltype(&rt_launch_pick_strict) pick;
+    decltype(&rt_launch_object_extents_strict) object_extents;
     decltype(&rt_launch_trace_rays_strict) trace_rays;
     decltype(&rt_launch_occluded_rays_strict) occluded_rays;
     decltype(&rt_launch_shade_rays_strict) shade_rays;
-    decltype(&rt_launch_object_extents_strict) object_extents;
     decltype(&rt_launch_trace_paths_strict) trace_paths;
-    decltype(&rt_launch_primary_rays_strict) primary_rays;
+};
+// the launchers a context calls per variant; rt_create picks one of the two instances (rt_capi.cpp) from RT_FLAG_FAST
+struct Kernels {
+    // rt_render: the simple, the product, the streamed kernel, and the streamed one culling (rt_get_stream_cull, rt_get_stream_cull_bounce)
+    decltype(&rt_launch_trace_strict) trace;
+    decltype(&rt_launch_wavefront_strict) wavefront;
     decltype(&rt_launch_stream_strict) stream;
-    // the query launchers of a context whose queries are streamed (rt_get_streamed_queries): the types are the staged twins'
-    decltype(&rt_launch_gbuffer_strict) stream_gbuffer;
-    decltype(&rt_launch_pick_strict) stream_pick;
-    decltype(&rt_launch_object_extents_strict) stream_object_extents;
-    decltype(&rt_launch_trace_rays_strict) stream_trace_rays;
-    decltype(&rt_launch_occluded_rays_strict) stream_occluded_rays;
-    decltype(&rt_launch_shade_rays_strict) stream_shade_rays;
-    decltype(&rt_launch_trace_paths_strict) stream_trace_paths;
-    // the halo and refine passes of a context whose adaptive passes are streamed (rt_get_streamed_adaptive)
-    decltype(&rt_launch_stream_ray_list_strict) stream_ray_list;
-    // rt_render of a context whose RT_FLAG_STREAM_CULL decision is true (rt_get_stream_cull)
     decltype(&rt_launch_stream_cull_strict) stream_cull;
-    // rt_render of a context whose RT_FLAG_STREAM_CULL_BOUNCE decision is true (rt_get_stream_cull_bounce)
     decltype(&rt_launch_stream_cull_bounce_strict) stream_cull_bounce;
-    // the ray queries of a context whose RT_FLAG_STREAM_CULL_RAYS decision is true (rt_get_stream_cull_rays)
-    decltype(&rt_launch_stream_cull_trace_rays_strict) stream_cull_trace_rays;
-    decltype(&rt_launch_stream_cull_occluded_rays_strict) stream_cull_occluded_rays;
-    decltype(&rt_launch_stream_cull_shade_rays_strict) stream_cull_shade_rays;
-    decltype(&rt_launch_stream_cull_trace_paths_strict) stream_cull_trace_paths;
-    // the pixel queries of a context whose RT_FLAG_STREAM_CULL_PIXELS decision is true (rt_get_stream_cull_pixels)
-    decltype(&rt_launch_pixel_cull_gbuffer_strict) pixel_cull_gbuffer;
-    decltype(&rt_launch_pixel_cull_pick_strict) pixel_cull_pick;
-    decltype(&rt_launch_pixel_cull_object_extents_strict) pixel_cull_object_extents;
-    // the halo and refine passes of a context whose streamed adaptive passes cull as well (rt_get_stream_cull_adaptive)
+    // the halo and refine passes of an adaptive frame: staged, streamed (rt_get_streamed_adaptive), and streamed and culling (rt_get_stream_cull_adaptive)
+    decltype(&rt_launch_ray_list_strict) ray_list;
+    decltype(&rt_launch_stream_ray_list_strict) stream_ray_list;
     decltype(&rt_launch_stream_cull_ray_list_strict) stream_cull_ray_list;
+    decltype(&rt_launch_primary_rays_strict) primary_rays;
+    QueryLaunchers query[3]; // by TablePath
 };
 
 // rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements

@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256) void primary_rays_kernel(const FrameArgs fa, c
 // rays = n rt_ray, segments = [max_segments][n] rt_hit (NULL iff max_segments == 0), last = n rt_hit or NULL, ends = n rt_path_end, all
 // in device memory and 16-byte aligned; at most max_grid workgroups.  The scene must fit the LDS limit (rt_rays_lds_bytes).
 extern "C" hipError_t RT_SYM(rt_launch_trace_paths)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
-                                                     void *last, void *ends, uint32_t max_grid, hipStream_t stream)
+                                                     void *last, void *ends, uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;

@@ -41,7 +41,8 @@ static hipError_t launch(const FrameArgs *fa, const void *scene, const void *ray
 extern "C" size_t RT_SYM(rt_rays_lds_bytes)(const FrameArgs *fa) { return (size_t) (fa->off_mat - fa->off_us); }
 
 // rays = n rt_ray, out = n rt_hit, both in device memory and 16-byte aligned; at most max_grid workgroups
-extern "C" hipError_t RT_SYM(rt_launch_trace_rays)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid, hipStream_t stream)
+extern "C" hipError_t RT_SYM(rt_launch_trace_rays)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
+                                                    const ChunkTables *, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::launch<false>(fa, scene, rays, nullptr, n, out, max_grid, stream);
@@ -49,7 +50,7 @@ extern "C" hipError_t RT_SYM(rt_launch_trace_rays)(const FrameArgs *fa, const vo
 
 // t_max = n doubles or NULL (MAX_T for every ray), out = n int32
 extern "C" hipError_t RT_SYM(rt_launch_occluded_rays)(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
-                                                       uint32_t max_grid, hipStream_t stream)
+                                                       uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::launch<true>(fa, scene, rays, t_max, n, out, max_grid, stream);

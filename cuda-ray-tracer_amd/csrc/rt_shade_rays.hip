@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void shade_rays_kernel(const ShadeRaysArgs sa,
 // rays = n rt_ray, rgba = n x 4 float32, hits = n rt_hit or NULL, all in device memory and 16-byte aligned; lights = the context's
 // DevLight array; at most max_grid workgroups.  The scene must fit the LDS limit (rt_rays_lds_bytes).
 extern "C" hipError_t RT_SYM(rt_launch_shade_rays)(const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
-                                                    uint32_t max_grid, hipStream_t stream)
+                                                    uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;

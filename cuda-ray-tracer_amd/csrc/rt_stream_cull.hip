@@ -39,16 +39,15 @@ __global__ __launch_bounds__(256) void stream_cull_frame_kernel(const FrameArgs 
 
 } // namespace RT_SYM(rtk)
 
-// rt_launch_stream's arguments, and: bounds = the context's chunk-bound table, [n_chunks] UsEntry for the ceil(n_us / 64) chunks of the
-// blob's (ordered) unit-sphere table; stats = 8 work words to add to, or NULL.
+// rt_launch_stream's arguments, and the context's chunks (rt_launch.h: ChunkTables).
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull)(const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
-                                                    const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+                                                    const ChunkTables *chunks, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (fa->n_tiles == 0u) return hipSuccess;
     const RayQueryArgs qa = rq_args(fa, 0u);
-    if (n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (n_chunks && !bounds)) return hipErrorInvalidValue;
-    const StreamCullArgs ca{reinterpret_cast<const UsEntry *>(bounds), stats, n_chunks, 0u};
+    StreamCullArgs ca;
+    if (!sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     const dim3 g(fa->n_tiles), block(256);
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     const DevLight *lt = reinterpret_cast<const DevLight *>(lights);

@@ -26,6 +26,15 @@ struct StreamCullArgs {
     uint32_t pad;
 };
 
+// (host) a context's chunks (rt_launch.h) as the kernels take them; false: the bounds do not belong to this scene's unit-sphere table.  The one
+// rule every culled launcher refuses by.
+static inline bool sc_cull_args(const FrameArgs *fa, const ChunkTables *chunks, StreamCullArgs &ca)
+{
+    if (chunks->n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (chunks->n_chunks && !chunks->bounds)) return false;
+    ca = StreamCullArgs{reinterpret_cast<const UsEntry *>(chunks->bounds), chunks->stats, chunks->n_chunks, 0u};
+    return true;
+}
+
 // a wave's work words (rt_debug_stream_cull); wave-uniform, touched only behind a wave-uniform `if (on)`
 struct ScStats {
     bool on;

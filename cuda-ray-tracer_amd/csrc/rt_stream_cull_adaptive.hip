@@ -165,20 +165,20 @@ static hipError_t sca_launch(const FrameArgs *fa, const StreamCullArgs &ca, cons
 
 } // namespace RT_SYM(rtk)
 
-// rt_launch_stream_ray_list's arguments, and: bounds = the context's chunk-bound table, [n_chunks] UsEntry for the ceil(n_us / 64) chunks
-// of the blob's (ordered) unit-sphere table; stats = 8 work words to add to (rt_debug_stream_cull_adaptive), or NULL.  One graph node.
+// rt_launch_stream_ray_list's arguments, and the context's chunks (rt_launch.h: ChunkTables; the work words are rt_debug_stream_cull_adaptive's).
+// One graph node.
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull_ray_list)(const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
                                                               const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out,
-                                                              int rgba8, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+                                                              int rgba8, const ChunkTables *chunks, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (grid == 0u) return hipSuccess;
-    if (n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (n_chunks && !bounds)) return hipErrorInvalidValue;
-    const StreamCullArgs ca{reinterpret_cast<const UsEntry *>(bounds), stats, n_chunks, 0u};
+    StreamCullArgs ca;
+    if (!sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     return sl_for_shapes(k, rgba8, [&](auto kk, auto r8) {
         constexpr int K = decltype(kk)::value;
         constexpr bool RGBA8 = decltype(r8)::value;
-        return stats ? sca_launch<K, RGBA8, true>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream)
+        return ca.stats ? sca_launch<K, RGBA8, true>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream)
                      : sca_launch<K, RGBA8, false>(fa, ca, scene, lights, camx, camy, list, count_ptr, n_items, grid, out, stream);
     });
 }

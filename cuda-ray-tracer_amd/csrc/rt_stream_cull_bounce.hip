@@ -122,16 +122,15 @@ __global__ __launch_bounds__(256) void stream_cull_bounce_frame_kernel(const Fra
 } // namespace RT_SYM(rtk)
 
 // rt_launch_stream_cull's arguments, and: bounce_stats = 8 bounce work words to add to (the kernel writes the first five), NULL exactly where
-// stats is NULL.
+// chunks->stats is NULL.
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull_bounce)(const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
-                                                           const void *bounds, uint32_t n_chunks, unsigned long long *stats, unsigned long long *bounce_stats,
-                                                           hipStream_t stream)
+                                                           const ChunkTables *chunks, unsigned long long *bounce_stats, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (fa->n_tiles == 0u) return hipSuccess;
     const RayQueryArgs qa = rq_args(fa, 0u);
-    if (n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (n_chunks && !bounds) || (stats == nullptr) != (bounce_stats == nullptr)) return hipErrorInvalidValue;
-    const StreamCullArgs ca{reinterpret_cast<const UsEntry *>(bounds), stats, n_chunks, 0u};
+    StreamCullArgs ca;
+    if (!sc_cull_args(fa, chunks, ca) || (ca.stats == nullptr) != (bounce_stats == nullptr)) return hipErrorInvalidValue;
     const dim3 g(fa->n_tiles), block(256);
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     const DevLight *lt = reinterpret_cast<const DevLight *>(lights);

@@ -53,20 +53,12 @@ __global__ __launch_bounds__(256) void extents_cull_kernel(const FrameArgs fa, c
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------
-// the chunk bounds as the kernels take them; false: they do not belong to this scene's table, or the context does not cull (no cone)
-static inline bool scp_cull_args(const FrameArgs *fa, const void *bounds, uint32_t n_chunks, unsigned long long *stats, StreamCullArgs &ca)
-{
-    if (fa->cull == 0u || n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (n_chunks && !bounds)) return false;
-    ca = StreamCullArgs{reinterpret_cast<const UsEntry *>(bounds), stats, n_chunks, 0u};
-    return true;
-}
-
+// (sc_cull_args, and: a context that does not cull has no cone)
 static hipError_t scp_launch_pixels(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, uint32_t grid, int32_t *out_object, double *out_t,
-                                    float *out_normal, const uint32_t *xy, uint32_t n, void *rec, const void *bounds, uint32_t n_chunks, unsigned long long *stats,
-                                    hipStream_t stream)
+                                    float *out_normal, const uint32_t *xy, uint32_t n, void *rec, const ChunkTables *chunks, hipStream_t stream)
 {
     StreamCullArgs ca;
-    if (!scp_cull_args(fa, bounds, n_chunks, stats, ca)) return hipErrorInvalidValue;
+    if (fa->cull == 0u || !sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     const RayQueryArgs qa = rq_args(fa, 0u);
     const unsigned char *s = reinterpret_cast<const unsigned char *>(scene);
     float4 *nrm = reinterpret_cast<float4 *>(out_normal);
@@ -77,31 +69,30 @@ static hipError_t scp_launch_pixels(const FrameArgs *fa, const void *scene, cons
 
 } // namespace RT_SYM(rtk)
 
-// The streamed launchers' arguments (rt_stream_queries.hip), and: the chunk bounds ([n_chunks] UsEntry, n_chunks = ceil(n_us / 64)) and the
-// work words to add to (8, the kernels write the first four; or NULL).  A launch is the same number of graph nodes as its twin's.
+// The streamed launchers' arguments (rt_stream_queries.hip), read: chunks = the context's chunk bounds and the work words to add to (8, the
+// kernels write the first four; or NULL).  A launch is the same number of graph nodes as its twin's.
 extern "C" hipError_t RT_SYM(rt_launch_pixel_cull_gbuffer)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
-                                                            float *out_normal, const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+                                                            float *out_normal, const ChunkTables *chunks, hipStream_t stream)
 {
     if (fa->n_tiles == 0u) return hipSuccess;
-    return RT_SYM(rtk)::scp_launch_pixels(fa, scene, camx, camy, fa->n_tiles, out_object, out_t, out_normal, nullptr, 0u, nullptr, bounds, n_chunks, stats, stream);
+    return RT_SYM(rtk)::scp_launch_pixels(fa, scene, camx, camy, fa->n_tiles, out_object, out_t, out_normal, nullptr, 0u, nullptr, chunks, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_pixel_cull_pick)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
-                                                         const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+                                                         const ChunkTables *chunks, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
-    return RT_SYM(rtk)::scp_launch_pixels(fa, scene, camx, camy, (n + 255u) / 256u, nullptr, nullptr, nullptr, xy, n, out, bounds, n_chunks, stats, stream);
+    return RT_SYM(rtk)::scp_launch_pixels(fa, scene, camx, camy, (n + 255u) / 256u, nullptr, nullptr, nullptr, xy, n, out, chunks, stream);
 }
 
 // Two nodes on `stream`, as rt_launch_stream_object_extents: the identities, then -- when this rank owns a row of the rectangle -- the kernel.
 extern "C" hipError_t RT_SYM(rt_launch_pixel_cull_object_extents)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect,
-                                                                   void *out, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats,
-                                                                   hipStream_t stream)
+                                                                   void *out, uint32_t max_grid, const ChunkTables *chunks, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (fa->n_obj == 0u) return hipSuccess;
     StreamCullArgs ca;
-    if (!scp_cull_args(fa, bounds, n_chunks, stats, ca)) return hipErrorInvalidValue;
+    if (fa->cull == 0u || !sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     ExtRecord *rec = reinterpret_cast<ExtRecord *>(out);
     hipLaunchKernelGGL(ext_identities_cull_kernel, dim3((fa->n_obj + 255u) / 256u), dim3(256), 0, stream, rec, fa->n_obj);
     const hipError_t e = hipGetLastError();

@@ -57,20 +57,12 @@ __global__ __launch_bounds__(256) void path_query_cull_kernel(const PathArgs pa,
 }
 
 // ---- launchers -------------------------------------------------------------------------------------------------------------------------------
-// the chunk bounds as the kernels take them; false: they do not belong to this scene's table
-static inline bool scr_cull_args(const FrameArgs *fa, const void *bounds, uint32_t n_chunks, unsigned long long *stats, StreamCullArgs &ca)
-{
-    if (n_chunks != (fa->n_us + SQ_CHUNK - 1u) / SQ_CHUNK || (n_chunks && !bounds)) return false;
-    ca = StreamCullArgs{reinterpret_cast<const UsEntry *>(bounds), stats, n_chunks, 0u};
-    return true;
-}
-
 template <bool OCCLUSION>
-static hipError_t scr_launch_rays(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, void *out, uint32_t max_grid, const void *bounds,
-                                  uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+static hipError_t scr_launch_rays(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, void *out, uint32_t max_grid,
+                                  const ChunkTables *chunks, hipStream_t stream)
 {
     StreamCullArgs ca;
-    if (!scr_cull_args(fa, bounds, n_chunks, stats, ca)) return hipErrorInvalidValue;
+    if (!sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     const RayQueryArgs qa = rq_args(fa, n);
     RK_LAUNCH(fa, (ray_query_cull_kernel<GQ, CUB, OCCLUSION>), rk_ray_grid(n, max_grid), 0, stream, qa, ca, reinterpret_cast<const unsigned char *>(scene),
               reinterpret_cast<const RqRay *>(rays), t_max, OCCLUSION ? nullptr : reinterpret_cast<RqRecord *>(out), OCCLUSION ? reinterpret_cast<int32_t *>(out) : nullptr);
@@ -79,31 +71,29 @@ static hipError_t scr_launch_rays(const FrameArgs *fa, const void *scene, const 
 
 } // namespace RT_SYM(rtk)
 
-// The streamed launchers' arguments (rt_stream_queries.hip), and: the chunk bounds ([n_chunks] UsEntry, n_chunks = ceil(n_us / 64)) and the
-// work words to add to (8, the kernels write the first five; or NULL).  A launch is the same number of graph nodes as its twin's.
+// The streamed launchers' arguments (rt_stream_queries.hip), read: chunks = the context's chunk bounds and the work words to add to (8, the
+// kernels write the first five; or NULL).  A launch is the same number of graph nodes as its twin's.
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull_trace_rays)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
-                                                                const void *bounds, uint32_t n_chunks, unsigned long long *stats, hipStream_t stream)
+                                                                const ChunkTables *chunks, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
-    return RT_SYM(rtk)::scr_launch_rays<false>(fa, scene, rays, nullptr, n, out, max_grid, bounds, n_chunks, stats, stream);
+    return RT_SYM(rtk)::scr_launch_rays<false>(fa, scene, rays, nullptr, n, out, max_grid, chunks, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull_occluded_rays)(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
-                                                                   uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats,
-                                                                   hipStream_t stream)
+                                                                   uint32_t max_grid, const ChunkTables *chunks, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
-    return RT_SYM(rtk)::scr_launch_rays<true>(fa, scene, rays, t_max, n, out, max_grid, bounds, n_chunks, stats, stream);
+    return RT_SYM(rtk)::scr_launch_rays<true>(fa, scene, rays, t_max, n, out, max_grid, chunks, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull_shade_rays)(const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba,
-                                                                void *hits, uint32_t max_grid, const void *bounds, uint32_t n_chunks, unsigned long long *stats,
-                                                                hipStream_t stream)
+                                                                void *hits, uint32_t max_grid, const ChunkTables *chunks, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
     StreamCullArgs ca;
-    if (!scr_cull_args(fa, bounds, n_chunks, stats, ca)) return hipErrorInvalidValue;
+    if (!sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     const ShadeRaysArgs sa = rk_shade_args(fa, n);
     RK_LAUNCH(fa, (shade_rays_cull_kernel<GQ, CUB>), rk_ray_grid(n, max_grid), 0, stream, sa, ca, reinterpret_cast<const unsigned char *>(scene),
               reinterpret_cast<const DevLight *>(lights), reinterpret_cast<const RqRay *>(rays), reinterpret_cast<float4 *>(rgba), reinterpret_cast<RqRecord *>(hits));
@@ -111,13 +101,12 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_cull_shade_rays)(const FrameArgs *
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_cull_trace_paths)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
-                                                                 void *last, void *ends, uint32_t max_grid, const void *bounds, uint32_t n_chunks,
-                                                                 unsigned long long *stats, hipStream_t stream)
+                                                                 void *last, void *ends, uint32_t max_grid, const ChunkTables *chunks, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
     StreamCullArgs ca;
-    if (!scr_cull_args(fa, bounds, n_chunks, stats, ca)) return hipErrorInvalidValue;
+    if (!sc_cull_args(fa, chunks, ca)) return hipErrorInvalidValue;
     const PathArgs pa = rk_path_args(fa, n, max_segments);
     RK_LAUNCH(fa, (path_query_cull_kernel<GQ, CUB>), rk_ray_grid(n, max_grid), 0, stream, pa, ca, reinterpret_cast<const unsigned char *>(scene),
               reinterpret_cast<const RqRay *>(rays), reinterpret_cast<RqRecord *>(segments), reinterpret_cast<RqRecord *>(last), reinterpret_cast<PathEnd *>(ends));

@@ -157,14 +157,14 @@ static hipError_t sqk_launch_pixels(const FrameArgs *fa, const void *scene, cons
 // The signatures are the staged launchers' (rt_gbuffer.hip, rt_rays.hip, rt_shade_rays.hip, rt_paths.hip), so an entry point picks one
 // or the other by the context's one decision; a launch is the same number of graph nodes as its twin's.
 extern "C" hipError_t RT_SYM(rt_launch_stream_gbuffer)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, int32_t *out_object, double *out_t,
-                                                        float *out_normal, hipStream_t stream)
+                                                        float *out_normal, const ChunkTables *, hipStream_t stream)
 {
     if (fa->n_tiles == 0u) return hipSuccess;
     return RT_SYM(rtk)::sqk_launch_pixels(fa, scene, camx, camy, fa->n_tiles, out_object, out_t, out_normal, nullptr, 0u, nullptr, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_pick)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *xy, uint32_t n, void *out,
-                                                     hipStream_t stream)
+                                                     const ChunkTables *, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::sqk_launch_pixels(fa, scene, camx, camy, (n + 255u) / 256u, nullptr, nullptr, nullptr, xy, n, out, stream);
@@ -172,7 +172,7 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_pick)(const FrameArgs *fa, const v
 
 // Two nodes on `stream`, as rt_launch_object_extents: the identities, then -- when this rank owns a row of the rectangle -- the kernel.
 extern "C" hipError_t RT_SYM(rt_launch_stream_object_extents)(const FrameArgs *fa, const void *scene, const double *camx, const double *camy, const uint32_t *rect, void *out,
-                                                               uint32_t max_grid, hipStream_t stream)
+                                                               uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (fa->n_obj == 0u) return hipSuccess;
@@ -201,21 +201,21 @@ static hipError_t sqk_launch_rays(const FrameArgs *fa, const void *scene, const 
 } // namespace RT_SYM(rtk)
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_trace_rays)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, void *out, uint32_t max_grid,
-                                                           hipStream_t stream)
+                                                           const ChunkTables *, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::sqk_launch_rays<false>(fa, scene, rays, nullptr, n, out, max_grid, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_occluded_rays)(const FrameArgs *fa, const void *scene, const void *rays, const double *t_max, uint32_t n, int32_t *out,
-                                                              uint32_t max_grid, hipStream_t stream)
+                                                              uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     if (n == 0u) return hipSuccess;
     return RT_SYM(rtk)::sqk_launch_rays<true>(fa, scene, rays, t_max, n, out, max_grid, stream);
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_shade_rays)(const FrameArgs *fa, const void *scene, const void *lights, const void *rays, uint32_t n, float *rgba, void *hits,
-                                                           uint32_t max_grid, hipStream_t stream)
+                                                           uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;
@@ -226,7 +226,7 @@ extern "C" hipError_t RT_SYM(rt_launch_stream_shade_rays)(const FrameArgs *fa, c
 }
 
 extern "C" hipError_t RT_SYM(rt_launch_stream_trace_paths)(const FrameArgs *fa, const void *scene, const void *rays, uint32_t n, uint32_t max_segments, void *segments,
-                                                            void *last, void *ends, uint32_t max_grid, hipStream_t stream)
+                                                            void *last, void *ends, uint32_t max_grid, const ChunkTables *, hipStream_t stream)
 {
     using namespace RT_SYM(rtk);
     if (n == 0u) return hipSuccess;

@@ -15,6 +15,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import stream_adaptive_scenes as A  # noqa: E402
+import launch_table as LT  # noqa: E402
 import stream_cull_adaptive_scenes as CA  # noqa: E402
 
 CSRC = os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc")
@@ -38,7 +39,7 @@ def test_symbols_and_prototypes(pkg):
     assert len(re.findall(r"RT_PER_VARIANT\(hipError_t, rt_launch_stream_cull_ray_list,", launch)) == 1
     assert re.search(r"decltype\(&rt_launch_stream_cull_ray_list_strict\) stream_cull_ray_list;", launch)   # the Kernels member
     capi = open(os.path.join(CSRC, "rt_capi.cpp")).read()
-    assert "RT_CAT(rt_launch_stream_cull_ray_list, V)}" in capi
+    assert LT.slot_of("rt_launch_stream_cull_ray_list") == "stream_cull_ray_list"      # ... filled by its name (tests/tools/launch_table.py)
     # the halo and the refine launch go through one function, which holds the one call of each of the three launchers
     one = capi.split("static hipError_t ray_list_launch(")[1].split("\n}\n")[0]
     for launcher in ("kern->stream_cull_ray_list(", "kern->stream_ray_list(", "kern->ray_list("):

@@ -18,7 +18,7 @@ CSRC = os.path.join(ROOT, "cuda-ray-tracer_amd", "csrc")
 NEW_FILES = ("rt_stream_cull_pixels.hpp", "rt_stream_cull_pixels.hip")
 KERNELS = {"gbuffer_cull_kernel": 4, "extents_cull_kernel": 4}   # instantiations per build
 LAUNCHERS = ("rt_launch_pixel_cull_gbuffer", "rt_launch_pixel_cull_pick", "rt_launch_pixel_cull_object_extents")
-DECISION = "ctx->stream_cull_pixels = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_PIXELS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;"
+DECISION = "cull[CULL_PIXELS] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_PIXELS) && cull[CULL_FRAME] && ctx->stream_queries && ctx->n_chunks >= 2u;"
 
 
 @pytest.fixture(autouse=True)
@@ -70,12 +70,15 @@ def test_symbols_and_prototypes(pkg):
     assert lib.rt_debug_stream_cull_pixels.argtypes[1] == C.POINTER(C.c_uint64)
     assert isinstance(pkg.Renderer.stream_cull_pixels, property) and callable(pkg.Renderer.stream_cull_pixels_stats)
     assert isinstance(pkg.MultiRenderer.stream_cull_pixels, property)
+    # declared once through RT_PER_VARIANT, with its query's one signature (the chunks in one record), and named by one slot of the launcher
+    # table: the culled path's, under its own query (tests/tools/launch_table.py)
+    import launch_table as LT
     launch = open(os.path.join(CSRC, "rt_launch.h")).read()
-    capi = open(os.path.join(CSRC, "rt_capi.cpp")).read()
     for l in LAUNCHERS:
-        assert re.search(rf"RT_PER_VARIANT\(hipError_t, {l},[^)]*const void \*bounds, uint32_t n_chunks, unsigned long long \*stats, hipStream_t stream\)", launch), l
-        assert re.search(rf"decltype\(&{l}_strict\) {l[len('rt_launch_'):]};", launch), l
-        assert f"RT_CAT({l}, V)" in capi, l
+        assert len(re.findall(rf"RT_PER_VARIANT\(hipError_t, {l},", launch)) == 1, l
+        assert LT.declared()[l].endswith(", const ChunkTables *chunks, hipStream_t stream") and "n_chunks" not in LT.declared()[l], l
+        assert LT.declared()[l] == LT.declared()[l.replace("pixel_cull_", "")], l      # the staged twin's
+        assert LT.slot_of(l) == f"query[PATH_CULLED].{l[len('rt_launch_pixel_cull_'):]}", l
     # the update.h adapter reads MI355RT_STREAM_CULL_PIXELS
     assert b"MI355RT_STREAM_CULL_PIXELS" in open(pkg.UPDATE_LIB_PATH, "rb").read()
 
@@ -174,17 +177,23 @@ def test_the_new_files_have_no_workgroup_barrier_and_one_body_each():
 
 def test_the_launch_sites_pick_by_the_one_decision():
     capi = open(os.path.join(CSRC, "rt_capi.cpp")).read()
-    assert DECISION in capi and capi.count("ctx->stream_cull_pixels =") == 1
-    # rt_render_gbuffer, rt_pick, rt_object_extents and rt_object_extents_host: the culled launcher by the decision, else the one as before
-    for name, sites in (("gbuffer", 1), ("pick", 1), ("object_extents", 2)):
-        assert len(re.findall(rf"ctx->stream_cull_pixels \? ctx->kern->pixel_cull_{name}\([^\n]*RT_CULL_PIXELS_ARGS\(ctx\), stream\)\n\s*: RT_QUERY_KERNEL\(ctx, {name}\)\(", capi)) == sites, name
-        assert len(re.findall(rf"pixel_cull_{name}\(", capi)) == sites == len(re.findall(rf"RT_QUERY_KERNEL\(ctx, {name}\)", capi)), name
-    assert "#define RT_CULL_PIXELS_ARGS(ctx) (ctx)->d_bounds, (ctx)->n_chunks, (ctx)->d_cull_pixels_stats" in capi
-    # the work words: only under the environment switch and a true decision
-    assert re.search(r'if \(e && !std::strcmp\(e, "1"\) && ctx->stream_cull_pixels\)\n\s*if \(int rc = device_table\(ctx->d_cull_pixels_stats,', capi)
-    # the G pass of an adaptive frame keeps the streamed kernels
+    assert DECISION in capi and capi.count("cull[CULL_PIXELS] =") == 1
+    # ... which picks the launchers once, for the context's life: the culled ones by the decision, else the ones as before
+    assert capi.count("ctx->pixel_q = &ctx->kern->query[cull[CULL_PIXELS] ? PATH_CULLED : plain];") == 1 == capi.count("ctx->pixel_q =")
+    assert "const TablePath plain = ctx->stream_queries ? PATH_STREAMED : PATH_STAGED;" in capi
+    # rt_render_gbuffer, rt_pick, and rt_object_extents and rt_object_extents_host through their one helper: one site each, with the family's chunks
+    for name in ("gbuffer", "pick", "object_extents"):
+        assert len(re.findall(rf"ctx->pixel_q->{name}\([^\n]*, &ctx->chunks\[CULL_PIXELS\], stream\);", capi)) == 1 == len(re.findall(rf"pixel_q->{name}\(", capi)), name
+    assert capi.count("extents_launch(") == 3 and all(f'extents_launch("{who}", ctx, fa, r, ' in capi for who in ("rt_object_extents", "rt_object_extents_host"))
+    # the work words: only under the environment switch and a true decision -- one allocation for all families, a family's eight where it culls
+    assert re.search(r'if \(e && !std::strcmp\(e, "1"\)\)\n\s*if \(int rc = device_table\(ctx->d_cull_words, nullptr, sizeof\(unsigned long long\) \* 8 \* N_CULL_FAMILIES,', capi)
+    assert "const bool words = ctx->d_cull_words && !(f == CULL_ADAPTIVE && fa.n_gq && fa.n_cub);" in capi
+    assert "if (ctx->cull[f]) ctx->chunks[f] = ChunkTables{ctx->d_bounds.p, ctx->n_chunks, words ? ctx->d_cull_words + 8 * f : nullptr};" in capi
+    assert capi.count("ctx->chunks[f] =") == 1 and len(re.findall(r"ctx->chunks\[\w+\](\.\w+)? =[^=]", capi)) == 1 and capi.count("d_cull_words.alloc") == 0
+    # the G pass of an adaptive frame keeps the streamed kernels: it names its path itself
     g = capi.split("if (ctx->geometry) {")[1].split("RT_HIP(rt_launch_classify_geometry_strict(")[0]
-    assert "pixel_cull" not in g and "stream_cull_pixels" not in g
+    assert "pixel_q" not in g and "PATH_CULLED" not in g and "CULL_PIXELS" not in g
+    assert "const QueryLaunchers &g = ctx->kern->query[ctx->stream_adaptive ? PATH_STREAMED : PATH_STAGED];" in g and g.count("g.gbuffer(") == 1 == g.count("g.pick(")
 
 
 def test_the_docs_name_the_flag():

@@ -64,12 +64,15 @@ def test_symbols_and_prototypes(pkg):
     assert lib.rt_debug_stream_cull_rays.argtypes[1] == C.POINTER(C.c_uint64)
     assert isinstance(pkg.Renderer.stream_cull_rays, property) and callable(pkg.Renderer.stream_cull_rays_stats)
     assert isinstance(pkg.MultiRenderer.stream_cull_rays, property)
+    # declared once through RT_PER_VARIANT, with its query's one signature (the chunks in one record), and named by one slot of the launcher
+    # table: the culled path's, under its own query (tests/tools/launch_table.py)
+    import launch_table as LT
     launch = open(os.path.join(CSRC, "rt_launch.h")).read()
-    capi = open(os.path.join(CSRC, "rt_capi.cpp")).read()
     for l in LAUNCHERS:
-        assert re.search(rf"RT_PER_VARIANT\(hipError_t, {l},[^)]*const void \*bounds, uint32_t n_chunks, unsigned long long \*stats, hipStream_t stream\)", launch), l
-        assert re.search(rf"decltype\(&{l}_strict\) {l[len('rt_launch_'):]};", launch), l
-        assert f"RT_CAT({l}, V)" in capi, l
+        assert len(re.findall(rf"RT_PER_VARIANT\(hipError_t, {l},", launch)) == 1, l
+        assert LT.declared()[l].endswith(", const ChunkTables *chunks, hipStream_t stream") and "n_chunks" not in LT.declared()[l], l
+        assert LT.declared()[l] == LT.declared()[l.replace("stream_cull_", "")], l      # the staged twin's
+        assert LT.slot_of(l) == f"query[PATH_CULLED].{l[len('rt_launch_stream_cull_'):]}", l
     # the update.h adapter reads MI355RT_STREAM_CULL_RAYS
     assert b"MI355RT_STREAM_CULL_RAYS" in open(pkg.UPDATE_LIB_PATH, "rb").read()
 
@@ -185,13 +188,15 @@ def test_the_neighbours_are_untouched():
 
 def test_the_launch_sites_pick_by_the_one_decision():
     capi = open(os.path.join(CSRC, "rt_capi.cpp")).read()
-    assert ("ctx->stream_cull_rays = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_RAYS) && ctx->stream_cull && ctx->stream_queries && ctx->n_chunks >= 2u;") in capi
-    assert capi.count("ctx->stream_cull_rays =") == 1
-    for name in ("trace_rays", "occluded_rays", "shade_rays", "trace_paths"):
-        assert len(re.findall(rf"ctx->kern->stream_cull_{name}\(", capi)) == 1, name
-        assert len(re.findall(rf"RT_QUERY_KERNEL\(ctx, {name}\)", capi)) == 1, name      # one site each, behind trace_launch / shade_launch / paths_launch
+    assert ("cull[CULL_RAYS] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_RAYS) && cull[CULL_FRAME] && ctx->stream_queries && ctx->n_chunks >= 2u;") in capi
+    assert capi.count("cull[CULL_RAYS] =") == 1
+    # ... which picks the launchers once, for the context's life
+    assert capi.count("ctx->ray_q = &ctx->kern->query[cull[CULL_RAYS] ? PATH_CULLED : plain];") == 1 == capi.count("ctx->ray_q =")
+    assert "const TablePath plain = ctx->stream_queries ? PATH_STREAMED : PATH_STAGED;" in capi
+    for name in ("trace_rays", "occluded_rays", "shade_rays", "trace_paths"):      # one site each (three behind trace_launch / shade_launch / paths_launch), with the family's chunks
+        assert len(re.findall(rf"ctx->ray_q->{name}\([^\n]*, &ctx->chunks\[CULL_RAYS\], stream\);", capi)) == 1 == len(re.findall(rf"->{name}\(", capi)), name
     for name in ("gbuffer", "pick", "object_extents"):      # the pixel queries keep theirs
-        assert f"stream_cull_{name}" not in capi, name
+        assert f"ray_q->{name}" not in capi and len(re.findall(rf"{name}\([^\n]*CULL_RAYS", capi)) == 0, name
 
 
 # ---- the predicate, asked about bounds ----------------------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 import gbuffer_ref  # noqa: E402
+import launch_table as LT  # noqa: E402
 import query_table_scenes as Q  # noqa: E402
 import stream_query_scenes as B  # noqa: E402
 import stream_scenes as S  # noqa: E402
@@ -53,7 +54,10 @@ def test_symbols_and_prototypes(pkg):
         for variant in ("strict", "fast"):
             assert re.search(rf"\bT rt_launch_stream_{what}_{variant}\b", names), (what, variant)
         # declared once for both variants, with the staged twin's type in the table the contexts call through
-        assert re.search(rf"RT_PER_VARIANT\(hipError_t, rt_launch_stream_{what},", launch) and re.search(rf"decltype\(&rt_launch_{what}_strict\) stream_{what};", launch), what
+        # (the table: struct QueryLaunchers has one member per query, of the staged launcher's type, and the streamed path's slot names this launcher)
+        assert re.search(rf"RT_PER_VARIANT\(hipError_t, rt_launch_stream_{what},", launch) and LT.members()[0][what] == f"rt_launch_{what}", what
+        assert LT.declared()[f"rt_launch_stream_{what}"] == LT.declared()[f"rt_launch_{what}"], what
+        assert LT.slot_of(f"rt_launch_stream_{what}") == f"query[PATH_STREAMED].{what}" and LT.slot_of(f"rt_launch_{what}") == f"query[PATH_STAGED].{what}", what
     lib = pkg.lib()
     assert lib.rt_get_streamed_queries.argtypes[1] == C.POINTER(C.c_uint32)
     assert isinstance(pkg.Renderer.streamed_queries, property)

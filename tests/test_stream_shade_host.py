@@ -298,8 +298,10 @@ def test_the_pixel_kernels_bodies_exist_once():
     # the G pass of an adaptive frame with the geometric term: the two launchers rt_render_gbuffer / rt_pick call, chosen by the context's one decision
     capi = code_of("rt_capi.cpp")
     g = capi.split("if (ctx->geometry) {")[1].split("RT_HIP(rt_launch_classify_geometry_strict(")[0]
-    assert "(ctx->stream_adaptive ? k->stream_gbuffer : k->gbuffer)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, stream)" in g
-    assert "(ctx->stream_adaptive ? k->stream_pick : k->pick)(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, stream)" in g
+    # (the streamed or the staged path of the launcher table -- DESIGN.md section 35 --, named here and never the pixel entry points' culled one)
+    assert "const QueryLaunchers &g = ctx->kern->query[ctx->stream_adaptive ? PATH_STREAMED : PATH_STAGED];" in g
+    assert "g.gbuffer(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_obj, nullptr, nrm, nullptr, stream)" in g
+    assert "g.pick(&fa, ctx->d_obj, ctx->d_camx, ctx->d_camy, ctx->d_geo_xy, ctx->halo_slots * ctx->width, ctx->d_geo_halo, nullptr, stream)" in g
     assert g.count("RT_HIP(") == 2
 
 
