@@ -38,6 +38,7 @@ RT_FLAG_STREAM_CULL = 524288                # a streamed context keeps its unit 
 RT_FLAG_STREAM_CULL_BOUNCE = 1048576        # ... and culls the chunks of its bounce rays per ray (with RT_FLAG_STREAM_CULL, mirrors and at least two chunks; same frame)
 RT_FLAG_STREAM_CULL_RAYS = 2097152          # ... and culls the chunks per caller-supplied ray in the ray queries (with RT_FLAG_STREAM_CULL, streamed queries and at least two chunks; same outputs)
 RT_FLAG_STREAM_CULL_PIXELS = 4194304        # ... and culls the chunks by the block's cone in the pixel queries (with RT_FLAG_STREAM_CULL, streamed queries and at least two chunks; same outputs)
+RT_FLAG_STREAM_CULL_REORDER = 8388608       # ... and reorder_scene() puts the unit spheres back into that spatial order after set_scene moved them (with RT_FLAG_STREAM_CULL; same frame)
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -57,13 +58,13 @@ ABI_SYMBOLS = [
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
     "rt_sort_rays_work_bytes", "rt_sort_rays", "rt_permute",
-    "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob",
+    "rt_set_scene", "rt_set_scene_host", "rt_set_scene_status", "rt_debug_scene_blob", "rt_reorder_scene", "rt_get_stream_cull_reorder",
     "rt_get_counters", "rt_get_counters_detail", "rt_debug_counters", "rt_debug_stamp_rows", "rt_debug_wave_box", "rt_destroy",
 ]
 # ... and the ones libmi355rt_multi.so exports
 MULTI_ABI_SYMBOLS = ["rt_create_multi", "rt_render_multi", "rt_multi_wait", "rt_multi_fb", "rt_multi_stream", "rt_multi_download", "rt_multi_info",
                      "rt_multi_last_transfer", "rt_multi_set_ssaa_threshold", "rt_multi_set_ssaa_geometry", "rt_multi_destroy",
-                     "rt_set_scene_multi", "rt_multi_set_scene_status", "rt_multi_query_ctx", "rt_render_gbuffer_multi", "rt_object_extents_multi",
+                     "rt_set_scene_multi", "rt_reorder_scene_multi", "rt_multi_set_scene_status", "rt_multi_query_ctx", "rt_render_gbuffer_multi", "rt_object_extents_multi",
                      "rt_object_extents_multi_host"]
 RT_MULTI_SELF_EXCHANGE = 0x10000
 RT_MULTI_BANDWISE = 0x20000
@@ -260,6 +261,9 @@ def lib():
         L.rt_set_scene_host.argtypes = [vp, C.POINTER(SceneUpdate), vp]
         L.rt_set_scene_status.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.rt_debug_scene_blob.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        if LIB_PATH != os.environ.get("MI355RT_LIB") or hasattr(L, "rt_reorder_scene"):   # (an earlier build under MI355RT_LIB: as rt_sort_rays below)
+            L.rt_reorder_scene.argtypes = [vp, vp]
+            L.rt_get_stream_cull_reorder.argtypes = [vp, C.POINTER(C.c_uint32)]
         L.rt_assemble_planes.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint32, vp]
         L.rt_merge_object_extents.argtypes = [vp, vp, C.c_uint32, vp, vp]
         if LIB_PATH != os.environ.get("MI355RT_LIB") or hasattr(L, "rt_sort_rays"):   # (an earlier build of this ABI under MI355RT_LIB: calling them raises)
@@ -313,6 +317,7 @@ def multi_lib():
         M.rt_multi_set_ssaa_threshold.argtypes = [vp, C.c_float]
         M.rt_multi_set_ssaa_geometry.argtypes = [vp, C.c_float]
         M.rt_set_scene_multi.argtypes = [vp, C.POINTER(SceneUpdate)]
+        M.rt_reorder_scene_multi.argtypes = [vp]
         M.rt_multi_set_scene_status.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         M.rt_multi_query_ctx.argtypes = [vp]
         M.rt_multi_query_ctx.restype = vp
@@ -826,10 +831,10 @@ class Renderer:
                                    ends.ctypes.data_as(C.POINTER(PathEnd)), C.c_void_p(stream) if stream else None))
         return seg, ends
 
-    def set_scene(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None):
+    def set_scene(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None, reorder=False):
         """Replace the scene's raw descriptor arrays (numpy, rt_scene_desc layout; None = keep what the context holds) without a new
         context (rt_set_scene_host; blocks).  Raises SceneException when the update would change the scene's layout (include/mi355rt.h,
-        "Scene updates"): nothing was written then."""
+        "Scene updates"): nothing was written then.  reorder=True: reorder_scene() behind the applied update, on the same stream."""
         given = dict(coefs=coefs, reflection=reflection, albedo=albedo, light_p=light_p, light_color=light_color)
         keep = {n: np.ascontiguousarray(given[n], dtype=dt) for n, dt in SCENE_UPDATE_FIELDS if given[n] is not None}
         no, nl = self._desc.n_objects, self._desc.n_lights
@@ -839,12 +844,32 @@ class Renderer:
                 raise ValueError(f"set_scene: {n} has {a.size} values, the scene takes {want[n]}")
         u = SceneUpdate(**{n: (a.ctypes.data if a.size else None) for n, a in keep.items()})
         _check(lib().rt_set_scene_host(self._h, C.byref(u), C.c_void_p(stream) if stream else None))
+        if reorder:
+            self.reorder_scene(stream)
 
-    def set_scene_into(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None):
+    def set_scene_into(self, coefs=None, reflection=None, albedo=None, light_p=None, light_color=None, stream=None, reorder=False):
         """rt_set_scene on the caller's device memory (raw pointers, for example tensor.data_ptr(); None = keep): enqueues one kernel
-        and returns -- capturable into a graph; whether it was applied is on the device (set_scene_status)."""
+        and returns -- capturable into a graph; whether it was applied is on the device (set_scene_status).  reorder=True: reorder_scene()
+        is enqueued behind it on the same stream (a rejected update wrote nothing, and the reorder then re-sorts what the context held)."""
         u = SceneUpdate(coefs or None, reflection or None, albedo or None, light_p or None, light_color or None)
         _check(lib().rt_set_scene(self._h, C.byref(u), C.c_void_p(stream) if stream else None))
+        if reorder:
+            self.reorder_scene(stream)
+
+    def reorder_scene(self, stream=None):
+        """rt_reorder_scene: put the unit-sphere table the device holds into the spatial order a fresh Renderer on the current scene would
+        choose and rebuild the chunk bounds -- kernels only, in the context's frame order, capturable into a graph.  No frame and no
+        query changes, only the work they do: set_scene keeps the order chosen at creation, so the chunks of spheres that mix stop
+        culling until this is called.  Enqueues nothing where stream_cull_reorder is False."""
+        _check(lib().rt_reorder_scene(self._h, C.c_void_p(stream) if stream else None))
+
+    @property
+    def stream_cull_reorder(self):
+        """True where reorder_scene() re-sorts: RT_FLAG_STREAM_CULL_REORDER on a context whose stream_cull is True
+        (rt_get_stream_cull_reorder)."""
+        n = C.c_uint32()
+        _check(lib().rt_get_stream_cull_reorder(self._h, C.byref(n)))
+        return bool(n.value)
 
     def set_scene_status(self):
         """Updates applied / rejected since the context was created and the reason / index of the last rejection (waits)."""
@@ -1111,6 +1136,10 @@ class MultiRenderer:
                 raise ValueError(f"set_scene: {n} has {a.size} values, the scene takes {want[n]}")
         u = SceneUpdate(**{n: (a.ctypes.data if a.size else None) for n, a in keep.items()})
         _check(multi_lib().rt_set_scene_multi(self._h, C.byref(u)))
+
+    def reorder_scene(self):
+        """Renderer.reorder_scene on every context (rt_reorder_scene_multi): enqueues only, in every context's frame order."""
+        _check(multi_lib().rt_reorder_scene_multi(self._h))
 
     def set_scene_status(self):
         """Updates applied / rejected and the reason / index of the last rejection, the same on every context (waits for all of them)."""

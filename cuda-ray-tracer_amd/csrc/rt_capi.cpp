@@ -283,6 +283,11 @@ struct rt_ctx {
     uint32_t n_chunks = 0;
     DevMem<UsEntry> d_bounds;
     DevMem<unsigned long long> d_cull_words; // [N_CULL_FAMILIES][8]; only with MI355RT_STREAM_CULL_STATS=1 in the environment at rt_create
+    // rt_reorder_scene (rt_reorder_scene.hip): the decision (create_scene; RT_FLAG_STREAM_CULL_REORDER on a context whose frame culls), its work space (sized
+    // from n_us alone) and the workgroups a launch of it may take (MI355RT_REORDER_MAX_GRID at rt_create lowers it: the tests reach the grids' second trip with it)
+    bool reorder = false;
+    DevMem<unsigned char> d_reorder_work;
+    uint32_t reorder_max_grid = 0;
     // the launchers of the pixel and the ray entry points: the staged, the streamed (stream_queries) or the culled (cull[CULL_PIXELS], cull[CULL_RAYS]) path of kern->query
     const QueryLaunchers *pixel_q = nullptr, *ray_q = nullptr;
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
@@ -608,6 +613,9 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
         im.bounds = rtp::stream_cull_image(im, fa);
         ctx->n_chunks = (uint32_t) im.bounds.size();
     }
+    // ... and can rt_reorder_scene put that table back into this order after rt_set_scene has moved the spheres (rt_reorder_scene.hip)?  The flag and the
+    // decision above.  False: call for call the context without the flag -- no work space, and rt_reorder_scene enqueues nothing.
+    ctx->reorder = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_REORDER) && cull[CULL_FRAME];
     // ... and do the halo and refine passes cull them too (rt_stream_cull_adaptive.hip)?  Both decisions above, and a second chunk: with one,
     // the chunk level can remove nothing and is paid per query.
     cull[CULL_ADAPTIVE] = cull[CULL_FRAME] && ctx->stream_adaptive && ctx->n_chunks >= 2u;
@@ -652,6 +660,16 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
         for (int f = 0; f < N_CULL_FAMILIES; f++) {
             const bool words = ctx->d_cull_words && !(f == CULL_ADAPTIVE && fa.n_gq && fa.n_cub);
             if (ctx->cull[f]) ctx->chunks[f] = ChunkTables{ctx->d_bounds.p, ctx->n_chunks, words ? ctx->d_cull_words + 8 * f : nullptr};
+        }
+    }
+    if (ctx->reorder) {
+        RT_TRY("hipMalloc(reorder work space)", ctx->d_reorder_work.alloc(rt_reorder_scene_work_size(fa.n_us)));
+        ctx->reorder_max_grid = ctx->wg_slots / 6u * 4u;
+        if (const char *e = std::getenv("MI355RT_REORDER_MAX_GRID")) {
+            char *end = nullptr;
+            const unsigned long v = std::strtoul(e, &end, 10);
+            if (!*e || *end || v == 0ul || v > 65535ul) return fail(RT_ERR_INVALID, "rt_create: MI355RT_REORDER_MAX_GRID=%s: expected a number of workgroups, 1 .. 65535", e);
+            ctx->reorder_max_grid = (uint32_t) v;
         }
     }
     RT_TRY("hipEventCreate", ctx->ev0.create());
@@ -1471,7 +1489,7 @@ static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update
     a.off_lin = fa.off_lin;
     a.off_mat = fa.off_mat;
     a.has_mirror = fa.has_mirror;
-    a.n_chunks = ctx->cull[CULL_FRAME] ? ctx->n_chunks : 0u; // (the chunk bounds follow the rebuilt entries; the order chosen at rt_create stays)
+    a.n_chunks = ctx->cull[CULL_FRAME] ? ctx->n_chunks : 0u; // (the chunk bounds follow the rebuilt entries; the slots keep their objects: only rt_reorder_scene moves an entry)
     a.bounds = ctx->cull[CULL_FRAME] ? ctx->d_bounds.p : nullptr;
     const hipError_t e = rt_launch_set_scene(&a, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
@@ -1522,6 +1540,30 @@ extern "C" int rt_set_scene_host(rt_ctx *ctx, const rt_scene_update *host, void 
     RT_HIP(hipStreamSynchronize(stream));
     if (st.last == 2u)
         return fail(RT_ERR_SCENE, "rt_set_scene_host: update rejected, nothing was written: reason %u at index %u: %s", st.reason, st.index, reject_text(st.reason));
+    return RT_OK;
+}
+
+// Re-sort the unit-sphere table the device holds now into the order rt_create would choose for it, and rebuild the chunk bounds: kernels only, in the
+// context's frame order (order_begin / order_end, as rt_set_scene), every launch decided at rt_create.  A context whose decision is false enqueues nothing.
+extern "C" int rt_reorder_scene(rt_ctx *ctx, void *stream_)
+{
+    if (!ctx) return fail(RT_ERR_INVALID, "rt_reorder_scene: null argument");
+    if (!ctx->reorder) return RT_OK;
+    hipStream_t stream = (hipStream_t) stream_;
+    if (int rc = use_device(ctx)) return rc;
+    bool capturing = false;
+    if (int rc = order_begin("rt_reorder_scene", ctx, stream, &capturing)) return rc;
+    const FrameArgs &fa = ctx->fa;
+    unsigned char *blob = reinterpret_cast<unsigned char *>(ctx->d_obj.p);
+    const hipError_t e = rt_launch_reorder_scene(blob + fa.off_us, fa.n_us, fa.n_obj, ctx->d_bounds.p, ctx->d_reorder_work.p, ctx->reorder_max_grid, stream);
+    if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_reorder_scene: kernel launch failed: %s", hipGetErrorString(e));
+    return order_end(ctx, stream, capturing);
+}
+
+extern "C" int rt_get_stream_cull_reorder(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_cull_reorder: null argument");
+    *on = ctx->reorder ? 1u : 0u;
     return RT_OK;
 }
 

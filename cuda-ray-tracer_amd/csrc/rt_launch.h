@@ -126,6 +126,11 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, 
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
+// rt_reorder_scene.hip, built once likewise (the key and the bounds are the host's functions): the bytes of work space a table of n_us entries takes (0 for
+// n_us == 0), and the re-sort of the blob's unit-sphere table t_us into the order of rtp::stream_cull_image with the chunk bounds rebuilt -- work holds
+// at least rt_reorder_scene_work_size(n_us) bytes, n_us > 0, every entry's orig is below n_obj
+extern "C" size_t rt_reorder_scene_work_size(uint32_t n_us);
+extern "C" hipError_t rt_launch_reorder_scene(void *t_us, uint32_t n_us, uint32_t n_obj, void *bounds, void *work, uint32_t max_grid, hipStream_t stream);
 
 // how a query reads the class tables: staged in LDS, streamed through a slice, or streamed with whole chunks culled
 enum TablePath { PATH_STAGED, PATH_STREAMED, PATH_CULLED };

@@ -37,6 +37,10 @@
 
 #include "mi355rt.h"
 
+// A weak reference: the recording runtime this file is also linked against without a GPU (tests/tools/multi_shim.cpp) holds the entry points of the
+// recorded call orders, which were not extended by this one; libmi355rt.so always defines it.
+extern "C" int rt_reorder_scene(rt_ctx *ctx, void *stream) __attribute__((weak));
+
 namespace {
 
 int fail(int code, const char *fmt, ...)
@@ -727,6 +731,26 @@ extern "C" int rt_set_scene_multi(rt_multi *m, const rt_scene_update *host)
         M_HIP(hipEventRecord(m->ev_scene[r], m->s_render[r]));
     }
     m->have_scene_event = true;
+    guard.ok = true;
+    return RT_OK;
+}
+
+// rt_reorder_scene on every context, device by device on its render stream: behind an earlier rt_set_scene_multi, in front of later frames
+extern "C" int rt_reorder_scene_multi(rt_multi *m)
+{
+    if (!m) return fail(RT_ERR_INVALID, "rt_reorder_scene_multi: null argument");
+    if (int rc = refuse_failed(m, "rt_reorder_scene_multi")) return rc;
+    if (!rt_reorder_scene) return fail(RT_ERR_DEVICE, "rt_reorder_scene_multi: this runtime has no rt_reorder_scene");
+    DeviceRestore restore;
+    CallGuard guard{m, false};
+    for (uint32_t r = 0; r < m->n; r++) {
+        ON_DEVICE(r);
+        for (uint32_t p = 0; p < m->parts; p++) {
+            const int rc = rt_reorder_scene(m->ctx[p * m->n + r], m->s_render[r]);
+            if (rc != RT_OK) return rc;
+            guard.armed = true; // from here on the contexts may hold different orders (no result depends on that, but a launch failed: the object is done)
+        }
+    }
     guard.ok = true;
     return RT_OK;
 }

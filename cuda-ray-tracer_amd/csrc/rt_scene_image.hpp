@@ -114,11 +114,12 @@ inline SceneImage scene_image(const rt_scene_desc &sd, uint32_t flags, FrameArgs
 // moves; an entry keeps its bytes, `orig` included.
 //
 // The order (slot_orig == nullptr, rt_create): the spheres with a bounding radius first, by the Morton key of their centres, ties by
-// object index; the others behind them in index order.  Key: per axis q = (uint64) ((c - lo) / (hi - lo) * 2097151.0) (21 bits; 0 where
-// hi == lo), lo / hi = the box of the bounded spheres' centres; bit 3 b + 2 of the key is bit b of q_x, 3 b + 1 that of q_y, 3 b that of
-// q_z.  No result depends on it: it only decides which spheres share a chunk.
+// object index; the others behind them in index order.  Key (rt_scene_pack.hpp, stream_cull_key: one copy for the host and the device): per axis
+// q = (uint64) ((c - lo) / (hi - lo) * 2097151.0) (21 bits; 0 where hi == lo), lo / hi = the box of the bounded spheres' centres; bit 3 b + 2 of the
+// key is bit b of q_x, 3 b + 1 that of q_y, 3 b that of q_z.  No result depends on it: it only decides which spheres share a chunk.
 // slot_orig != nullptr (the tests, for a context that has seen rt_set_scene): slot s takes the entry of object slot_orig[s] -- the order
-// is the context's, chosen at rt_create, and stays.
+// is the context's, chosen at rt_create, and rt_set_scene keeps it.  (rt_reorder_scene, rt_reorder_scene.hip, chooses it anew on the device by the rule
+// above -- the same key function, stream_cull_key -- and then the device holds what this function packs with slot_orig == nullptr.)
 inline std::vector<UsEntry> stream_cull_image(SceneImage &im, const FrameArgs &fa, unsigned char fill = 0, const uint32_t *slot_orig = nullptr)
 {
     const uint32_t n = fa.n_us;
@@ -139,21 +140,8 @@ inline std::vector<UsEntry> stream_cull_image(SceneImage &im, const FrameArgs &f
                 hi[k] = c[k] > hi[k] ? c[k] : hi[k];
             }
         }
-        std::vector<uint64_t> key(n, ~(uint64_t) 0); // (unbounded: behind every bounded sphere)
-        for (uint32_t j = 0; j < n; j++) {
-            const UsEntry &e = old[j];
-            if (!(e.r < INFINITY)) continue;
-            const double c[3] = {-0.5 * e.kx, -0.5 * e.ky, -0.5 * e.kz};
-            uint64_t m = 0;
-            for (int k = 0; k < 3; k++) {
-                const double span = hi[k] - lo[k];
-                double f = (span > 0.0 && finite64(span)) ? (c[k] - lo[k]) / span * 2097151.0 : 0.0;
-                f = f > 0.0 ? (f < 2097151.0 ? f : 2097151.0) : 0.0;
-                const uint64_t q = (uint64_t) f;
-                for (int b = 0; b < 21; b++) m |= ((q >> b) & 1u) << (3 * b + (2 - k));
-            }
-            key[j] = m;
-        }
+        std::vector<uint64_t> key(n);
+        for (uint32_t j = 0; j < n; j++) key[j] = stream_cull_key(old[j], lo, hi); // (unbounded: ~0, behind every bounded sphere)
         for (uint32_t j = 0; j < n; j++) order[j] = j;
         std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] != key[b] ? key[a] < key[b] : old[a].orig < old[b].orig; });
     }

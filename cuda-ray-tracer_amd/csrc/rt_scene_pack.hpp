@@ -186,6 +186,31 @@ RT_PACK_FN void pack_chunk_bound(UsEntry &out, const UsEntry *members, uint32_t 
     out.c = bounded ? ((Cx * Cx + Cy * Cy) + Cz * Cz) - r * r : 0.0;
 }
 
+// The key the unit-sphere table of a culling context is ordered by (RT_FLAG_STREAM_CULL; rt_scene_image.hpp, stream_cull_image, on the host and
+// rt_reorder_scene.hip on the device): entries ascend by (key, orig).  lo / hi: the box of the centres (-k / 2) of the entries with a
+// bounding radius.  Per axis q = (uint64) ((c - lo) / (hi - lo) * 2097151.0), clamped to 0 .. 2097151 (21 bits) and 0 where the span is
+// not a positive finite number; bit 3 b + 2 of the key is bit b of q_x, 3 b + 1 that of q_y, 3 b that of q_z: 63 bits.  An entry
+// without a bounding radius gets ~0 and so stands behind every bounded one.
+// The sign of a zero in lo / hi does not reach the key: c - lo differs between lo = +0 and lo = -0 only where c is a zero too, and then
+// it is a zero of either sign, whose quotient and product are zeros that the clamp (f > 0.0) sends to +0; hi - lo differs only where
+// both are zeros, and a zero span of either sign fails span > 0.0.  So a box reduced in another order than the host's (the device's
+// integer minimum / maximum puts -0 below +0, the host's sequential < / > keeps whichever came first) gives the same keys.
+RT_PACK_FN uint64_t stream_cull_key(const UsEntry &e, const double *lo, const double *hi)
+{
+    RT_PACK_STRICT
+    if (!(e.r < INFINITY)) return ~(uint64_t) 0;
+    const double c[3] = {-0.5 * e.kx, -0.5 * e.ky, -0.5 * e.kz};
+    uint64_t m = 0;
+    for (int k = 0; k < 3; k++) {
+        const double span = hi[k] - lo[k];
+        double f = (span > 0.0 && finite64(span)) ? (c[k] - lo[k]) / span * 2097151.0 : 0.0;
+        f = f > 0.0 ? (f < 2097151.0 ? f : 2097151.0) : 0.0;
+        const uint64_t q = (uint64_t) f;
+        for (int b = 0; b < 21; b++) m |= ((q >> b) & 1u) << (3 * b + (2 - k));
+    }
+    return m;
+}
+
 RT_PACK_FN void pack_gq(GqEntry &e, const DevObject &o, uint32_t orig)
 {
     e.x2 = o.c[K_X2]; e.y2 = o.c[K_Y2]; e.z2 = o.c[K_Z2];

@@ -54,10 +54,13 @@
 //                             same answers); nothing changes without MI355RT_STREAM_CULL and MI355RT_STREAM_QUERIES or below 65 unit spheres
 //   MI355RT_STREAM_CULL_PIXELS=1  ... and the pixel hooks (pick, extents) cull the chunks by the block's cone (RT_FLAG_STREAM_CULL_PIXELS;
 //                             same answers); nothing changes without MI355RT_STREAM_CULL and MI355RT_STREAM_QUERIES or below 65 unit spheres
+//   MI355RT_STREAM_CULL_REORDER=1  ... and mi355rt_update_scene puts the unit spheres back into that spatial order behind every applied update
+//                             (RT_FLAG_STREAM_CULL_REORDER, rt_reorder_scene; same frame); nothing changes without MI355RT_STREAM_CULL
 namespace {
 
 rt_ctx *g_ctx = nullptr;
 rt_multi *g_multi = nullptr;
+bool g_reorder = false; // MI355RT_STREAM_CULL_REORDER=1: mi355rt_update_scene reorders behind every applied update
 void *g_multi_lib = nullptr;
 struct MultiApi {
     int (*create)(rt_multi **, const rt_scene_desc *, const int *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) = nullptr;
@@ -70,6 +73,7 @@ struct MultiApi {
     void *(*stream)(rt_multi *) = nullptr;
     int (*set_scene)(rt_multi *, const rt_scene_update *) = nullptr;
     int (*scene_status)(rt_multi *, uint64_t *, uint64_t *, uint32_t *, uint32_t *) = nullptr;
+    int (*reorder_scene)(rt_multi *) = nullptr;
 } g_mapi;
 unsigned int g_texture = 0;
 unsigned int g_width = 0, g_height = 0;
@@ -143,8 +147,9 @@ void load_multi()
     g_mapi.stream = (decltype(g_mapi.stream)) dlsym(g_multi_lib, "rt_multi_stream");
     g_mapi.set_scene = (decltype(g_mapi.set_scene)) dlsym(g_multi_lib, "rt_set_scene_multi");
     g_mapi.scene_status = (decltype(g_mapi.scene_status)) dlsym(g_multi_lib, "rt_multi_set_scene_status");
+    g_mapi.reorder_scene = (decltype(g_mapi.reorder_scene)) dlsym(g_multi_lib, "rt_reorder_scene_multi");
     if (!g_mapi.create || !g_mapi.render || !g_mapi.download || !g_mapi.destroy || !g_mapi.set_threshold || !g_mapi.set_geometry || !g_mapi.query_ctx || !g_mapi.stream ||
-        !g_mapi.set_scene || !g_mapi.scene_status)
+        !g_mapi.set_scene || !g_mapi.scene_status || !g_mapi.reorder_scene)
         die_text("libmi355rt_multi.so", "missing entry points");
 }
 
@@ -308,7 +313,10 @@ extern "C" int mi355rt_update_scene(const Scene &scene)
         u.light_p = flat.light_p.data();
         u.light_color = flat.light_c.data();
     }
-    if (!g_multi) return rt_set_scene_host(g_ctx, &u, nullptr);
+    if (!g_multi) {
+        if (int rc = rt_set_scene_host(g_ctx, &u, nullptr)) return rc;
+        return g_reorder ? rt_reorder_scene(g_ctx, nullptr) : RT_OK;
+    }
     uint64_t before = 0, after = 0;
     uint32_t reason = 0, index = 0;
     if (int rc = g_mapi.scene_status(g_multi, nullptr, &before, nullptr, nullptr)) return rc;
@@ -320,7 +328,7 @@ extern "C" int mi355rt_update_scene(const Scene &scene)
         rt_set_last_error(text);
         return RT_ERR_SCENE;
     }
-    return RT_OK;
+    return g_reorder ? g_mapi.reorder_scene(g_multi) : RT_OK;
 }
 
 void init_update(unsigned int texture, const Scene &scene)
@@ -376,6 +384,12 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_CULL_PIXELS")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_PIXELS;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_PIXELS", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_CULL_REORDER=1: ... and mi355rt_update_scene re-sorts the unit spheres behind every applied update
+    g_reorder = false;
+    if (const char *f = std::getenv("MI355RT_STREAM_CULL_REORDER")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_REORDER, g_reorder = true;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_REORDER", "expected 0 or 1");
     }
     bool adaptive = false;
     float tau = 1.0f / 32.0f;

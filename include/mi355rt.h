@@ -390,6 +390,20 @@ typedef struct rt_scene_desc {
  * for the other classes; the flag as a default.  Supersampling contexts stay refused by the G-buffer family as before. */
 #define RT_FLAG_STREAM_CULL_PIXELS 4194304u
 
+/* Re-sorting a culled scene (csrc/rt_reorder_scene.hip): RT_FLAG_STREAM_CULL and the flags built on it cull because the
+ * unit-sphere table is in Morton order, chosen once by rt_create; rt_set_scene keeps that order, so the chunks of a scene whose spheres
+ * mix grow towards the whole field and the frames, still correct, again stage every chunk.  With this flag rt_reorder_scene ("Scene
+ * updates") puts the table the device holds into the order a fresh rt_create would choose and rebuilds the chunk bounds, on the device and
+ * in stream order.  One decision per context, made in rt_create and never revisited; rt_get_stream_cull_reorder reports it:
+ *     reorder = RT_FLAG_STREAM_CULL_REORDER && rt_get_stream_cull
+ * False: the context is, call for call and byte for byte, the context without the flag: no extra allocation, and rt_reorder_scene returns
+ * RT_OK and enqueues nothing.  True: rt_create also allocates the reorder work space (sized from the number of unit spheres alone: 96
+ * bytes per sphere and the sort's histogram tables; freed by rt_destroy).  The flag combines with every other and reaches every context
+ * of rt_create_multi.  No result depends on the table's order ("Order"), so no frame and no query changes.
+ * Diagnostics: MI355RT_REORDER_MAX_GRID=<1 .. 65535> in the environment at rt_create caps the workgroups of every launch of
+ * rt_reorder_scene (default: four per compute unit); any other value is refused (RT_ERR_INVALID).  Results do not depend on it. */
+#define RT_FLAG_STREAM_CULL_REORDER 8388608u
+
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
                                  produces (src/update-cpu.cpp:128-131) plus an alpha lane for 16-byte stores */
@@ -935,7 +949,8 @@ int rt_permute(rt_ctx *ctx, const uint32_t *dev_perm, uint32_t n, const void *de
  * scene blob and both light tables with the very functions rt_create packs them with (csrc/rt_scene_pack.hpp), so the device holds,
  * byte for byte, what a fresh rt_create of the new scene with the same rt_config would have uploaded (rt_debug_scene_blob shows it) --
  * in a context whose RT_FLAG_STREAM_CULL decision is true: what rt_create packs for the new scene under the context's order of the
- * unit-sphere table, which was chosen at rt_create and stays, and the bounds of its chunks (rt_debug_stream_bounds).
+ * unit-sphere table, which rt_set_scene never changes (chosen at rt_create; the one exception is rt_reorder_scene below, which chooses
+ * it anew), and the bounds of its chunks (rt_debug_stream_bounds).
  * Any of the five pointers may be NULL = "keep what the context holds" (the kernel takes those raw values from its own records), not all
  * five.  n_objects, n_lights and every light's kind are fixed, and so are the background, field of view and max_reflections.
  *
@@ -963,6 +978,21 @@ int rt_permute(rt_ctx *ctx, const uint32_t *dev_perm, uint32_t n, const void *de
  * rt_set_scene when issued on another stream, and that ordering is the caller's to establish (on one stream it is automatic).
  * Frame-to-frame state (launch order, census, tile words) survives an update: it affects speed only, never the image, exactly as under
  * a moving camera.  Works in every context kind.  The multi-GPU layer's entry point is rt_set_scene_multi ("Several GPUs").
+ *
+ * Re-sorting (RT_FLAG_STREAM_CULL_REORDER; csrc/rt_reorder_scene.hip).  rt_set_scene rebuilds every slot of the
+ * unit-sphere table from the slot's object and never moves an entry, so in a culling context the chunks of spheres that mix lose their
+ * locality.  rt_reorder_scene puts the table the device holds NOW into the order rt_create's packer would choose for it: the spheres
+ * with a bounding radius first, by the 63-bit Morton key of their centres over the box of those centres, ties by object index; the
+ * spheres without a radius behind them in object-index order; and it rebuilds the chunk bounds.  Afterwards rt_debug_scene_blob and
+ * rt_debug_stream_bounds return, byte for byte, what a fresh rt_create of the scene the context currently holds would have uploaded.
+ * Entries are moved as they are (rt_set_scene has re-packed them); nothing else in the blob moves.  The layout rule above keeps the
+ * number of bounded spheres fixed, and they stand first before and after: a chunk is finite or infinite after a reorder exactly as
+ * before it.  No result depends on the order, so frames and queries are bit for bit what they were -- only the work changes.
+ * The calling rules are rt_set_scene's: the call takes part in the context's frame order with the same stream, event and capture rules;
+ * it enqueues kernels only -- no allocation, no host read-back, no wait -- and every launch shape was decided at rt_create (by the numbers
+ * of unit spheres and of objects), so `(rt_set_scene, rt_reorder_scene, rt_render) x K` can be captured once and replayed; ordering
+ * against reading passes on other streams is the caller's.  How often to reorder is the caller's choice too: rt_set_scene itself never
+ * does it.  A context whose decision is false (rt_get_stream_cull_reorder) enqueues nothing and returns RT_OK.
  * ------------------------------------------------------------------------------------------------- */
 typedef struct rt_scene_update {
     const double *coefs;       /* [n_objects][RT_NCOEF]  or NULL */
@@ -990,6 +1020,12 @@ int rt_set_scene_host(rt_ctx *ctx, const rt_scene_update *host, void *stream);
  * rejected since rt_create, and the reason / index of the most recent rejection (0 / 0 before the first).  Any output pointer may be
  * NULL.  RT_ERR_INVALID while that stream is capturing. */
 int rt_set_scene_status(rt_ctx *ctx, uint64_t *applied, uint64_t *rejected, uint32_t *reason, uint32_t *index);
+/* Re-sort the unit-sphere table into rt_create's order and rebuild the chunk bounds ("Re-sorting" above); enqueues kernels on `stream`
+ * and returns.  RT_ERR_INVALID for a NULL context, decided before a device is looked for. */
+int rt_reorder_scene(rt_ctx *ctx, void *stream);
+/* *on = 1 where rt_reorder_scene re-sorts (RT_FLAG_STREAM_CULL_REORDER on a context whose rt_get_stream_cull is 1), else 0.
+ * RT_ERR_INVALID for a NULL context or a NULL `on`, decided before a device is looked for. */
+int rt_get_stream_cull_reorder(const rt_ctx *ctx, uint32_t *on);
 /* Diagnostics: the scene as the device holds it -- the blob, then DevLight[n_lights], then LightK[n_lights] (csrc/rt_scene_dev.h).
  * *bytes receives the size; out may be NULL (size only), else cap must be at least that.  Waits as rt_set_scene_status does. */
 int rt_debug_scene_blob(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
@@ -1108,6 +1144,9 @@ int rt_multi_set_ssaa_geometry(rt_multi *m, float min_cos);
  * fails after the first context has been enqueued leaves the contexts with different scenes and the object failed. */
 int rt_set_scene_multi(rt_multi *m, const rt_scene_update *host);
 int rt_multi_set_scene_status(rt_multi *m, uint64_t *applied, uint64_t *rejected, uint32_t *reason, uint32_t *index);
+/* rt_reorder_scene on every context, on its device's render stream and in frame order, as rt_set_scene_multi enqueues rt_set_scene:
+ * behind an earlier rt_set_scene_multi, in front of later frames.  Enqueue-only.  Contexts whose decision is false enqueue nothing. */
+int rt_reorder_scene_multi(rt_multi *m);
 /* The root's context 0, borrowed until rt_multi_destroy, for the queries that depend neither on row ownership nor on frame state:
  * rt_pick, rt_pick_paths, rt_primary_rays, rt_trace_rays, rt_occluded_rays, rt_shade_rays, rt_trace_paths and their _host forms, all on
  * rt_multi_stream(m), where they are ordered behind rt_set_scene_multi on the root.  Nothing else may be called on it: frames, scene
