@@ -39,6 +39,7 @@ RT_FLAG_STREAM_CULL_BOUNCE = 1048576        # ... and culls the chunks of its bo
 RT_FLAG_STREAM_CULL_RAYS = 2097152          # ... and culls the chunks per caller-supplied ray in the ray queries (with RT_FLAG_STREAM_CULL, streamed queries and at least two chunks; same outputs)
 RT_FLAG_STREAM_CULL_PIXELS = 4194304        # ... and culls the chunks by the block's cone in the pixel queries (with RT_FLAG_STREAM_CULL, streamed queries and at least two chunks; same outputs)
 RT_FLAG_STREAM_CULL_REORDER = 8388608       # ... and reorder_scene() puts the unit spheres back into that spatial order after set_scene moved them (with RT_FLAG_STREAM_CULL; same frame)
+RT_FLAG_STREAM_CULL_GROUPS = 16777216       # ... and update() asks a second level of bounds first, one per 64 chunk bounds (with RT_FLAG_STREAM_CULL and at least two groups: 4 097 unit spheres; same frame)
 SSAA_DEFAULT_THRESHOLD = 1.0 / 32.0
 RT_FMT_RGBA32F, RT_FMT_RGBA8 = 0, 1
 RT_ERR_NO_DEVICE = -4
@@ -53,7 +54,7 @@ ABI_SYMBOLS = [
     "rt_set_ssaa_threshold", "rt_set_ssaa_geometry", "rt_get_ssaa_refined", "rt_get_streamed", "rt_get_streamed_queries", "rt_get_streamed_adaptive",
     "rt_get_stream_cull", "rt_debug_stream_bounds", "rt_debug_stream_cull", "rt_get_stream_cull_adaptive", "rt_debug_stream_cull_adaptive",
     "rt_get_stream_cull_bounce", "rt_debug_stream_cull_bounce", "rt_get_stream_cull_rays", "rt_debug_stream_cull_rays",
-    "rt_get_stream_cull_pixels", "rt_debug_stream_cull_pixels",
+    "rt_get_stream_cull_pixels", "rt_debug_stream_cull_pixels", "rt_get_stream_groups", "rt_debug_stream_groups", "rt_debug_stream_group_bounds",
     "rt_render_gbuffer", "rt_pick", "rt_object_extents", "rt_object_extents_host",
     "rt_trace_rays", "rt_occluded_rays", "rt_trace_rays_host", "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_paths", "rt_trace_paths_host", "rt_primary_rays", "rt_pick_paths",
@@ -244,6 +245,10 @@ def lib():
         if LIB_PATH != os.environ.get("MI355RT_LIB") or hasattr(L, "rt_get_stream_cull_pixels"):   # (an earlier build under MI355RT_LIB: as rt_sort_rays below)
             L.rt_get_stream_cull_pixels.argtypes = [vp, C.POINTER(C.c_uint32)]
             L.rt_debug_stream_cull_pixels.argtypes = [vp, C.POINTER(C.c_uint64)]
+        if LIB_PATH != os.environ.get("MI355RT_LIB") or hasattr(L, "rt_get_stream_groups"):   # (an earlier build under MI355RT_LIB: as rt_sort_rays below)
+            L.rt_get_stream_groups.argtypes = [vp, C.POINTER(C.c_uint32)]
+            L.rt_debug_stream_groups.argtypes = [vp, C.POINTER(C.c_uint64)]
+            L.rt_debug_stream_group_bounds.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.rt_render_gbuffer.argtypes = [vp, dp, vp, vp, vp, vp, fp]
         L.rt_pick.argtypes = [vp, dp, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(Hit), vp]
         L.rt_object_extents.argtypes = [vp, dp, C.POINTER(C.c_uint32), vp, vp, fp]
@@ -574,6 +579,31 @@ class Renderer:
         out = np.zeros(n.value, dtype=np.uint8)
         if n.value:
             _check(lib().rt_debug_stream_bounds(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
+        return out
+
+    @property
+    def stream_groups(self):
+        """True where update() asks a second level of bounds, one per 64 chunk bounds, before the chunk bounds: RT_FLAG_STREAM_CULL_GROUPS
+        on a context whose stream_cull is True, with at least two groups (4 097 unit spheres; rt_get_stream_groups)."""
+        n = C.c_uint32()
+        _check(lib().rt_get_stream_groups(self._h, C.byref(n)))
+        return bool(n.value)
+
+    def debug_stream_groups(self):
+        """The eight group work words since the context was created (rt_debug_stream_groups; waits).  They exist only where stream_groups
+        is True and MI355RT_STREAM_CULL_STATS=1 was in the environment when the context was created."""
+        w = (C.c_uint64 * 8)()
+        _check(lib().rt_debug_stream_groups(self._h, w))
+        return [int(v) for v in w]
+
+    def debug_stream_group_bounds(self):
+        """Diagnostics: the group-bound table as the device holds it, as bytes (64 per group of 64 chunks; rt_debug_stream_group_bounds;
+        waits).  Empty where stream_groups is False."""
+        n = C.c_size_t()
+        _check(lib().rt_debug_stream_group_bounds(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            _check(lib().rt_debug_stream_group_bounds(self._h, out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)))
         return out
 
     @property
@@ -1191,6 +1221,11 @@ class MultiRenderer:
         """Renderer.stream_cull_bounce of the contexts: they share scene, flags and max_reflections, hence the decision (read from
         rt_multi_query_ctx's context)."""
         return self.query.stream_cull_bounce
+
+    @property
+    def stream_groups(self):
+        """Renderer.stream_groups of the contexts: they share scene and flags, hence the decision (read from rt_multi_query_ctx's context)."""
+        return self.query.stream_groups
 
     @property
     def stream_cull_rays(self):

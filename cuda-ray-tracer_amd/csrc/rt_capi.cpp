@@ -63,6 +63,14 @@
         return k;                                                                                   \
     }()
 static const Kernels kernels_strict = RT_KERNELS(strict), kernels_fast = RT_KERNELS(fast);
+// ... and the launchers of a groups context (RT_FLAG_STREAM_CULL_GROUPS; rt_launch.h, struct GroupLaunchers), in a record of their own
+#define RT_GROUP_LAUNCHERS(V)                                     \
+    [] {                                                          \
+        GroupLaunchers k{};                                       \
+        k.frame = RT_CAT(rt_launch_stream_cull_groups, V);        \
+        return k;                                                 \
+    }()
+static const GroupLaunchers group_launchers_strict = RT_GROUP_LAUNCHERS(strict), group_launchers_fast = RT_GROUP_LAUNCHERS(fast);
 
 namespace {
 
@@ -288,6 +296,15 @@ struct rt_ctx {
     bool reorder = false;
     DevMem<unsigned char> d_reorder_work;
     uint32_t reorder_max_grid = 0;
+    // A second level over those bounds (RT_FLAG_STREAM_CULL_GROUPS; rt_stream_cull_groups.hip): the decision (create_scene), one bound per 64 chunk bounds, the
+    // launchers of the variant, and 8 work words of its own (only with MI355RT_STREAM_CULL_STATS=1 at rt_create)
+    bool words_wanted = false; // MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create (read once, in create_scene)
+    bool groups = false;
+    uint32_t n_groups = 0;
+    DevMem<UsEntry> d_groups;
+    DevMem<unsigned long long> d_group_words;
+    GroupTables group_tables = {};
+    const GroupLaunchers *group_kern = &group_launchers_strict; // RT_FLAG_FAST: &group_launchers_fast
     // the launchers of the pixel and the ray entry points: the staged, the streamed (stream_queries) or the culled (cull[CULL_PIXELS], cull[CULL_RAYS]) path of kern->query
     const QueryLaunchers *pixel_q = nullptr, *ray_q = nullptr;
     bool lean_ok = false;         // the scene qualifies for the wave-per-block instantiation (FrameArgs::lean; dense frames only)
@@ -531,6 +548,7 @@ static void create_frame(rt_ctx *ctx, const rt_scene_desc *sd, int device)
     const rt_config &cfg = ctx->cfg;
     ctx->device = device;
     ctx->kern = (cfg.flags & RT_FLAG_FAST) ? &kernels_fast : &kernels_strict;
+    ctx->group_kern = (cfg.flags & RT_FLAG_FAST) ? &group_launchers_fast : &group_launchers_strict;
     ctx->width = sd->width;
     ctx->height = sd->height;
     if (const char *e = std::getenv("MI355RT_RESOLVE_NT")) ctx->resolve_nt = std::atoi(e) != 0; // (experiments)
@@ -607,6 +625,9 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
         return fail(RT_ERR_SCENE, "rt_create: RT_FLAG_SSAA_GEOMETRY stages %zu bytes of LDS per workgroup (limit 160 KiB)", rt_gbuffer_lds_bytes_strict(&fa));
     // Does rt_render cull whole chunks of the unit-sphere table (rt_stream_cull.hip)?  One decision, as above.  True: the table takes the
     // context's spatial order and every chunk gets its bound (rt_scene_image.hpp); false: nothing of the context differs from one without the flag.
+    // ... and do the culling families keep work words?  Asked once, here: a decision below and the allocation in create_device_state both go by it.
+    const char *stats_env = std::getenv("MI355RT_STREAM_CULL_STATS");
+    ctx->words_wanted = stats_env && !std::strcmp(stats_env, "1");
     bool *cull = ctx->cull;
     cull[CULL_FRAME] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL) && ctx->streamed && fa.cull;
     if (cull[CULL_FRAME]) {
@@ -629,6 +650,16 @@ static int create_scene(rt_ctx *ctx, const rt_scene_desc *sd, rtp::SceneImage &i
     // ... and do the pixel queries cull the chunks by the block's cone (rt_stream_cull_pixels.hip)?  The same three conditions under a flag of its own.
     // False: launch for launch the context without the flag.  (cull[CULL_FRAME] implies fa.cull: the cone exists.)
     cull[CULL_PIXELS] = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_PIXELS) && cull[CULL_FRAME] && ctx->stream_queries && ctx->n_chunks >= 2u;
+    // ... and does rt_render ask a second level of bounds first, one per 64 chunk bounds (rt_stream_cull_groups.hip)?  The flag, the culling decision and a
+    // second group: with one, the group level can remove nothing and is paid per query.  False: launch for launch the context without the flag.  rt_set_scene
+    // and rt_reorder_scene keep the chunk layout, so this holds for the context's life.
+    ctx->n_groups = (ctx->n_chunks + 63u) / 64u;
+    // One instantiation is not built (rt_stream_cull_groups.hip): the kernel that counts and culls bounce rays for general quadrics plus degree 3.  A context
+    // that would need it -- such a scene, a true bounce decision and the work words asked for -- is the context without the flag.
+    const bool not_built = fa.n_gq && fa.n_cub && cull[CULL_BOUNCE] && ctx->words_wanted;
+    ctx->groups = (ctx->cfg.flags & RT_FLAG_STREAM_CULL_GROUPS) && cull[CULL_FRAME] && ctx->n_groups >= 2u && !not_built;
+    if (ctx->groups) im.groups = rtp::stream_group_image(im.bounds);
+    else ctx->n_groups = 0u;
     // So the launchers the query entry points call, for the context's life: the culled path where the family culls, else the streamed or the staged one.
     const TablePath plain = ctx->stream_queries ? PATH_STREAMED : PATH_STAGED;
     ctx->pixel_q = &ctx->kern->query[cull[CULL_PIXELS] ? PATH_CULLED : plain];
@@ -652,7 +683,7 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
     if (int rc = device_table(ctx->d_ss_status, nullptr, sizeof(SetSceneStatus), "scene-update status")) return rc;
     if (ctx->cull[CULL_FRAME]) {
         if (int rc = device_table(ctx->d_bounds, im.bounds.data(), sizeof(UsEntry) * im.bounds.size(), "chunk bounds")) return rc;
-        const char *e = std::getenv("MI355RT_STREAM_CULL_STATS");
+        const char *e = ctx->words_wanted ? "1" : nullptr; // (MI355RT_STREAM_CULL_STATS as create_scene read it: one reading for the decisions and the words)
         if (e && !std::strcmp(e, "1"))
             if (int rc = device_table(ctx->d_cull_words, nullptr, sizeof(unsigned long long) * 8 * N_CULL_FAMILIES, "stream-cull work words")) return rc;
         // a family that culls takes the bounds, and its own 8 words where there are any (the adaptive kernel that counts for a scene with both general
@@ -661,6 +692,12 @@ static int create_device_state(rt_ctx *ctx, const rtp::SceneImage &im)
             const bool words = ctx->d_cull_words && !(f == CULL_ADAPTIVE && fa.n_gq && fa.n_cub);
             if (ctx->cull[f]) ctx->chunks[f] = ChunkTables{ctx->d_bounds.p, ctx->n_chunks, words ? ctx->d_cull_words + 8 * f : nullptr};
         }
+    }
+    if (ctx->groups) {
+        if (int rc = device_table(ctx->d_groups, im.groups.data(), sizeof(UsEntry) * im.groups.size(), "group bounds")) return rc;
+        if (ctx->d_cull_words)
+            if (int rc = device_table(ctx->d_group_words, nullptr, sizeof(unsigned long long) * 8, "stream-cull group work words")) return rc;
+        ctx->group_tables = GroupTables{ctx->d_groups.p, ctx->n_groups, ctx->d_group_words.p};
     }
     if (ctx->reorder) {
         RT_TRY("hipMalloc(reorder work space)", ctx->d_reorder_work.alloc(rt_reorder_scene_work_size(fa.n_us)));
@@ -1009,7 +1046,8 @@ static int render_impl(rt_ctx *ctx, const double cam[16], void *dev_fb, void *st
         if (int rc = rotate_launch_order(ctx, fa, stream)) return rc;
     if (int rc = timer_begin(ctx, stream, ms)) return rc;
     const ChunkTables *frame_chunks = &ctx->chunks[CULL_FRAME]; // (the bounce kernel books the frame's words as well as its own)
-    const hipError_t e = ctx->cull[CULL_BOUNCE] ? ctx->kern->stream_cull_bounce(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, frame_chunks, ctx->chunks[CULL_BOUNCE].stats, stream)
+    const hipError_t e = ctx->groups ? ctx->group_kern->frame(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, frame_chunks, &ctx->group_tables, ctx->chunks[CULL_BOUNCE].stats, ctx->cull[CULL_BOUNCE], stream)
+                         : ctx->cull[CULL_BOUNCE] ? ctx->kern->stream_cull_bounce(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, frame_chunks, ctx->chunks[CULL_BOUNCE].stats, stream)
                          : ctx->cull[CULL_FRAME] ? ctx->kern->stream_cull(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, frame_chunks, stream)
                          : ctx->streamed ? ctx->kern->stream(&fa, ctx->d_obj, ctx->d_light, ctx->d_camx, ctx->d_camy, fb, stream)
                          : (ctx->cfg.flags & RT_FLAG_SIMPLE) ? ctx->kern->trace(&fa, ctx->d_obj, ctx->d_light, fb, ctx->d_counters, fa.rgba8 != 0u, count, stream)
@@ -1491,7 +1529,8 @@ static int set_scene_enqueue(const char *who, rt_ctx *ctx, const rt_scene_update
     a.has_mirror = fa.has_mirror;
     a.n_chunks = ctx->cull[CULL_FRAME] ? ctx->n_chunks : 0u; // (the chunk bounds follow the rebuilt entries; the slots keep their objects: only rt_reorder_scene moves an entry)
     a.bounds = ctx->cull[CULL_FRAME] ? ctx->d_bounds.p : nullptr;
-    const hipError_t e = rt_launch_set_scene(&a, stream);
+    hipError_t e = rt_launch_set_scene(&a, stream);
+    if (e == hipSuccess && ctx->groups) e = rt_launch_group_bounds(ctx->d_bounds.p, ctx->n_chunks, ctx->d_groups.p, stream); // (a refused update: the same bytes again)
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "%s: kernel launch failed: %s", who, hipGetErrorString(e));
     return order_end(ctx, stream, capturing);
 }
@@ -1555,7 +1594,8 @@ extern "C" int rt_reorder_scene(rt_ctx *ctx, void *stream_)
     if (int rc = order_begin("rt_reorder_scene", ctx, stream, &capturing)) return rc;
     const FrameArgs &fa = ctx->fa;
     unsigned char *blob = reinterpret_cast<unsigned char *>(ctx->d_obj.p);
-    const hipError_t e = rt_launch_reorder_scene(blob + fa.off_us, fa.n_us, fa.n_obj, ctx->d_bounds.p, ctx->d_reorder_work.p, ctx->reorder_max_grid, stream);
+    hipError_t e = rt_launch_reorder_scene(blob + fa.off_us, fa.n_us, fa.n_obj, ctx->d_bounds.p, ctx->d_reorder_work.p, ctx->reorder_max_grid, stream);
+    if (e == hipSuccess && ctx->groups) e = rt_launch_group_bounds(ctx->d_bounds.p, ctx->n_chunks, ctx->d_groups.p, stream);
     if (e != hipSuccess) return fail(RT_ERR_DEVICE, "rt_reorder_scene: kernel launch failed: %s", hipGetErrorString(e));
     return order_end(ctx, stream, capturing);
 }
@@ -1851,6 +1891,32 @@ extern "C" int rt_debug_stream_bounds(rt_ctx *ctx, void *out, size_t cap, size_t
     if (!out || !need) return RT_OK;
     if (cap < need) return fail(RT_ERR_INVALID, "rt_debug_stream_bounds: %zu bytes offered, the bounds take %zu", cap, need);
     return read_behind_last_call("rt_debug_stream_bounds", ctx, out, ctx->d_bounds, need);
+}
+
+// RT_FLAG_STREAM_CULL_GROUPS: the decision, the group work words, the group bounds as the device holds them
+extern "C" int rt_get_stream_groups(const rt_ctx *ctx, uint32_t *on)
+{
+    if (!ctx || !on) return fail(RT_ERR_INVALID, "rt_get_stream_groups: null argument");
+    *on = ctx->groups ? 1u : 0u;
+    return RT_OK;
+}
+
+extern "C" int rt_debug_stream_groups(rt_ctx *ctx, uint64_t out[8])
+{
+    if (!ctx || !out) return fail(RT_ERR_INVALID, "rt_debug_stream_groups: null argument");
+    if (!ctx->group_tables.stats)
+        return fail(RT_ERR_INVALID, "rt_debug_stream_groups: the context keeps no work words (they exist where rt_get_stream_groups says 1%s)", STATS_SET);
+    return read_behind_last_call("rt_debug_stream_groups", ctx, out, ctx->group_tables.stats, sizeof(uint64_t) * 8);
+}
+
+extern "C" int rt_debug_stream_group_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes)
+{
+    if (!ctx || !bytes) return fail(RT_ERR_INVALID, "rt_debug_stream_group_bounds: null argument");
+    const size_t need = ctx->groups ? sizeof(UsEntry) * (size_t) ctx->n_groups : 0u;
+    *bytes = need;
+    if (!out || !need) return RT_OK;
+    if (cap < need) return fail(RT_ERR_INVALID, "rt_debug_stream_group_bounds: %zu bytes offered, the group bounds take %zu", cap, need);
+    return read_behind_last_call("rt_debug_stream_group_bounds", ctx, out, ctx->d_groups, need);
 }
 
 extern "C" int rt_get_streamed(const rt_ctx *ctx, uint32_t *streamed)

@@ -123,6 +123,17 @@ RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_bounce, const FrameArgs *fa, co
 RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_ray_list, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy,
                const uint32_t *list, const uint32_t *count_ptr, uint32_t n_items, uint32_t k, uint32_t grid, void *out, int rgba8, const ChunkTables *chunks,
                hipStream_t stream)
+// The group bounds of a context whose culled frame asks a second level first (RT_FLAG_STREAM_CULL_GROUPS): [n_groups] UsEntry for the n_groups =
+// ceil(n_chunks / 64) groups of 64 consecutive chunk bounds, and the 8 group work words the launch adds to (NULL exactly where the chunks' words are)
+struct GroupTables {
+    const void *groups;
+    uint32_t n_groups;
+    unsigned long long *stats;
+};
+// rt_stream_cull_groups.hip: rt_launch_stream_cull_bounce's arguments and the groups; bounce != 0: the bounce rays are culled per ray as well, 0: they keep
+// the full sweep of rt_launch_stream_cull (bounce_stats NULL)
+RT_PER_VARIANT(hipError_t, rt_launch_stream_cull_groups, const FrameArgs *fa, const void *scene, const void *lights, const double *camx, const double *camy, void *fb,
+               const ChunkTables *chunks, const GroupTables *groups, unsigned long long *bounce_stats, int bounce, hipStream_t stream)
 // built once without FMA contraction and used by both variants: the supersampling resolve (rt_resolve.hip) and the scene update (rt_set_scene.hip)
 extern "C" hipError_t rt_launch_resolve(const void *in, void *out, uint32_t width, uint32_t rows, uint32_t k, int rgba8, int nt, hipStream_t stream);
 extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t stream);
@@ -131,6 +142,9 @@ extern "C" hipError_t rt_launch_set_scene(const SetSceneArgs *args, hipStream_t 
 // at least rt_reorder_scene_work_size(n_us) bytes, n_us > 0, every entry's orig is below n_obj
 extern "C" size_t rt_reorder_scene_work_size(uint32_t n_us);
 extern "C" hipError_t rt_launch_reorder_scene(void *t_us, uint32_t n_us, uint32_t n_obj, void *bounds, void *work, uint32_t max_grid, hipStream_t stream);
+// rt_group_bounds.hip, built once likewise (the bounds are the host's function): groups[G] = rtp::pack_chunk_bound over chunk bounds 64 G .., G below
+// ceil(n_chunks / 64), from the chunk bounds as the stream holds them behind either update's launcher
+extern "C" hipError_t rt_launch_group_bounds(const void *bounds, uint32_t n_chunks, void *groups, hipStream_t stream);
 
 // how a query reads the class tables: staged in LDS, streamed through a slice, or streamed with whole chunks culled
 enum TablePath { PATH_STAGED, PATH_STREAMED, PATH_CULLED };
@@ -158,6 +172,12 @@ struct Kernels {
     decltype(&rt_launch_stream_cull_ray_list_strict) stream_cull_ray_list;
     decltype(&rt_launch_primary_rays_strict) primary_rays;
     QueryLaunchers query[3]; // by TablePath
+};
+
+// the launchers of a groups context per variant, in a record of their own (struct Kernels is the contexts' without the flag); rt_create picks one of the two
+// instances (rt_capi.cpp) from RT_FLAG_FAST
+struct GroupLaunchers {
+    decltype(&rt_launch_stream_cull_groups_strict) frame;
 };
 
 // rt_planes.hip, built once (no floating-point arithmetic in it): the reassembly of a gathered plane of 4-, 8- or 16-byte elements

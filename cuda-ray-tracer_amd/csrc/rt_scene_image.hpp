@@ -24,6 +24,7 @@ struct SceneImage {
     std::vector<double> cub_coefs;   // the 20 coefficients of the first RT_CUB_AT_MAX degree-3 objects (FrameArgs::cub_rec is formed from them every frame)
     uint32_t n_cullable = 0;         // objects with a bounding radius
     std::vector<UsEntry> bounds;     // RT_FLAG_STREAM_CULL contexts: the bound of every 64-entry chunk of the ordered unit-sphere table (stream_cull_image)
+    std::vector<UsEntry> groups;     // RT_FLAG_STREAM_CULL_GROUPS contexts: the bound of every 64 consecutive chunk bounds (stream_group_image)
     bool lean_ok = false;            // the scene and the flags qualify for the wave-per-block instantiation (FrameArgs::lean)
 };
 
@@ -151,6 +152,19 @@ inline std::vector<UsEntry> stream_cull_image(SceneImage &im, const FrameArgs &f
     if (n_chunks) std::memset(bounds.data(), fill, sizeof(UsEntry) * n_chunks);
     for (uint32_t c = 0; c < n_chunks; c++) pack_chunk_bound(bounds[c], t_us + 64u * c, (n - 64u * c < 64u) ? n - 64u * c : 64u, c);
     return bounds;
+}
+
+// The group bounds of an RT_FLAG_STREAM_CULL_GROUPS context: one bound per 64 consecutive chunk bounds, formed by the function that
+// forms the chunk bounds themselves -- pack_chunk_bound's proof asks of its members a centre -k / 2, an r and an inv_r, which a chunk bound has --, orig =
+// the group's index.  A group with an unbounded chunk (r = +inf) is unbounded.  bounds: stream_cull_image's result, or the chunk bounds a device holds;
+// fill: as in scene_image.  rt_group_bounds.hip forms the same bytes on the device.
+inline std::vector<UsEntry> stream_group_image(const std::vector<UsEntry> &bounds, unsigned char fill = 0)
+{
+    const uint32_t n = (uint32_t) bounds.size(), n_groups = (n + 63u) / 64u;
+    std::vector<UsEntry> groups(n_groups);
+    if (n_groups) std::memset(groups.data(), fill, sizeof(UsEntry) * n_groups);
+    for (uint32_t g = 0; g < n_groups; g++) pack_chunk_bound(groups[g], bounds.data() + 64u * g, (n - 64u * g < 64u) ? n - 64u * g : 64u, g);
+    return groups;
 }
 
 } // namespace rtp

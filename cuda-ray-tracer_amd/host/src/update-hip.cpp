@@ -56,6 +56,8 @@
 //                             same answers); nothing changes without MI355RT_STREAM_CULL and MI355RT_STREAM_QUERIES or below 65 unit spheres
 //   MI355RT_STREAM_CULL_REORDER=1  ... and mi355rt_update_scene puts the unit spheres back into that spatial order behind every applied update
 //                             (RT_FLAG_STREAM_CULL_REORDER, rt_reorder_scene; same frame); nothing changes without MI355RT_STREAM_CULL
+//   MI355RT_STREAM_CULL_GROUPS=1  ... and the culled frame asks a second level of bounds first, one per 64 chunk bounds
+//                             (RT_FLAG_STREAM_CULL_GROUPS; same frame); nothing changes without MI355RT_STREAM_CULL or below 4 097 unit spheres
 namespace {
 
 rt_ctx *g_ctx = nullptr;
@@ -384,6 +386,11 @@ void init_update(unsigned int texture, const Scene &scene)
     if (const char *f = std::getenv("MI355RT_STREAM_CULL_PIXELS")) {
         if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_PIXELS;
         else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_PIXELS", "expected 0 or 1");
+    }
+    // MI355RT_STREAM_CULL_GROUPS=1: ... and the culled frame asks a second level of bounds first, one per 64 chunk bounds
+    if (const char *f = std::getenv("MI355RT_STREAM_CULL_GROUPS")) {
+        if (!std::strcmp(f, "1")) streamed |= RT_FLAG_STREAM_CULL_GROUPS;
+        else if (std::strcmp(f, "0") && *f) die_text("MI355RT_STREAM_CULL_GROUPS", "expected 0 or 1");
     }
     // MI355RT_STREAM_CULL_REORDER=1: ... and mi355rt_update_scene re-sorts the unit spheres behind every applied update
     g_reorder = false;

@@ -291,8 +291,8 @@ typedef struct rt_scene_desc {
  * nothing and pays one decision per chunk, and so does a scene of a single chunk (measured: 20spheres with its 19 lights takes 1.67 x
  * the time of RT_FLAG_STREAM alone; the 1 685- and 10 000-sphere fields of DESIGN.md section 25 take 0.215 x and 0.026 x).  Bounce
  * rays: RT_FLAG_STREAM_CULL_BOUNCE below; caller-supplied rays: RT_FLAG_STREAM_CULL_RAYS below; the pixel queries:
- * RT_FLAG_STREAM_CULL_PIXELS below.  Out of scope: bounds for the other classes; a second level over the chunk bounds; reordering the
- * refine list for tighter wave cones; counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
+ * RT_FLAG_STREAM_CULL_PIXELS below; a second level over the chunk bounds: RT_FLAG_STREAM_CULL_GROUPS below.  Out of scope: bounds for the
+ * other classes; reordering the refine list for tighter wave cones; counters (RT_FLAG_COUNT) in streamed passes; the flag as a default. */
 #define RT_FLAG_STREAM_CULL 524288u
 
 /* Culled bounce rays (csrc/rt_stream_cull_bounce.hip): in a culled streamed frame the nearest-hit query of a bounce
@@ -403,6 +403,54 @@ typedef struct rt_scene_desc {
  * Diagnostics: MI355RT_REORDER_MAX_GRID=<1 .. 65535> in the environment at rt_create caps the workgroups of every launch of
  * rt_reorder_scene (default: four per compute unit); any other value is refused (RT_ERR_INVALID).  Results do not depend on it. */
 #define RT_FLAG_STREAM_CULL_REORDER 8388608u
+
+/* Grouped chunk bounds (csrc/rt_stream_cull_groups.hip): a culled streamed frame asks one verdict per chunk bound --
+ * per 8 x 8 block for the primary rays, per (wave, light) for the shadow rays and, with RT_FLAG_STREAM_CULL_BOUNCE, per lane and bounce
+ * ray -- so its cost still grows with the number of chunks: at 100 000 spheres 1 563 bounds per query, almost all of them nowhere near
+ * it.  With this flag the context keeps a second level: a GROUP is 64 consecutive chunks (4 096 entries of the ordered unit-sphere table,
+ * a compact cell of the Morton order), and its bound is formed from the group's chunk bounds by the function that forms a chunk bound
+ * from its spheres (csrc/rt_scene_pack.hpp, pack_chunk_bound, orig = the group's index; a group with an unbounded chunk is unbounded and
+ * never skipped).  That function's proof -- bound skipped => member skipped by its own predicate, by a margin that dwarfs rounding --
+ * asks of a member a centre, an r and an inv_r, which a chunk bound has: a skipped group implies 64 skipped chunk bounds, and those every
+ * sphere.  One decision per context, made in rt_create and never revisited (rt_set_scene and rt_reorder_scene keep the chunk layout);
+ * rt_get_stream_groups reports it:
+ *     stream groups = RT_FLAG_STREAM_CULL_GROUPS && rt_get_stream_cull && at least 2 groups (65 chunks: 4 097 unit spheres)
+ *                     && the kernel is built (below: every context but one diagnostic combination)
+ * False: the context is, launch for launch and byte for byte, the context without the flag; the flag without RT_FLAG_STREAM_CULL is simply
+ * false.  There is no refusal of its own, and the flag combines with every other.  True: rt_render launches
+ * stream_cull_groups_frame_kernel.  Primary and shadow queries: per block of 64 groups lane j asks the query's own predicate (the block's
+ * cone; the ball of the wave's hits and the light) about group bound j, one ballot is the mask of the groups to enter, and only those run
+ * the chunk loop of RT_FLAG_STREAM_CULL for their 64 chunks.  Bounce rays, where rt_get_stream_cull_bounce is 1: every lane asks about its
+ * own ray and the group bound, and the 64 chunks of a group that no lane in use reaches are passed over; where it is 0 bounce rays keep
+ * the full sweep.  The group bounds follow the chunk bounds: rt_set_scene and rt_reorder_scene each enqueue one more small kernel behind
+ * their own (one more graph node each; both stay capturable, a refused update recomputes the same bytes).
+ * Results are unchanged by definition: the chunks staged, the order they are staged in and the place of the occlusion early-out are those
+ * of the same context without the flag, so every frame is that context's bit for bit -- strict and RT_FLAG_FAST, both formats, every
+ * degree, rank and RT_FLAG_SSAA2/4 mode.  ms, capturability, ranks and rt_pack_sparse are those of RT_FLAG_STREAM_CULL.  Through
+ * rt_create_multi the flag reaches every context.  Work words: with MI355RT_STREAM_CULL_STATS=1 rt_debug_stream_cull and
+ * rt_debug_stream_cull_bounce count what the kernel now asks and stages -- the staged words are those of the unflagged context, the
+ * decision words ([0], [2]; bounce [0], [2]) count only the chunk bounds of entered groups --, and rt_debug_stream_groups has the group
+ * verdicts.  The fifteen instantiations of each build that are built fit two waves per SIMD without a spill (at most 254 VGPRs; the eight
+ * that do not count at most 235).  Not built: the kernel that COUNTS and culls bounce rays for a scene with both general quadrics and
+ * degree-3 objects, which does not fit two waves per SIMD in either build.  The decision is false for the contexts that would need it:
+ * such a scene, rt_get_stream_cull_bounce 1 and MI355RT_STREAM_CULL_STATS=1 in the environment at rt_create.  Without the diagnostic
+ * switch no scene is excluded.
+ * Known limits: three groups cannot remove much and cost one more verdict per query; groups are Morton runs, and a run that straddles two
+ * clusters has a bound around both; on a scene with both general quadrics and degree-3 objects and culled bounce rays the diagnostic switch
+ * MI355RT_STREAM_CULL_STATS=1 makes the decision false, so the work words of the grouped kernel that such a context runs WITHOUT the
+ * switch cannot be read -- profile such a scene without RT_FLAG_STREAM_CULL_BOUNCE, or by time alone; every rt_set_scene and
+ * rt_reorder_scene of a groups context is followed by one more small kernel (one thread per group, 128 dependent 64-byte loads long).
+ * Measured (profiles/stream_cull_groups.txt; MI355X, 1920 x 1080, strict RGBA32F, the
+ * sphere field, against the same context without the flag): A SMALL GAIN, 0.1 - 2.2 %.  10 000 spheres 945.4 -> 936.7 us, 100 000 spheres
+ * 42 018 -> 41 966 us (inside the unflagged series' spread of 93 us), 400 000 spheres 218 601 -> 218 117 us, although there 82 % of the
+ * primary and 57 % of the shadow chunk verdicts are gone: the time of a large scene is in the staged chunks of its shadow rays (768 million
+ * entries decided per frame at 100 000 spheres), not in the verdicts.  The mirrored field with RT_FLAG_STREAM_CULL_BOUNCE, whose per-lane
+ * loop pays most per chunk: 10 000 spheres 4 413 -> 4 318 us, 100 000 spheres 170 913 -> 168 008 us (37 % of the bounce chunk verdicts gone;
+ * a wave's 64 bounce rays together still enter 62 % of the groups).  No case lost.  The group-bounds kernel adds 33 - 47 us to every
+ * rt_set_scene and rt_reorder_scene, more than a frame gains below about 100 000 spheres.
+ * Out of scope: the adaptive, ray-query and pixel-query culling kernels keep their chunk loops (on a groups context they run unchanged and
+ * return the same bits); any fan-out other than 64; a third level; best_t pruning; the flag as a default. */
+#define RT_FLAG_STREAM_CULL_GROUPS 16777216u
 
 /* rt_config.format -- framebuffer pixel format */
 #define RT_FMT_RGBA32F 0u     /* 4 x float per pixel, alpha 1.0: the un-quantised colours the CPU back end
@@ -616,6 +664,9 @@ int rt_get_stream_cull_adaptive(const rt_ctx *ctx, uint32_t *on);
 /* Culled bounce rays (RT_FLAG_STREAM_CULL_BOUNCE above): *on = 1 where rt_render culls the unit-sphere chunks of its bounce rays per ray,
  * else 0.  RT_ERR_INVALID for a NULL argument (before a device is looked for). */
 int rt_get_stream_cull_bounce(const rt_ctx *ctx, uint32_t *on);
+/* Grouped chunk bounds (RT_FLAG_STREAM_CULL_GROUPS above): *on = 1 where rt_render asks a second level of bounds, one per 64 chunk
+ * bounds, before the chunk bounds, else 0.  RT_ERR_INVALID for a NULL argument (before a device is looked for). */
+int rt_get_stream_groups(const rt_ctx *ctx, uint32_t *on);
 /* Culled ray queries (RT_FLAG_STREAM_CULL_RAYS above): *on = 1 where rt_trace_rays, rt_occluded_rays, rt_shade_rays, rt_trace_paths and
  * rt_pick_paths cull the unit-sphere chunks per caller-supplied ray, else 0.  RT_ERR_INVALID for a NULL argument (before a device is
  * looked for). */
@@ -1032,7 +1083,20 @@ int rt_debug_scene_blob(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
 /* Diagnostics of RT_FLAG_STREAM_CULL: the chunk-bound table as the device holds it, one 64-byte UsEntry (csrc/rt_scene_dev.h) per
  * 64-entry chunk of the blob's unit-sphere table.  Calling conventions of rt_debug_scene_blob; 0 bytes where rt_get_stream_cull says 0. */
 int rt_debug_stream_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
-/* ... and the kernel's work words, cumulative since rt_create; waits for the context's last call as rt_set_scene_status does.
+/* Diagnostics of RT_FLAG_STREAM_CULL_GROUPS: the group-bound table as the device holds it, one 64-byte UsEntry per 64 chunk bounds.
+ * Calling conventions of rt_debug_scene_blob; 0 bytes where rt_get_stream_groups says 0. */
+int rt_debug_stream_group_bounds(rt_ctx *ctx, void *out, size_t cap, size_t *bytes);
+/* ... and the group verdicts of rt_render (rt_get_stream_groups), eight words of their own, cumulative since rt_create.  Waits as
+ * rt_set_scene_status does.
+ *   [0] primary group verdicts asked (one per wave and group bound)      [1] primary groups entered
+ *   [2] shadow group verdicts asked, one per (wave, segment, light, group) where culling applied, up to the occlusion early-out
+ *   [3] shadow groups entered
+ *   [4] bounce queries' group verdicts, one per (wave, segment >= 1, group bound)      [5] bounce groups entered by the wave's union
+ *   [6], [7] 0
+ * The words exist only when MI355RT_STREAM_CULL_STATS=1 was in the environment at rt_create and the decision is true; otherwise the
+ * kernel counts nothing and the call answers RT_ERR_INVALID.  RT_ERR_INVALID for a NULL argument, before a device is looked for. */
+int rt_debug_stream_groups(rt_ctx *ctx, uint64_t out[8]);
+/* The work words of RT_FLAG_STREAM_CULL's kernel, cumulative since rt_create; waits for the context's last call as rt_set_scene_status does.
  *   [0] primary chunk decisions (one per wave and chunk bound asked)      [1] primary chunks staged
  *   [2] shadow chunk decisions, one per (wave, segment, light, chunk) where culling applied      [3] shadow chunks staged
  *   [4] shadow entries decided (the entries of the staged chunks)         [5] shadow entries swept
